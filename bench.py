@@ -9,11 +9,15 @@ frame records to rank 0 (m17hip_gather_frames_device; the torch all_gather of m1
 be had).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's frame records as DIR/*.npy (dump_outputs)
+    python bench.py --full            # + parity checks, the other regimes and configs[1], `roofline`, `cpu_baseline` (minutes)
     python bench.py --gpus 8                       # starts its 8 ranks itself (one process per GPU, 127.0.0.1 rendezvous); --dry-launch shows them
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --config 2        # BASELINE configs[1]: 1024 channels, FIR + correlator outputs materialised (26 B/sample)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step) and the configuration.
+A plain run sets up, warms up, times its --steps steps and prints the line; everything else the line can report (`single_stream`,
+`roofline`, `cpu_baseline`, `config2`, `bursty`, `h2d`, the parity checks against the oracle) is measured only with --full, null otherwise.
 """
 import argparse
 import json
@@ -208,7 +212,17 @@ def parse_args():
                     "loud noise for the rest: the carrier detect is off 80 % of the time) reported as `bursty`; 0 = skip")
     ap.add_argument("--launch-timeout", type=float, default=3600.0, help="with --gpus N > 1 and no launcher: seconds after which the ranks are stopped (exit code 124)")
     ap.add_argument("--force-gather", action="store_true", help="run the N > 1 code path (process group, communicators, gather per step) with WORLD_SIZE = 1")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else the line reports: the parity checks against the oracle, the "
+                    "single-stream, one-at-a-time, bursty, PCIe-inclusive and configs[1] legs, the roofline objects and the CPU baseline (without it those "
+                    "options are ignored and their objects are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame records the last timed step delivered as "
+                    "DIR/*.npy (float64 / float32): the record count of every channel and every field of the records of a fixed, seeded sample of channels")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 3:
+        ap.error("--dump-outputs: the headline path (--config 3) only")
+    return args
 
 
 class Bench:
@@ -267,7 +281,7 @@ class Bench:
         self.ctx = self.ctxs[0]
         for c_ in self.ctxs:
             c_.synth(self.p, C, T, chan0=self.rank * C)
-        self.x = self.ctx.download() if self.rank == 0 else None   # host copy for the parity checks, the cpu_baseline and the PCIe-inclusive leg (rank 0)
+        self.x = self.ctx.download() if (self.rank == 0 and args.full) else None   # host copy for the parity checks, the cpu_baseline and the PCIe-inclusive leg (rank 0, --full)
         self.t_gen = time.time() - t_gen
         self.rec_cap_local = C * (2 * (T // 1920 + 2) + 4)
 
@@ -391,9 +405,9 @@ class Bench:
         return total
 
     def leg_headline(self):
-        """W warm-up steps, then EXACTLY K timed steps between barrier + synchronize brackets; max over ranks.  Then, outside the timed region:
-        the records of the last timed step (rank 0), the parity spot check against the oracle, and (N > 1) the check that the gathered set is
-        one (channel, seq)-ordered, duplicate-free set."""
+        """W warm-up steps, then EXACTLY K timed steps between barrier + synchronize brackets; max over ranks.  Then, outside the timed region
+        (rank 0): with --dump-outputs the records the last timed step delivered; with --full those records, the parity spot check against the
+        oracle, and (N > 1) the check that the gathered set is one (channel, seq)-ordered, duplicate-free set."""
         args, np_, m17hip, C, T, F = self.args, np, self.m17hip, self.C, self.T, self.F
         # Untimed pre-warm before the W warm-up steps: a GPU that has been idle needs about a second of load before its clocks and the
         # two batches' interleaving settle (measured: the first process on a fresh box ran 29.4 ms/step with 5 warm-up steps, 26.4 with 60)
@@ -421,6 +435,14 @@ class Bench:
 
         self.parity = self.good = self.gathered_ok = self.recs = None
         if self.rank != 0:
+            return
+        if args.dump_outputs:   # what the caller of the timed path received from its last step: the records in the device buffer (N > 1: gathered)
+            if self.multi and not self.comms:
+                raw = self.last["allrecs"].cpu().numpy().tobytes()
+            else:
+                raw = self.last["buf"][: self.total_frames * 64].cpu().numpy().tobytes()
+            dump_outputs(args.dump_outputs, np_.frombuffer(raw, dtype=m17hip.FRAME_REC), C * self.world)
+        if not args.full:
             return
         if not self.multi:
             recs = self.ctxs[(args.steps - 1) % F].frames()
@@ -796,31 +818,35 @@ def main():
     if args.dry_launch:
         sys.exit("--dry-launch: only with --gpus N > 1 and WORLD_SIZE unset")
     # the streams of a context (main, K1, K3, K2-ahead, copy) and of different contexts must not share a hardware queue: a kernel queued
-    # behind another stream's event wait in the same queue waits with it (the runtime's default is 4 queues)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+    # behind another stream's event wait in the same queue waits with it (the runtime's default is 4 queues): 16, also over an
+    # inherited smaller value (a larger one given from outside is kept)
+    if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
+        os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
     B = Bench(args)
     if args.config == 2:
         return bench_front(args, B.ctx, B.ol, B.x, B.C, B.T, B.rank, B.world, B.dev, B.sync, B.ncpu, B.ncpu_affinity, B.cpu_quota, B.t_gen)
     B.setup_gather()
-    B.leg_headline()                          # `value`
-    single = B.leg_single_stream()            # `value_single_stream`
-    seq_kern, seq_ms, seq_ms_plain = B.leg_one_at_a_time()  # `roofline`'s launch durations
-    bursty = B.leg_bursty()
+    B.leg_headline()                          # `value` (and --dump-outputs)
+    # everything below the headline figure only with --full: a plain run sets up, warms up, times its steps and prints the line
+    full = args.full
+    single = B.leg_single_stream() if full else None            # `value_single_stream`
+    seq_kern, seq_ms, seq_ms_plain = B.leg_one_at_a_time() if full else (None, None, None)  # `roofline`'s launch durations
+    bursty = B.leg_bursty() if full else None
     if B.rank != 0:
         B.shutdown()
         return
 
     C, T, F, world = B.C, B.T, B.F, B.world
     value = C * T * world * args.steps / B.dt / 1e6
-    roofline = B.roofline(value, seq_kern, seq_ms, single, seq_ms_plain)
-    h2d = B.leg_h2d()
-    config2 = B.leg_config2()
+    roofline = B.roofline(value, seq_kern, seq_ms, single, seq_ms_plain) if full else None
+    h2d = B.leg_h2d() if full else None
+    config2 = B.leg_config2() if full else None
 
     # the oracle over (as many as fit the time of) the channels of the step: its throughput is the cpu_baseline, its RECORDS are compared, all of
     # them, with the last timed step's — a mismatch is printed in the line and is the exit code
     kept, parity_all, parity_all_channels = {}, None, 0
-    cpu = cpu_baseline(args, B.ol, B.x, C, T, B.ncpu, B.ncpu_affinity, B.cpu_quota, chain=True, keep=kept) if (args.cpu_seconds > 0 and not B.multi) else None
+    cpu = cpu_baseline(args, B.ol, B.x, C, T, B.ncpu, B.ncpu_affinity, B.cpu_quota, chain=True, keep=kept) if (full and args.cpu_seconds > 0 and not B.multi) else None
     if kept:
         parity_all_channels = int(kept["channels"])
         got = B.recs[B.recs["channel"] < parity_all_channels]
@@ -848,7 +874,7 @@ def main():
                    "parallelism": f"channels sharded contiguously over {world} GPU(s), global channel ids", "gather": B.gather_kind,
                    "steps_in_flight": F, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "hw_queue_advice": int(B.ctx.lib.m17hip_advice(B.ctx.h)), "prewarm_steps": args.prewarm, "batches": "pipelined" if args.stagger else "launched and waited for in groups",
                    "gathered_set_ordered_and_unique": B.gathered_ok, "tune": B.tuned or None,
-                   "redo_policy": "library default (m17hip_tune key 20 = 0: beside K5)"},
+                   "redo_policy": "library default (m17hip_tune key 20 = 0: beside K5)", "full": full},
         "single_stream": single,
         "value_with_h2d": h2d["value_with_h2d"] if h2d else None, "h2d": h2d,
         "roofline": roofline, "cpu_baseline": cpu, "config2": config2, "bursty": bursty,
@@ -863,6 +889,28 @@ def main():
     if B.parity is False or parity_all is False or (single and single.get("parity_vs_oracle_3_runs_first_channels") is False) or \
             (bursty and bursty.get("parity_vs_oracle_first_channels") is False) or (config2 and config2.get("outputs_bit_exact_first_channels") is False):
         sys.exit(3)   # a fast result that differs from the reference's is not a result
+
+
+DUMP_SEED = 20260101
+DUMP_CHANNELS = 256          # channels whose records --dump-outputs writes field for field (a fixed, seeded sample of the step's channels)
+DUMP_MAX_RECORDS = 250000    # x (8 x 8 + 32 x 4) bytes = 48 MB at most: with the per-channel counts the dump stays under 64 MB
+RECORD_FIELDS = ("channel", "seq", "sample_pos", "cost", "frame_type", "sync_type", "len", "flags")
+
+
+def dump_outputs(d, recs, n_channels):
+    """--dump-outputs DIR: the frame records one step delivered (m17hip.FRAME_REC), as float arrays two builds can be compared by element for element.
+      frames_per_channel.npy  float64 [n_channels]        records of every channel of the step
+      sampled_channels.npy    float64 [<= 256]            the channels sampled (seeded, the same for every run with the same channel count)
+      frame_fields.npy        float64 [n, 8]              RECORD_FIELDS of every record of the sampled channels, in delivery order
+      frame_payload.npy       float32 [n, 32]             the 32 payload bytes of the same records"""
+    os.makedirs(d, exist_ok=True)
+    counts = np.bincount(recs["channel"].astype(np.int64), minlength=n_channels).astype(np.float64)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_channels, size=min(n_channels, DUMP_CHANNELS), replace=False))
+    sel = recs[np.isin(recs["channel"], pick)][:DUMP_MAX_RECORDS]
+    np.save(os.path.join(d, "frames_per_channel.npy"), counts)
+    np.save(os.path.join(d, "sampled_channels.npy"), pick.astype(np.float64))
+    np.save(os.path.join(d, "frame_fields.npy"), np.stack([sel[f].astype(np.float64) for f in RECORD_FIELDS], axis=1).reshape(-1, len(RECORD_FIELDS)))
+    np.save(os.path.join(d, "frame_payload.npy"), sel["payload"].astype(np.float32).reshape(-1, 32))
 
 
 def cpu_baseline(args, ol, x, C, T, ncpu, ncpu_affinity, cpu_quota, chain, keep=None):
@@ -964,7 +1012,7 @@ def bench_front(args, ctx, ol, x, C, T, rank, world, dev, sync, ncpu, ncpu_affin
         ms, n = ctx.timing_get(name)
         kern[name] = {"ms_avg": (ms / n) if n else None, "launches": n, "ms_per_step": ms / args.steps}
     parity = None
-    if rank == 0 and args.parity_channels > 0:   # soft outputs: north star asks 1e-5 relative; they are bit-exact
+    if rank == 0 and args.full and args.parity_channels > 0:   # soft outputs: north star asks 1e-5 relative; they are bit-exact
         k = min(4, C)
         n = min(T, 48000)
         ctx2 = type(ctx)(k, n)
@@ -987,7 +1035,7 @@ def bench_front(args, ctx, ol, x, C, T, rank, world, dev, sync, ncpu, ncpu_affin
                 "kernel_ms": {k: round(v["ms_per_step"], 4) for k, v in kern.items()},
                 "chain_achieved_GBs": round(FRONT_BYTES * C * T * args.steps / dt / 1e9 / world, 2),
                 "chain_frac": round(FRONT_BYTES * C * T * args.steps / dt / 1e9 / world / HBM_PEAK_GBS, 6)}
-    cpu = cpu_baseline(args, ol, x, C, T, ncpu, ncpu_affinity, cpu_quota, chain=False) if (args.cpu_seconds > 0 and world == 1) else None
+    cpu = cpu_baseline(args, ol, x, C, T, ncpu, ncpu_affinity, cpu_quota, chain=False) if (args.full and args.cpu_seconds > 0 and world == 1) else None
     print(json.dumps({
         "metric": "Msamples/s through FIR + correlator (48 kSPS 4-FSK in -> matched-filter output, limit, 4 sync correlations)",
         "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

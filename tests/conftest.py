@@ -1,7 +1,10 @@
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # before anything initialises the HIP runtime (include/m17hip.h, m17hip_advice)
+# before anything initialises the HIP runtime (include/m17hip.h, m17hip_advice): the suite's own value, 16, also over an inherited smaller one
+# (with fewer than 8, m17hip_ctx_create refuses; a larger value given from outside is kept)
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 import pytest
 

@@ -111,3 +111,42 @@ def test_ranks_that_never_end_are_stopped_after_the_launch_timeout_and_killed_if
     out, err = capfd.readouterr()
     assert code == 124 and out == "" and 11 < time.time() - t0 < 40
     assert "still running after --launch-timeout 2 s" in err
+
+
+def test_dump_outputs_writes_float_arrays_of_a_fixed_channel_sample(tmp_path, monkeypatch):
+    """--dump-outputs (bench.dump_outputs): float arrays only; every channel's record count; every field of the records of a seeded sample of
+    channels, the same sample for the same channel count; the records cut at DUMP_MAX_RECORDS, so that a dump stays under 64 MB."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "m17-cxx-demod_amd"))
+    import m17hip
+    b = _bench_module()
+    C, k = 4096, 40
+    rng = np.random.default_rng(7)
+    recs = np.zeros(C * k, dtype=m17hip.FRAME_REC)
+    recs["channel"] = np.repeat(np.arange(C), k)
+    recs["seq"] = np.tile(np.arange(k), C)
+    recs["sample_pos"] = recs["seq"].astype(np.uint64) * 1920 + 3072 + (1 << 40)
+    recs["cost"] = rng.integers(-1, 50, recs.size)
+    recs["frame_type"] = rng.integers(0, 6, recs.size)
+    recs["payload"] = rng.integers(0, 256, (recs.size, 32))
+    recs = recs[recs["channel"] % 7 != 3]          # channels without records count 0
+    b.dump_outputs(str(tmp_path / "a"), recs, C)
+    b.dump_outputs(str(tmp_path / "b"), recs, C)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["frame_fields.npy", "frame_payload.npy", "frames_per_channel.npy", "sampled_channels.npy"]
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], np.load(tmp_path / "b" / f)), f
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    counts = a["frames_per_channel.npy"]
+    assert counts.shape == (C,) and np.array_equal(counts, np.where(np.arange(C) % 7 != 3, k, 0))
+    pick = a["sampled_channels.npy"].astype(np.int64)
+    assert pick.size == b.DUMP_CHANNELS and np.all(np.diff(pick) > 0) and pick.max() < C
+    sel = recs[np.isin(recs["channel"], pick)]
+    assert a["frame_fields.npy"].shape == (sel.size, 8) and np.array_equal(a["frame_payload.npy"], sel["payload"].astype(np.float32))
+    for i, f in enumerate(b.RECORD_FIELDS):
+        assert np.array_equal(a["frame_fields.npy"][:, i], sel[f].astype(np.float64)), f
+    monkeypatch.setattr(b, "DUMP_MAX_RECORDS", 1000)
+    b.dump_outputs(str(tmp_path / "c"), recs, C)
+    assert np.load(tmp_path / "c" / "frame_fields.npy").shape == (1000, 8) and np.load(tmp_path / "c" / "frame_payload.npy").shape == (1000, 32)
+    assert np.array_equal(np.load(tmp_path / "c" / "sampled_channels.npy"), a["sampled_channels.npy"])

@@ -422,13 +422,45 @@ def test_bench_multi_gpu_code_path_with_one_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29617", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-gather", "--gather", "cabi", "--channels", "64", "--samples", "48000",
-                        "--steps", "2", "--warmup", "1", "--prewarm", "2", "--cpu-seconds", "0", "--h2d-steps", "0", "--parity-channels", "8"],
+                        "--steps", "2", "--warmup", "1", "--prewarm", "2", "--cpu-seconds", "0", "--h2d-steps", "0", "--parity-channels", "8", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])   # (RCCL prints its version banner on stdout too)
     assert line["n_gpus"] == 1 and line["config"]["gather"].startswith("m17hip_gather_frames_device")
     assert line["config"]["gathered_set_ordered_and_unique"] is True and line["config"]["parity_vs_oracle_first_channels"] is True
     assert line["value"] > 0 and line["value_single_stream"] > 0
+
+
+def test_bench_plain_run_dumps_the_records_of_its_last_timed_step(tmp_path):
+    """bench.py without --full: the headline keys, --steps timed steps and nothing of the --full legs.  --dump-outputs writes the records the last
+    timed step delivered: the same files from a second run with the same arguments, and the oracle's records of the same synthetic input."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    C, T, steps = 64, 48000, 3
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--channels", str(C), "--samples", str(T), "--steps", str(steps),
+                            "--warmup", "1", "--prewarm", "2", "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Msamples/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["config"]["full"] is False
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["single_stream"] is None and line["config2"] is None
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["frame_fields.npy", "frame_payload.npy", "frames_per_channel.npy", "sampled_channels.npy"]
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]), f
+    assert a["sampled_channels.npy"].tolist() == list(range(C))   # (fewer channels than the sample size: all of them)
+    assert int(a["frames_per_channel.npy"].sum()) == line["config"]["frames_decoded_per_step"] == a["frame_fields.npy"].shape[0] > 0
+    p = ol.gen_params(seed=20260101, kind=-1, n_frames=T // 1920 - 6, lead_in=3072, noise_sigma=600.0, tail_sigma=600.0, lead_sigma=40000.0, total=T)
+    er, ec, _ = ol.demod_batch(ol.generate_batch(p, C, T), cap=2 * (T // 1920 + 2) + 4)
+    exp = np.concatenate([er[c, : ec[c]] for c in range(C)])
+    assert np.array_equal(a["frame_fields.npy"], np.stack([exp[f].astype(np.float64) for f in ("channel", "seq", "sample_pos", "cost", "frame_type",
+                                                                                                  "sync_type", "len", "flags")], axis=1))
+    assert np.array_equal(a["frame_payload.npy"], exp["payload"].astype(np.float32))
 
 
 _WORKER = r"""

@@ -6,7 +6,7 @@ A=$1; B=$2; R=${3:-2}
 out=gpurun_out/r6/ab_$(basename $A .so)_vs_$(basename $B .so).txt; mkdir -p gpurun_out/r6; : > $out
 for r in $(seq $R); do
   for lib in $A $B; do
-    M17HIP_LIB=$PWD/$lib python3 bench.py --bursty-steps 0 --config2-steps 0 --h2d-steps 0 --cpu-seconds 0 --parity-channels 16 2>/dev/null | python3 -c "
+    M17HIP_LIB=$PWD/$lib python3 bench.py --full --bursty-steps 0 --config2-steps 0 --h2d-steps 0 --cpu-seconds 0 --parity-channels 16 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$lib', 'value', j['value'], 'ms', j['ms_per_step'], 'single', j['value_single_stream'], j['ms_per_step_single_stream'], 'one-at-a-time', j['roofline']['ms_per_step'], 'parity', j['config']['parity_vs_oracle_first_channels'], j['single_stream']['parity_vs_oracle_3_runs_first_channels'])" >> $out
