@@ -107,7 +107,9 @@ int m17hip_replay_drops(m17hip_ctx* ctx, uint64_t* count);
  * PyTorch, wraps this one: torch.cuda.ExternalStream(handle)); results fetched into host memory are complete when the fetch returns, as ever. */
 int m17hip_get_stream(m17hip_ctx* ctx, void** hip_stream);
 /* For hosts that insist: launch all work of this context on `hip_stream` instead (a hipStream_t; NULL = the default stream — what a context ran on
- * up to round 5 when this was not called).  The library's main stream stays with the context, idle.  M17HIP_STREAM_SETS=0 in the environment restores
+ * up to round 5 when this was not called).  The library's main stream stays with the context, idle.  The switch is ordered: what the context queues
+ * on `hip_stream` afterwards starts behind everything it had queued before (a run still in flight, its payload work, the reset kernels of
+ * m17hip_ctx_create), so it may be called at any time between calls.  M17HIP_STREAM_SETS=0 in the environment restores
  * the older behaviour altogether (streams per context, destroyed with it, main = the default stream): a diagnostic, not a deployment mode. */
 int m17hip_set_stream(m17hip_ctx* ctx, void* hip_stream);
 

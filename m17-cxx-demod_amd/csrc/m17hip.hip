@@ -147,6 +147,7 @@ struct m17hip_ctx {
     bool streams() const { return copy && xstage; }   // input has been staged (stage_prepare): the copy stream is at work (a parked set may bring one along — that alone changes nothing)
     hipStream_t pay() const { return streams() ? copy : stream; }
     hipEvent_t ev_dst = nullptr;      // the caller's main-stream work on a device destination is done (a fetch of the LATEST run orders itself behind it)
+    hipEvent_t ev_switch = nullptr;   // m17hip_set_stream: what was queued before the switch (the new main stream waits for it)
     uint32_t* overflow = nullptr;     // [8]: four words per record set
     uint64_t* rec_offsets = nullptr;  // exclusive prefix of rec_count (+ total at [C]): scratch of a compaction (payload stream)
     FrameRec* compact = nullptr;      // lazily sized
@@ -914,7 +915,7 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     if (hipFuncSetAttribute((const void*)decode_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (92 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipMemset(c->overflow, 0, 32) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);   // (default-stream work of the creation is through before the context's own streams start)
-    for (hipEvent_t* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst})
+    for (hipEvent_t* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch})
         if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
     { std::lock_guard<std::mutex> lk(g_runs.mu); c->seen_overlap = g_runs.overlaps; g_runs.ctxs.push_back(c); }   // (a new context has seen no overlap yet)
     *out = c;
@@ -951,6 +952,7 @@ void m17hip_ctx_destroy(m17hip_ctx* c)
         if (c->copy && !c->foreign_streams[3]) hipStreamDestroy(c->copy);
     }
     if (c->ev_dst) hipEventDestroy(c->ev_dst);
+    if (c->ev_switch) hipEventDestroy(c->ev_switch);
     for (hipEvent_t e : {c->ev_copy, c->ev_in_ready, c->ev_end[0], c->ev_end[1], c->ev_mark, c->ev_tail, c->sets[0].done, c->sets[1].done, c->sets[0].chain, c->sets[1].chain})
         if (e) hipEventDestroy(e);
     for (int q = 0; q < 2; ++q)
@@ -976,7 +978,18 @@ int m17hip_set_stream(m17hip_ctx* c, void* hip_stream)
 {
     if (!c) return M17HIP_EINVAL;
     GUARD(c);
-    c->stream = (hipStream_t)hip_stream;
+    // an ordered switch: the new stream starts behind everything queued so far on the old one (a run in flight, its payload work, the reset
+    // kernels of m17hip_ctx_create) and on the payload stream where that is another (the copy stream of a context that streams)
+    const hipStream_t to = (hipStream_t)hip_stream;
+    if (to != c->stream) {
+        HIPCHK(c, hipEventRecord(c->ev_switch, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(to, c->ev_switch, 0));
+        if (c->pay() != c->stream) {
+            HIPCHK(c, hipEventRecord(c->ev_switch, c->pay()));
+            HIPCHK(c, hipStreamWaitEvent(to, c->ev_switch, 0));
+        }
+    }
+    c->stream = to;
     return M17HIP_OK;
 }
 
@@ -1004,6 +1017,8 @@ static int stage_prepare(m17hip_ctx* c)
         if (fresh_y) HIPCHK(c, hipMemsetAsync(c->yalt, 0, (size_t)c->maxC * c->ypitch * sizeof(float), c->copy));
         if (!c->ev_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
         if (!c->ev_in_ready) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in_ready, hipEventDisableTiming));
+        // (from here on the copy stream is the PAYLOAD stream: behind the last reset, as m17hip_demod_reset orders the payload stream it sees)
+        HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_mark, 0));
         if ((r = alloc((void**)&c->xstage, (size_t)c->maxC * c->xpitch * sizeof(int16_t)))) return r;   // last: its presence says "all of it is there"
     }
     return M17HIP_OK;
@@ -1622,6 +1637,16 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
     return M17HIP_OK;
 }
 
+// A fetch reads what a run and its payload work wrote, on the payload stream of NOW — which need not be the stream that work went to: a
+// context that ran in place made it on the main stream, its first staged input moves the payload stream to the copy stream, and
+// m17hip_set_stream moves the main one.  So the fetch orders the payload stream behind the run itself: its `done`, or its `chain` while
+// its payload work is still to be queued (flush_payload queues it behind `chain`).  (An event that was never recorded: no wait.)
+static int pay_after(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
+{
+    HIPCHK(c, hipStreamWaitEvent(c->pay(), rs.pending ? rs.chain : rs.done, 0));
+    return M17HIP_OK;
+}
+
 // BASELINE configs[1] as ONE call: matched filter, limit filter and the four correlations of `samples` samples per channel, pipelined in time.
 // The limit filter is one dependent chain per channel over the whole run (12 ns per sample) and is what the call lasts; the matched filter
 // (K1) of piece k + 1 and the correlations of piece k run beside the chain's piece k on two side streams, the chain's state (four history
@@ -1961,6 +1986,7 @@ static int compact_into(m17hip_ctx* c, FrameRec* dev_out, uint64_t cap, uint64_t
     m17hip_ctx::RecSet* rs = selected_set(c);
     if (!rs) return M17HIP_ESTATE;
     if (int fr = flush_payload(c, true)) return fr;
+    if (int fr = pay_after(c, *rs)) return fr;   // (behind the selected run wherever its payload work was queued)
     const uint32_t C = rs->C;
     if (dev_out && dev_out != c->compact && c->sel_back == 0 && c->pay() != c->stream) {
         // a device destination of the caller's: whatever the caller queued on the main stream for it (a fill, its previous consumer) comes first —
@@ -2096,6 +2122,9 @@ int m17hip_bert_stats(m17hip_ctx* c, m17_bert_stat* stats_host, uint32_t C)
     GUARD(c);
     if (!c->bert) return M17HIP_ESTATE;
     if (int fr = flush_payload(c)) return fr;
+    for (const auto& rs : c->sets)   // (every run's consumer adds to the state: behind both runs, wherever their payload work was queued)
+        if (rs.valid)
+            if (int fr = pay_after(c, rs)) return fr;
     std::vector<BertState> tmp(C);
     HIPCHK(c, hipMemcpyAsync(tmp.data(), c->bert_state, (size_t)C * sizeof(BertState), hipMemcpyDeviceToHost, c->pay()));   // (behind the consumers of the runs queued so far)
     HIPCHK(c, hipStreamSynchronize(c->pay()));
@@ -2139,6 +2168,8 @@ int m17hip_packets_fetch(m17hip_ctx* c, m17_packet_rec* recs_host, uint32_t capa
     const int ps = c->cur ^ (int)(c->sel_back & 1u);   // the packets completed by the SELECTED run (m17hip_frames_select)
     if (c->sel_back && !c->sets[ps].valid) return M17HIP_ESTATE;
     if (int fr = flush_payload(c, true)) return fr;
+    if (c->sets[ps].valid)   // (the selected run's store, wherever its consumer was queued)
+        if (int fr = pay_after(c, c->sets[ps])) return fr;
     uint32_t total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, c->pkt_count2 + ps, 4, hipMemcpyDeviceToHost, c->pay()));
     HIPCHK(c, hipStreamSynchronize(c->pay()));
@@ -2306,7 +2337,8 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
     const bool is_root = m->rank == root;
     auto hip_code = [&](hipError_t e) { c->last_hip = (int)e; return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP; };
     auto comm_failed = [&](ncclResult_t q) { comm_give_up(m, (int)q); return M17HIP_ECOMM; };   // a collective call itself failed: nothing more can be agreed on
-    // 1. this rank's records, dense and (channel, seq)-ordered, in the context's compaction buffer
+    // 1. this rank's records, dense and (channel, seq)-ordered, in the context's compaction buffer (compact_into orders the payload stream
+    //    behind the selected run: every transfer of the records below is queued behind that)
     uint64_t mine = 0;
     int local = selected_set(c) ? M17HIP_OK : M17HIP_ESTATE;
     bool overflow = false;
