@@ -249,6 +249,19 @@ typedef struct m17_synth_params {
     double lead_sigma, noise_sigma, dc_offset, gain, tail_sigma;   /* LSB */
 } m17_synth_params;
 int m17hip_synth_i16(m17hip_ctx* ctx, const m17_synth_params* params, uint32_t channels, uint32_t samples, uint32_t chan0);
+/* An impairment SWEEP in one synthesis (BASELINE config 5, SURVEY §8(d): AWGN, DC offset = FM frequency offset, gain): channel c
+ * takes point p = (chan0 + c) % n_points of `points` — interleaved, so that every contiguous shard carries every point.  Row c is,
+ * int16 for int16, row c of m17hip_synth_i16(ctx, base', channels, samples, chan0) with base' = *base and its noise_sigma, tail_sigma,
+ * dc_offset and gain replaced by points[p]; every other field (kind < 0 mixed, phase, lead_in, invert, n_preamble, lead_sigma) and the
+ * per-channel seeding come from `base`, so a shard synthesised with its global chan0 is bitwise the matching rows of the whole set.
+ * Tuning knob 16 (staging) applies as to m17hip_synth_i16.  M17HIP_EINVAL for n_points == 0 or above M17HIP_MAX_SWEEP_POINTS, points
+ * == NULL, a non-finite or negative sigma, a non-finite dc_offset or gain, and whatever m17hip_synth_i16 refuses. */
+typedef struct m17_impairment {   /* one point of a sweep grid */
+    double noise_sigma, tail_sigma, dc_offset, gain;   /* LSB, LSB, LSB, x */
+} m17_impairment;                 /* 32 bytes */
+#define M17HIP_MAX_SWEEP_POINTS 4096u
+int m17hip_synth_sweep_i16(m17hip_ctx* ctx, const m17_synth_params* base, const m17_impairment* points, uint32_t n_points,
+                           uint32_t channels, uint32_t samples, uint32_t chan0);
 /* Read the input slab back: out[channels][samples] (row pitch in samples). */
 int m17hip_download_i16(m17hip_ctx* ctx, int16_t* host, uint32_t channels, uint32_t samples, size_t pitch);
 
@@ -263,6 +276,21 @@ typedef struct m17_bert_stat {
     uint32_t frames;  /* BERT frames seen */
 } m17_bert_stat;
 int m17hip_bert_stats(m17hip_ctx* ctx, m17_bert_stat* stats_host, uint32_t channels);
+
+/* One 32-byte word per channel for an impairment sweep (m17hip_synth_sweep_i16): m17hip_bert_stats and the `evm` field of
+ * m17hip_diag_fetch in one pass on the device and ONE copy.  Replaces, per channel, PRBS9::bits() / errors() / sync() (Util.h:320-413),
+ * the count of BERT frames and SymbolEvm::evm() (SymbolEvm.h:31-51).  Ordered as those two calls are: behind the latest run's last EVM
+ * fold and the payload work of every run whose record set is still there (wherever it was queued), whatever the caller has queued
+ * since.  M17HIP_ESTATE if BERT statistics are off (m17hip_tune key 6) or no run has been made since the last m17hip_demod_reset;
+ * M17HIP_EOVERFLOW when m17hip_diag_fetch would return it — every word is still written, with flag bit 0 cleared. */
+typedef struct m17_chan_stat {
+    uint32_t channel;   /* channel_base + local index (m17hip_set_channel_base) */
+    uint32_t point;     /* channel % n_points */
+    uint32_t bits, errors, synced, frames;   /* = m17_bert_stat */
+    float    evm;       /* = m17_diag.evm */
+    uint32_t flags;     /* bit 0: evm is valid (no deferred-EVM overflow, m17hip_tune key 18); other bits 0 */
+} m17_chan_stat;        /* 32 bytes */
+int m17hip_sweep_stats(m17hip_ctx* ctx, uint32_t n_points, m17_chan_stat* host, uint32_t channels);
 
 /* Payload consumer: packet reassembly — decode_packet (apps/m17-demod.cpp:207-253) with the per-transmission
  * reset of dump_lsf (:154-155), per channel, over the packet frame records of every run since the last m17hip_demod_reset:
@@ -346,6 +374,13 @@ int m17hip_gather_frames(m17hip_ctx* ctx, m17hip_comm* comm, int root, m17_frame
 /* Same, with the root's destination in DEVICE memory on the root's GPU (the gathered set stays in HBM for a device-side consumer). */
 int m17hip_gather_frames_device(m17hip_ctx* ctx, m17hip_comm* comm, int root, m17_frame_rec* recs_dev, uint64_t capacity, uint64_t* counts,
                                 uint64_t* total);
+/* The per-channel sweep words of every rank (m17hip_sweep_stats: words the CALLER supplies — a rank may have processed its shard in
+ * several runs) gathered to `root`: mine[n_mine] of each rank land in out_host[capacity] rank after rank — with contiguous shards, global
+ * channel order.  The protocol of m17hip_gather_frames, the same code: counts[nranks] (optional) and *total on every rank, the two
+ * all-gathers and their failure agreement, the root's staging growth, M17HIP_ETRUNC, the deadlines (key 31) and fault injection (key 30;
+ * here 1 = this rank's upload of its words fails). */
+int m17hip_gather_sweep_stats(m17hip_ctx* ctx, m17hip_comm* comm, int root, const m17_chan_stat* mine, uint64_t n_mine,
+                              m17_chan_stat* out_host, uint64_t capacity, uint64_t* counts, uint64_t* total);
 
 /* Knobs of a context (never results).  M17HIP_EINVAL for a key the library does not have.
  * key 3: samples per segment a run is processed in (default 48000; 0 = one segment): the granule of the K2 / K5 alternation — shorter
@@ -398,13 +433,14 @@ int m17hip_gather_frames_device(m17hip_ctx* ctx, m17hip_comm* comm, int root, m1
  * key 18 (tests): floats per channel row of deferred EVM operations (key 17), 0 (default) = what a run of max_samples can produce; with a
  *        smaller row a channel outruns it, the operations beyond are dropped and m17hip_diag_fetch / m17hip_diag_log_fetch return
  *        M17HIP_EOVERFLOW (every diagnostic field but `evm` is still right; the frame records are not affected).
- * key 16: 1 = m17hip_upload_i16, m17hip_upload_i16_device and m17hip_synth_i16 write the context's STAGING slab (as
+ * key 16: 1 = m17hip_upload_i16, m17hip_upload_i16_device, m17hip_synth_i16 and m17hip_synth_sweep_i16 write the context's STAGING slab (as
  *        m17hip_upload_i16_async does, but complete when they return) and stage it for the next run; 0 (default) = the current slab.
- * key 30 (tests): fault injection for m17hip_gather_frames*: 1 = this rank's compaction fails inside the call, 2 = the root's staging
+ * key 30 (tests): fault injection for m17hip_gather_frames* and m17hip_gather_sweep_stats: 1 = this rank's compaction (its upload of
+ *        the words) fails inside the call, 2 = the root's staging
  *        allocation fails, 3 = this rank's word of the second exchange cannot be written (and, on the root, the staging is grown whether
  *        it has to be or not), 4 = this rank cannot read the first exchange, 5 = this rank cannot read the second exchange; 0 = none.
  *        Under 1-4 every rank makes all its collective calls and all return from the same call; 5 is the case key 31 bounds.
- * key 31: deadline in milliseconds of every wait inside m17hip_gather_frames* (default 120000, 0 = none).
+ * key 31: deadline in milliseconds of every wait inside m17hip_gather_frames* and m17hip_gather_sweep_stats (default 120000, 0 = none).
  * The measurement build of the library (make -C m17-cxx-demod_amd/csrc tools -> libm17hip_tools.so, -DM17_TOOLS; tools/ only) adds
  * key 1 / key 19 (section timers / per-wave working times of the sequential kernel -> m17hip_debug_counters) and the schedule
  * experiments 4, 5, 12, 14, 21, 25 (csrc/m17hip.hip, m17hip_tune). */

@@ -254,12 +254,15 @@ __device__ inline int16_t mod_sat16(double v)
     return (int16_t)r;
 }
 
-__global__ __launch_bounds__(256) void mod_shape_kernel(ModParams base, uint32_t C, uint32_t T, uint32_t chan0, const int8_t* sym, size_t sym_pitch,
-                                                        const uint32_t* nsym_in, int16_t* x, size_t xpitch)
+// One point of an impairment sweep grid: layout of m17_impairment (include/m17hip.h)
+struct ModImpair {
+    double noise_sigma, tail_sigma, dc_offset, gain;
+};
+
+// Sample n of channel c (global id chan0 + c) of the synthesised slab, under the impairments `im` (every other field from `base`)
+__device__ inline int16_t mod_shape_sample(const ModParams& base, const ModImpair& im, uint32_t c, uint32_t n, uint32_t chan0, const int8_t* sym,
+                                           size_t sym_pitch, const uint32_t* nsym_in)
 {
-    const uint32_t c = blockIdx.y;
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C || n >= T) return;
     const uint64_t cc = (uint64_t)chan0 + c;
     const uint64_t seed = mod_channel_seed(base.seed, cc);
     const int kind = base.kind < 0 ? (int)(cc % 2) : base.kind;
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(256) void mod_shape_kernel(ModParams base, uint32_t
     if (kind == 3) phase = 0;
     const uint32_t start = (uint32_t)base.lead_in + phase;
     const uint64_t ns = mod_splitmix64(seed ^ 0x5EEDull);
-    const double tail_sigma = base.noise_sigma > base.tail_sigma ? base.noise_sigma : base.tail_sigma;
+    const double tail_sigma = im.noise_sigma > im.tail_sigma ? im.noise_sigma : im.tail_sigma;
     const bool in_burst = kind != 3 && n >= start && n < start + nburst + 150u;
     double v;
     if (n < (uint32_t)base.lead_in) {
@@ -290,18 +293,41 @@ __global__ __launch_bounds__(256) void mod_shape_kernel(ModParams base, uint32_t
         double b = acc * 7168.0;
         b = b * (base.invert ? -1.0 : 1.0);
         const double s = (double)(int16_t)(int32_t)b;   // the reference casts the shaped sample to int16 (truncation)
-        double t = s * base.gain;
-        t = t + base.dc_offset;
-        const double q = mod_unit_noise(ns, n) * base.noise_sigma;
+        double t = s * im.gain;
+        t = t + im.dc_offset;
+        const double q = mod_unit_noise(ns, n) * im.noise_sigma;
         v = t + q;
     } else {
-        const double q = mod_unit_noise(ns, n) * (n < start ? base.noise_sigma : tail_sigma);
-        v = base.dc_offset + q;
+        const double q = mod_unit_noise(ns, n) * (n < start ? im.noise_sigma : tail_sigma);
+        v = im.dc_offset + q;
     }
     int16_t o = mod_sat16(v);
     // never emit exact zeros outside the burst when there is no noise at all (NaN poisoning of the DCD)
-    if (base.noise_sigma == 0.0 && tail_sigma == 0.0 && o == 0 && !in_burst) o = (int16_t)((mod_splitmix64(ns + n) & 1ull) ? 1 : -1);
-    x[(size_t)c * xpitch + XPRE + n] = o;
+    if (im.noise_sigma == 0.0 && tail_sigma == 0.0 && o == 0 && !in_burst) o = (int16_t)((mod_splitmix64(ns + n) & 1ull) ? 1 : -1);
+    return o;
+}
+
+__global__ __launch_bounds__(256) void mod_shape_kernel(ModParams base, uint32_t C, uint32_t T, uint32_t chan0, const int8_t* sym, size_t sym_pitch,
+                                                        const uint32_t* nsym_in, int16_t* x, size_t xpitch)
+{
+    const uint32_t c = blockIdx.y;
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C || n >= T) return;
+    const ModImpair im{base.noise_sigma, base.tail_sigma, base.dc_offset, base.gain};
+    x[(size_t)c * xpitch + XPRE + n] = mod_shape_sample(base, im, c, n, chan0, sym, sym_pitch, nsym_in);
+}
+
+// m17hip_synth_sweep_i16: the same samples, channel c under point (chan0 + c) % n_points of the grid — uniform over the block (blockIdx.y is
+// the channel), read once by it
+__global__ __launch_bounds__(256) void mod_shape_grid_kernel(ModParams base, const ModImpair* points, uint32_t n_points, uint32_t C, uint32_t T,
+                                                             uint32_t chan0, const int8_t* sym, size_t sym_pitch, const uint32_t* nsym_in, int16_t* x,
+                                                             size_t xpitch)
+{
+    const uint32_t c = blockIdx.y;
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C || n >= T) return;
+    const ModImpair im = points[((uint64_t)chan0 + c) % n_points];
+    x[(size_t)c * xpitch + XPRE + n] = mod_shape_sample(base, im, c, n, chan0, sym, sym_pitch, nsym_in);
 }
 
 }  // namespace m17

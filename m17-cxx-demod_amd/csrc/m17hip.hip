@@ -71,7 +71,7 @@ struct m17hip_ctx {
     int slot = 0;                     // slab pair the pointers xbuf / ybuf / hbuf / dcd_table name
     bool staged = false, staged_h2d = false;
     bool stage_inputs = false;        // tuning knob 16: the in-place producers write the staging slab
-    void* synth_scratch = nullptr;    // symbol staging of m17hip_synth_i16
+    void* synth_scratch = nullptr;    // symbol staging of m17hip_synth_i16 (and the impairment grid of m17hip_synth_sweep_i16)
     size_t synth_bytes = 0;
     uint32_t runT = 0;                // samples of the latest run
     hipEvent_t ev_tail = nullptr;     // the latest run has carried its tails into its prefixes (K5 is done with its last segment)
@@ -94,6 +94,8 @@ struct m17hip_ctx {
     uint32_t* dropped = nullptr;      // [maxC] K5: the segment dropped the speculation
     void* bert_state = nullptr;       // [maxC] BertState (tuning knob 6)
     bool bert = false;
+    void* chan_words = nullptr;       // [chan_words_cap] ChanStat: m17hip_sweep_stats' words on their way out / a rank's words on their way into m17hip_gather_sweep_stats (payload stream)
+    uint64_t chan_words_cap = 0;
     void* pkt_state = nullptr;        // [maxC] PacketState (tuning knob 7)
     void* pkt_recs2[2] = {nullptr, nullptr};        // [pkt_cap] PacketRec: packets completed by a run, one store per record set
     uint32_t* pkt_count2 = nullptr;   // [2]
@@ -104,9 +106,9 @@ struct m17hip_ctx {
     uint32_t* diag_count = nullptr;   // [maxC]
     uint32_t diag_cap = 0;
     uint32_t kalman_order = 3;        // evaluation order of the Kalman updates (m17hip_set_kalman_order)
-    int gather_fault = 0;             // tuning knob 30 (tests): 1 = this rank's compaction fails inside the gather, 2 = the root's staging allocation fails, 3 = its word of exchange 2 is not written,
+    int gather_fault = 0;             // tuning knob 30 (tests): 1 = this rank's compaction (m17hip_gather_sweep_stats: its upload) fails inside the gather, 2 = the root's staging allocation fails, 3 = its word of exchange 2 is not written,
                                       // 4 = it cannot read exchange 1, 5 = it cannot read exchange 2
-    uint32_t gather_timeout_ms = 120000;   // tuning knob 31: bound of every wait inside m17hip_gather_frames (0 = none)
+    uint32_t gather_timeout_ms = 120000;   // tuning knob 31: bound of every wait inside m17hip_gather_frames / m17hip_gather_sweep_stats (0 = none)
     uint32_t channel_base = 0;        // global id of channel 0 (m17hip_set_channel_base): records carry channel_base + c
     uint32_t front_first = 0;         // tuning knob 12: segments of K1 that must be complete before the first K5 starts (0 = its own only)
     int redo_form = 0;                // tuning knob 20: the replay's redo beside K5, state only (0, default), or in front of K5 with the history stored (1)
@@ -148,6 +150,7 @@ struct m17hip_ctx {
     hipStream_t pay() const { return streams() ? copy : stream; }
     hipEvent_t ev_dst = nullptr;      // the caller's main-stream work on a device destination is done (a fetch of the LATEST run orders itself behind it)
     hipEvent_t ev_switch = nullptr;   // m17hip_set_stream: what was queued before the switch (the new main stream waits for it)
+    hipEvent_t ev_fetch = nullptr;    // m17hip_sweep_stats: the main stream's last EVM fold (the payload stream waits for it)
     uint32_t* overflow = nullptr;     // [8]: four words per record set
     uint64_t* rec_offsets = nullptr;  // exclusive prefix of rec_count (+ total at [C]): scratch of a compaction (payload stream)
     FrameRec* compact = nullptr;      // lazily sized
@@ -210,8 +213,8 @@ struct m17hip_comm {
     uint64_t* words_host = nullptr;   // pinned, [2 + 2 * nranks]: this rank's word pair on its way out, every rank's on the way in — no copy of an exchange ever
                                       // targets memory that a call which ran out of time has already given back
     uint32_t serial = 0;              // gather calls made through this communicator (every rank counts the same)
-    FrameRec* gathered = nullptr;     // root: every rank's records, rank after rank
-    uint64_t gathered_cap = 0;
+    char* gathered = nullptr;         // root: every rank's contribution (frame records, sweep words), rank after rank
+    uint64_t gathered_bytes = 0;
     bool dead = false;                // an exchange did not end in time or a collective call failed: given up, every later call returns M17HIP_ECOMM
 };
 
@@ -509,6 +512,23 @@ __global__ void bert_stats_kernel(const FrameRec* recs, uint32_t rec_cap, const 
     state[c] = b;
 }
 
+// m17hip_sweep_stats: one packed word per channel (layout of m17_chan_stat) from the PRBS9 receiver's state and SymbolEvm's value; one lane per channel
+struct ChanStat { uint32_t channel, point, bits, errors, synced, frames; float evm; uint32_t flags; };
+__global__ void sweep_stats_kernel(const BertState* bert, const SeqState* seq, const uint32_t* ovf, uint32_t C, uint32_t channel_base, uint32_t n_points,
+                                   ChanStat* out)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const BertState& b = bert[c];
+    ChanStat w;
+    w.channel = channel_base + c;
+    w.point = w.channel % n_points;
+    w.bits = b.bit_count; w.errors = b.err_count; w.synced = b.synced; w.frames = b.frames;
+    w.evm = seq[c].cold.diag.evm;
+    w.flags = (ovf[2] | ovf[6]) ? 0u : 1u;   // (deferred EVM operations were dropped: see m17hip_diag_fetch)
+    out[c] = w;
+}
+
 // LinkSetupFrame::decode_callsign + type field + CRC of a batch of LSFs: one lane per frame
 struct LsfInfo { char dst[10], src[10]; uint16_t type; uint8_t crc_ok; uint8_t reserved[9]; };
 __global__ void lsf_info_kernel(const uint8_t* lsf, uint32_t n, LsfInfo* out)
@@ -780,7 +800,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 601; }
+int m17hip_version(void) { return 602; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -915,7 +935,7 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     if (hipFuncSetAttribute((const void*)decode_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (92 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipMemset(c->overflow, 0, 32) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);   // (default-stream work of the creation is through before the context's own streams start)
-    for (hipEvent_t* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch})
+    for (hipEvent_t* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch, &c->ev_fetch})
         if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
     { std::lock_guard<std::mutex> lk(g_runs.mu); c->seen_overlap = g_runs.overlaps; g_runs.ctxs.push_back(c); }   // (a new context has seen no overlap yet)
     *out = c;
@@ -953,6 +973,7 @@ void m17hip_ctx_destroy(m17hip_ctx* c)
     }
     if (c->ev_dst) hipEventDestroy(c->ev_dst);
     if (c->ev_switch) hipEventDestroy(c->ev_switch);
+    if (c->ev_fetch) hipEventDestroy(c->ev_fetch);
     for (hipEvent_t e : {c->ev_copy, c->ev_in_ready, c->ev_end[0], c->ev_end[1], c->ev_mark, c->ev_tail, c->sets[0].done, c->sets[1].done, c->sets[0].chain, c->sets[1].chain})
         if (e) hipEventDestroy(e);
     for (int q = 0; q < 2; ++q)
@@ -961,7 +982,7 @@ void m17hip_ctx_destroy(m17hip_ctx* c)
     void* ptrs[] = {c->xbuf, c->ybuf, c->dcd_table, c->dcd_state, c->seq_state, c->sets[0].recs, c->sets[0].rec_count, c->sets[0].defer_llr,
                     c->sets[1].recs, c->sets[1].rec_count, c->sets[1].defer_llr, c->rec_offsets,
                     c->overflow, c->tables, c->taps, c->taps_skew, c->llr_edges, c->level_gain, c->compact, c->scratch, c->dbg, c->hbuf, c->final_h, c->gate_exp, c->dropped, c->bert_state, c->xstage, c->pkt_state, c->pkt_recs2[0], c->pkt_recs2[1], c->pkt_count2, c->diag_log, c->diag_count, c->defer_hist,
-                    c->yalt, c->halt, c->dcd_alt, c->synth_scratch, c->bnd, c->ev_ops2[0], c->ev_ops2[1], c->ev_cur, c->ev_state, c->truth, c->first_needed};
+                    c->yalt, c->halt, c->dcd_alt, c->synth_scratch, c->chan_words, c->bnd, c->ev_ops2[0], c->ev_ops2[1], c->ev_cur, c->ev_state, c->truth, c->first_needed};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);   // (the context is going away: nothing to report to)
     delete c;
@@ -1112,35 +1133,64 @@ int m17hip_input_alternate(m17hip_ctx* c, uint32_t C, uint32_t T)
     return M17HIP_OK;
 }
 
-int m17hip_synth_i16(m17hip_ctx* c, const m17_synth_params* params, uint32_t C, uint32_t T, uint32_t chan0)
+// m17hip_synth_i16 (points == nullptr: the impairments of `params`) and m17hip_synth_sweep_i16 (channel c under points[(chan0 + c) % n_points])
+static int synth_impl(m17hip_ctx* c, const m17_synth_params* params, const m17_impairment* points, uint32_t n_points, uint32_t C, uint32_t T,
+                      uint32_t chan0)
 {
     if (!c || !params || C == 0 || T == 0 || C > c->maxC || T > c->maxT || params->n_frames < 0 || params->kind > 4) return M17HIP_EINVAL;
     GUARD(c);
     if (c->front_pending) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
     if (params->kind == 4 && (params->n_frames < 1 || params->n_frames > 33)) return M17HIP_EINVAL;   // 5-bit frame numbers
     static_assert(sizeof(ModParams) == sizeof(m17_synth_params), "parameter block layout");
+    static_assert(sizeof(ModImpair) == sizeof(m17_impairment) && sizeof(ModImpair) == 32, "m17_impairment layout");
     ModParams mp;
     std::memcpy(&mp, params, sizeof(mp));
     const size_t sym_pitch = round_up((size_t)mod_max_symbols(mp.n_frames, mp.n_preamble), 16);
     const size_t sym_bytes = round_up((size_t)C * sym_pitch, 256);
+    const size_t pts_at = sym_bytes + round_up((size_t)C * 4, 256);
+    const size_t need = points ? pts_at + (size_t)n_points * sizeof(ModImpair) : sym_bytes + (size_t)C * 4;
     InputTarget in;
     int r = input_target(c, in);
     if (r) return r;
     // the symbol staging lives in its own allocation: the per-operator scratch may be in use by work queued on the main stream
-    if (sym_bytes + (size_t)C * 4 > c->synth_bytes) {
+    if (need > c->synth_bytes) {
         if (c->synth_scratch) { HIPCHK(c, hipDeviceSynchronize()); free_dev(c->synth_scratch, &c->last_hip); c->synth_bytes = 0; }
-        HIPCHK(c, hipMalloc(&c->synth_scratch, sym_bytes + (size_t)C * 4));
-        c->synth_bytes = sym_bytes + (size_t)C * 4;
+        HIPCHK(c, hipMalloc(&c->synth_scratch, need));
+        c->synth_bytes = need;
     }
     int8_t* sym = reinterpret_cast<int8_t*>(c->synth_scratch);
     uint32_t* nsym = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->synth_scratch) + sym_bytes);
     hipLaunchKernelGGL(mod_symbols_kernel, dim3((C + 63) / 64), dim3(64), 0, in.st, mp, C, chan0, sym, sym_pitch, nsym);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(mod_shape_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, C, T, chan0, sym, sym_pitch, nsym, in.x, c->xpitch);
+    if (points) {
+        ModImpair* pts = reinterpret_cast<ModImpair*>(reinterpret_cast<char*>(c->synth_scratch) + pts_at);
+        HIPCHK(c, hipMemcpyAsync(pts, points, (size_t)n_points * sizeof(ModImpair), hipMemcpyHostToDevice, in.st));
+        hipLaunchKernelGGL(mod_shape_grid_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, pts, n_points, C, T, chan0, sym, sym_pitch, nsym, in.x,
+                           c->xpitch);
+    } else {
+        hipLaunchKernelGGL(mod_shape_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, C, T, chan0, sym, sym_pitch, nsym, in.x, c->xpitch);
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(in.st));
     input_done(c, in, C, T);
     return M17HIP_OK;
+}
+
+int m17hip_synth_i16(m17hip_ctx* c, const m17_synth_params* params, uint32_t C, uint32_t T, uint32_t chan0)
+{
+    return synth_impl(c, params, nullptr, 0, C, T, chan0);
+}
+
+int m17hip_synth_sweep_i16(m17hip_ctx* c, const m17_synth_params* base, const m17_impairment* points, uint32_t n_points, uint32_t C, uint32_t T,
+                           uint32_t chan0)
+{
+    if (!points || n_points == 0 || n_points > M17HIP_MAX_SWEEP_POINTS) return M17HIP_EINVAL;
+    for (uint32_t i = 0; i < n_points; ++i) {
+        const m17_impairment& p = points[i];
+        if (!std::isfinite(p.noise_sigma) || !std::isfinite(p.tail_sigma) || p.noise_sigma < 0.0 || p.tail_sigma < 0.0) return M17HIP_EINVAL;
+        if (!std::isfinite(p.dc_offset) || !std::isfinite(p.gain)) return M17HIP_EINVAL;
+    }
+    return synth_impl(c, base, points, n_points, C, T, chan0);
 }
 
 int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch)
@@ -2135,6 +2185,47 @@ int m17hip_bert_stats(m17hip_ctx* c, m17_bert_stat* stats_host, uint32_t C)
     return M17HIP_OK;
 }
 
+// The payload stream's buffer of sweep words holds at least n (nothing on that stream still uses the old one: the callers wait for it)
+static int ensure_chan_words(m17hip_ctx* c, uint64_t n)
+{
+    if (n <= c->chan_words_cap) return M17HIP_OK;
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
+    free_dev(c->chan_words, &c->last_hip); c->chan_words_cap = 0;
+    HIPCHK(c, hipMalloc(&c->chan_words, (size_t)n * sizeof(ChanStat)));
+    c->chan_words_cap = n;
+    return M17HIP_OK;
+}
+
+int m17hip_sweep_stats(m17hip_ctx* c, uint32_t n_points, m17_chan_stat* host, uint32_t C)
+{
+    if (!c || !host || n_points == 0 || C == 0 || C > c->maxC) return M17HIP_EINVAL;
+    GUARD(c);
+    static_assert(sizeof(ChanStat) == sizeof(m17_chan_stat) && sizeof(ChanStat) == 32, "m17_chan_stat layout");
+    if (!c->bert || !c->have_run) return M17HIP_ESTATE;
+    // m17hip_diag_fetch's order for `evm`: the latest run's last fold pass on the main stream (or the replay m17hip_demod_front queued is making it)
+    if (int fr = flush_fold(c)) return fr;
+    if (c->front_pending && c->gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
+    // ... m17hip_bert_stats' order for the PRBS9 state: the payload work of both runs, wherever it was queued
+    if (int fr = flush_payload(c)) return fr;
+    for (const auto& rs : c->sets)
+        if (rs.valid)
+            if (int fr = pay_after(c, rs)) return fr;
+    // ... and the words are made and copied on the payload stream, behind the main stream's work so far
+    if (c->pay() != c->stream) {
+        HIPCHK(c, hipEventRecord(c->ev_fetch, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->pay(), c->ev_fetch, 0));
+    }
+    if (int r = ensure_chan_words(c, c->maxC)) return r;
+    hipLaunchKernelGGL(sweep_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), (const BertState*)c->bert_state, c->seq_state, c->overflow, C,
+                       c->channel_base, n_points, (ChanStat*)c->chan_words);
+    HIPCHK(c, hipGetLastError());
+    uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(host, c->chan_words, (size_t)C * sizeof(ChanStat), hipMemcpyDeviceToHost, c->pay()));
+    HIPCHK(c, hipMemcpyAsync(ovf, c->overflow, 32, hipMemcpyDeviceToHost, c->pay()));
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
+    return (ovf[2] | ovf[6]) ? M17HIP_EOVERFLOW : M17HIP_OK;
+}
+
 int m17hip_packets_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t C, uint32_t pitch)
 {
     if (!c || !recs_host || !counts_host || C == 0 || C > c->maxC || pitch == 0) return M17HIP_EINVAL;
@@ -2327,40 +2418,38 @@ static int comm_wait(m17hip_ctx* c, m17hip_comm* m)
     }
 }
 
-static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame_rec* recs_host, uint64_t capacity, uint64_t* counts_host,
-                              uint64_t* total_out, bool dest_is_device)
+static int gather_hip_code(m17hip_ctx* c, hipError_t e)
+{
+    c->last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP;
+}
+
+// The gather protocol above over what a rank contributes: `elem` bytes per element; prepare(src, mine, overflow) puts this rank's elements
+// dense on the device (the payload stream's work) and returns its local status.  m17hip_gather_frames[_device]: the selected run's frame
+// records, compacted; m17hip_gather_sweep_stats: the caller's sweep words, uploaded.
+extern "C++" {   // (a template inside the C ABI's extern "C" block)
+template <class Prepare>
+static int gather_impl(m17hip_ctx* c, m17hip_comm* m, int root, size_t elem, Prepare&& prepare, void* recs_host, uint64_t capacity, uint64_t* counts_host,
+                       uint64_t* total_out, bool dest_is_device)
 {
     if (!c || !m || m->device != c->device || root < 0 || root >= m->nranks || (m->rank == root && capacity && !recs_host)) return M17HIP_EINVAL;
     GUARD(c);
     if (m->dead) return M17HIP_ECOMM;
     const Rccl& R = rccl();
     const bool is_root = m->rank == root;
-    auto hip_code = [&](hipError_t e) { c->last_hip = (int)e; return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP; };
+    auto hip_code = [&](hipError_t e) { return gather_hip_code(c, e); };
     auto comm_failed = [&](ncclResult_t q) { comm_give_up(m, (int)q); return M17HIP_ECOMM; };   // a collective call itself failed: nothing more can be agreed on
-    // 1. this rank's records, dense and (channel, seq)-ordered, in the context's compaction buffer (compact_into orders the payload stream
-    //    behind the selected run: every transfer of the records below is queued behind that)
+    // 1. this rank's elements, dense on the device
+    const void* src = nullptr;
     uint64_t mine = 0;
-    int local = selected_set(c) ? M17HIP_OK : M17HIP_ESTATE;
     bool overflow = false;
-    if (local == M17HIP_OK) {
-        int r = c->gather_fault == 1 ? M17HIP_EHIP : compact_into(c, c->compact, c->compact_cap, &mine);
-        // the dense buffer must hold ALL of this rank's records before anything is sent from it, whatever the first pass said
-        // (an overflowed run reports EOVERFLOW before the truncation is looked at)
-        if ((r == M17HIP_OK || r == M17HIP_ETRUNC || r == M17HIP_EOVERFLOW) && mine > c->compact_cap) {
-            free_dev(c->compact, &c->last_hip); c->compact_cap = 0;
-            const uint64_t want = std::max<uint64_t>(mine + mine / 8, 1024);
-            const hipError_t e = hipMalloc((void**)&c->compact, (size_t)want * sizeof(FrameRec));
-            if (e != hipSuccess) r = hip_code(e);
-            else { c->compact_cap = want; r = compact_into(c, c->compact, c->compact_cap, &mine); }
-        }
-        overflow = r == M17HIP_EOVERFLOW;
-        if (r && !overflow) { local = r; mine = 0; }
-    }
+    int local = prepare(src, mine, overflow);
     if (is_root && !m->gathered && local == M17HIP_OK) {   // a first staging buffer (grown below when a gathered set outgrows it)
         const uint64_t want = std::max<uint64_t>(2 * mine * (uint64_t)m->nranks, 1024);
-        if (c->gather_fault != 2 && hipMalloc((void**)&m->gathered, (size_t)want * sizeof(FrameRec)) == hipSuccess) m->gathered_cap = want;
-        else { m->gathered = nullptr; m->gathered_cap = 0; }
+        if (c->gather_fault != 2 && hipMalloc((void**)&m->gathered, (size_t)want * elem) == hipSuccess) m->gathered_bytes = want * elem;
+        else { m->gathered = nullptr; m->gathered_bytes = 0; }
     }
+    const uint64_t gathered_cap = m->gathered_bytes / elem;   // (in elements of this call)
     // 2. exchange 1
     const uint64_t serial = (uint64_t)(++m->serial & 0xFFFFu);
     constexpr uint64_t COUNT_MASK = (1ull << 40) - 1;
@@ -2368,7 +2457,7 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
     uint64_t* const word = m->words_host;        // (pinned, owned by the communicator: see there)
     uint64_t* const words = m->words_host + 2;
     word[0] = (mine & COUNT_MASK) | (serial << 40) | ((uint64_t)(uint8_t)(-local) << 56);
-    word[1] = is_root ? m->gathered_cap : 0ull;
+    word[1] = is_root ? gathered_cap : 0ull;
     const size_t words_n = 2 * (size_t)m->nranks;
     int unread = M17HIP_OK;   // this rank could not read exchange 1
     {
@@ -2400,11 +2489,11 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
     // 3. exchange 2: every rank, whatever it knows by now.  The root grows its staging when the gathered set does not fit it
     //    (only when the records are going to travel: every rank that read exchange 1 comes to the same conclusion about that)
     int rc = unread;
-    if (!unread && !local && !remote && is_root && (total > m->gathered_cap || c->gather_fault == 3)) {   // (fault 3 on the root: grown in any case)
-        free_dev(m->gathered, &c->last_hip); m->gathered_cap = 0;
+    if (!unread && !local && !remote && is_root && (total > gathered_cap || c->gather_fault == 3)) {   // (fault 3 on the root: grown in any case)
+        free_dev(m->gathered, &c->last_hip); m->gathered_bytes = 0;
         const uint64_t want = std::max<uint64_t>(total + total / 8, 1024);
-        const hipError_t e = c->gather_fault == 2 ? hipErrorOutOfMemory : hipMalloc((void**)&m->gathered, (size_t)want * sizeof(FrameRec));
-        if (e != hipSuccess) rc = hip_code(e); else m->gathered_cap = want;
+        const hipError_t e = c->gather_fault == 2 ? hipErrorOutOfMemory : hipMalloc((void**)&m->gathered, (size_t)want * elem);
+        if (e != hipSuccess) rc = hip_code(e); else m->gathered_bytes = want * elem;
     }
     constexpr uint64_t PHASE2 = 0xA5ull << 56;
     {
@@ -2436,7 +2525,7 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
         ncclResult_t q = R.GroupStart();
         uint64_t off = 0;
         for (int k = 0; k < m->nranks && q == ncclSuccess; ++k) {
-            if (k != root && counts[k]) q = R.Recv(m->gathered + off, (size_t)counts[k] * sizeof(FrameRec), ncclUint8, k, m->comm, c->pay());
+            if (k != root && counts[k]) q = R.Recv(m->gathered + off * elem, (size_t)counts[k] * elem, ncclUint8, k, m->comm, c->pay());
             off += counts[k];
         }
         const ncclResult_t qe = R.GroupEnd();   // the group is closed whatever happened inside it
@@ -2445,7 +2534,7 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
         off = 0;
         hipError_t he = hipSuccess;
         for (int k = 0; k < m->nranks; ++k) {   // the root's own share: a plain copy, outside the group
-            if (k == root && mine) he = hipMemcpyAsync(m->gathered + off, c->compact, (size_t)mine * sizeof(FrameRec), hipMemcpyDeviceToDevice, c->pay());
+            if (k == root && mine) he = hipMemcpyAsync(m->gathered + off * elem, src, (size_t)mine * elem, hipMemcpyDeviceToDevice, c->pay());
             off += counts[k];
         }
         if (he != hipSuccess) return hip_code(he);
@@ -2458,7 +2547,7 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
                 HIPCHK(c, hipEventRecord(c->ev_dst, c->stream));
                 HIPCHK(c, hipStreamWaitEvent(c->pay(), c->ev_dst, 0));
             }
-            HIPCHK(c, hipMemcpyAsync(recs_host, m->gathered, (size_t)n * sizeof(FrameRec), dest_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->pay()));
+            HIPCHK(c, hipMemcpyAsync(recs_host, m->gathered, (size_t)n * elem, dest_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->pay()));
             HIPCHK(c, hipStreamSynchronize(c->pay()));
         }
         if (overflow) return M17HIP_EOVERFLOW;
@@ -2466,13 +2555,43 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
     }
     if (mine) {
         ncclResult_t q = R.GroupStart();
-        if (q == ncclSuccess) q = R.Send(c->compact, (size_t)mine * sizeof(FrameRec), ncclUint8, root, m->comm, c->pay());
+        if (q == ncclSuccess) q = R.Send(src, (size_t)mine * elem, ncclUint8, root, m->comm, c->pay());
         const ncclResult_t qe = R.GroupEnd();
         if (q == ncclSuccess) q = qe;
         if (q != ncclSuccess) return comm_failed(q);
     }
     if (const int w = comm_wait(c, m)) return w;
     return overflow ? M17HIP_EOVERFLOW : M17HIP_OK;
+}
+}   // extern "C++"
+
+// m17hip_gather_frames[_device]: the selected run's records, dense and (channel, seq)-ordered, in the context's compaction buffer
+// (compact_into orders the payload stream behind the selected run: every transfer of the records is queued behind that)
+static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame_rec* recs, uint64_t capacity, uint64_t* counts_host, uint64_t* total_out,
+                              bool dest_is_device)
+{
+    auto prepare = [c](const void*& src, uint64_t& mine, bool& overflow) {
+        mine = 0;
+        int local = selected_set(c) ? M17HIP_OK : M17HIP_ESTATE;
+        overflow = false;
+        if (local == M17HIP_OK) {
+            int r = c->gather_fault == 1 ? M17HIP_EHIP : compact_into(c, c->compact, c->compact_cap, &mine);
+            // the dense buffer must hold ALL of this rank's records before anything is sent from it, whatever the first pass said
+            // (an overflowed run reports EOVERFLOW before the truncation is looked at)
+            if ((r == M17HIP_OK || r == M17HIP_ETRUNC || r == M17HIP_EOVERFLOW) && mine > c->compact_cap) {
+                free_dev(c->compact, &c->last_hip); c->compact_cap = 0;
+                const uint64_t want = std::max<uint64_t>(mine + mine / 8, 1024);
+                const hipError_t e = hipMalloc((void**)&c->compact, (size_t)want * sizeof(FrameRec));
+                if (e != hipSuccess) r = gather_hip_code(c, e);
+                else { c->compact_cap = want; r = compact_into(c, c->compact, c->compact_cap, &mine); }
+            }
+            overflow = r == M17HIP_EOVERFLOW;
+            if (r && !overflow) { local = r; mine = 0; }
+        }
+        src = c->compact;
+        return local;
+    };
+    return gather_impl(c, m, root, sizeof(FrameRec), prepare, recs, capacity, counts_host, total_out, dest_is_device);
 }
 
 int m17hip_gather_frames(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame_rec* recs_host, uint64_t capacity, uint64_t* counts_host, uint64_t* total_out)
@@ -2482,6 +2601,30 @@ int m17hip_gather_frames(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame_rec*
 int m17hip_gather_frames_device(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame_rec* recs_dev, uint64_t capacity, uint64_t* counts_host, uint64_t* total_out)
 {
     return gather_frames_impl(c, m, root, recs_dev, capacity, counts_host, total_out, true);
+}
+
+
+int m17hip_gather_sweep_stats(m17hip_ctx* c, m17hip_comm* m, int root, const m17_chan_stat* mine_host, uint64_t n_mine, m17_chan_stat* out_host,
+                              uint64_t capacity, uint64_t* counts_host, uint64_t* total_out)
+{
+    if (n_mine && !mine_host) return M17HIP_EINVAL;
+    // this rank's words (the caller's: a rank may have processed its shard in several runs), uploaded to the payload stream's buffer
+    auto prepare = [c, mine_host, n_mine](const void*& src, uint64_t& mine, bool& overflow) {
+        overflow = false;
+        mine = 0;
+        src = nullptr;
+        if (c->gather_fault == 1) return (int)M17HIP_EHIP;
+        if (n_mine) {
+            if (int r = ensure_chan_words(c, n_mine)) return r;
+            hipError_t e = hipMemcpyAsync(c->chan_words, mine_host, (size_t)n_mine * sizeof(ChanStat), hipMemcpyHostToDevice, c->pay());
+            if (e == hipSuccess) e = hipStreamSynchronize(c->pay());   // (the caller's memory is not read once the call has returned, whatever happens in it)
+            if (e != hipSuccess) return gather_hip_code(c, e);
+        }
+        src = c->chan_words;
+        mine = n_mine;
+        return (int)M17HIP_OK;
+    };
+    return gather_impl(c, m, root, sizeof(ChanStat), prepare, out_host, capacity, counts_host, total_out, false);
 }
 
 int m17hip_comm_last_error(const m17hip_comm* m) { return m ? m->last_rccl : 0; }

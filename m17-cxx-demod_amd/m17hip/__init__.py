@@ -36,6 +36,11 @@ PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8")
                        ("frames", "u1"), ("seq_errors", "u1"), ("reserved", "u1"), ("data", "u1", (840,))])
 assert PACKET_REC.itemsize == 864
 VITERBI_SHAPES = {0: (488, 240), 1: (296, 144), 2: (420, 206), 3: (402, 197)}
+IMPAIRMENT_DTYPE = np.dtype([("noise_sigma", "<f8"), ("tail_sigma", "<f8"), ("dc_offset", "<f8"), ("gain", "<f8")])   # m17_impairment
+CHAN_STAT_DTYPE = np.dtype([("channel", "<u4"), ("point", "<u4"), ("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4"),
+                            ("evm", "<f4"), ("flags", "<u4")])   # m17_chan_stat; flags bit 0: evm is valid
+assert IMPAIRMENT_DTYPE.itemsize == 32 and CHAN_STAT_DTYPE.itemsize == 32
+MAX_SWEEP_POINTS = 4096
 
 EXPORTS = [
     "m17hip_strerror", "m17hip_last_hip_error", "m17hip_version", "m17hip_ctx_create", "m17hip_ctx_destroy", "m17hip_set_stream", "m17hip_get_stream",
@@ -45,8 +50,10 @@ EXPORTS = [
     "m17hip_set_kalman_order", "m17hip_kalman_trace", "m17hip_set_channel_base", "m17hip_upload_wait", "m17hip_comm_get_id", "m17hip_comm_create",
     "m17hip_comm_destroy", "m17hip_comm_last_error", "m17hip_gather_frames", "m17hip_gather_frames_device", "m17hip_diag_log_fetch",
     "m17hip_upload_i16_device_async", "m17hip_input_alternate", "m17hip_demod_front", "m17hip_advice", "m17hip_replay_drops", "m17hip_frames_select",
+    "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats",
 ]
 ETRUNC = -6
+EOVERFLOW = -5
 COMM_ID_BYTES = 128
 
 
@@ -187,9 +194,19 @@ class Context:
         self.C, self.T = int(channels), int(samples)
         self._chk(self.lib.m17hip_synth_i16(self.h, C.byref(params), C.c_uint32(self.C), C.c_uint32(self.T), C.c_uint32(chan0)))
 
-    def download(self):
-        out = np.empty((self.C, self.T), dtype=np.int16)
-        self._chk(self.lib.m17hip_download_i16(self.h, _ptr(out), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(self.T)))
+    def synth_sweep(self, base, points, channels, samples, chan0=0):
+        """An impairment sweep in one synthesis (m17hip_synth_sweep_i16): channel c under points[(chan0 + c) % len(points)], everything else
+        from `base` (an m17_synth_params block).  `points`: an IMPAIRMENT_DTYPE array or a sequence of (noise_sigma, tail_sigma, dc_offset, gain)."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=IMPAIRMENT_DTYPE).reshape(-1))
+        self.C, self.T = int(channels), int(samples)
+        self._chk(self.lib.m17hip_synth_sweep_i16(self.h, C.byref(base), _ptr(pts), C.c_uint32(pts.size), C.c_uint32(self.C), C.c_uint32(self.T),
+                                                  C.c_uint32(chan0)))
+
+    def download(self, channels=None):
+        """The input slab's first `channels` rows (default: all of the last input)."""
+        n = channels or self.C
+        out = np.empty((n, self.T), dtype=np.int16)
+        self._chk(self.lib.m17hip_download_i16(self.h, _ptr(out), C.c_uint32(n), C.c_uint32(self.T), C.c_size_t(self.T)))
         return out
 
     def upload_device(self, dev_ptr, channels, samples, pitch=None):
@@ -371,6 +388,32 @@ class Context:
         st = np.zeros(n, dtype=BERT_STAT)
         self._chk(self.lib.m17hip_bert_stats(self.h, _ptr(st), C.c_uint32(n)))
         return st
+
+    def sweep_stats(self, n_points, channels=None):
+        """One CHAN_STAT_DTYPE word per channel: the PRBS9 counts of bert_stats and the `evm` of diag, with channel = channel base + index and
+        point = channel % n_points (m17hip_sweep_stats).  A deferred-EVM overflow (M17HIP_EOVERFLOW) is not raised: those words carry flags
+        bit 0 cleared."""
+        n = channels or self.C
+        w = np.zeros(n, dtype=CHAN_STAT_DTYPE)
+        code = self.lib.m17hip_sweep_stats(self.h, C.c_uint32(n_points), _ptr(w), C.c_uint32(n))
+        if code != EOVERFLOW:
+            self._chk(code)
+        return w
+
+    def gather_sweep_stats(self, comm, words, root=0, capacity=None):
+        """Collective: every rank's sweep words (any number per rank) gathered to `root` in rank order (m17hip_gather_sweep_stats).  Returns
+        (words or None off the root, counts per rank).  `capacity` (root): room for the gathered words, by default nranks x max(len(words),
+        max_channels); a gathered set that does not fit raises."""
+        w = np.ascontiguousarray(np.asarray(words, dtype=CHAN_STAT_DTYPE).reshape(-1))
+        counts = np.zeros(comm.nranks, dtype=np.uint64)
+        total = C.c_uint64(0)
+        is_root = comm.rank == root
+        if capacity is None:
+            capacity = comm.nranks * max(w.size, self.max_channels) if is_root else 0
+        out = np.zeros(capacity, dtype=CHAN_STAT_DTYPE) if is_root else None
+        self._chk(self.lib.m17hip_gather_sweep_stats(self.h, comm.h, C.c_int(root), _ptr(w), C.c_uint64(w.size), _ptr(out), C.c_uint64(capacity),
+                                                     _ptr(counts), C.byref(total)))
+        return (out[: total.value] if is_root else None), counts
 
     def packets(self, capacity=4096):
         """Packets the last run completed, ordered by (channel, seq) (enable with tune(7, room) before the runs)."""
