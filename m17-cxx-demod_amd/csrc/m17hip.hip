@@ -32,7 +32,62 @@ namespace {
 
 enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_N };
 
-struct TimedLaunch { hipEvent_t a, b; int which; };
+// Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
+// empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
+// hipFree (a pointer the runtime does not know, a dead device) drops the pointer all the same — never reused, never freed twice — and is
+// recorded in *last_hip where the caller passes one.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }   // (elements)
+    hipError_t alloc(size_t n)   // n elements in place of what it holds; empty when that fails
+    {
+        release();
+        const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+        if (e == hipSuccess) n_ = n; else p_ = nullptr;
+        return e;
+    }
+    hipError_t grow(size_t n, int* last_hip)   // at least n elements: reallocated (its contents lost) only when it holds fewer
+    {
+        if (n <= n_) return hipSuccess;
+        release(last_hip);
+        return alloc(n);
+    }
+    void release(int* last_hip = nullptr)
+    {
+        if (!p_) return;
+        const hipError_t e = hipFree((void*)p_);
+        if (e != hipSuccess && last_hip) *last_hip = (int)e;
+        p_ = nullptr;
+        n_ = 0;
+    }
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// A HIP event that destroys itself; reads as the hipEvent_t it holds (nullptr until created).  Movable: the timing pool hands them round.
+class Event {
+public:
+    Event() = default;
+    Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e_, o.e_); return *this; }
+    ~Event() { if (e_) (void)hipEventDestroy(e_); }
+    operator hipEvent_t() const { return e_; }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e_, flags); }
+private:
+    hipEvent_t e_ = nullptr;
+};
+
+struct TimedLaunch { Event a, b; int which; };
+
+struct BertState; struct ChanStat; struct PacketState; struct PacketRec;   // (with the host layer's kernels, below)
 
 }  // namespace
 
@@ -45,39 +100,41 @@ struct m17hip_ctx {
     hipStream_t side = nullptr;        // K3 runs here, concurrently with K1 (side2) and with K2/K5 of earlier segments (stream)
     hipStream_t side2 = nullptr;       // K1 of the segments of a run
     hipStream_t side3 = nullptr;       // K2 of segment k+1 while K5 works on segment k
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Event ev_fork, ev_join;
     // per segment: K1 / K3 / K2 (ahead) done, K2 redo done, K5 done — one set per slab pair (consecutive staged runs alternate)
-    std::vector<hipEvent_t> ev_fir_[2], ev_dcd_[2], ev_gate_[2], ev_redo_[2], ev_seq_[2];
+    std::vector<Event> ev_fir_[2], ev_dcd_[2], ev_gate_[2], ev_redo_[2], ev_seq_[2];
     uint32_t front_ahead = 0;         // tuning knob 5: segments the front end (K1, K3) may run ahead of K5 (0 = unlimited, measured best)
     uint32_t maxC = 0, maxT = 0;
     size_t xpitch = 0, ypitch = 0;
     uint32_t ticks_cap = 0, rec_cap = 0, rec_cap_alloc = 0;   // rec_cap: record slots per channel and run in use (<= allocated)
-    int16_t* xbuf = nullptr;
-    // Streaming: a second set of the per-run slabs.  The input of the NEXT run is staged in `xstage` while the current
-    // run computes; that run's front end (K1 -> yalt, K3 -> dcd_alt) may start before the current run's K2/K5 chain has ended
-    // (m17hip_demod_front), and K2 / K5 of the next run then work on yalt / halt.  The pointers swap when a staged run begins.
-    int16_t* xstage = nullptr;
-    float* yalt = nullptr;
-    float* halt = nullptr;
-    float* dcd_alt = nullptr;
+    // The per-run slabs (the kernels' comments call them xbuf, ybuf, hbuf): input x (pitch xpitch), matched-filter output y and K2's
+    // limit-filter history h (pitch ypitch), K3's table dcd (ticks_cap rows of 12 per channel).
+    // Streaming: a second pair.  The input of the NEXT run is staged in other().x while the current run computes; that
+    // run's front end (K1 -> other().y, K3 -> other().dcd) may start before the current run's K2/K5 chain has ended (m17hip_demod_front),
+    // and K2 / K5 of the next run then work on other().y / .h.  The pairs change roles (slot ^= 1) when a staged run begins.
+    struct Slab {
+        DevBuf<int16_t> x;
+        DevBuf<float> y, h, dcd;
+    } slab[2];                        // [1]: allocated the first time input is staged (stage_prepare)
+    Slab& now() { return slab[slot]; }         // the current / latest run's
+    Slab& other() { return slab[slot ^ 1]; }   // the staging pair (the run before the latest one's)
     bool foreign_streams[4] = {false, false, false, false};   // tools build, keys 40-43: side / side2 / side3 / copy belong to the experiment, not to the context
     hipStream_t copy = nullptr;       // host -> device copies of staged input only
-    hipEvent_t ev_copy = nullptr;     // the staged copy has left its source buffer
-    hipEvent_t ev_in_ready = nullptr; // the staged slab and its carried 152-sample prefix are complete
-    hipEvent_t ev_end[2] = {nullptr, nullptr};   // the last run on slab pair 0 / 1 is done with its slabs
-    hipEvent_t ev_mark = nullptr;     // last main-stream operation a front end must not overtake (reset)
+    Event ev_copy;                    // the staged copy has left its source buffer
+    Event ev_in_ready;                // the staged slab and its carried 152-sample prefix are complete
+    Event ev_end[2];                  // the last run on slab pair 0 / 1 is done with its slabs
+    Event ev_mark;                    // last main-stream operation a front end must not overtake (reset)
     bool slot_used[2] = {false, false};
     bool inplace_after_run = false;   // the current input slab was overwritten in place after its last run: its data region no longer holds that run's tail
-    int slot = 0;                     // slab pair the pointers xbuf / ybuf / hbuf / dcd_table name
+    int slot = 0;                     // the slab pair now() names (0 until the first staged run begins)
     bool staged = false, staged_h2d = false;
     bool stage_inputs = false;        // tuning knob 16: the in-place producers write the staging slab
-    void* synth_scratch = nullptr;    // symbol staging of m17hip_synth_i16 (and the impairment grid of m17hip_synth_sweep_i16)
-    size_t synth_bytes = 0;
+    DevBuf<char> synth_scratch;       // symbol staging of m17hip_synth_i16 (and the impairment grid of m17hip_synth_sweep_i16)
     uint32_t runT = 0;                // samples of the latest run
-    hipEvent_t ev_tail = nullptr;     // the latest run has carried its tails into its prefixes (K5 is done with its last segment)
+    Event ev_tail;                    // the latest run has carried its tails into its prefixes (K5 is done with its last segment)
     bool gate0_queued = false;        // m17hip_demod_front has queued the replay of the staged run's first segment (and the prefix copies in front of it)
     int gate0_early = 1;              // tuning knob 25: 1 = it does so
-    Boundary* bnd = nullptr;          // [2][maxC] boundary records (by segment parity): K5 -> the redo of K2 (m17_state.hpp)
+    DevBuf<Boundary> bnd;             // [2][maxC] boundary records (by segment parity): K5 -> the redo of K2 (m17_state.hpp)
     uint32_t front_k1_after = 0;      // tuning knob 21: the matched filter of a staged run starts after K5 of this segment (1-based) of the run before it; 0 = at once
     uint32_t last_nseg = 0;           // segments of the latest run
     bool wave_times = false;          // tuning knob 19: K5 writes each wave's working time per segment (m17hip_debug_counters)
@@ -87,23 +144,19 @@ struct m17hip_ctx {
     uint32_t frontC = 0, frontT = 0, front_flags = 0, front_segs = 0;
     bool front_was_staged = false;    // the run whose front end is queued works on freshly swapped slabs (prefixes still to be carried)
     uint32_t carryT = 0;              // length of the run whose tail those prefixes come from (0 = none since the reset)
-    float* ybuf = nullptr;
-    float* hbuf = nullptr;            // K2's limit-filter history, same pitch as ybuf
-    float* final_h = nullptr;         // [2][maxC][4], by segment parity
-    GateExport* gate_exp = nullptr;   // [maxC] K2's own state at the end of a segment
-    uint32_t* dropped = nullptr;      // [maxC] K5: the segment dropped the speculation
-    void* bert_state = nullptr;       // [maxC] BertState (tuning knob 6)
+    DevBuf<float> final_h;            // [2][maxC][4], by segment parity
+    DevBuf<GateExport> gate_exp;      // [maxC] K2's own state at the end of a segment
+    DevBuf<uint32_t> dropped;         // [maxC] K5: the segment dropped the speculation
+    DevBuf<BertState> bert_state;     // [maxC] (tuning knob 6)
     bool bert = false;
-    void* chan_words = nullptr;       // [chan_words_cap] ChanStat: m17hip_sweep_stats' words on their way out / a rank's words on their way into m17hip_gather_sweep_stats (payload stream)
-    uint64_t chan_words_cap = 0;
-    void* pkt_state = nullptr;        // [maxC] PacketState (tuning knob 7)
-    void* pkt_recs2[2] = {nullptr, nullptr};        // [pkt_cap] PacketRec: packets completed by a run, one store per record set
-    uint32_t* pkt_count2 = nullptr;   // [2]
-    int pkt_fed_set = 0;              // the store m17hip_packets_feed wrote last
+    DevBuf<ChanStat> chan_words;      // m17hip_sweep_stats' words on their way out / a rank's words on their way into m17hip_gather_sweep_stats (payload stream)
+    DevBuf<PacketState> pkt_state;    // [maxC] (tuning knob 7)
+    DevBuf<PacketRec> pkt_recs2[2];   // [pkt_cap]: packets completed by a run, one store per record set
+    DevBuf<uint32_t> pkt_count2;      // [2]
     uint32_t pkt_cap = 0;
     bool pkt_fed = false;
-    Diag* diag_log = nullptr;         // [maxC][diag_cap] one entry per diagnostic callback of the last run (tuning knob 9)
-    uint32_t* diag_count = nullptr;   // [maxC]
+    DevBuf<Diag> diag_log;            // [maxC][diag_cap] one entry per diagnostic callback of the last run (tuning knob 9)
+    DevBuf<uint32_t> diag_count;      // [maxC]
     uint32_t diag_cap = 0;
     uint32_t kalman_order = 3;        // evaluation order of the Kalman updates (m17hip_set_kalman_order)
     int gather_fault = 0;             // tuning knob 30 (tests): 1 = this rank's compaction (m17hip_gather_sweep_stats: its upload) fails inside the gather, 2 = the root's staging allocation fails, 3 = its word of exchange 2 is not written,
@@ -115,25 +168,24 @@ struct m17hip_ctx {
     int dcd_form = -1;                // tuning knob 10: K3 as one wave per 32 channels (0), as the four-wave latency pipeline (1), or chosen per run (-1: the pipeline for runs queued by m17hip_demod_front)
     bool dcd_latency = false;         // what the launches of the run being queued use
     uint64_t seen_overlap = 0;        // (run registry below) the overlap count this context's previous run saw
-    hipEvent_t last_end = nullptr;    // ev_end of the run queued last
+    hipEvent_t last_end = nullptr;    // ev_end of the run queued last (not owned)
     uint32_t seg_len = 48000;         // tuning knob 3: samples per K2+K5 segment of a run (0 = the whole run)
     uint32_t seg0_len = 0;            // tuning knob 4: samples of the FIRST segment (a short one starts K5 early; 0 = like the others; measured neutral)
     int64_t seg_ramp = -1;            // tuning knob 33: first segment of a ramp r, 2 r, 4 r, ... up to seg_len (0 = none; -1 = per run: AUTO_RAMP when the run is the only thing in flight)
     uint32_t ramp_now = 0;            // what the run being queued uses (a staged run: decided when its front end is queued)
-    float* dcd_table = nullptr;
-    DcdState* dcd_state = nullptr;
-    SeqState* seq_state = nullptr;
+    DevBuf<DcdState> dcd_state;
+    DevBuf<SeqState> seq_state;
     // Two RECORD SETS that alternate run by run (what a run writes for its consumers: record slots, counts, the deferred-frame store, the
     // run's overflow words).  The payload work of run k — deferred decode, consumers, compaction, the gather — runs on the PAYLOAD stream
     // beside the chain of run k + 1, which writes the other set; m17hip_frames_select says which run's records the fetch family names.
     struct RecSet {
-        FrameRec* recs = nullptr;         // [maxC][rec_cap_alloc]
-        uint32_t* rec_count = nullptr;    // [maxC]
-        uint32_t* defer_llr = nullptr;    // [maxC][rec_cap_alloc][46]: LLR frames (nibbles) K5 leaves for decode_deferred_kernel (tune 15), lazily
+        DevBuf<FrameRec> recs;            // [maxC][rec_cap_alloc]
+        DevBuf<uint32_t> rec_count;       // [maxC]
+        DevBuf<uint32_t> defer_llr;       // [maxC][rec_cap_alloc][46]: LLR frames (nibbles) K5 leaves for decode_deferred_kernel (tune 15), lazily
         uint32_t* ovf = nullptr;          // -> overflow + 4 * index: [0] record overflow of the run, [1] channels that left the replay (since reset, this set's runs),
                                           //    [2] deferred EVM operations dropped (since reset), [3] channel-segments of the run that ended with the carrier off
-        hipEvent_t chain = nullptr;       // the run that wrote this set has left the main stream (state settled): what its payload work waits for
-        hipEvent_t done = nullptr;        // the payload stream is through with the run that wrote this set
+        Event chain;                      // the run that wrote this set has left the main stream (state settled): what its payload work waits for
+        Event done;                       // the payload stream is through with the run that wrote this set
         uint32_t C = 0, rec_cap = 0, nseg = 0;
         bool valid = false;               // holds a finished run's records in the layout (rec_cap) they were written with
         bool pending = false;             // its payload work (deferred decode, consumers) is not queued yet (flush_payload)
@@ -146,49 +198,48 @@ struct m17hip_ctx {
     // 24 to 27-37 ms whatever its place in the creation order (which streams share a hardware pipe: NOTES 4.14, 6.3).  The copy stream also
     // carries the next run's staged input and prefix copies, which must never wait for a FUTURE event: so a run's payload work is queued
     // when somebody asks for its results (or needs its record set back), not when the run is queued — flush_payload.
-    bool streams() const { return copy && xstage; }   // input has been staged (stage_prepare): the copy stream is at work (a parked set may bring one along — that alone changes nothing)
+    bool streams() const { return copy && slab[1].x; }   // input has been staged (stage_prepare): the copy stream is at work (a parked set may bring one along — that alone changes nothing)
     hipStream_t pay() const { return streams() ? copy : stream; }
-    hipEvent_t ev_dst = nullptr;      // the caller's main-stream work on a device destination is done (a fetch of the LATEST run orders itself behind it)
-    hipEvent_t ev_switch = nullptr;   // m17hip_set_stream: what was queued before the switch (the new main stream waits for it)
-    hipEvent_t ev_fetch = nullptr;    // m17hip_sweep_stats: the main stream's last EVM fold (the payload stream waits for it)
-    uint32_t* overflow = nullptr;     // [8]: four words per record set
-    uint64_t* rec_offsets = nullptr;  // exclusive prefix of rec_count (+ total at [C]): scratch of a compaction (payload stream)
-    FrameRec* compact = nullptr;      // lazily sized
-    uint64_t compact_cap = 0;
-    DecodeTables* tables = nullptr;
-    float* taps = nullptr;
-    float* taps_skew = nullptr;      // tap table of fir_rrc150_skew_kernel (fs_build_tap_table)
+    Event ev_dst;                     // the caller's main-stream work on a device destination is done (a fetch of the LATEST run orders itself behind it)
+    Event ev_switch;                  // m17hip_set_stream: what was queued before the switch (the new main stream waits for it)
+    Event ev_fetch;                   // m17hip_sweep_stats: the main stream's last EVM fold (the payload stream waits for it)
+    DevBuf<uint32_t> overflow;        // [8]: four words per record set
+    DevBuf<uint64_t> rec_offsets;     // exclusive prefix of rec_count (+ total at [C]): scratch of a compaction (payload stream)
+    DevBuf<FrameRec> compact;         // lazily sized
+    DevBuf<DecodeTables> tables;
+    DevBuf<float> taps;
+    DevBuf<float> taps_skew;         // tap table of fir_rrc150_skew_kernel (fs_build_tap_table)
     int limit_form = 1;              // (tools build only, key 27) configs[1]'s limit filter: 1 = the chain relayed between two waves, 0 = round 4's one recurrence wave
     int fir_form = 1;                // (tools build, key 11) K1: 1 = skewed-pair form on a bounded grid, 0 = round 4's rolled R = 15 form, one workgroup per tile
     int gate_aware = -1;             // tuning knob 26: K1 skips what the carrier cannot be on for (1), never (0), or chosen per run from how much of the previous run's channel-segments ended with the carrier off (-1, default)
     bool gate_run = false;           // the run being queued is gate-aware
-    GateTruth* truth = nullptr;      // [2][maxC] by segment parity: K5's gate state at the end of a segment
-    uint32_t* first_needed = nullptr;   // [maxC] gate_forecast_kernel -> K1
+    DevBuf<GateTruth> truth;         // [2][maxC] by segment parity: K5's gate state at the end of a segment
+    DevBuf<uint32_t> first_needed;   // [maxC] gate_forecast_kernel -> K1
     uint32_t off_segs_prev = 0, chan_segs_prev = 0;   // channel-segments of the last FETCHED run that ended with the carrier off / in all
     uint32_t fir_grid = 0;           // tuning knob 13: workgroups of K1's grid (0 = default: from the items per workgroup below)
     bool fir_latency = false;        // the run being queued is one whose chain of K5 launches decides (= it gets K3's latency form): few items per K1 workgroup
     uint32_t n_cu = 256;
-    uint32_t* defer_hist = nullptr;  // [maxC][101][64]: decode_deferred_kernel's decision words (one launch at a time: payload stream)
+    DevBuf<uint32_t> defer_hist;     // [maxC][101][64]: decode_deferred_kernel's decision words (one launch at a time: payload stream)
     bool defer_decode = true;
     // the running EVM folded outside K5, one lane per channel (m17_state.hpp, evm_fold_pass; tune 17)
     bool defer_evm = true;
-    float* ev_ops2[2] = {nullptr, nullptr};   // [maxC][ev_pitch] operations of a run (lazily allocated); the second one where a run begins while the last fold pass of the run before is still to come
+    DevBuf<float> ev_ops2[2];        // [maxC][ev_pitch] operations of a run (lazily allocated); the second one where a run begins while the last fold pass of the run before is still to come
     int ev_par = 0;                  // the buffer of the current / latest run
     const float* fold_ops = nullptr; // what the pending last fold pass works on: the run's buffer, its channels, its end-of-run cursors
     uint32_t fold_C = 0;
     const uint32_t* fold_end = nullptr;
     uint32_t ev_pitch = 0;
     uint32_t ev_pitch_override = 0;  // tuning knob 18 (tests): floats per operation row instead of ev_row_floats(maxT)
-    uint32_t* ev_cur = nullptr;      // [3][maxC] K5's operation cursor at the end of a segment, by segment parity; [2]: at the end of the run's LAST segment
+    DevBuf<uint32_t> ev_cur;         // [4][maxC] K5's operation cursor at the end of a segment: [0], [1] by segment parity; [2], [3] at the end of a run's
+                                     // LAST segment, by the run's buffer (ev_par)
     bool fold_pending = false;       // the last EVM fold pass of the latest run (the operations of its last two segments) is still to be made: it rides the next
                                      // run's first limit-filter replay (which K5 of that run waits for anyway), or is made when somebody asks for m17_diag (flush_fold)
     bool fold_with_decode = false;   // (inside m17hip_demod_run) ... or the latest run's deferred decode, where that is queued behind the run at once
-    EvState* ev_state = nullptr;     // [maxC]
+    DevBuf<EvState> ev_state;        // [maxC]
     uint32_t seq_lds_bytes = 0; // tune 14: LDS bytes a workgroup of the sequential kernel asks for (0 = SEQ_LDS_BYTES_4 for four waves)
-    float* llr_edges = nullptr;
-    core::Kalman2Gain* level_gain = nullptr;   // [8 orders][LEVEL_SCHED_N] gain schedules of the level filters (core.h)
-    void* scratch = nullptr;          // per-operator staging (correlator outputs, viterbi io)
-    size_t scratch_bytes = 0;
+    DevBuf<float> llr_edges;
+    DevBuf<core::Kalman2Gain> level_gain;   // [8 orders][LEVEL_SCHED_N] gain schedules of the level filters (core.h)
+    DevBuf<char> scratch;             // per-operator staging (correlator outputs, viterbi io)
     DcdCoef coef{};
     uint64_t pos = 0;          // samples consumed since reset
     uint32_t lastC = 0, lastT = 0;
@@ -196,10 +247,10 @@ struct m17hip_ctx {
     bool uploaded = false;
     bool timing = false;
     bool profile = false;      // K5 writes per-channel tick counters (tuning knob 1)
-    unsigned long long* dbg = nullptr;  // [maxC][8] diagnostic cycle counters of K5
+    DevBuf<unsigned long long> dbg;  // [maxC][8] diagnostic cycle counters of K5
     uint32_t dbg_waves = 0;
     std::vector<TimedLaunch> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     double acc_ms[KT_N] = {0};
     uint64_t acc_n[KT_N] = {0};
 };
@@ -209,12 +260,11 @@ struct m17hip_comm {
     int device = 0;                   // any context on this device may gather through the communicator (one call at a time)
     int rank = 0, nranks = 1;
     int last_rccl = 0;
-    uint64_t* counts_dev = nullptr;   // [2 * nranks] words of the status / count exchanges
+    DevBuf<uint64_t> counts_dev;      // [2 * nranks] words of the status / count exchanges
     uint64_t* words_host = nullptr;   // pinned, [2 + 2 * nranks]: this rank's word pair on its way out, every rank's on the way in — no copy of an exchange ever
                                       // targets memory that a call which ran out of time has already given back
     uint32_t serial = 0;              // gather calls made through this communicator (every rank counts the same)
-    char* gathered = nullptr;         // root: every rank's contribution (frame records, sweep words), rank after rank
-    uint64_t gathered_bytes = 0;
+    DevBuf<char> gathered;            // root: every rank's contribution (frame records, sweep words), rank after rank
     bool dead = false;                // an exchange did not end in time or a collective call failed: given up, every later call returns M17HIP_ECOMM
 };
 
@@ -231,15 +281,13 @@ namespace {
 
 size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
-// Give device memory back and forget the pointer.  hipFree fails only for a pointer the runtime does not know (or a dead device): the
-// pointer is dropped either way — never reused, never freed twice — and the code is kept where a context is at hand.
-template <typename T>
-void free_dev(T*& p, int* last_hip = nullptr)
+// The code of a failed allocation (or of a failed step of the gather): M17HIP_ENOMEM when the device is out of memory, M17HIP_EHIP
+// otherwise; the error is kept in last_hip.  M17HIP_OK for hipSuccess.
+int alloc_code(m17hip_ctx* c, hipError_t e)
 {
-    if (!p) return;
-    const hipError_t e = hipFree((void*)p);
-    if (e != hipSuccess && last_hip) *last_hip = (int)e;
-    p = nullptr;
+    if (e == hipSuccess) return M17HIP_OK;
+    c->last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP;
 }
 
 // ---- constant tables ------------------------------------------------------------------------------------------
@@ -305,52 +353,50 @@ DcdCoef build_coef()  // SlidingDFT.h:85-95
 }
 
 // ---- timing ---------------------------------------------------------------------------------------------------
-hipEvent_t get_event(m17hip_ctx* c)   // nullptr (and last_hip set) when the runtime cannot create one
+Event get_event(m17hip_ctx* c)   // empty (and last_hip set) when the runtime cannot create one
 {
-    if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    const hipError_t r = hipEventCreate(&e);
-    if (r != hipSuccess) { c->last_hip = (int)r; return nullptr; }
+    Event e;
+    if (!c->pool.empty()) { e = std::move(c->pool.back()); c->pool.pop_back(); return e; }
+    const hipError_t r = e.create(hipEventDefault);
+    if (r != hipSuccess) c->last_hip = (int)r;
     return e;
 }
+// (a pair of timing events back to the pool: those of a launch that is not timed after all, or of one drain_timing has read)
+void pool_events(m17hip_ctx* c, Event& a, Event& b)
+{
+    if (a) c->pool.push_back(std::move(a));
+    if (b) c->pool.push_back(std::move(b));
+}
 struct Timed {  // HIP events on the stream the kernel is launched on; a launch whose events could not be had is not timed
-    m17hip_ctx* c; int which; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
+    m17hip_ctx* c; int which; hipStream_t st; Event a, b;
     Timed(m17hip_ctx* ctx, int w, hipStream_t stream) : c(ctx), which(w), st(stream)
     {
         if (!c->timing) return;
         a = get_event(c); b = get_event(c);
-        if (!a || !b || hipEventRecord(a, st) != hipSuccess) {
-            if (a) c->pool.push_back(a);
-            if (b) c->pool.push_back(b);
-            a = b = nullptr;
-        }
+        if (!a || !b || hipEventRecord(a, st) != hipSuccess) pool_events(c, a, b);
     }
     Timed(m17hip_ctx* ctx, int w) : Timed(ctx, w, ctx->stream) {}
     ~Timed()
     {
         if (!a) return;
-        if (hipEventRecord(b, st) == hipSuccess) c->pending.push_back({a, b, which});
-        else { c->pool.push_back(a); c->pool.push_back(b); }
+        if (hipEventRecord(b, st) == hipSuccess) c->pending.push_back({std::move(a), std::move(b), which});
+        else pool_events(c, a, b);
     }
 };
 // One kernel, timed by events BOUND to its launch (hipExtLaunchKernelGGL's start / stop events: the dispatch's own time stamps, what rocprofv3 reports) — nothing
 // is put into the stream around it.  Two recorded events per launch (Timed above) cost a continued stream 0.65 ms of its 21.7 ms step (tools/stream_only.py,
 // TIMING=1): for the five kernels of a run's chain that is the wrong price for being measured.
 struct TimedK {
-    m17hip_ctx* c; int which; hipEvent_t a = nullptr, b = nullptr;
+    m17hip_ctx* c; int which; Event a, b;
     TimedK(m17hip_ctx* ctx, int w) : c(ctx), which(w)
     {
         if (!c->timing) return;
         a = get_event(c); b = get_event(c);
-        if (!a || !b) {
-            if (a) c->pool.push_back(a);
-            if (b) c->pool.push_back(b);
-            a = b = nullptr;
-        }
+        if (!a || !b) pool_events(c, a, b);
     }
-    ~TimedK() { if (a) c->pending.push_back({a, b, which}); }
+    ~TimedK() { if (a) c->pending.push_back({std::move(a), std::move(b), which}); }
     template <typename... P, typename... A>
-    void launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, A... args)
+    void launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const A&... args)
     {   // (the arguments converted to the kernel's own parameter types: hipExtLaunchKernelGGL copies them as they come)
         if (a) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, a, b, 0, static_cast<P>(args)...);
         else hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
@@ -400,19 +446,9 @@ void drain_timing(m17hip_ctx* c)
         hipEventSynchronize(t.b);
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) { c->acc_ms[t.which] += ms; c->acc_n[t.which]++; }
-        c->pool.push_back(t.a);
-        c->pool.push_back(t.b);
+        pool_events(c, t.a, t.b);
     }
     c->pending.clear();
-}
-
-int ensure_scratch(m17hip_ctx* c, size_t bytes)
-{
-    if (bytes <= c->scratch_bytes) return M17HIP_OK;
-    free_dev(c->scratch, &c->last_hip); c->scratch_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
-    return M17HIP_OK;
 }
 
 // ---- small device kernels owned by the host layer ----------------------------------------------------------------
@@ -714,7 +750,7 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_
 #ifdef M17_TOOLS
     if (c->fir_form == 0) {   // round 4's kernel: the measurement build keeps it for same-box comparisons (tools/k1_forms.py, the clk_k1 pass of tools/profile_round.sh)
         dim3 grid((T + FIR_TILE - 1) / FIR_TILE, C);
-        tm.launch((fir_rrc150_rolled_kernel<FIR_R, 4>), grid, dim3(FIR_THREADS), 0, st, c->xbuf + t0, c->xpitch, c->ybuf + t0, c->ypitch, T, flags, c->taps);
+        tm.launch((fir_rrc150_rolled_kernel<FIR_R, 4>), grid, dim3(FIR_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, flags, c->taps);
     } else
 #endif
     {
@@ -726,9 +762,9 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
         if (flags & 1u)
-            tm.launch(fir_rrc150_skew_kernel<true>, grid, dim3(FS_THREADS), 0, st, c->xbuf + t0, c->xpitch, c->ybuf + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
+            tm.launch(fir_rrc150_skew_kernel<true>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
         else
-            tm.launch(fir_rrc150_skew_kernel<false>, grid, dim3(FS_THREADS), 0, st, c->xbuf + t0, c->xpitch, c->ybuf + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
+            tm.launch(fir_rrc150_skew_kernel<false>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
     }
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
@@ -740,14 +776,14 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_
     const uint64_t row0 = (c->pos + t0) / TICK - c->pos / TICK;
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
     if (!c->dcd_latency || T % DP_BLK != 0 || (c->pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK)
-        tm.launch(dcd_kernel, dim3((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB)), dim3(64 * DCD_WPB), 0, st, c->xbuf + t0, c->xpitch, c->dcd_state,
-                           c->dcd_table + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+        tm.launch(dcd_kernel, dim3((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB)), dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
     else if (flags & 1u)
-        tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->xbuf + t0, c->xpitch, c->dcd_state,
-                           c->dcd_table + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+        tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
     else
-        tm.launch(dcd_pipe_kernel<false>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->xbuf + t0, c->xpitch, c->dcd_state,
-                           c->dcd_table + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+        tm.launch(dcd_pipe_kernel<false>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -828,40 +864,38 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     c->ticks_cap = max_samples / TICK + 2;
     c->rec_cap = c->rec_cap_alloc = 2 * (max_samples / 1920 + 2) + 4;  // <= 2 callbacks per 1920-sample frame
     const size_t C = max_channels;
-#define ALLOC(ptr, bytes)                                                            \
-    do {                                                                             \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                          \
-        if (e_ != hipSuccess) { c->last_hip = (int)e_; return fail(e_ == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP); } \
-    } while (0)
-    ALLOC(c->xbuf, C * c->xpitch * sizeof(int16_t));
-    ALLOC(c->ybuf, C * c->ypitch * sizeof(float));
+    int r = M17HIP_OK;   // (the first allocation that fails ends the creation)
+    auto alloc = [&](auto& buf, size_t n) { if (!r) r = alloc_code(c, buf.alloc(n)); };
+    m17hip_ctx::Slab& s = c->slab[0];   // (the second pair: the first time input is staged, stage_prepare)
+    alloc(s.x, C * c->xpitch);
+    alloc(s.y, C * c->ypitch);
+    alloc(s.h, C * c->ypitch);
+    alloc(c->final_h, 2 * C * 4);
+    alloc(c->gate_exp, C);
+    alloc(c->dropped, 2 * C);
+    alloc(c->bert_state, C);
+    alloc(s.dcd, C * c->ticks_cap * 12);
+    alloc(c->dcd_state, C);
+    alloc(c->seq_state, C);
+    alloc(c->ev_state, C);
+    alloc(c->ev_cur, 4 * C);
+    alloc(c->sets[0].recs, C * c->rec_cap);      // (the second set: with the second run, m17hip_demod_run)
+    alloc(c->sets[0].rec_count, C);
+    alloc(c->rec_offsets, C + 1);
+    alloc(c->overflow, 8);
+    alloc(c->tables, 1);
+    alloc(c->taps, 160);
+    alloc(c->taps_skew, FS_NBODY * FS_TAB);
+    alloc(c->llr_edges, 64);
+    alloc(c->level_gain, 8 * (size_t)core::LEVEL_SCHED_N);
+    alloc(c->dbg, (C + 1) * DBG_SLOTS);   // (tools build: per-wave counters of K5)
+    if (r) return fail(r);
+    c->sets[0].ovf = c->overflow; c->sets[1].ovf = c->overflow + 4;
     // (a gate-aware K1 leaves tiles unwritten: what K2's replay may read there must be finite.  A memset is queued, not done, when it returns: wait —
     //  the first run's K1 is on a stream of its own that would not)
-    if (hipMemset(c->ybuf, 0, C * c->ypitch * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);
-    ALLOC(c->hbuf, C * c->ypitch * sizeof(float));
-    ALLOC(c->final_h, 2 * C * 4 * sizeof(float));
-    ALLOC(c->gate_exp, C * sizeof(GateExport));
-    ALLOC(c->dropped, 2 * C * sizeof(uint32_t));
-    ALLOC(c->bert_state, C * sizeof(BertState));
-    hipLaunchKernelGGL(bert_reset_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, 0, (BertState*)c->bert_state, (uint32_t)C);
+    if (hipMemset(s.y, 0, C * c->ypitch * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);
+    hipLaunchKernelGGL(bert_reset_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, 0, c->bert_state, (uint32_t)C);
     if (hipGetLastError() != hipSuccess) return fail(M17HIP_EHIP);
-    ALLOC(c->dcd_table, C * c->ticks_cap * 12 * sizeof(float));
-    ALLOC(c->dcd_state, C * sizeof(DcdState));
-    ALLOC(c->seq_state, C * sizeof(SeqState));
-    ALLOC(c->ev_state, C * sizeof(EvState));
-    ALLOC(c->ev_cur, 4 * C * sizeof(uint32_t));   // [0], [1]: by segment parity; [2], [3]: at the end of a run, by the run's buffer
-    ALLOC(c->sets[0].recs, C * c->rec_cap * sizeof(FrameRec));      // (the second set: with the second run, ensure_set)
-    ALLOC(c->sets[0].rec_count, C * sizeof(uint32_t));
-    ALLOC(c->rec_offsets, (C + 1) * sizeof(uint64_t));
-    ALLOC(c->overflow, 8 * sizeof(uint32_t));
-    c->sets[0].ovf = c->overflow; c->sets[1].ovf = c->overflow + 4;
-    ALLOC(c->tables, sizeof(DecodeTables));
-    ALLOC(c->taps, 160 * sizeof(float));
-    ALLOC(c->taps_skew, FS_NBODY * FS_TAB * sizeof(float));
-    ALLOC(c->llr_edges, 64 * sizeof(float));
-    ALLOC(c->level_gain, 8 * (size_t)core::LEVEL_SCHED_N * sizeof(core::Kalman2Gain));
-    ALLOC(c->dbg, (C + 1) * DBG_SLOTS * sizeof(unsigned long long));   // (tools build: per-wave counters of K5)
-#undef ALLOC
     {
         DecodeTables* t = new DecodeTables;
         build_tables(*t);
@@ -922,12 +956,8 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
         //  process: four rank processes on one GPU, 32 + queues in all, ran tests/test_gpu_gather_ranks.py twice as long.  Not kept: NOTES 6.6)
     }
     if (c->own_main) c->stream = c->own_main;
-    if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
-    if (hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
-    if (hipEventCreateWithFlags(&c->ev_mark, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
-    if (hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
-    for (int q = 0; q < 2; ++q)
-        if (hipEventCreateWithFlags(&c->ev_end[q], hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
+    for (Event* e : {&c->ev_fork, &c->ev_join, &c->ev_mark, &c->ev_tail, &c->ev_end[0], &c->ev_end[1]})
+        if (e->create() != hipSuccess) return fail(M17HIP_EHIP);
     if (hipFuncSetAttribute((const void*)viterbi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (122 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipFuncSetAttribute((const void*)decode_deferred_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DEFER_LDS_BYTES) != hipSuccess)
@@ -935,12 +965,11 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     if (hipFuncSetAttribute((const void*)decode_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (92 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipMemset(c->overflow, 0, 32) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);   // (default-stream work of the creation is through before the context's own streams start)
-    for (hipEvent_t* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch, &c->ev_fetch})
-        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(M17HIP_EHIP);
+    for (Event* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch, &c->ev_fetch})
+        if (e->create() != hipSuccess) return fail(M17HIP_EHIP);
     { std::lock_guard<std::mutex> lk(g_runs.mu); c->seen_overlap = g_runs.overlaps; g_runs.ctxs.push_back(c); }   // (a new context has seen no overlap yet)
     *out = c;
-    const int r = m17hip_demod_reset(c);
-    if (r != M17HIP_OK) { *out = nullptr; return fail(r); }
+    if ((r = m17hip_demod_reset(c)) != M17HIP_OK) { *out = nullptr; return fail(r); }
     return M17HIP_OK;
 }
 
@@ -954,9 +983,6 @@ void m17hip_ctx_destroy(m17hip_ctx* c)
     }
     DeviceGuard guard_(c);
     drain_timing(c);
-    for (auto e : c->pool) hipEventDestroy(e);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
     const bool any_foreign = c->foreign_streams[0] || c->foreign_streams[1] || c->foreign_streams[2] || c->foreign_streams[3];
     if (c->set_mode && !any_foreign && c->own_main && c->side && c->side2 && c->side3) {
         // the set is parked as a SET: the next context of this device gets the same five streams in the same roles
@@ -971,21 +997,7 @@ void m17hip_ctx_destroy(m17hip_ctx* c)
         if (c->side3 && !c->foreign_streams[2]) hipStreamDestroy(c->side3);
         if (c->copy && !c->foreign_streams[3]) hipStreamDestroy(c->copy);
     }
-    if (c->ev_dst) hipEventDestroy(c->ev_dst);
-    if (c->ev_switch) hipEventDestroy(c->ev_switch);
-    if (c->ev_fetch) hipEventDestroy(c->ev_fetch);
-    for (hipEvent_t e : {c->ev_copy, c->ev_in_ready, c->ev_end[0], c->ev_end[1], c->ev_mark, c->ev_tail, c->sets[0].done, c->sets[1].done, c->sets[0].chain, c->sets[1].chain})
-        if (e) hipEventDestroy(e);
-    for (int q = 0; q < 2; ++q)
-        for (auto* v : {&c->ev_fir_[q], &c->ev_dcd_[q], &c->ev_gate_[q], &c->ev_redo_[q], &c->ev_seq_[q]})
-            for (auto e : *v) hipEventDestroy(e);
-    void* ptrs[] = {c->xbuf, c->ybuf, c->dcd_table, c->dcd_state, c->seq_state, c->sets[0].recs, c->sets[0].rec_count, c->sets[0].defer_llr,
-                    c->sets[1].recs, c->sets[1].rec_count, c->sets[1].defer_llr, c->rec_offsets,
-                    c->overflow, c->tables, c->taps, c->taps_skew, c->llr_edges, c->level_gain, c->compact, c->scratch, c->dbg, c->hbuf, c->final_h, c->gate_exp, c->dropped, c->bert_state, c->xstage, c->pkt_state, c->pkt_recs2[0], c->pkt_recs2[1], c->pkt_count2, c->diag_log, c->diag_count, c->defer_hist,
-                    c->yalt, c->halt, c->dcd_alt, c->synth_scratch, c->chan_words, c->bnd, c->ev_ops2[0], c->ev_ops2[1], c->ev_cur, c->ev_state, c->truth, c->first_needed};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);   // (the context is going away: nothing to report to)
-    delete c;
+    delete c;   // (its members give the device memory and the events back — on the context's device: the guard still holds it)
 }
 
 int m17hip_get_stream(m17hip_ctx* c, void** hip_stream)
@@ -1015,34 +1027,26 @@ int m17hip_set_stream(m17hip_ctx* c, void* hip_stream)
 }
 
 // ---- staged input (streaming) -------------------------------------------------------------------------------------------
-// Second slab pair, streams and events: allocated the first time input is staged.
+// Second slab pair, streams and events: allocated the first time input is staged.  (slot is 0 until a staged run begins, and that needs
+// staged input: the second pair is slab[1].)
 static int stage_prepare(m17hip_ctx* c)
 {
-    if (!c->xstage) {
-        auto alloc = [&](void** p, size_t bytes) -> int {
-            const hipError_t e = hipMalloc(p, bytes);
-            if (e != hipSuccess) { c->last_hip = (int)e; return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP; }
-            return M17HIP_OK;
-        };
-        int r;   // (a call that failed half way is picked up where it stopped: nothing is allocated twice)
-        bool fresh_y = false;
-        if (!c->yalt) {
-            if ((r = alloc((void**)&c->yalt, (size_t)c->maxC * c->ypitch * sizeof(float)))) return r;
-            fresh_y = true;
-        }
-        if (!c->halt && (r = alloc((void**)&c->halt, (size_t)c->maxC * c->ypitch * sizeof(float)))) return r;
-        if (!c->dcd_alt && (r = alloc((void**)&c->dcd_alt, (size_t)c->maxC * c->ticks_cap * 12 * sizeof(float)))) return r;
-        if (!c->copy) HIPCHK(c, hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-        // (zeroed as ybuf is — ON the copy stream: the staged run's K1 waits for that stream's ev_in_ready, a memset on the default stream would
-        //  sit behind the run in flight and land in the middle of the staged one)
-        if (fresh_y) HIPCHK(c, hipMemsetAsync(c->yalt, 0, (size_t)c->maxC * c->ypitch * sizeof(float), c->copy));
-        if (!c->ev_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
-        if (!c->ev_in_ready) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in_ready, hipEventDisableTiming));
-        // (from here on the copy stream is the PAYLOAD stream: behind the last reset, as m17hip_demod_reset orders the payload stream it sees)
-        HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_mark, 0));
-        if ((r = alloc((void**)&c->xstage, (size_t)c->maxC * c->xpitch * sizeof(int16_t)))) return r;   // last: its presence says "all of it is there"
-    }
-    return M17HIP_OK;
+    m17hip_ctx::Slab& s = c->slab[1];
+    if (s.x) return M17HIP_OK;
+    int r;   // (a call that failed half way is picked up where it stopped: nothing is allocated twice)
+    const bool fresh_y = !s.y;
+    if (!s.y && (r = alloc_code(c, s.y.alloc((size_t)c->maxC * c->ypitch)))) return r;
+    if (!s.h && (r = alloc_code(c, s.h.alloc((size_t)c->maxC * c->ypitch)))) return r;
+    if (!s.dcd && (r = alloc_code(c, s.dcd.alloc((size_t)c->maxC * c->ticks_cap * 12)))) return r;
+    if (!c->copy) HIPCHK(c, hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
+    // (zeroed as slab[0].y is — ON the copy stream: the staged run's K1 waits for that stream's ev_in_ready, a memset on the default stream would
+    //  sit behind the run in flight and land in the middle of the staged one)
+    if (fresh_y) HIPCHK(c, hipMemsetAsync(s.y, 0, (size_t)c->maxC * c->ypitch * sizeof(float), c->copy));
+    if (!c->ev_copy) HIPCHK(c, c->ev_copy.create());
+    if (!c->ev_in_ready) HIPCHK(c, c->ev_in_ready.create());
+    // (from here on the copy stream is the PAYLOAD stream: behind the last reset, as m17hip_demod_reset orders the payload stream it sees)
+    HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_mark, 0));
+    return alloc_code(c, s.x.alloc((size_t)c->maxC * c->xpitch));   // last: its presence says "all of it is there"
 }
 
 // Where an in-place producer (m17hip_upload_i16, m17hip_upload_i16_device, m17hip_synth_i16) writes: the current input slab on the
@@ -1050,12 +1054,12 @@ static int stage_prepare(m17hip_ctx* c)
 struct InputTarget { int16_t* x = nullptr; hipStream_t st = nullptr; bool stage = false; };
 static int input_target(m17hip_ctx* c, InputTarget& t)
 {
-    if (!c->stage_inputs) { t.x = c->xbuf; t.st = c->stream; t.stage = false; return M17HIP_OK; }
+    if (!c->stage_inputs) { t.x = c->now().x; t.st = c->stream; t.stage = false; return M17HIP_OK; }
     const int r = stage_prepare(c);
     if (r) return r;
     const int other = c->slot ^ 1;
     if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
-    t.x = c->xstage; t.st = c->copy; t.stage = true;
+    t.x = c->other().x; t.st = c->copy; t.stage = true;
     return M17HIP_OK;
 }
 static void input_done(m17hip_ctx* c, const InputTarget& t, uint32_t C, uint32_t T)
@@ -1096,7 +1100,7 @@ int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint
     // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
     const int other = c->slot ^ 1;
     if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
-    HIPCHK(c, hipMemcpy2DAsync(c->xstage + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
+    HIPCHK(c, hipMemcpy2DAsync(c->other().x + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
                                hipMemcpyHostToDevice, c->copy));
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
     c->staged = true; c->staged_h2d = true; c->stagedC = C; c->stagedT = T;
@@ -1114,7 +1118,7 @@ int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C
     const int other = c->slot ^ 1;
     if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
     dim3 grid(((T + 7) / 8 + 255) / 256, C);
-    hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, c->copy, dev, pitch, c->xstage, c->xpitch, T);
+    hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, c->copy, dev, pitch, c->other().x, c->xpitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
     c->staged = true; c->staged_h2d = false; c->stagedC = C; c->stagedT = T;
@@ -1128,7 +1132,7 @@ int m17hip_input_alternate(m17hip_ctx* c, uint32_t C, uint32_t T)
     GUARD(c);
     if (c->front_pending) return M17HIP_ESTATE;
     const int other = c->slot ^ 1;
-    if (!c->xstage || c->slabC[other] != C || c->slabT[other] != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
+    if (!c->other().x || c->slabC[other] != C || c->slabT[other] != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
     c->staged = true; c->staged_h2d = false; c->stagedC = C; c->stagedT = T;
     return M17HIP_OK;
 }
@@ -1153,17 +1157,14 @@ static int synth_impl(m17hip_ctx* c, const m17_synth_params* params, const m17_i
     int r = input_target(c, in);
     if (r) return r;
     // the symbol staging lives in its own allocation: the per-operator scratch may be in use by work queued on the main stream
-    if (need > c->synth_bytes) {
-        if (c->synth_scratch) { HIPCHK(c, hipDeviceSynchronize()); free_dev(c->synth_scratch, &c->last_hip); c->synth_bytes = 0; }
-        HIPCHK(c, hipMalloc(&c->synth_scratch, need));
-        c->synth_bytes = need;
-    }
-    int8_t* sym = reinterpret_cast<int8_t*>(c->synth_scratch);
-    uint32_t* nsym = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->synth_scratch) + sym_bytes);
+    if (need > c->synth_scratch.size() && c->synth_scratch) HIPCHK(c, hipDeviceSynchronize());   // (nothing still reads the one it outgrew)
+    HIPCHK(c, c->synth_scratch.grow(need, &c->last_hip));
+    int8_t* sym = reinterpret_cast<int8_t*>(c->synth_scratch.get());
+    uint32_t* nsym = reinterpret_cast<uint32_t*>(c->synth_scratch + sym_bytes);
     hipLaunchKernelGGL(mod_symbols_kernel, dim3((C + 63) / 64), dim3(64), 0, in.st, mp, C, chan0, sym, sym_pitch, nsym);
     HIPCHK(c, hipGetLastError());
     if (points) {
-        ModImpair* pts = reinterpret_cast<ModImpair*>(reinterpret_cast<char*>(c->synth_scratch) + pts_at);
+        ModImpair* pts = reinterpret_cast<ModImpair*>(c->synth_scratch + pts_at);
         HIPCHK(c, hipMemcpyAsync(pts, points, (size_t)n_points * sizeof(ModImpair), hipMemcpyHostToDevice, in.st));
         hipLaunchKernelGGL(mod_shape_grid_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, pts, n_points, C, T, chan0, sym, sym_pitch, nsym, in.x,
                            c->xpitch);
@@ -1198,7 +1199,7 @@ int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, si
     if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
     if (!c->uploaded) return M17HIP_ESTATE;
-    HIPCHK(c, hipMemcpy2DAsync(host, pitch * sizeof(int16_t), c->xbuf + XPRE, c->xpitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
+    HIPCHK(c, hipMemcpy2DAsync(host, pitch * sizeof(int16_t), c->now().x + XPRE, c->xpitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return M17HIP_OK;
@@ -1230,7 +1231,7 @@ int m17hip_fir_rrc150(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, flo
     int r = launch_fir(c, C, T, flags, c->stream);
     if (r) return r;
     if (out_host) {
-        HIPCHK(c, hipMemcpy2DAsync(out_host, (size_t)T * sizeof(float), c->ybuf + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C,
+        HIPCHK(c, hipMemcpy2DAsync(out_host, (size_t)T * sizeof(float), c->now().y + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C,
                                    hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1243,27 +1244,26 @@ int m17hip_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, float* limit_host, 
     GUARD(c);
     if (c->front_pending) return M17HIP_ESTATE;
     const size_t n = (size_t)C * T;
-    int r = ensure_scratch(c, 5 * n * sizeof(float));
-    if (r) return r;
-    float* limit = (float*)c->scratch;
+    HIPCHK(c, c->scratch.grow(5 * n * sizeof(float), &c->last_hip));
+    float* limit = (float*)c->scratch.get();
     float* corr = limit + n;
     {   // the limit filter is a handful of latency-bound workgroups, the correlations an HBM-bound elementwise pass: side by side
         Timed tm(c, KT_CORR);
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        if (T % 4 == 0) hipLaunchKernelGGL(correlate4_kernel, dim3((T / 4 + 255) / 256, C), dim3(256), 0, c->side, c->ybuf, c->ypitch, corr, C, T, 0u, T);
-        else hipLaunchKernelGGL(correlate_kernel, dim3((T + 255) / 256, C), dim3(256), 0, c->side, c->ybuf, c->ypitch, corr, C, T, 0u, T);
+        if (T % 4 == 0) hipLaunchKernelGGL(correlate4_kernel, dim3((T / 4 + 255) / 256, C), dim3(256), 0, c->side, c->now().y, c->ypitch, corr, C, T, 0u, T);
+        else hipLaunchKernelGGL(correlate_kernel, dim3((T + 255) / 256, C), dim3(256), 0, c->side, c->now().y, c->ypitch, corr, C, T, 0u, T);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(c->ev_join, c->side));
 #ifdef M17_TOOLS
         if (c->limit_form == 0 && T % LP_TILE == 0 && T >= 4 * LP_TILE && (((size_t)C * T) & 3) == 0)
-            hipLaunchKernelGGL(limit_pipe_kernel, dim3((C + LP_CH - 1) / LP_CH), dim3(320), 0, c->stream, c->ybuf, c->ypitch, limit, (size_t)T, C, T, (const float*)nullptr, (float*)nullptr);
+            hipLaunchKernelGGL(limit_pipe_kernel, dim3((C + LP_CH - 1) / LP_CH), dim3(320), 0, c->stream, c->now().y, c->ypitch, limit, (size_t)T, C, T, (const float*)nullptr, (float*)nullptr);
         else
 #endif
         if (T % LR_TILE == 0 && (((size_t)C * T) & 3) == 0)
-            hipLaunchKernelGGL(limit_relay_kernel, dim3((C + LR_CH - 1) / LR_CH), dim3(320), 0, c->stream, c->ybuf, c->ypitch, limit, (size_t)T, C, T, (const float*)nullptr, (float*)nullptr);
+            hipLaunchKernelGGL(limit_relay_kernel, dim3((C + LR_CH - 1) / LR_CH), dim3(320), 0, c->stream, c->now().y, c->ypitch, limit, (size_t)T, C, T, (const float*)nullptr, (float*)nullptr);
         else
-            hipLaunchKernelGGL(limit_kernel, dim3((C + 63) / 64), dim3(64), 0, c->stream, c->ybuf, c->ypitch, limit, C, T);
+            hipLaunchKernelGGL(limit_kernel, dim3((C + 63) / 64), dim3(64), 0, c->stream, c->now().y, c->ypitch, limit, C, T);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     }
@@ -1292,7 +1292,7 @@ int m17hip_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, float* sum
     const uint32_t ticks = T / TICK;
     if (ticks_out) *ticks_out = ticks;
     if (sums_host && ticks)
-        HIPCHK(c, hipMemcpy2DAsync(sums_host, (size_t)ticks * 12 * sizeof(float), c->dcd_table, (size_t)c->ticks_cap * 12 * sizeof(float),
+        HIPCHK(c, hipMemcpy2DAsync(sums_host, (size_t)ticks * 12 * sizeof(float), c->now().dcd, (size_t)c->ticks_cap * 12 * sizeof(float),
                                    (size_t)ticks * 12 * sizeof(float), C, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return M17HIP_OK;
@@ -1305,9 +1305,8 @@ int m17hip_viterbi(m17hip_ctx* c, const int8_t* soft_host, uint32_t n, int kind,
     static const int IN[4] = {488, 296, 420, 402}, OUT[4] = {240, 144, 206, 197};
     const size_t in_b = (size_t)n * IN[kind], out_b = (size_t)n * OUT[kind];
     const size_t o1 = round_up(in_b, 256), o2 = o1 + round_up(out_b, 256);
-    int r = ensure_scratch(c, o2 + (size_t)n * 4);
-    if (r) return r;
-    char* base = (char*)c->scratch;
+    HIPCHK(c, c->scratch.grow(o2 + (size_t)n * 4, &c->last_hip));
+    char* base = c->scratch;
     HIPCHK(c, hipMemcpyAsync(base, soft_host, in_b, hipMemcpyHostToDevice, c->stream));
     {
         Timed tm(c, KT_DEC);
@@ -1327,9 +1326,8 @@ int m17hip_slice_llr(m17hip_ctx* c, const float* sym_host, uint32_t rows, uint32
     GUARD(c);
     const size_t cnt = (size_t)rows * n;
     const size_t o1 = round_up(cnt * 4, 256), o2 = o1 + round_up(cnt * 2, 256);
-    int r = ensure_scratch(c, o2 + cnt * 4);
-    if (r) return r;
-    char* b = (char*)c->scratch;
+    HIPCHK(c, c->scratch.grow(o2 + cnt * 4, &c->last_hip));
+    char* b = c->scratch;
     HIPCHK(c, hipMemcpyAsync(b, sym_host, cnt * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(slice_kernel, dim3((rows + 63) / 64), dim3(64), 0, c->stream, (const float*)b, rows, n, (int8_t*)(b + o1),
                        (float*)(b + o2), c->llr_edges);
@@ -1350,9 +1348,8 @@ int m17hip_decode_frames(m17hip_ctx* c, const int8_t* llr368_host, uint32_t n, c
     auto take = [&](size_t bytes) { const size_t o = off; off += round_up(bytes, 256); return o; };
     const size_t o_llr = take((size_t)n * 368), o_st = take(n), o_state = take(n), o_lich = take(n), o_lsf = take((size_t)n * 30),
                  o_dep = take(n), o_cost = take((size_t)n * 8), o_rec = take((size_t)n * 2 * sizeof(FrameRec)), o_nrec = take(n);
-    int r = ensure_scratch(c, off);
-    if (r) return r;
-    char* b = (char*)c->scratch;
+    HIPCHK(c, c->scratch.grow(off, &c->last_hip));
+    char* b = c->scratch;
     HIPCHK(c, hipMemcpyAsync(b + o_llr, llr368_host, (size_t)n * 368, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_st, sync_type, n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o_state, state_io, n, hipMemcpyHostToDevice, c->stream));
@@ -1400,13 +1397,13 @@ int m17hip_demod_reset(m17hip_ctx* c)
     c->fold_pending = false;   // (the EVM state it would have updated is reset below)
     hipLaunchKernelGGL(seq_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->dcd_state, c->ev_state, c->maxC);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->xbuf, c->xpitch, c->ybuf, c->ypitch, c->maxC);
+    hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, c->maxC);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemset2DAsync(c->hbuf, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
-    hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, (BertState*)c->bert_state, c->maxC);
+    HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
+    hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->bert_state, c->maxC);
     HIPCHK(c, hipGetLastError());
     if (c->pkt_cap) {
-        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, (PacketState*)c->pkt_state, c->maxC);
+        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->pkt_state, c->maxC);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
     }
@@ -1461,9 +1458,9 @@ static int ensure_seg_events(m17hip_ctx* c, int q, uint32_t nseg)
 {
     while (c->ev_fir_[q].size() < nseg) {
         for (auto* v : {&c->ev_fir_[q], &c->ev_dcd_[q], &c->ev_gate_[q], &c->ev_redo_[q], &c->ev_seq_[q]}) {
-            hipEvent_t e;
-            HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            v->push_back(e);
+            Event e;
+            HIPCHK(c, e.create());
+            v->push_back(std::move(e));
         }
     }
     return M17HIP_OK;
@@ -1481,8 +1478,8 @@ static int gate_mode_for_run(m17hip_ctx* c, const SegPlan& sp)
     // 2.2-3.7): the wave slots it takes are free on such input.
     if (c->gate_run && c->dcd_form < 0) c->dcd_latency = true;
     if (!c->truth) {   // (K5 leaves the gate state and counts the closed gates in every mode: the next run's choice comes from it)
-        HIPCHK(c, hipMalloc((void**)&c->truth, 2 * (size_t)c->maxC * sizeof(GateTruth)));
-        HIPCHK(c, hipMalloc((void**)&c->first_needed, (size_t)c->maxC * sizeof(uint32_t)));
+        HIPCHK(c, c->truth.alloc(2 * (size_t)c->maxC));
+        HIPCHK(c, c->first_needed.alloc(c->maxC));
     }
     return M17HIP_OK;
 }
@@ -1534,7 +1531,7 @@ static int launch_gated_fir(m17hip_ctx* c, const SegPlan& sp, uint32_t k, uint32
     const uint32_t t1 = sp.t0(k + 1u), t2 = sp.t0(k + 2u), t3 = sp.t0(k + 3u);
     HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k], 0));
     HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_dcd_[q][k + 2u], 0));
-    hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, c->truth + (size_t)(k & 1u) * c->maxC, c->dcd_table, c->ticks_cap,
+    hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, c->truth + (size_t)(k & 1u) * c->maxC, c->now().dcd, c->ticks_cap,
                        (uint64_t)(c->pos / TICK), (uint64_t)(c->pos + t1), t2 - t1, t3 - t1, c->first_needed, C);
     HIPCHK(c, hipGetLastError());
     int r = launch_fir(c, C, t3 - t2, flags, c->side2, t2, c->first_needed);
@@ -1550,8 +1547,8 @@ static int launch_gate_seg(m17hip_ctx* c, const SegPlan& sp, uint32_t k, hipStre
     const uint32_t t0 = sp.t0(k), len = sp.t0(k + 1) - t0;
     TimedK tm(c, KT_GATE);
     GateParams G{};
-    G.x = c->xbuf + t0; G.xpitch = c->xpitch; G.y = c->ybuf + t0; G.ypitch = c->ypitch; G.h = c->hbuf + t0;
-    G.dcd_table = c->dcd_table; G.ticks_cap = c->ticks_cap; G.state = c->seq_state;
+    G.x = c->now().x + t0; G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
+    G.dcd_table = c->now().dcd; G.ticks_cap = c->ticks_cap; G.state = c->seq_state;
     G.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
     G.only = redo ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (flags by segment parity)
@@ -1585,12 +1582,8 @@ static int begin_staged(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, b
 {
     if (C != c->stagedC || T != c->stagedT) return M17HIP_EINVAL;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
-    const int16_t* xprev = c->xbuf;
-    std::swap(c->xbuf, c->xstage);
-    std::swap(c->ybuf, c->yalt);
-    std::swap(c->hbuf, c->halt);
-    std::swap(c->dcd_table, c->dcd_alt);
-    c->slot ^= 1;
+    const int16_t* xprev = c->now().x;
+    c->slot ^= 1;   // (the staged input's pair becomes now(), the previous run's other())
     c->staged = false;
     c->uploaded = true;
     c->carryT = c->have_run ? c->runT : 0;
@@ -1598,11 +1591,11 @@ static int begin_staged(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, b
     // stream waited for it when the input was staged — m17hip_input_alternate stages without a copy, so wait here as well)
     if (c->slot_used[c->slot]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[c->slot], 0));
     if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)   // the tail of the previous input, where it lies (that slab is only read while its run is in flight)
-        hipLaunchKernelGGL(copy_tail_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->xbuf, c->xpitch, c->carryT);
+        hipLaunchKernelGGL(copy_tail_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch, c->carryT);
     else if (c->carryT) {              // (or its data region was overwritten in place since: the tail its last kernel carried into its prefix)              // a run shorter than the prefix: its tail reaches into its own prefix, which its last kernel rewrites — wait for that
         HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[c->slot ^ 1], 0));
-        hipLaunchKernelGGL(copy_prefix_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->xbuf, c->xpitch);
-    } else HIPCHK(c, hipMemset2DAsync(c->xbuf, c->xpitch * sizeof(int16_t), 0, XPRE * sizeof(int16_t), C, c->copy));
+        hipLaunchKernelGGL(copy_prefix_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch);
+    } else HIPCHK(c, hipMemset2DAsync(c->now().x, c->xpitch * sizeof(int16_t), 0, XPRE * sizeof(int16_t), C, c->copy));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_in_ready, c->copy));
     for (hipStream_t st : {c->side, c->side2}) {
@@ -1674,11 +1667,11 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
             HIPCHK(c, hipGetLastError());
         }
         if (rs.bert && c->bert_state)   // payload consumer: PRBS9 statistics over this run's BERT records
-            hipLaunchKernelGGL(bert_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, (BertState*)c->bert_state, C);
+            hipLaunchKernelGGL(bert_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->bert_state, C);
         if (rs.pkt && c->pkt_cap) {   // payload consumer: packet reassembly over this run's packet records
             HIPCHK(c, hipMemsetAsync(c->pkt_count2 + i, 0, 4, ps));
-            hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, (PacketState*)c->pkt_state, C,
-                               (PacketRec*)c->pkt_recs2[i], c->pkt_cap, c->pkt_count2 + i, c->channel_base);
+            hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->pkt_state, C,
+                               c->pkt_recs2[i], c->pkt_cap, c->pkt_count2 + i, c->channel_base);
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(rs.done, ps));
@@ -1709,9 +1702,8 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     if (!c->uploaded) return M17HIP_ESTATE;
     const size_t n = (size_t)C * T;
     c->fir_latency = false;
-    int r = ensure_scratch(c, 5 * n * sizeof(float) + (size_t)C * 4 * sizeof(float));
-    if (r) return r;
-    float* limit = (float*)c->scratch;
+    HIPCHK(c, c->scratch.grow(5 * n * sizeof(float) + (size_t)C * 4 * sizeof(float), &c->last_hip));
+    float* limit = (float*)c->scratch.get();
     float* corr = limit + n;
     float* lstate = corr + 4 * n;
     // pieces of whole 256-sample tiles (the limit pipeline's granule), about a tenth of the run each; anything else: one piece, the plain kernels
@@ -1719,7 +1711,8 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     const uint32_t piece = tiled ? std::max<uint32_t>((uint32_t)round_up((T + 9) / 10, LP_TILE), 4 * LP_TILE) : T;
     uint32_t npieces = (T + piece - 1) / piece;
     if (tiled && npieces > 1 && T - (npieces - 1) * piece < 4 * LP_TILE) --npieces;   // (a last piece of fewer than four tiles joins the one before it)
-    if ((r = ensure_seg_events(c, c->slot, npieces))) return r;
+    int r = ensure_seg_events(c, c->slot, npieces);
+    if (r) return r;
     auto& ev_fir = c->ev_fir_[c->slot];
     // (Tried: the chain on compute units of its own — hipExtStreamCreateWithCUMask, a quarter of the chip — with the two throughput kernels on
     //  the rest: the chain's pieces 0.79 -> 0.74 ms, the call 8.2 -> 9.0 ms.  What stretches the chain beside them is not its SIMD: NOTES 5.4.)
@@ -1738,27 +1731,27 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
         {   // each kernel timed on the stream it runs on, under its own key: the correlations as "correlator", the limit chain as "limit_track"
             Timed tc(c, KT_CORR, st_corr);
             if (T % 4 == 0 && t0 % 4 == 0 && len % 4 == 0)
-                hipLaunchKernelGGL(correlate4_kernel, dim3((len / 4 + 255) / 256, C), dim3(256), 0, st_corr, c->ybuf, c->ypitch, corr, C, len, t0, T);
+                hipLaunchKernelGGL(correlate4_kernel, dim3((len / 4 + 255) / 256, C), dim3(256), 0, st_corr, c->now().y, c->ypitch, corr, C, len, t0, T);
             else
-                hipLaunchKernelGGL(correlate_kernel, dim3((len + 255) / 256, C), dim3(256), 0, st_corr, c->ybuf, c->ypitch, corr, C, len, t0, T);
+                hipLaunchKernelGGL(correlate_kernel, dim3((len + 255) / 256, C), dim3(256), 0, st_corr, c->now().y, c->ypitch, corr, C, len, t0, T);
         }
         Timed tm(c, KT_GATE, st_chain);
 #ifdef M17_TOOLS
         if (tiled && c->limit_form == 0)
-            hipLaunchKernelGGL(limit_pipe_kernel, dim3(chain_wgs), dim3(320), 0, st_chain, c->ybuf + t0, c->ypitch, limit + t0, (size_t)T, C, len,
+            hipLaunchKernelGGL(limit_pipe_kernel, dim3(chain_wgs), dim3(320), 0, st_chain, c->now().y + t0, c->ypitch, limit + t0, (size_t)T, C, len,
                                (const float*)lstate, lstate);
         else
 #endif
         if (tiled)
-            hipLaunchKernelGGL(limit_relay_kernel, dim3(chain_wgs), dim3(320), 0, st_chain, c->ybuf + t0, c->ypitch, limit + t0, (size_t)T, C, len,
+            hipLaunchKernelGGL(limit_relay_kernel, dim3(chain_wgs), dim3(320), 0, st_chain, c->now().y + t0, c->ypitch, limit + t0, (size_t)T, C, len,
                                (const float*)lstate, lstate);
         else
-            hipLaunchKernelGGL(limit_kernel, dim3((C + 63) / 64), dim3(64), 0, st_chain, c->ybuf, c->ypitch, limit, C, T);
+            hipLaunchKernelGGL(limit_kernel, dim3((C + 63) / 64), dim3(64), 0, st_chain, c->now().y, c->ypitch, limit, C, T);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev_join, st_corr));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    if (y_host) HIPCHK(c, hipMemcpy2DAsync(y_host, (size_t)T * sizeof(float), c->ybuf + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C, hipMemcpyDeviceToHost, c->stream));
+    if (y_host) HIPCHK(c, hipMemcpy2DAsync(y_host, (size_t)T * sizeof(float), c->now().y + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C, hipMemcpyDeviceToHost, c->stream));
     if (limit_host) HIPCHK(c, hipMemcpyAsync(limit_host, limit, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (corr_host) HIPCHK(c, hipMemcpyAsync(corr_host, corr, 4 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1779,9 +1772,9 @@ int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     if (c->gate0_early && c->have_run && c->carryT && !c->profile) {
         const int q = c->slot;
         const SegPlan sp(c, T);
-        for (hipEvent_t e : {c->ev_tail, c->ev_in_ready, c->ev_fir_[q][0], c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, e, 0));
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->yalt, c->ybuf, c->ypitch);
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->halt, c->hbuf, c->ypitch);
+        for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &c->ev_fir_[q][0], &c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
         HIPCHK(c, hipGetLastError());
         if ((r = launch_gate_seg(c, sp, 0, c->side3, false, false, C, flags))) return r;
         HIPCHK(c, hipEventRecord(c->ev_gate_[q][0], c->side3));
@@ -1830,12 +1823,12 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
         if (c->gate0_queued) {
             // (m17hip_demod_front has queued these copies on the replay stream, in front of the first segment's replay)
         } else if (c->carryT) {   // (the previous run ended by carrying its tails into its own prefixes: copy those)
-            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->yalt, c->ybuf, c->ypitch);
-            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->halt, c->hbuf, c->ypitch);
+            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->other().y, c->now().y, c->ypitch);
+            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->other().h, c->now().h, c->ypitch);
             HIPCHK(c, hipGetLastError());
         } else {
-            HIPCHK(c, hipMemset2DAsync(c->ybuf, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
-            HIPCHK(c, hipMemset2DAsync(c->hbuf, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
+            HIPCHK(c, hipMemset2DAsync(c->now().y, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
+            HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
         }
     } else {
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
@@ -1851,14 +1844,14 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     const int si = (c->sets[0].valid || c->sets[1].valid || c->have_run) ? (c->cur ^ 1) : c->cur;
     m17hip_ctx::RecSet& rs = c->sets[si];
     if (!rs.recs) {   // the second set appears with the second run
-        HIPCHK(c, hipMalloc((void**)&rs.recs, (size_t)c->maxC * c->rec_cap_alloc * sizeof(FrameRec)));
-        HIPCHK(c, hipMalloc((void**)&rs.rec_count, (size_t)c->maxC * sizeof(uint32_t)));
+        HIPCHK(c, rs.recs.alloc((size_t)c->maxC * c->rec_cap_alloc));
+        HIPCHK(c, rs.rec_count.alloc(c->maxC));
         HIPCHK(c, hipMemsetAsync(rs.rec_count, 0, (size_t)c->maxC * 4, c->stream));
     }
     if (c->defer_decode && !rs.defer_llr)   // the deferred-frame stores exist only where that mode is used (184 B per record slot)
-        HIPCHK(c, hipMalloc((void**)&rs.defer_llr, (size_t)c->maxC * c->rec_cap_alloc * 46 * sizeof(uint32_t)));
+        HIPCHK(c, rs.defer_llr.alloc((size_t)c->maxC * c->rec_cap_alloc * 46));
     if (c->defer_decode && !c->defer_hist)
-        HIPCHK(c, hipMalloc((void**)&c->defer_hist, (size_t)c->maxC * DEFER_HIST_WORDS * 64 * sizeof(uint32_t)));
+        HIPCHK(c, c->defer_hist.alloc((size_t)c->maxC * DEFER_HIST_WORDS * 64));
     if (rs.valid) {   // the run that wrote it last: its payload work must be through (queued now if nobody asked for it)
         if (rs.pending && (r = flush_payload(c, false, true))) return r;
         HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
@@ -1868,7 +1861,7 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
         if (c->fold_pending) c->ev_par ^= 1;   // (the run before still has a fold pass to come: it keeps its rows, this run writes the other buffer)
         if (!c->ev_ops2[c->ev_par]) {
             c->ev_pitch = c->ev_pitch_override ? c->ev_pitch_override : ev_row_floats(c->maxT);
-            HIPCHK(c, hipMalloc((void**)&c->ev_ops2[c->ev_par], (size_t)c->maxC * c->ev_pitch * sizeof(float)));
+            HIPCHK(c, c->ev_ops2[c->ev_par].alloc((size_t)c->maxC * c->ev_pitch));
         }
     }
     c->dbg_waves = (c->profile || c->wave_times) ? C : 0;
@@ -1878,7 +1871,7 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     // channels serve themselves in segment k (m17_wave_kernel.hpp) — and makes the replay of segment k + 1 good for them again; K5 never
     // waits for it.
     if (!c->bnd) {
-        HIPCHK(c, hipMalloc((void**)&c->bnd, 2 * (size_t)c->maxC * sizeof(Boundary)));
+        HIPCHK(c, c->bnd.alloc(2 * (size_t)c->maxC));
         HIPCHK(c, hipMemsetAsync(c->bnd, 0, 2 * (size_t)c->maxC * sizeof(Boundary), c->stream));
     }
     uint32_t* const drop_of[2] = {c->dropped, c->dropped + c->maxC};   // by segment parity
@@ -1905,10 +1898,10 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     const size_t lds = std::max((size_t)wave_lds_words((int)wpb) * 4, c->seq_lds_bytes ? (size_t)c->seq_lds_bytes : (size_t)SEQ_LDS_BYTES_4);
     auto seq_params = [&](uint32_t k, uint32_t t0, uint32_t len) {
         SeqParams P{};
-        P.h = c->hbuf + t0; P.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
+        P.h = c->now().h + t0; P.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
         P.dropped = drop_of[k & 1u];
-        P.x = c->xbuf + t0; P.xpitch = c->xpitch; P.y = c->ybuf + t0; P.ypitch = c->ypitch;
-        P.dcd_table = c->dcd_table; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
+        P.x = c->now().x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+        P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
         P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
         P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
         P.C = C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (flags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8);
@@ -1976,8 +1969,8 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     HIPCHK(c, hipGetLastError());
     // the tails a run that continues in THESE slabs (input uploaded in place) will find as its prefixes; a staged run takes them from
     // here into the other slab pair itself.  (Before the deferred decode: the next staged run's first replay waits for these, not for that.)
-    hipLaunchKernelGGL(carry_tail_kernel, dim3(C), dim3(64), 0, c->stream, c->xbuf, c->xpitch, c->ybuf, c->ypitch, C, T);
-    hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->hbuf, c->ypitch, T);
+    hipLaunchKernelGGL(carry_tail_kernel, dim3(C), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, C, T);
+    hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().h, c->ypitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_tail, c->stream));
     c->gate0_queued = false;
@@ -2097,14 +2090,10 @@ int m17hip_frames_fetch(m17hip_ctx* c, m17_frame_rec* recs_host, uint64_t capaci
     // one compaction into the context's dense buffer; it is sized for the caller's capacity (records beyond it are not
     // wanted anyway), so a second pass is never needed
     const uint64_t want = std::max<uint64_t>(std::min<uint64_t>(capacity, (uint64_t)rs->C * rs->rec_cap), 1024);
-    if (want > c->compact_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->pay()));   // (nothing still reads the old one)
-        free_dev(c->compact, &c->last_hip); c->compact_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->compact, (size_t)want * sizeof(FrameRec)));
-        c->compact_cap = want;
-    }
+    if (want > c->compact.size()) HIPCHK(c, hipStreamSynchronize(c->pay()));   // (nothing still reads the one it outgrew)
+    HIPCHK(c, c->compact.grow(want, &c->last_hip));
     uint64_t total = 0;
-    const int r = compact_into(c, c->compact, std::min<uint64_t>(capacity, c->compact_cap), &total);
+    const int r = compact_into(c, c->compact, std::min<uint64_t>(capacity, c->compact.size()), &total);
     if (r && r != M17HIP_EOVERFLOW && r != M17HIP_ETRUNC) return r;
     const uint64_t n = std::min(total, capacity);
     if (n) HIPCHK(c, hipMemcpy(recs_host, c->compact, (size_t)n * sizeof(FrameRec), hipMemcpyDeviceToHost));
@@ -2154,9 +2143,8 @@ int m17hip_lsf_info(m17hip_ctx* c, const uint8_t* lsf30_host, uint32_t n, m17_ls
     GUARD(c);
     static_assert(sizeof(LsfInfo) == sizeof(m17_lsf_info) && sizeof(LsfInfo) == 32, "m17_lsf_info layout");
     const size_t in_b = round_up((size_t)n * 30, 256);
-    int r = ensure_scratch(c, in_b + (size_t)n * sizeof(LsfInfo));
-    if (r) return r;
-    uint8_t* din = reinterpret_cast<uint8_t*>(c->scratch);
+    HIPCHK(c, c->scratch.grow(in_b + (size_t)n * sizeof(LsfInfo), &c->last_hip));
+    uint8_t* din = reinterpret_cast<uint8_t*>(c->scratch.get());
     LsfInfo* dout = reinterpret_cast<LsfInfo*>(din + in_b);
     HIPCHK(c, hipMemcpyAsync(din, lsf30_host, (size_t)n * 30, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(lsf_info_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, din, n, dout);
@@ -2188,11 +2176,8 @@ int m17hip_bert_stats(m17hip_ctx* c, m17_bert_stat* stats_host, uint32_t C)
 // The payload stream's buffer of sweep words holds at least n (nothing on that stream still uses the old one: the callers wait for it)
 static int ensure_chan_words(m17hip_ctx* c, uint64_t n)
 {
-    if (n <= c->chan_words_cap) return M17HIP_OK;
-    HIPCHK(c, hipStreamSynchronize(c->pay()));
-    free_dev(c->chan_words, &c->last_hip); c->chan_words_cap = 0;
-    HIPCHK(c, hipMalloc(&c->chan_words, (size_t)n * sizeof(ChanStat)));
-    c->chan_words_cap = n;
+    if (n > c->chan_words.size()) HIPCHK(c, hipStreamSynchronize(c->pay()));
+    HIPCHK(c, c->chan_words.grow(n, &c->last_hip));
     return M17HIP_OK;
 }
 
@@ -2216,8 +2201,8 @@ int m17hip_sweep_stats(m17hip_ctx* c, uint32_t n_points, m17_chan_stat* host, ui
         HIPCHK(c, hipStreamWaitEvent(c->pay(), c->ev_fetch, 0));
     }
     if (int r = ensure_chan_words(c, c->maxC)) return r;
-    hipLaunchKernelGGL(sweep_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), (const BertState*)c->bert_state, c->seq_state, c->overflow, C,
-                       c->channel_base, n_points, (ChanStat*)c->chan_words);
+    hipLaunchKernelGGL(sweep_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), c->bert_state, c->seq_state, c->overflow, C,
+                       c->channel_base, n_points, c->chan_words);
     HIPCHK(c, hipGetLastError());
     uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(host, c->chan_words, (size_t)C * sizeof(ChanStat), hipMemcpyDeviceToHost, c->pay()));
@@ -2233,17 +2218,16 @@ int m17hip_packets_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uin
     if (!c->pkt_cap) return M17HIP_ESTATE;
     if (int fr = flush_payload(c)) return fr;
     const size_t rec_b = round_up((size_t)C * pitch * sizeof(FrameRec), 256);
-    int r = ensure_scratch(c, rec_b + (size_t)C * 4);
-    if (r) return r;
-    FrameRec* drec = reinterpret_cast<FrameRec*>(c->scratch);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->scratch) + rec_b);
+    HIPCHK(c, c->scratch.grow(rec_b + (size_t)C * 4, &c->last_hip));
+    FrameRec* drec = reinterpret_cast<FrameRec*>(c->scratch.get());
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(c->scratch + rec_b);
     // (the payload stream: where the runs' own packet consumer works on the same reassembly state)
     HIPCHK(c, hipMemcpyAsync(drec, recs_host, (size_t)C * pitch * sizeof(FrameRec), hipMemcpyHostToDevice, c->pay()));
     HIPCHK(c, hipMemcpyAsync(dcnt, counts_host, (size_t)C * 4, hipMemcpyHostToDevice, c->pay()));
     const int ps = c->cur;   // (the store of the latest run's set: what m17hip_packets_fetch names unless m17hip_frames_select says otherwise)
     HIPCHK(c, hipMemsetAsync(c->pkt_count2 + ps, 0, 4, c->pay()));
-    hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), drec, pitch, dcnt, (PacketState*)c->pkt_state, C,
-                       (PacketRec*)c->pkt_recs2[ps], c->pkt_cap, c->pkt_count2 + ps, c->channel_base);
+    hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), drec, pitch, dcnt, c->pkt_state, C,
+                       c->pkt_recs2[ps], c->pkt_cap, c->pkt_count2 + ps, c->channel_base);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->pay()));   // the host buffers may go away
     c->pkt_fed = true;
@@ -2295,9 +2279,8 @@ int m17hip_kalman_trace(m17hip_ctx* c, const float* z_host, const uint32_t* dt_h
     GUARD(c);
     const size_t cnt = (size_t)rows * n;
     const size_t o1 = round_up(cnt * 4, 256), o2 = o1 + round_up(cnt * 4, 256);
-    int r = ensure_scratch(c, o2 + cnt * 24);
-    if (r) return r;
-    char* b = (char*)c->scratch;
+    HIPCHK(c, c->scratch.grow(o2 + cnt * 24, &c->last_hip));
+    char* b = c->scratch;
     HIPCHK(c, hipMemcpyAsync(b, z_host, cnt * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b + o1, dt_host, cnt * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(kalman_kernel, dim3((rows + 63) / 64), dim3(64), 0, c->stream, (const float*)b, (const uint32_t*)(b + o1), rows, n, wrap, z0,
@@ -2342,14 +2325,14 @@ int m17hip_comm_create(m17hip_ctx* c, const void* id128, int rank, int nranks, m
     std::memcpy(&id, id128, sizeof(id));
     const ncclResult_t r = R.CommInitRank(&m->comm, nranks, id, rank);
     if (r != ncclSuccess) { c->last_hip = 0x10000 | (int)r; delete m; return M17HIP_ECOMM; }   // (no communicator to ask: the ncclResult_t is left in m17hip_last_hip_error, | 0x10000)
-    hipError_t e = hipMalloc((void**)&m->counts_dev, 2 * (size_t)nranks * sizeof(uint64_t));
+    hipError_t e = m->counts_dev.alloc(2 * (size_t)nranks);
     // (no slot looks like a word of call 1.  ON the stream the gather works on, and waited for: a plain hipMemset runs on the default stream and is not waited
     //  for — with the library's own non-blocking streams it could land behind the first exchange's words: one first gather in a few hundred then read 0xFF..
     //  where a peer's word had been and answered ECOMM.  Found by tests/test_gpu_gather_ranks.py, four ranks, 2 of 25 suite runs)
     if (e == hipSuccess) e = hipMemsetAsync(m->counts_dev, 0xFF, 2 * (size_t)nranks * sizeof(uint64_t), c->pay());
     if (e == hipSuccess) e = hipStreamSynchronize(c->pay());
     if (e == hipSuccess) e = hipHostMalloc((void**)&m->words_host, (2 + 2 * (size_t)nranks) * sizeof(uint64_t), hipHostMallocDefault);
-    if (e != hipSuccess) { c->last_hip = (int)e; free_dev(m->counts_dev); R.CommDestroy(m->comm); delete m; return M17HIP_ENOMEM; }
+    if (e != hipSuccess) { c->last_hip = (int)e; m17hip_comm_destroy(m); return M17HIP_ENOMEM; }
     *out = m;
     return M17HIP_OK;
 }
@@ -2360,12 +2343,11 @@ void m17hip_comm_destroy(m17hip_comm* m)
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     hipSetDevice(m->device);
-    free_dev(m->counts_dev);
-    free_dev(m->gathered);
-    if (m->words_host) { (void)hipHostFree(m->words_host); m->words_host = nullptr; }
-    if (m->comm && !m->dead) rccl().CommDestroy(m->comm);   // (a communicator that was given up is not waited for)
+    const ncclComm_t comm = m->dead ? nullptr : m->comm;   // (a communicator that was given up is not waited for)
+    if (m->words_host) (void)hipHostFree(m->words_host);
+    delete m;   // (its device memory goes before the communicator)
+    if (comm) rccl().CommDestroy(comm);
     if (prev >= 0) hipSetDevice(prev);
-    delete m;
 }
 
 // Every rank makes the same sequence of collective calls whatever goes wrong locally: a failure travels as a status inside the words
@@ -2418,12 +2400,6 @@ static int comm_wait(m17hip_ctx* c, m17hip_comm* m)
     }
 }
 
-static int gather_hip_code(m17hip_ctx* c, hipError_t e)
-{
-    c->last_hip = (int)e;
-    return e == hipErrorOutOfMemory ? M17HIP_ENOMEM : M17HIP_EHIP;
-}
-
 // The gather protocol above over what a rank contributes: `elem` bytes per element; prepare(src, mine, overflow) puts this rank's elements
 // dense on the device (the payload stream's work) and returns its local status.  m17hip_gather_frames[_device]: the selected run's frame
 // records, compacted; m17hip_gather_sweep_stats: the caller's sweep words, uploaded.
@@ -2437,19 +2413,16 @@ static int gather_impl(m17hip_ctx* c, m17hip_comm* m, int root, size_t elem, Pre
     if (m->dead) return M17HIP_ECOMM;
     const Rccl& R = rccl();
     const bool is_root = m->rank == root;
-    auto hip_code = [&](hipError_t e) { return gather_hip_code(c, e); };
+    auto hip_code = [&](hipError_t e) { return alloc_code(c, e); };
     auto comm_failed = [&](ncclResult_t q) { comm_give_up(m, (int)q); return M17HIP_ECOMM; };   // a collective call itself failed: nothing more can be agreed on
     // 1. this rank's elements, dense on the device
     const void* src = nullptr;
     uint64_t mine = 0;
     bool overflow = false;
     int local = prepare(src, mine, overflow);
-    if (is_root && !m->gathered && local == M17HIP_OK) {   // a first staging buffer (grown below when a gathered set outgrows it)
-        const uint64_t want = std::max<uint64_t>(2 * mine * (uint64_t)m->nranks, 1024);
-        if (c->gather_fault != 2 && hipMalloc((void**)&m->gathered, (size_t)want * elem) == hipSuccess) m->gathered_bytes = want * elem;
-        else { m->gathered = nullptr; m->gathered_bytes = 0; }
-    }
-    const uint64_t gathered_cap = m->gathered_bytes / elem;   // (in elements of this call)
+    if (is_root && !m->gathered && local == M17HIP_OK && c->gather_fault != 2)   // a first staging buffer (grown below when a gathered set outgrows it)
+        (void)m->gathered.alloc((size_t)std::max<uint64_t>(2 * mine * (uint64_t)m->nranks, 1024) * elem);
+    const uint64_t gathered_cap = m->gathered.size() / elem;   // (in elements of this call)
     // 2. exchange 1
     const uint64_t serial = (uint64_t)(++m->serial & 0xFFFFu);
     constexpr uint64_t COUNT_MASK = (1ull << 40) - 1;
@@ -2490,10 +2463,10 @@ static int gather_impl(m17hip_ctx* c, m17hip_comm* m, int root, size_t elem, Pre
     //    (only when the records are going to travel: every rank that read exchange 1 comes to the same conclusion about that)
     int rc = unread;
     if (!unread && !local && !remote && is_root && (total > gathered_cap || c->gather_fault == 3)) {   // (fault 3 on the root: grown in any case)
-        free_dev(m->gathered, &c->last_hip); m->gathered_bytes = 0;
+        m->gathered.release(&c->last_hip);
         const uint64_t want = std::max<uint64_t>(total + total / 8, 1024);
-        const hipError_t e = c->gather_fault == 2 ? hipErrorOutOfMemory : hipMalloc((void**)&m->gathered, (size_t)want * elem);
-        if (e != hipSuccess) rc = hip_code(e); else m->gathered_bytes = want * elem;
+        const hipError_t e = c->gather_fault == 2 ? hipErrorOutOfMemory : m->gathered.alloc((size_t)want * elem);
+        if (e != hipSuccess) rc = hip_code(e);
     }
     constexpr uint64_t PHASE2 = 0xA5ull << 56;
     {
@@ -2575,15 +2548,12 @@ static int gather_frames_impl(m17hip_ctx* c, m17hip_comm* m, int root, m17_frame
         int local = selected_set(c) ? M17HIP_OK : M17HIP_ESTATE;
         overflow = false;
         if (local == M17HIP_OK) {
-            int r = c->gather_fault == 1 ? M17HIP_EHIP : compact_into(c, c->compact, c->compact_cap, &mine);
+            int r = c->gather_fault == 1 ? M17HIP_EHIP : compact_into(c, c->compact, c->compact.size(), &mine);
             // the dense buffer must hold ALL of this rank's records before anything is sent from it, whatever the first pass said
             // (an overflowed run reports EOVERFLOW before the truncation is looked at)
-            if ((r == M17HIP_OK || r == M17HIP_ETRUNC || r == M17HIP_EOVERFLOW) && mine > c->compact_cap) {
-                free_dev(c->compact, &c->last_hip); c->compact_cap = 0;
-                const uint64_t want = std::max<uint64_t>(mine + mine / 8, 1024);
-                const hipError_t e = hipMalloc((void**)&c->compact, (size_t)want * sizeof(FrameRec));
-                if (e != hipSuccess) r = gather_hip_code(c, e);
-                else { c->compact_cap = want; r = compact_into(c, c->compact, c->compact_cap, &mine); }
+            if ((r == M17HIP_OK || r == M17HIP_ETRUNC || r == M17HIP_EOVERFLOW) && mine > c->compact.size()) {
+                const hipError_t e = c->compact.grow(std::max<uint64_t>(mine + mine / 8, 1024), &c->last_hip);
+                r = e != hipSuccess ? alloc_code(c, e) : compact_into(c, c->compact, c->compact.size(), &mine);
             }
             overflow = r == M17HIP_EOVERFLOW;
             if (r && !overflow) { local = r; mine = 0; }
@@ -2618,7 +2588,7 @@ int m17hip_gather_sweep_stats(m17hip_ctx* c, m17hip_comm* m, int root, const m17
             if (int r = ensure_chan_words(c, n_mine)) return r;
             hipError_t e = hipMemcpyAsync(c->chan_words, mine_host, (size_t)n_mine * sizeof(ChanStat), hipMemcpyHostToDevice, c->pay());
             if (e == hipSuccess) e = hipStreamSynchronize(c->pay());   // (the caller's memory is not read once the call has returned, whatever happens in it)
-            if (e != hipSuccess) return gather_hip_code(c, e);
+            if (e != hipSuccess) return alloc_code(c, e);
         }
         src = c->chan_words;
         mine = n_mine;
@@ -2659,16 +2629,16 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
         if (int fr = flush_payload(c)) return fr;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipStreamSynchronize(c->pay()));
-        free_dev(c->pkt_recs2[0], &c->last_hip); free_dev(c->pkt_recs2[1], &c->last_hip); c->pkt_cap = 0; c->pkt_fed = false;
+        c->pkt_recs2[0].release(&c->last_hip); c->pkt_recs2[1].release(&c->last_hip); c->pkt_cap = 0; c->pkt_fed = false;
         if (value == 0) return M17HIP_OK;
         if (!c->pkt_state) {
-            HIPCHK(c, hipMalloc(&c->pkt_state, (size_t)c->maxC * sizeof(PacketState)));
-            HIPCHK(c, hipMalloc((void**)&c->pkt_count2, 8));
+            HIPCHK(c, c->pkt_state.alloc(c->maxC));
+            HIPCHK(c, c->pkt_count2.alloc(2));
         }
-        HIPCHK(c, hipMalloc(&c->pkt_recs2[0], (size_t)value * sizeof(PacketRec)));
-        HIPCHK(c, hipMalloc(&c->pkt_recs2[1], (size_t)value * sizeof(PacketRec)));
+        HIPCHK(c, c->pkt_recs2[0].alloc((size_t)value));
+        HIPCHK(c, c->pkt_recs2[1].alloc((size_t)value));
         c->pkt_cap = (uint32_t)value;
-        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, (PacketState*)c->pkt_state, c->maxC);
+        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->pkt_state, c->maxC);
         HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
         HIPCHK(c, hipGetLastError());
         return M17HIP_OK;
@@ -2683,11 +2653,11 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
         if (int fr = flush_payload(c)) return fr;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipStreamSynchronize(c->pay()));
-        free_dev(c->diag_log, &c->last_hip); c->diag_cap = 0;
+        c->diag_log.release(&c->last_hip); c->diag_cap = 0;
         if (value == 0) return M17HIP_OK;
-        if (!c->diag_count) HIPCHK(c, hipMalloc((void**)&c->diag_count, (size_t)c->maxC * 4));
+        if (!c->diag_count) HIPCHK(c, c->diag_count.alloc(c->maxC));
         HIPCHK(c, hipMemsetAsync(c->diag_count, 0, (size_t)c->maxC * 4, c->stream));   // (on the stream the kernels that count into it run on)
-        HIPCHK(c, hipMalloc((void**)&c->diag_log, (size_t)c->maxC * (size_t)value * sizeof(Diag)));
+        HIPCHK(c, c->diag_log.alloc((size_t)c->maxC * (size_t)value));
         c->diag_cap = (uint32_t)value;
         return M17HIP_OK;
     }
@@ -2706,14 +2676,14 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
             c->defer_evm = value != 0;
             hipLaunchKernelGGL(ev_move_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->ev_state, c->maxC, c->defer_evm ? 1 : 0);
             HIPCHK(c, hipGetLastError());
-            if (!c->defer_evm) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_dev(c->ev_ops2[0], &c->last_hip); free_dev(c->ev_ops2[1], &c->last_hip); c->fold_ops = nullptr; }
+            if (!c->defer_evm) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->ev_ops2[0].release(&c->last_hip); c->ev_ops2[1].release(&c->last_hip); c->fold_ops = nullptr; }
         }
         return M17HIP_OK;
     case 18:  // (tests) floats per channel row of deferred EVM operations, 0 = what a run of max_samples can produce: a smaller value makes the overflow flag reachable
         if (value < 0 || value > (1 << 28) || (value & 3)) return M17HIP_EINVAL;
         if (int fr = flush_fold(c)) return fr;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        free_dev(c->ev_ops2[0], &c->last_hip); free_dev(c->ev_ops2[1], &c->last_hip); c->fold_ops = nullptr;
+        c->ev_ops2[0].release(&c->last_hip); c->ev_ops2[1].release(&c->last_hip); c->fold_ops = nullptr;
         c->ev_pitch_override = (uint32_t)value;
         return M17HIP_OK;
     case 15:  // payload frames of running stream / BERT transmissions decoded after the run, one lane per frame (1, default), or in K5 (0)
@@ -2722,8 +2692,8 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
             if (int fr = flush_payload(c)) return fr;
             HIPCHK(c, hipStreamSynchronize(c->stream));
             HIPCHK(c, hipStreamSynchronize(c->pay()));
-            for (auto& rs_ : c->sets) free_dev(rs_.defer_llr, &c->last_hip);
-            free_dev(c->defer_hist, &c->last_hip);
+            for (auto& rs_ : c->sets) rs_.defer_llr.release(&c->last_hip);
+            c->defer_hist.release(&c->last_hip);
         }
         return M17HIP_OK;
     case 30:  // fault injection for m17hip_gather_frames (tests): 0 = none, 1 = this rank's compaction fails, 2 = the root's staging allocation fails,
