@@ -283,9 +283,10 @@ __global__ __launch_bounds__(64) void settle_tail_kernel(SettleParams P)
     L.src = &P.tables->src[0][0]; L.lich_src = P.tables->lich_src;
     auto resolve = [&](uint32_t tag) -> uint32_t {
         const uint32_t slot = tag & ~DEFER_TAG;
+        if (slot >= P.rec_cap) return 0u;   // no such record (defer_frame hands out no tag beyond the slots): the reference's initial viterbi_cost, nothing dereferenced, no tag left in the state
         uint32_t* w = reinterpret_cast<uint32_t*>(P.recs + (size_t)c * P.rec_cap + slot);
         const uint32_t have = (uint32_t)__builtin_amdgcn_readfirstlane((int)w[4]);
-        if (!cost_is_deferred(have) || slot >= P.rec_cap) return have;   // the wave decoded it after all (a missed sync word asked for its cost)
+        if (!cost_is_deferred(have)) return have;   // the wave decoded it after all (a missed sync word asked for its cost)
         const int kind = kind_of_frame_type(w[5] & 0xFFu);
         int stale = (int)w[14];
         const uint32_t* src = P.defer + ((size_t)c * P.rec_cap + slot) * 46;

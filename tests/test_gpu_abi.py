@@ -80,7 +80,8 @@ def test_truncated_fetch_reports_total():
 def test_record_buffer_overflow_is_reported():
     """M17HIP_EOVERFLOW: with the default sizing a run cannot outgrow its record slots (2 callbacks per 1920 samples + 8; 25 short
     runs on a context sized for one frame prove the slots start afresh every run); with the slots cut to 3 per channel (knob 8)
-    the fetch reports the overflow, still returns the records that fit, and a reset clears the condition."""
+    the fetch reports the overflow, still returns the records that fit, leaves no deferred-cost tag in m17_diag, and a reset clears the
+    condition: the next run's records and diagnostics are the oracle's again."""
     x = _signals(8, 48000, seed=3)
     c = m17hip.Context(8, 1920)      # 10 record slots per channel and run
     c.reset()
@@ -101,9 +102,19 @@ def test_record_buffer_overflow_is_reported():
     full = _oracle_flat(x)
     first3 = np.concatenate([full[full["channel"] == ch][:3] for ch in range(8)])
     assert n.value == 24 and got[:24].tobytes() == first3.tobytes()
+    # the input is BERT / voice: payload frames were deferred until the slots ran out, the later ones decoded in place.  No deferred-cost
+    # tag is left in the state the run ends with (settle_tail_kernel resolves tags against the slots that exist): bit 31 only in -1
+    cost = c.diag(8)["viterbi_cost"]
+    assert ((cost >= 0) | (cost == -1)).all(), cost.tolist()
     c.tune(8, 0)
     c.upload(x); c.reset(); c.run()
     assert c.frames().tobytes() == full.tobytes()
+    _, _, diags = ol.demod_batch(x, cap=2 * (x.shape[1] // 1920 + 2) + 4, threads=8)
+    d = c.diag(8)
+    for f in ("dcd", "locked", "sample_index", "sync_index", "clock_index", "viterbi_cost", "n_diag", "demod_state", "n_frames"):
+        assert np.array_equal(d[f], diags[f]), f
+    for f in ("evm", "deviation", "offset", "clock", "dcd_level"):
+        assert np.array_equal(d[f], diags[f], equal_nan=True), f
     # the packet consumer has its own room: more completed packets than tune(7, room) -> EOVERFLOW from the fetch
     p = ol.gen_params(seed=6, kind=4, n_frames=3, lead_in=3072, noise_sigma=300.0, tail_sigma=300.0, lead_sigma=40000.0, total=48000)
     c.tune(7, 2)
