@@ -89,6 +89,20 @@ struct TimedLaunch { Event a, b; int which; };
 
 struct BertState; struct ChanStat; struct PacketState; struct PacketRec;   // (with the host layer's kernels, below)
 
+// What a run looks like: decided once (plan_run) and handed to every launch of the run.  Between m17hip_demod_front and m17hip_demod_run the
+// context keeps it (front_plan), and the run call uses it as it is.
+struct RunPlan {
+    uint32_t C = 0, T = 0, flags = 0, nseg = 0;
+    std::vector<uint32_t> b;      // b[k] = first sample of segment k; b[nseg] = T (segment_bounds)
+    bool staged = false, from_front = false;   // it works on freshly swapped slabs (prefixes still to be carried), not in place; m17hip_demod_front queued its front end
+    uint32_t ramp = 0;            // first segment of its ramp (tuning knob 33), 0 = none
+    bool dcd_latency = false, fir_latency = false;   // K3 as the four-wave latency pipeline (tuning knob 10); few items per K1 workgroup: the chain of K5 launches decides
+    bool gate_run = false;        // it is gate-aware (tuning knob 26)
+    uint32_t front_segs = 0;      // segments whose front end is queued at once (tuning knob 5)
+    bool gate0_queued = false;    // m17hip_demod_front has queued the replay of its first segment (and the prefix copies in front of it)
+    uint32_t t0(uint32_t k) const { return b[std::min<size_t>(k, nseg)]; }
+};
+
 }  // namespace
 
 struct m17hip_ctx {
@@ -127,12 +141,11 @@ struct m17hip_ctx {
     bool slot_used[2] = {false, false};
     bool inplace_after_run = false;   // the current input slab was overwritten in place after its last run: its data region no longer holds that run's tail
     int slot = 0;                     // the slab pair now() names (0 until the first staged run begins)
-    bool staged = false, staged_h2d = false;
+    bool staged = false;
     bool stage_inputs = false;        // tuning knob 16: the in-place producers write the staging slab
     DevBuf<char> synth_scratch;       // symbol staging of m17hip_synth_i16 (and the impairment grid of m17hip_synth_sweep_i16)
     uint32_t runT = 0;                // samples of the latest run
     Event ev_tail;                    // the latest run has carried its tails into its prefixes (K5 is done with its last segment)
-    bool gate0_queued = false;        // m17hip_demod_front has queued the replay of the staged run's first segment (and the prefix copies in front of it)
     int gate0_early = 1;              // tuning knob 25: 1 = it does so
     DevBuf<Boundary> bnd;             // [2][maxC] boundary records (by segment parity): K5 -> the redo of K2 (m17_state.hpp)
     uint32_t front_k1_after = 0;      // tuning knob 21: the matched filter of a staged run starts after K5 of this segment (1-based) of the run before it; 0 = at once
@@ -140,9 +153,8 @@ struct m17hip_ctx {
     bool wave_times = false;          // tuning knob 19: K5 writes each wave's working time per segment (m17hip_debug_counters)
     uint32_t stagedC = 0, stagedT = 0;
     uint32_t slabC[2] = {0, 0}, slabT[2] = {0, 0};   // what the input slab of each pair holds (m17hip_input_alternate)
-    bool front_pending = false;       // m17hip_demod_front has queued the front end of the run that must follow
-    uint32_t frontC = 0, frontT = 0, front_flags = 0, front_segs = 0;
-    bool front_was_staged = false;    // the run whose front end is queued works on freshly swapped slabs (prefixes still to be carried)
+    bool front_queued = false;        // m17hip_demod_front has queued the front end of the run that must follow:
+    RunPlan front_plan;               // that run, as m17hip_demod_run will make it
     uint32_t carryT = 0;              // length of the run whose tail those prefixes come from (0 = none since the reset)
     DevBuf<float> final_h;            // [2][maxC][4], by segment parity
     DevBuf<GateExport> gate_exp;      // [maxC] K2's own state at the end of a segment
@@ -166,13 +178,11 @@ struct m17hip_ctx {
     uint32_t front_first = 0;         // tuning knob 12: segments of K1 that must be complete before the first K5 starts (0 = its own only)
     int redo_form = 0;                // tuning knob 20: the replay's redo beside K5, state only (0, default), or in front of K5 with the history stored (1)
     int dcd_form = -1;                // tuning knob 10: K3 as one wave per 32 channels (0), as the four-wave latency pipeline (1), or chosen per run (-1: the pipeline for runs queued by m17hip_demod_front)
-    bool dcd_latency = false;         // what the launches of the run being queued use
     uint64_t seen_overlap = 0;        // (run registry below) the overlap count this context's previous run saw
     hipEvent_t last_end = nullptr;    // ev_end of the run queued last (not owned)
     uint32_t seg_len = 48000;         // tuning knob 3: samples per K2+K5 segment of a run (0 = the whole run)
     uint32_t seg0_len = 0;            // tuning knob 4: samples of the FIRST segment (a short one starts K5 early; 0 = like the others; measured neutral)
     int64_t seg_ramp = -1;            // tuning knob 33: first segment of a ramp r, 2 r, 4 r, ... up to seg_len (0 = none; -1 = per run: AUTO_RAMP when the run is the only thing in flight)
-    uint32_t ramp_now = 0;            // what the run being queued uses (a staged run: decided when its front end is queued)
     DevBuf<DcdState> dcd_state;
     DevBuf<SeqState> seq_state;
     // Two RECORD SETS that alternate run by run (what a run writes for its consumers: record slots, counts, the deferred-frame store, the
@@ -212,12 +222,10 @@ struct m17hip_ctx {
     int limit_form = 1;              // (tools build only, key 27) configs[1]'s limit filter: 1 = the chain relayed between two waves, 0 = round 4's one recurrence wave
     int fir_form = 1;                // (tools build, key 11) K1: 1 = skewed-pair form on a bounded grid, 0 = round 4's rolled R = 15 form, one workgroup per tile
     int gate_aware = -1;             // tuning knob 26: K1 skips what the carrier cannot be on for (1), never (0), or chosen per run from how much of the previous run's channel-segments ended with the carrier off (-1, default)
-    bool gate_run = false;           // the run being queued is gate-aware
     DevBuf<GateTruth> truth;         // [2][maxC] by segment parity: K5's gate state at the end of a segment
     DevBuf<uint32_t> first_needed;   // [maxC] gate_forecast_kernel -> K1
     uint32_t off_segs_prev = 0, chan_segs_prev = 0;   // channel-segments of the last FETCHED run that ended with the carrier off / in all
     uint32_t fir_grid = 0;           // tuning knob 13: workgroups of K1's grid (0 = default: from the items per workgroup below)
-    bool fir_latency = false;        // the run being queued is one whose chain of K5 launches decides (= it gets K3's latency form): few items per K1 workgroup
     uint32_t n_cu = 256;
     DevBuf<uint32_t> defer_hist;     // [maxC][101][64]: decode_deferred_kernel's decision words (one launch at a time: payload stream)
     bool defer_decode = true;
@@ -234,7 +242,6 @@ struct m17hip_ctx {
                                      // LAST segment, by the run's buffer (ev_par)
     bool fold_pending = false;       // the last EVM fold pass of the latest run (the operations of its last two segments) is still to be made: it rides the next
                                      // run's first limit-filter replay (which K5 of that run waits for anyway), or is made when somebody asks for m17_diag (flush_fold)
-    bool fold_with_decode = false;   // (inside m17hip_demod_run) ... or the latest run's deferred decode, where that is queued behind the run at once
     DevBuf<EvState> ev_state;        // [maxC]
     uint32_t seq_lds_bytes = 0; // tune 14: LDS bytes a workgroup of the sequential kernel asks for (0 = SEQ_LDS_BYTES_4 for four waves)
     DevBuf<float> llr_edges;
@@ -242,7 +249,7 @@ struct m17hip_ctx {
     DevBuf<char> scratch;             // per-operator staging (correlator outputs, viterbi io)
     DcdCoef coef{};
     uint64_t pos = 0;          // samples consumed since reset
-    uint32_t lastC = 0, lastT = 0;
+    uint32_t lastC = 0;
     bool have_run = false;     // a run has been made since the last reset (the stream continues)
     bool uploaded = false;
     bool timing = false;
@@ -744,7 +751,7 @@ constexpr size_t SEQ_LDS_BYTES_4 = 34816;   // see the K5 launch
 // items per workgroup for the runs that get the latency form of K3 (a continued stream, or nothing else in flight), eight for the others, and
 // never fewer workgroups than a CU can hold of them five times over.
 constexpr uint32_t FIR_GRID_PER_CU = 5, FIR_ITEMS_LATENCY = 3, FIR_ITEMS_THROUGHPUT = 8;
-int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_t st, uint32_t t0 = 0, const uint32_t* first_needed = nullptr)
+int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool latency, hipStream_t st, uint32_t t0 = 0, const uint32_t* first_needed = nullptr)
 {
     TimedK tm(c, KT_FIR);
 #ifdef M17_TOOLS
@@ -758,7 +765,7 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_
         const uint64_t items64 = (uint64_t)tiles * C;
         if (items64 > 0xFFFFFFFFull) return M17HIP_EINVAL;
         const uint32_t items = (uint32_t)items64;
-        const uint32_t per = c->fir_latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
+        const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
         if (flags & 1u)
@@ -769,21 +776,22 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
-int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, hipStream_t st, uint32_t t0 = 0)
+// `pos`: the stream position of the slab's first sample (of the run, where t0 names a segment); `latency`: the four-wave pipeline where the piece allows it
+int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t pos, bool latency, hipStream_t st, uint32_t t0 = 0)
 {
     TimedK tm(c, KT_DCD);
     // table rows are numbered from the first tick of the RUN: a later segment continues where the previous one stopped
-    const uint64_t row0 = (c->pos + t0) / TICK - c->pos / TICK;
+    const uint64_t row0 = (pos + t0) / TICK - pos / TICK;
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
-    if (!c->dcd_latency || T % DP_BLK != 0 || (c->pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK)
+    if (!latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK)
         tm.launch(dcd_kernel, dim3((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB)), dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     else if (flags & 1u)
         tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     else
         tm.launch(dcd_pipe_kernel<false>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, c->pos + t0, c->coef, flags);
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1065,13 +1073,13 @@ static int input_target(m17hip_ctx* c, InputTarget& t)
 static void input_done(m17hip_ctx* c, const InputTarget& t, uint32_t C, uint32_t T)
 {
     if (t.stage) {
-        c->staged = true; c->staged_h2d = false; c->stagedC = C; c->stagedT = T;
+        c->staged = true; c->stagedC = C; c->stagedT = T;
         c->slabC[c->slot ^ 1] = C; c->slabT[c->slot ^ 1] = T;
         return;
     }
     c->uploaded = true;
     c->slabC[c->slot] = C; c->slabT[c->slot] = T;
-    c->lastC = C; c->lastT = T;
+    c->lastC = C;
     if (c->have_run) c->inplace_after_run = true;
 }
 
@@ -1079,7 +1087,7 @@ int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T
 {
     if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
     InputTarget in;
     int r = input_target(c, in);
     if (r) return r;
@@ -1094,7 +1102,7 @@ int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint
 {
     if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     int r = stage_prepare(c);
     if (r) return r;
     // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
@@ -1103,7 +1111,7 @@ int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint
     HIPCHK(c, hipMemcpy2DAsync(c->other().x + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
                                hipMemcpyHostToDevice, c->copy));
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->staged_h2d = true; c->stagedC = C; c->stagedT = T;
+    c->staged = true; c->stagedC = C; c->stagedT = T;
     c->slabC[other] = C; c->slabT[other] = T;
     return M17HIP_OK;
 }
@@ -1112,7 +1120,7 @@ int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C
 {
     if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     int r = stage_prepare(c);
     if (r) return r;
     const int other = c->slot ^ 1;
@@ -1121,7 +1129,7 @@ int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C
     hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, c->copy, dev, pitch, c->other().x, c->xpitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->staged_h2d = false; c->stagedC = C; c->stagedT = T;
+    c->staged = true; c->stagedC = C; c->stagedT = T;
     c->slabC[other] = C; c->slabT[other] = T;
     return M17HIP_OK;
 }
@@ -1130,10 +1138,10 @@ int m17hip_input_alternate(m17hip_ctx* c, uint32_t C, uint32_t T)
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     const int other = c->slot ^ 1;
     if (!c->other().x || c->slabC[other] != C || c->slabT[other] != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
-    c->staged = true; c->staged_h2d = false; c->stagedC = C; c->stagedT = T;
+    c->staged = true; c->stagedC = C; c->stagedT = T;
     return M17HIP_OK;
 }
 
@@ -1143,7 +1151,7 @@ static int synth_impl(m17hip_ctx* c, const m17_synth_params* params, const m17_i
 {
     if (!c || !params || C == 0 || T == 0 || C > c->maxC || T > c->maxT || params->n_frames < 0 || params->kind > 4) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
     if (params->kind == 4 && (params->n_frames < 1 || params->n_frames > 33)) return M17HIP_EINVAL;   // 5-bit frame numbers
     static_assert(sizeof(ModParams) == sizeof(m17_synth_params), "parameter block layout");
     static_assert(sizeof(ModImpair) == sizeof(m17_impairment) && sizeof(ModImpair) == 32, "m17_impairment layout");
@@ -1209,7 +1217,7 @@ int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint
 {
     if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
     InputTarget in;
     int r = input_target(c, in);
     if (r) return r;
@@ -1225,11 +1233,9 @@ int m17hip_fir_rrc150(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, flo
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     if (!c->uploaded) return M17HIP_ESTATE;
-    c->fir_latency = false;   // (an operator call: the whole chip is its own)
-    int r = launch_fir(c, C, T, flags, c->stream);
-    if (r) return r;
+    if (int r = launch_fir(c, C, T, flags, false, c->stream)) return r;   // (an operator call: the whole chip is its own)
     if (out_host) {
         HIPCHK(c, hipMemcpy2DAsync(out_host, (size_t)T * sizeof(float), c->now().y + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C,
                                    hipMemcpyDeviceToHost, c->stream));
@@ -1242,7 +1248,7 @@ int m17hip_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, float* limit_host, 
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     const size_t n = (size_t)C * T;
     HIPCHK(c, c->scratch.grow(5 * n * sizeof(float), &c->last_hip));
     float* limit = (float*)c->scratch.get();
@@ -1279,16 +1285,11 @@ int m17hip_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, float* sum
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
     if (flags & ~M17HIP_FLAG_INVERT) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     if (!c->uploaded) return M17HIP_ESTATE;
     // operator-level call: always from a fresh DFT state at stream position 0
     HIPCHK(c, hipMemsetAsync(c->dcd_state, 0, (size_t)C * sizeof(DcdState), c->stream));
-    const uint64_t saved = c->pos;
-    c->pos = 0;
-    c->dcd_latency = c->dcd_form == 1;
-    int r = launch_dcd(c, C, T, flags, c->stream);
-    c->pos = saved;
-    if (r) return r;
+    if (int r = launch_dcd(c, C, T, flags, 0, c->dcd_form == 1, c->stream)) return r;
     const uint32_t ticks = T / TICK;
     if (ticks_out) *ticks_out = ticks;
     if (sums_host && ticks)
@@ -1381,12 +1382,11 @@ int m17hip_demod_reset(m17hip_ctx* c)
 {
     if (!c) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) {   // a front end queued by m17hip_demod_front is abandoned: let it drain, its results are not used
+    if (c->front_queued) {   // a front end queued by m17hip_demod_front is abandoned: let it drain, its results are not used
         HIPCHK(c, hipStreamSynchronize(c->side));
         HIPCHK(c, hipStreamSynchronize(c->side2));
         HIPCHK(c, hipStreamSynchronize(c->side3));
-        c->front_pending = false;
-        c->gate0_queued = false;
+        c->front_queued = false;
     }
     // the payload work of the runs before (deferred decode, consumers: their state is reset below) is waited for ON the device
     // (payload work that was never asked for goes with the stream it belonged to: the consumers' state is reset below)
@@ -1428,31 +1428,57 @@ namespace {
 // where channels leave the limit-filter replay — at the start of a transmission, while sync is being acquired: a channel that leaves it in
 // segment k carries the filter itself to the end of segment k + 1, so what a drop costs the launches it falls into is twice the segment's length.
 constexpr uint32_t AUTO_RAMP = 9600;   // (2400 ... 24 000 measured: NOTES 6.5)
-struct SegPlan {
-    uint32_t T, seg_len, nseg;
-    std::vector<uint32_t> b;   // b[k] = first sample of segment k; b[nseg] = T
-    SegPlan(const m17hip_ctx* c, uint32_t T_) : T(T_)
-    {
-        seg_len = (!c->profile && c->seg_len) ? c->seg_len : T;
-        b.push_back(0);
-        uint32_t pos = 0;
-        if (seg_len < T && !c->profile) {
-            if (c->ramp_now && c->ramp_now < seg_len) {
-                for (uint32_t len = c->ramp_now; len < seg_len && pos + len < T; len *= 2) { pos += len; b.push_back(pos); }
-            } else if (c->seg0_len && c->seg0_len < seg_len) {
-                pos = c->seg0_len; b.push_back(pos);
-            }
+static std::vector<uint32_t> segment_bounds(const m17hip_ctx* c, uint32_t T, uint32_t ramp)   // b[k] = first sample of segment k; the last entry = T
+{
+    const uint32_t seg_len = (!c->profile && c->seg_len) ? c->seg_len : T;
+    std::vector<uint32_t> b(1, 0u);
+    uint32_t pos = 0;
+    if (seg_len < T && !c->profile) {
+        if (ramp && ramp < seg_len) {
+            for (uint32_t len = ramp; len < seg_len && pos + len < T; len *= 2) { pos += len; b.push_back(pos); }
+        } else if (c->seg0_len && c->seg0_len < seg_len) {
+            pos = c->seg0_len; b.push_back(pos);
         }
-        while (pos + seg_len < T) { pos += seg_len; b.push_back(pos); }
-        // Segment starts are multiples of eight samples: the matched filter loads its input sixteen bytes at a time and stores float4s from a
-        // segment's first sample on (an odd start made those accesses misaligned — the hardware splits them, C++ calls it undefined)
-        for (size_t k = 1; k < b.size(); ++k) b[k] &= ~7u;
-        b.erase(std::unique(b.begin(), b.end()), b.end());
-        b.push_back(T);
-        nseg = (uint32_t)b.size() - 1u;
     }
-    uint32_t t0(uint32_t k) const { return b[std::min<size_t>(k, nseg)]; }
-};
+    while (pos + seg_len < T) { pos += seg_len; b.push_back(pos); }
+    // Segment starts are multiples of eight samples: the matched filter loads its input sixteen bytes at a time and stores float4s from a
+    // segment's first sample on (an odd start made those accesses misaligned — the hardware splits them, C++ calls it undefined)
+    for (size_t k = 1; k < b.size(); ++k) b[k] &= ~7u;
+    b.erase(std::unique(b.begin(), b.end()), b.end());
+    b.push_back(T);
+    return b;
+}
+
+// The one place where a run is decided.  `kind`: on input uploaded in place; on staged input, begun by the run call or — a continued stream — by m17hip_demod_front.
+// Is the run the only thing in flight on the device?  (What a context can know of it: runs_overlap — which counts what it is asked: once per run at most, and only
+// where the answer is used.)  Then a step lasts what its chain of launches lasts: K3 and K1 take their latency forms, and a run in place starts with a ramp of short
+// segments (key 33) — one batch at a time 23.65 -> 22.8 ms per 4096 x 480 000; with batches in flight or a continued stream both cost more than they save.
+enum RunKind { RUN_IN_PLACE, RUN_STAGED, RUN_STAGED_FRONT };
+static RunPlan plan_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, RunKind kind)
+{
+    RunPlan p;
+    p.C = C; p.T = T; p.flags = flags; p.staged = kind != RUN_IN_PLACE; p.from_front = kind == RUN_STAGED_FRONT;
+    // kind              runs_overlap is asked                    ramp where key 33 = -1
+    // in place          always                                   AUTO_RAMP when chain-bound
+    // staged (run)      where key 10 = -1 leaves K3 to the run   none: as a rule a continued stream, where the extra launches of a ramp
+    // staged (front)    never: a continued stream, chain-bound   none  cost the chain more than the shorter drops save
+    const bool ask = kind == RUN_IN_PLACE || (kind == RUN_STAGED && c->dcd_form < 0);
+    const bool chain_bound = !ask || !runs_overlap(c);   // what key 10 = -1 goes by
+    p.ramp = c->seg_ramp > 0 ? (uint32_t)c->seg_ramp : (c->seg_ramp < 0 && kind == RUN_IN_PLACE && chain_bound) ? AUTO_RAMP : 0u;
+    p.b = segment_bounds(c, T, p.ramp); p.nseg = (uint32_t)p.b.size() - 1u;
+    p.front_segs = std::min(c->front_ahead ? c->front_ahead : p.nseg, p.nseg);
+    // Gate-aware (m17hip_tune key 26)?  -1: yes when more than a quarter of the channel-segments of the last fetched run ended with the carrier
+    // off (K5 counts them: overflow[3], read with every fetch) — an always-on load keeps K1 running ahead freely.
+    // Needs at least three segments and the default front-end schedule.
+    const bool want = c->gate_aware == 1 || (c->gate_aware < 0 && c->chan_segs_prev && 4ull * c->off_segs_prev > (uint64_t)c->chan_segs_prev);
+    p.gate_run = want && p.nseg >= 3u && !c->front_ahead && !c->profile;
+    p.fir_latency = c->dcd_form < 0 ? chain_bound : c->dcd_form == 1;
+    // A gate-aware run is a run on mostly idle channels: K1 skips most of its work, K5's waves jump from update point to update point — what is left of the step
+    // is K3's chain, which sees every sample whatever the gate does.  Its latency form then (four waves per 32 channels, 1.1-1.9 ms per launch against
+    // 2.2-3.7): the wave slots it takes are free on such input.
+    p.dcd_latency = p.fir_latency || (p.gate_run && c->dcd_form < 0);
+    return p;
+}
 
 static int ensure_seg_events(m17hip_ctx* c, int q, uint32_t nseg)
 {
@@ -1466,85 +1492,77 @@ static int ensure_seg_events(m17hip_ctx* c, int q, uint32_t nseg)
     return M17HIP_OK;
 }
 
-// Is the run being queued gate-aware (m17hip_tune key 26)?  -1: yes when more than a quarter of the channel-segments of the last fetched run
-// ended with the carrier off (K5 counts them: overflow[3], read with every fetch) — an always-on load keeps K1 running ahead freely.
-// Needs at least three segments and the default front-end schedule.
-static int gate_mode_for_run(m17hip_ctx* c, const SegPlan& sp)
-{
-    const bool want = c->gate_aware == 1 || (c->gate_aware < 0 && c->chan_segs_prev && 4ull * c->off_segs_prev > (uint64_t)c->chan_segs_prev);
-    c->gate_run = want && sp.nseg >= 3u && !c->front_ahead && !c->profile;
-    // A gate-aware run is a run on mostly idle channels: K1 skips most of its work, K5's waves jump from update point to update point — what is left of the step
-    // is K3's chain, which sees every sample whatever the gate does.  Its latency form then (four waves per 32 channels, 1.1-1.9 ms per launch against
-    // 2.2-3.7): the wave slots it takes are free on such input.
-    if (c->gate_run && c->dcd_form < 0) c->dcd_latency = true;
-    if (!c->truth) {   // (K5 leaves the gate state and counts the closed gates in every mode: the next run's choice comes from it)
-        HIPCHK(c, c->truth.alloc(2 * (size_t)c->maxC));
-        HIPCHK(c, c->first_needed.alloc(c->maxC));
-    }
-    return M17HIP_OK;
-}
-
 // K3 and K1 of segment k of the run being queued (slab pair c->slot), on the two side streams.
 // The front end of segment k may be held back until K5 of segment k - front_ahead is done (tuning knob 5), to spread it over
 // the step; measured, letting it run ahead freely is faster (K3 is a latency chain of 1.7 ms per segment: held back, it is
 // what K5 ends up waiting for).
-// `which`: bit 0 = K3, bit 1 = K1 (a gate-aware run queues K1 of segment k >= 2 later, behind K5 of segment k - 2: launch_gated_fir).
-static int launch_front_seg(m17hip_ctx* c, const SegPlan& sp, uint32_t k, uint32_t C, uint32_t flags, uint32_t which = 3u)
+// (A gate-aware run queues K1 of segment k >= 2 later, behind K5 of segment k - 2: launch_gated_fir.)
+static int launch_front_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 {
-    if (k >= sp.nseg) return M17HIP_OK;
+    if (k >= p.nseg) return M17HIP_OK;
     const int q = c->slot;
-    const uint32_t ahead = c->front_ahead ? c->front_ahead : sp.nseg;
-    const uint32_t t0 = sp.t0(k), len = sp.t0(k + 1) - t0;
-    if (k >= ahead) {
+    const uint32_t ahead = p.front_segs, t0 = p.t0(k), len = p.t0(k + 1) - t0;
+    if (k >= ahead) {   // (tuning knob 5 is set)
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_seq_[q][k - ahead], 0));
         HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k - ahead], 0));
     }
     if (k == 1) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fir_[q][0], 0));   // segment 0's front end first: K2/K5 wait for it
-    int r2;
-    if (which & 1u) {
-        if ((r2 = launch_dcd(c, C, len, flags, c->side, t0))) return r2;
-        HIPCHK(c, hipEventRecord(c->ev_dcd_[q][k], c->side));
-    }
-    if (which & 2u) {
-        if ((r2 = launch_fir(c, C, len, flags, c->side2, t0))) return r2;
-        HIPCHK(c, hipEventRecord(c->ev_fir_[q][k], c->side2));
-    }
+    if (int r = launch_dcd(c, p.C, len, p.flags, c->pos, p.dcd_latency, c->side, t0)) return r;
+    HIPCHK(c, hipEventRecord(c->ev_dcd_[q][k], c->side));
+    if (p.gate_run && k >= 2u) return M17HIP_OK;
+    if (int r = launch_fir(c, p.C, len, p.flags, p.fir_latency, c->side2, t0)) return r;
+    HIPCHK(c, hipEventRecord(c->ev_fir_[q][k], c->side2));
     return M17HIP_OK;
 }
 
 // The whole front end of a run as far as it can be queued at once: K3 and K1 of every segment — or, for a gate-aware run, K3 of every segment
 // and K1 of the first two (K1 of segment k >= 2 follows K5 of segment k - 2 and its forecast: launch_gated_fir, from the K5 loop).
-static int launch_front_all(m17hip_ctx* c, const SegPlan& sp, uint32_t C, uint32_t flags)
+// A run in place: behind what the main stream holds so far (its input); a staged one is ordered by begin_staged.
+static int launch_front_all(m17hip_ctx* c, const RunPlan& p)
 {
-    int r;
-    for (uint32_t k = 0; k < c->front_segs; ++k)
-        if ((r = launch_front_seg(c, sp, k, C, flags, (c->gate_run && k >= 2u) ? 1u : 3u))) return r;
+    if (int r = ensure_seg_events(c, c->slot, p.nseg)) return r;
+    if (!p.staged) {
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_fork, 0));
+    }
+    for (uint32_t k = 0; k < p.front_segs; ++k)
+        if (int r = launch_front_seg(c, p, k)) return r;
     return M17HIP_OK;
 }
 
 // Gate-aware run, after K5 of segment k has been queued (ev_seq[k] recorded): the forecast for segment k + 2 from K5's gate state at the
 // end of segment k and the table rows of segments k + 1 and k + 2, then K1 of segment k + 2 over what the carrier can be on for.
-static int launch_gated_fir(m17hip_ctx* c, const SegPlan& sp, uint32_t k, uint32_t C, uint32_t flags)
+static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 {
-    if (k + 2u >= sp.nseg) return M17HIP_OK;
+    if (k + 2u >= p.nseg) return M17HIP_OK;
     const int q = c->slot;
-    const uint32_t t1 = sp.t0(k + 1u), t2 = sp.t0(k + 2u), t3 = sp.t0(k + 3u);
+    const uint32_t C = p.C, t1 = p.t0(k + 1u), t2 = p.t0(k + 2u), t3 = p.t0(k + 3u);
     HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k], 0));
     HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_dcd_[q][k + 2u], 0));
     hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, c->truth + (size_t)(k & 1u) * c->maxC, c->now().dcd, c->ticks_cap,
                        (uint64_t)(c->pos / TICK), (uint64_t)(c->pos + t1), t2 - t1, t3 - t1, c->first_needed, C);
     HIPCHK(c, hipGetLastError());
-    int r = launch_fir(c, C, t3 - t2, flags, c->side2, t2, c->first_needed);
-    if (r) return r;
+    if (int r = launch_fir(c, C, t3 - t2, p.flags, p.fir_latency, c->side2, t2, c->first_needed)) return r;
     HIPCHK(c, hipEventRecord(c->ev_fir_[q][k + 2u], c->side2));
     return M17HIP_OK;
 }
 
+// A fold pass of the deferred EVM over `C` channels' operation rows `ops` up to the cursors `upto` (`last`: m17_state.hpp); the pending last
+// pass of the latest run (fold_pending); and none — what a kernel that can take a pass along is given when there is nothing to fold.
+static EvParams ev_fold(const m17hip_ctx* c, const float* ops, uint32_t C, const uint32_t* upto, uint32_t last) { return EvParams{ops, c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, C, upto, last}; }
+static EvParams ev_last_fold(const m17hip_ctx* c, uint32_t last) { return ev_fold(c, c->fold_ops, c->fold_C, c->fold_end, last); }
+static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}; }
+
 // One launch of K2 over segment k of the run whose slabs the context names: the whole segment from K5's state (first segment), ahead of
 // K5 from K2's own state, or the redo of the channels K5 flagged in the previous segment.
-static int launch_gate_seg(m17hip_ctx* c, const SegPlan& sp, uint32_t k, hipStream_t st, bool ahead, bool redo, uint32_t C, uint32_t flags, bool redo_stores = false)
+static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStream_t st, bool ahead, bool redo, bool redo_stores = false)
 {
-    const uint32_t t0 = sp.t0(k), len = sp.t0(k + 1) - t0;
+    if (k == 0 && p.gate0_queued) {   // m17hip_demod_front has queued this one on the replay stream, behind the prefix copies
+        HIPCHK(c, hipStreamWaitEvent(st, c->ev_gate_[c->slot][0], 0));
+        return M17HIP_OK;
+    }
+    const uint32_t C = p.C, t0 = p.t0(k), len = p.t0(k + 1) - t0;
     TimedK tm(c, KT_GATE);
     GateParams G{};
     G.x = c->now().x + t0; G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
@@ -1553,20 +1571,20 @@ static int launch_gate_seg(m17hip_ctx* c, const SegPlan& sp, uint32_t k, hipStre
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
     G.only = redo ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (flags by segment parity)
     G.bnd = redo ? c->bnd + (size_t)(k & 1u) * c->maxC : nullptr;   // (written by K5 of segment k - 1)
-    G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = flags | ((redo && !redo_stores) ? 2u : 0u);
+    G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.flags | ((redo && !redo_stores) ? 2u : 0u);
     G.nblk = (C + GT_CPW - 1) / GT_CPW;
     uint32_t fold_blocks = 0;
     if (ahead && k >= 2 && c->defer_evm && c->ev_ops2[c->ev_par]) {   // (K5 of segment k - 2 is through: its EVM operations ride along, sixteen channels per block)
-        G.ev = EvParams{c->ev_ops2[c->ev_par], c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, C, c->ev_cur + (size_t)((k - 2u) & 1u) * c->maxC, 0u};
+        G.ev = ev_fold(c, c->ev_ops2[c->ev_par], C, c->ev_cur + (size_t)((k - 2u) & 1u) * c->maxC, 0u);
         fold_blocks = ev_fold_blocks(C);
     }
     // The LAST pass of the run before (its buffer is not this run's): beside K5 of this run's first segment, with the replay that runs ahead for the
     // second one — or, for a run of one segment, with this replay, which K5 waits for (that K5 is the one that moves the end-of-run cursors on)
-    if (!redo && c->fold_pending && c->fold_ops && ((sp.nseg >= 2 && ahead && k == 1) || (sp.nseg < 2 && k == 0))) {
+    if (!redo && c->fold_pending && c->fold_ops && ((p.nseg >= 2 && ahead && k == 1) || (p.nseg < 2 && k == 0))) {
         // (beside the replay, last = 2: m17_diag is NOT settled by this pass — K5 of this run's first segment has the state in its hands meanwhile; found by the
         //  sweep: a run whose last segment fires no callback kept the value this pass had put over the first segment's mark.  In front of segment 0, which K5
         //  waits for, it is settled as always)
-        G.ev = EvParams{c->fold_ops, c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, c->fold_C, c->fold_end, k == 0 ? 1u : 2u};
+        G.ev = ev_last_fold(c, k == 0 ? 1u : 2u);
         fold_blocks = ev_fold_blocks(c->fold_C);
         c->fold_pending = false;
     }
@@ -1577,15 +1595,14 @@ static int launch_gate_seg(m17hip_ctx* c, const SegPlan& sp, uint32_t k, hipStre
 
 // A staged run begins: the slab pairs swap, the 152-sample tail of the previous input is carried into the new slab's prefix, and the
 // front end (K1, K3: nothing in them depends on the outcome of the run before) is queued on the side streams — NOT ordered behind
-// the main stream, where K2 / K5 of the previous run may still have a long way to go.
-static int begin_staged(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool from_front)
+// the main stream, where K2 / K5 of the previous run may still have a long way to go.  `p`: the run, decided here.
+static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint32_t flags, RunKind kind)
 {
     if (C != c->stagedC || T != c->stagedT) return M17HIP_EINVAL;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
     const int16_t* xprev = c->now().x;
     c->slot ^= 1;   // (the staged input's pair becomes now(), the previous run's other())
-    c->staged = false;
-    c->uploaded = true;
+    c->staged = false; c->uploaded = true;
     c->carryT = c->have_run ? c->runT : 0;
     // the new slab's prefix, behind the staged copy on the copy stream; the slab pair itself is free since ev_end[slot] (the copy
     // stream waited for it when the input was staged — m17hip_input_alternate stages without a copy, so wait here as well)
@@ -1606,19 +1623,8 @@ static int begin_staged(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, b
         const uint32_t j = std::min(c->front_k1_after, c->last_nseg) - 1u;
         HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[c->slot ^ 1][j], 0));
     }
-    c->ramp_now = c->seg_ramp > 0 ? (uint32_t)c->seg_ramp : 0u;   // (a continued stream: the extra launches of a ramp cost its chain more than the shorter drops save)
-    const SegPlan sp(c, T);
-    int r = ensure_seg_events(c, c->slot, sp.nseg);
-    if (r) return r;
-    const uint32_t ahead = c->front_ahead ? c->front_ahead : sp.nseg;
-    c->dcd_latency = c->dcd_form < 0 ? (from_front || !runs_overlap(c)) : c->dcd_form == 1;
-    c->fir_latency = c->dcd_latency;
-    c->front_segs = std::min(ahead, sp.nseg);
-    if ((r = gate_mode_for_run(c, sp))) return r;
-    if ((r = launch_front_all(c, sp, C, flags))) return r;
-    c->front_was_staged = true;
-    c->frontC = C; c->frontT = T; c->front_flags = flags;
-    return M17HIP_OK;
+    p = plan_run(c, C, T, flags, kind);
+    return launch_front_all(c, p);
 }
 
 }  // namespace
@@ -1629,8 +1635,7 @@ static int flush_fold(m17hip_ctx* c)
     if (!c->fold_pending) return M17HIP_OK;
     c->fold_pending = false;
     if (!c->fold_ops) return M17HIP_OK;
-    hipLaunchKernelGGL(evm_deferred_kernel, dim3(ev_fold_blocks(c->fold_C)), dim3(64), 0, c->stream,
-                       EvParams{c->fold_ops, c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, c->fold_C, c->fold_end, 1u});
+    hipLaunchKernelGGL(evm_deferred_kernel, dim3(ev_fold_blocks(c->fold_C)), dim3(64), 0, c->stream, ev_last_fold(c, 1u));
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1640,7 +1645,8 @@ static int flush_fold(m17hip_ctx* c)
 // `selected_only`: up to the run the fetch family names (m17hip_frames_select) — a fetch of run k must not queue the work of run k + 1, whose
 // chain may have just begun: everything behind it on the payload stream would wait for that run's end.
 // `older_only`: the run before the latest alone (its record set is about to be written again).
-static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_only = false)
+// `fold_beside_decode`: the latest run's pending last fold pass rides its deferred decode (m17hip_demod_run, where that is queued behind the run at once).
+static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_only = false, bool fold_beside_decode = false)
 {
     for (int j = 0; j < 2; ++j) {
         const int i = j == 0 ? (c->cur ^ 1) : c->cur;   // the older run first
@@ -1655,10 +1661,10 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
             DeferParams D{};
             D.recs = rs.recs; D.rec_cap = rs.rec_cap; D.rec_count = rs.rec_count; D.defer = rs.defer_llr; D.hist = c->defer_hist; D.tables = c->tables;
             D.state = c->seq_state; D.diag_log = c->diag_cap ? c->diag_log : nullptr; D.diag_cap = c->diag_cap; D.diag_count = c->diag_count; D.C = C;
-            D.ev = EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u};
+            D.ev = ev_no_fold(C);
             uint32_t fold_blocks = 0;
-            if (c->fold_with_decode && c->fold_pending && i == c->cur && c->fold_ops) {   // (the latest run's last fold pass, beside its decode on the main stream)
-                D.ev = EvParams{c->fold_ops, c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, c->fold_C, c->fold_end, 1u};
+            if (fold_beside_decode && c->fold_pending && i == c->cur && c->fold_ops) {   // (the latest run's last fold pass, beside its decode on the main stream)
+                D.ev = ev_last_fold(c, 1u);
                 fold_blocks = ev_fold_blocks(C);
                 c->fold_pending = false;
             }
@@ -1698,10 +1704,9 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     if (!c->uploaded) return M17HIP_ESTATE;
     const size_t n = (size_t)C * T;
-    c->fir_latency = false;
     HIPCHK(c, c->scratch.grow(5 * n * sizeof(float) + (size_t)C * 4 * sizeof(float), &c->last_hip));
     float* limit = (float*)c->scratch.get();
     float* corr = limit + n;
@@ -1724,7 +1729,7 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     if (tiled) HIPCHK(c, hipMemsetAsync(lstate, 0, (size_t)C * 4 * sizeof(float), st_chain));
     for (uint32_t k = 0; k < npieces; ++k) {
         const uint32_t t0 = k * piece, len = k + 1 < npieces ? piece : T - t0;
-        if ((r = launch_fir(c, C, len, flags, st_fir, t0))) return r;
+        if ((r = launch_fir(c, C, len, flags, false, st_fir, t0))) return r;
         HIPCHK(c, hipEventRecord(ev_fir[k], st_fir));
         HIPCHK(c, hipStreamWaitEvent(st_corr, ev_fir[k], 0));
         HIPCHK(c, hipStreamWaitEvent(st_chain, ev_fir[k], 0));
@@ -1758,91 +1763,28 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     return M17HIP_OK;
 }
 
-int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
+// The steps of a run (m17hip_demod_run), each on the context, the run's plan and its record set.  First: a staged run's y / h prefixes, on the main stream.
+static int carry_staged_prefixes(m17hip_ctx* c, const RunPlan& p)
 {
-    if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_pending || !c->staged) return M17HIP_ESTATE;
-    int r = begin_staged(c, C, T, flags, true);
-    if (r) return r;
-    c->front_pending = true;
-    // The replay of the staged run's first segment (K2 from K5's state) needs the run in flight only up to its last K5 launch and its
-    // carried tails — not its deferred decode, its consumers, the caller's fetch of its records or the launch of the next run from the
-    // host: queued here, on the replay stream, it runs beside all of those.
-    if (c->gate0_early && c->have_run && c->carryT && !c->profile) {
-        const int q = c->slot;
-        const SegPlan sp(c, T);
-        for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &c->ev_fir_[q][0], &c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
+    // K2 / K5 read the input slab too (snapshots, spliced-history FIR outputs); the y / h prefixes (the correlator ring and the limit
+    // filter's history reach back into the previous run) come from the previous run's slabs, final now that its K5 is done
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in_ready, 0));
+    if (p.gate0_queued) return M17HIP_OK;   // (m17hip_demod_front has queued these copies on the replay stream, in front of the first segment's replay)
+    if (c->carryT) {   // (the previous run ended by carrying its tails into its own prefixes: copy those)
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(p.C), dim3(64), 0, c->stream, c->other().y, c->now().y, c->ypitch);
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(p.C), dim3(64), 0, c->stream, c->other().h, c->now().h, c->ypitch);
         HIPCHK(c, hipGetLastError());
-        if ((r = launch_gate_seg(c, sp, 0, c->side3, false, false, C, flags))) return r;
-        HIPCHK(c, hipEventRecord(c->ev_gate_[q][0], c->side3));
-        c->gate0_queued = true;
+    } else {
+        HIPCHK(c, hipMemset2DAsync(c->now().y, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), p.C, c->stream));
+        HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), p.C, c->stream));
     }
     return M17HIP_OK;
 }
 
-int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
+// The run's record set `rs` is made free, and what the run needs beside the slabs is allocated the first time it is needed.
+static int prepare_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
 {
-    if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
-    GUARD(c);
     int r;
-    bool staged_run = false;
-    const bool from_front = c->front_pending;
-    if (c->front_pending) {   // the front end is already on its way (m17hip_demod_front): this call must be the run it was queued for
-        if (C != c->frontC || T != c->frontT || flags != c->front_flags) return M17HIP_ESTATE;
-        c->front_pending = false;
-        staged_run = true;
-    } else if (c->staged) {   // input staged by m17hip_upload_i16_async and friends: swap the slabs, queue the front end
-        if ((r = begin_staged(c, C, T, flags, false))) return r;
-        staged_run = true;
-    }
-    if (!c->uploaded) return M17HIP_ESTATE;
-    if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
-    // The run is processed in segments.  K1 (throughput-bound, the whole chip) and K3 (latency-bound lone waves) of ALL segments
-    // are queued on two side streams; the main stream runs K2 -> K5 per segment as soon as that segment's K1 and K3 are done,
-    // so the front end of segment k+1 fills the issue slots K5 of segment k leaves idle (its tail above all).
-    // Every K2 starts a fresh speculation from K5's own state, so a channel that had to drop it (forced unlock) carries the
-    // limit filter itself only until the end of its segment.
-    // Is this run the only thing in flight on the device?  (What a context can know of it: runs_overlap.)  Then a step lasts what its chain of launches lasts:
-    // K3 and K1 take their latency forms, and the run starts with a ramp of short segments (key 33) — one batch at a time 23.65 -> 22.8 ms per
-    // 4096 x 480 000; with batches in flight or a continued stream both cost more than they save.
-    const bool alone = !staged_run && !runs_overlap(c);
-    if (!staged_run) c->ramp_now = c->seg_ramp >= 0 ? (uint32_t)c->seg_ramp : (alone ? AUTO_RAMP : 0u);
-    const SegPlan sp(c, T);
-    const uint32_t nseg = sp.nseg;
-    const int q = c->slot;
-    if ((r = ensure_seg_events(c, q, nseg))) return r;
-    auto& ev_fir = c->ev_fir_[q]; auto& ev_dcd = c->ev_dcd_[q]; auto& ev_gate = c->ev_gate_[q]; auto& ev_redo = c->ev_redo_[q]; auto& ev_seq = c->ev_seq_[q];
-    const uint32_t ahead = c->front_ahead ? c->front_ahead : nseg;
-    if (staged_run) {
-        // K2 / K5 read the input slab too (snapshots, spliced-history FIR outputs); the y / h prefixes (the correlator ring and the limit
-        // filter's history reach back into the previous run) come from the previous run's slabs, final now that its K5 is done
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in_ready, 0));
-        if (c->gate0_queued) {
-            // (m17hip_demod_front has queued these copies on the replay stream, in front of the first segment's replay)
-        } else if (c->carryT) {   // (the previous run ended by carrying its tails into its own prefixes: copy those)
-            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->other().y, c->now().y, c->ypitch);
-            hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->other().h, c->now().h, c->ypitch);
-            HIPCHK(c, hipGetLastError());
-        } else {
-            HIPCHK(c, hipMemset2DAsync(c->now().y, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
-            HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), C, c->stream));
-        }
-    } else {
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_fork, 0));
-        c->dcd_latency = c->dcd_form < 0 ? alone : c->dcd_form == 1;
-        c->fir_latency = c->dcd_latency;
-        c->front_segs = std::min(ahead, nseg);
-        if ((r = gate_mode_for_run(c, sp))) return r;
-        if ((r = launch_front_all(c, sp, C, flags))) return r;
-    }
-    // this run's record set: the one the run before the previous one wrote (its payload work is long through; waited for on the device)
-    const int si = (c->sets[0].valid || c->sets[1].valid || c->have_run) ? (c->cur ^ 1) : c->cur;
-    m17hip_ctx::RecSet& rs = c->sets[si];
     if (!rs.recs) {   // the second set appears with the second run
         HIPCHK(c, rs.recs.alloc((size_t)c->maxC * c->rec_cap_alloc));
         HIPCHK(c, rs.rec_count.alloc(c->maxC));
@@ -1864,24 +1806,54 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
             HIPCHK(c, c->ev_ops2[c->ev_par].alloc((size_t)c->maxC * c->ev_pitch));
         }
     }
-    c->dbg_waves = (c->profile || c->wave_times) ? C : 0;
-    // K2 launches: the whole first segment from K5's state; every later segment AHEAD of K5 from the replay's own end state (replay
-    // stream); and the REDO: for the channels that left the replay in segment k - 1 (a forced dcd.unlock()), the replay's state at the
-    // end of segment k is re-derived from K5's boundary record, beside K5 of segment k on the replay stream.  It stores nothing — those
-    // channels serve themselves in segment k (m17_wave_kernel.hpp) — and makes the replay of segment k + 1 good for them again; K5 never
-    // waits for it.
+    c->dbg_waves = (c->profile || c->wave_times) ? p.C : 0;
     if (!c->bnd) {
         HIPCHK(c, c->bnd.alloc(2 * (size_t)c->maxC));
         HIPCHK(c, hipMemsetAsync(c->bnd, 0, 2 * (size_t)c->maxC * sizeof(Boundary), c->stream));
     }
-    uint32_t* const drop_of[2] = {c->dropped, c->dropped + c->maxC};   // by segment parity
-    auto launch_gate = [&](uint32_t k, hipStream_t st, bool ahead, bool redo, bool redo_stores = false) -> int {
-        if (k == 0 && c->gate0_queued) {   // m17hip_demod_front has queued this one on the replay stream, behind the prefix copies
-            HIPCHK(c, hipStreamWaitEvent(st, ev_gate[0], 0));
-            return M17HIP_OK;
-        }
-        return launch_gate_seg(c, sp, k, st, ahead, redo, C, flags, redo_stores);
-    };
+    if (!c->truth) {   // (K5 leaves the gate state and counts the closed gates in every mode: the next run's choice comes from it)
+        HIPCHK(c, c->truth.alloc(2 * (size_t)c->maxC));
+        HIPCHK(c, c->first_needed.alloc(c->maxC));
+    }
+    return M17HIP_OK;
+}
+
+// K5's parameters for segment k
+static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet& rs, uint32_t k)
+{
+    const uint32_t t0 = p.t0(k), len = p.t0(k + 1) - t0;
+    SeqParams P{};
+    P.h = c->now().h + t0; P.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
+    P.dropped = c->dropped + (size_t)(k & 1u) * c->maxC;   // (by segment parity)
+    P.x = c->now().x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+    P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
+    P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
+    P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
+    P.C = p.C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (p.flags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8);
+    P.kalman_order = c->kalman_order; P.channel_base = c->channel_base;
+    P.level_gain = c->level_gain + (size_t)(c->kalman_order & 7u) * core::LEVEL_SCHED_N;
+    P.diag_log = c->diag_cap ? c->diag_log : nullptr; P.diag_cap = c->diag_cap; P.diag_count = c->diag_count;
+    P.defer = c->defer_decode ? rs.defer_llr : nullptr;
+    if (c->defer_evm) { P.ev_ops = c->ev_ops2[c->ev_par]; P.ev_pitch = c->ev_pitch; P.ev_cursor_out = c->ev_cur + (size_t)(k + 1u == p.nseg ? 2u + (uint32_t)c->ev_par : (k & 1u)) * c->maxC; }
+    P.bnd_out = c->bnd + (size_t)((k + 1u) & 1u) * c->maxC;
+    P.truth_out = c->truth ? c->truth + (size_t)(k & 1u) * c->maxC : nullptr;
+    P.dbg = (c->profile || c->wave_times) ? c->dbg : nullptr;
+    P.dropped_in = (k > 0 && c->redo_form != 1) ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (redo in front: nobody starts a segment off the replay)
+    return P;
+}
+
+// The chain of the run: K2 -> K5 per segment on the main stream, the replay on its stream, and what of the front end follows K5 (tuning knob 5; a gate-aware run's K1).
+// K2 launches: the whole first segment from K5's state; every later segment AHEAD of K5 from the replay's own end state (replay
+// stream); and the REDO: for the channels that left the replay in segment k - 1 (a forced dcd.unlock()), the replay's state at the
+// end of segment k is re-derived from K5's boundary record, beside K5 of segment k on the replay stream.  It stores nothing — those
+// channels serve themselves in segment k (m17_wave_kernel.hpp) — and makes the replay of segment k + 1 good for them again; K5 never
+// waits for it.
+static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet& rs)
+{
+    int r;
+    const int q = c->slot;
+    const uint32_t nseg = p.nseg, ahead = p.front_segs;   // (ahead < nseg: tuning knob 5 is set)
+    auto& ev_fir = c->ev_fir_[q]; auto& ev_dcd = c->ev_dcd_[q]; auto& ev_gate = c->ev_gate_[q]; auto& ev_redo = c->ev_redo_[q]; auto& ev_seq = c->ev_seq_[q];
     // Redo policy (m17hip_tune key 20).  IN FRONT of K5: the redo stores the history of segment k for the channels that left the replay in
     // k - 1 before K5(k) starts — sixteen channels per instruction instead of one wave each carrying the filter itself through segment k
     // (3 dependent instructions per sample): fewer instructions, but 1-2 ms of replay latency on the K5 chain of every segment that follows
@@ -1890,70 +1862,39 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     // beside K5 wins (24.7 against 28.0 ms, 26.3 against 28.9); with round 4's matched filter several independent batches in flight were
     // 1.4 % faster with the redo in front (NOTES 4.11), with round 5's they are 5 % slower (22.6 against 21.4: NOTES 5.5).  Default: beside.
     const bool redo_front = c->redo_form == 1;
-    // one wave per channel, four waves per workgroup
-    constexpr uint32_t wpb = 4;
-    const dim3 grid((C + wpb - 1) / wpb), block(64 * wpb);
+    constexpr uint32_t wpb = 4;   // one wave per channel, four waves per workgroup
+    const dim3 grid((p.C + wpb - 1) / wpb), block(64 * wpb);
     // LDS: what the workgroup needs (31.8 KB for four waves), padded so that a CU holds FOUR of them and not five — the rest of
     // the CU (24 KB, 128 VGPRs per SIMD) is where a K2 wave or a K1 workgroup runs beside them without taking a K5 slot
     const size_t lds = std::max((size_t)wave_lds_words((int)wpb) * 4, c->seq_lds_bytes ? (size_t)c->seq_lds_bytes : (size_t)SEQ_LDS_BYTES_4);
-    auto seq_params = [&](uint32_t k, uint32_t t0, uint32_t len) {
-        SeqParams P{};
-        P.h = c->now().h + t0; P.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
-        P.dropped = drop_of[k & 1u];
-        P.x = c->now().x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
-        P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
-        P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
-        P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
-        P.C = C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (flags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8);
-        P.kalman_order = c->kalman_order; P.channel_base = c->channel_base;
-        P.level_gain = c->level_gain + (size_t)(c->kalman_order & 7u) * core::LEVEL_SCHED_N;
-        P.diag_log = c->diag_cap ? c->diag_log : nullptr; P.diag_cap = c->diag_cap; P.diag_count = c->diag_count;
-        P.defer = c->defer_decode ? rs.defer_llr : nullptr;
-        if (c->defer_evm) { P.ev_ops = c->ev_ops2[c->ev_par]; P.ev_pitch = c->ev_pitch; P.ev_cursor_out = c->ev_cur + (size_t)(k + 1u == nseg ? 2u + (uint32_t)c->ev_par : (k & 1u)) * c->maxC; }
-        P.bnd_out = c->bnd + (size_t)((k + 1u) & 1u) * c->maxC;
-        P.truth_out = c->truth ? c->truth + (size_t)(k & 1u) * c->maxC : nullptr;
-        P.dbg = (c->profile || c->wave_times) ? c->dbg : nullptr;
-        return P;
-    };
     HIPCHK(c, hipMemsetAsync(rs.ovf, 0, 4, c->stream));       // record overflow of THIS run
     HIPCHK(c, hipMemsetAsync(rs.ovf + 3, 0, 4, c->stream));   // channel-segments of THIS run that end with the carrier off (K5 counts)
     for (uint32_t k = 0; k < nseg; ++k) {
-        const uint32_t t0 = sp.t0(k), len = sp.t0(k + 1) - t0;
         HIPCHK(c, hipStreamWaitEvent(c->stream, ev_fir[k], 0));
         HIPCHK(c, hipStreamWaitEvent(c->stream, ev_dcd[k], 0));
         if (k == 0 && c->front_first > 1 && ahead >= nseg) {   // the matched filter of the first `front_first` segments has the chip to itself
             const uint32_t last = std::min(c->front_first, nseg) - 1u;
             HIPCHK(c, hipStreamWaitEvent(c->stream, ev_fir[last], 0));
         }
-        {
-            // replay stream: ahead(k) -> redo(k) [after K5(k - 1): its flags and its state] -> ahead(k + 1) -> ...; the main stream only
-            // ever waits for an `ahead`
-            if (k == 0) {
-                if ((r = launch_gate(0, c->stream, false, false))) return r;
-                HIPCHK(c, hipEventRecord(ev_redo[0], c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->side3, ev_redo[0], 0));
-            } else if (redo_front) {
-                HIPCHK(c, hipStreamWaitEvent(c->stream, ev_gate[k], 0));
-                if ((r = launch_gate(k, c->stream, false, true, true))) return r;   // (flagged channels only: from their boundary records, history stored)
-                HIPCHK(c, hipEventRecord(ev_redo[k], c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->side3, ev_redo[k], 0));
-            } else {
-                HIPCHK(c, hipStreamWaitEvent(c->stream, ev_gate[k], 0));
-                if (k + 1 < nseg) {
-                    HIPCHK(c, hipStreamWaitEvent(c->side3, ev_seq[k - 1], 0));
-                    if ((r = launch_gate(k, c->side3, false, true))) return r;
-                }
-            }
-            if (k + 1 < nseg) {
-                HIPCHK(c, hipStreamWaitEvent(c->side3, ev_fir[k + 1], 0));
-                HIPCHK(c, hipStreamWaitEvent(c->side3, ev_dcd[k + 1], 0));
-                if ((r = launch_gate(k + 1, c->side3, true, false))) return r;
-                HIPCHK(c, hipEventRecord(ev_gate[k + 1], c->side3));
-            }
+        // replay stream: ahead(k) -> redo(k) [after K5(k - 1): its flags and its state] -> ahead(k + 1) -> ...; the main stream only
+        // ever waits for an `ahead`
+        if (k > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_gate[k], 0));
+        if (k == 0 || redo_front) {   // the first segment whole; a redo in front: flagged channels only, from their boundary records, history stored
+            if ((r = launch_gate_seg(c, p, k, c->stream, false, k > 0, k > 0))) return r;
+            HIPCHK(c, hipEventRecord(ev_redo[k], c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_redo[k], 0));
+        } else if (k + 1 < nseg) {
+            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_seq[k - 1], 0));
+            if ((r = launch_gate_seg(c, p, k, c->side3, false, true))) return r;
+        }
+        if (k + 1 < nseg) {
+            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_fir[k + 1], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_dcd[k + 1], 0));
+            if ((r = launch_gate_seg(c, p, k + 1, c->side3, true, false))) return r;
+            HIPCHK(c, hipEventRecord(ev_gate[k + 1], c->side3));
         }
         TimedK tm(c, KT_SEQ);
-        SeqParams P = seq_params(k, t0, len);
-        P.dropped_in = (k > 0 && !redo_front) ? drop_of[(k - 1u) & 1u] : nullptr;   // (redo in front: nobody starts a segment off the replay)
+        const SeqParams P = seq_params(c, p, rs, k);
 #ifdef M17_TOOLS
         if (c->profile) tm.launch((demod_wave_kernel<4, true>), grid, block, lds, c->stream, P);
         else if (c->wave_times) tm.launch((demod_wave_kernel<4, false, true>), grid, block, lds, c->stream, P);
@@ -1963,22 +1904,30 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
         else tm.launch(demod_wave_kernel<4>, grid, block, lds, c->stream, P);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(ev_seq[k], c->stream));
-        if (k + ahead < nseg && (r = launch_front_seg(c, sp, k + ahead, C, flags))) return r;
-        if (c->gate_run && (r = launch_gated_fir(c, sp, k, C, flags))) return r;
+        if (k + ahead < nseg && (r = launch_front_seg(c, p, k + ahead))) return r;
+        if (p.gate_run && (r = launch_gated_fir(c, p, k))) return r;
     }
     HIPCHK(c, hipGetLastError());
+    return M17HIP_OK;
+}
+
+// The end of the run on the main stream, and the context's books: `rs` holds the latest run.
+static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
+{
+    int r;
+    const int q = c->slot;
+    const uint32_t C = p.C, T = p.T;
     // the tails a run that continues in THESE slabs (input uploaded in place) will find as its prefixes; a staged run takes them from
     // here into the other slab pair itself.  (Before the deferred decode: the next staged run's first replay waits for these, not for that.)
     hipLaunchKernelGGL(carry_tail_kernel, dim3(C), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, C, T);
     hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().h, c->ypitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_tail, c->stream));
-    c->gate0_queued = false;
     // ---- the end of the run on the MAIN stream: what the next run's chain needs of this one — the one or two deferred costs the state still
     //      names (settle_tail_kernel).  The rest of the run's EVM fold (the operations of its last two segments: 0.8 ms of one dependent chain
     //      per channel that nothing in the demodulator reads) is NOT made here: see fold_pending
     if (c->defer_decode) {
-        SettleParams S{rs.recs, c->rec_cap, rs.defer_llr, c->tables, c->seq_state, C, EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}};
+        SettleParams S{rs.recs, c->rec_cap, rs.defer_llr, c->tables, c->seq_state, C, ev_no_fold(C)};
         hipLaunchKernelGGL(settle_tail_kernel, dim3(C), dim3(64), SETTLE_LDS_BYTES, c->stream, S);
         HIPCHK(c, hipGetLastError());
     }
@@ -1988,28 +1937,78 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     HIPCHK(c, hipEventRecord(rs.chain, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_end[q], c->stream));
     { std::lock_guard<std::mutex> lk(g_runs.mu); c->last_end = c->ev_end[q]; }
-    c->slot_used[q] = true;
-    c->pos += T;
-    c->inplace_after_run = false;
-    c->lastC = C; c->lastT = T; c->runT = T; c->last_nseg = nseg;
-    c->have_run = true;
-    rs.valid = true; rs.C = C; rs.rec_cap = c->rec_cap; rs.nseg = nseg;
+    c->slot_used[q] = true; c->pos += T; c->inplace_after_run = false; c->have_run = true;
+    c->lastC = C; c->runT = T; c->last_nseg = p.nseg;
+    rs.valid = true; rs.C = C; rs.rec_cap = c->rec_cap; rs.nseg = p.nseg;
     rs.pending = true; rs.bert = c->bert; rs.pkt = c->pkt_cap != 0;
-    c->cur = si;
-    c->sel_back = 0;
-    // The run's payload work — the frames K5 did not decode itself, then the consumers — is queued when its results are asked for.  At once
-    // where that costs nothing or is needed: a context that does not stream (the work goes to the main stream, behind the run, as up to round 5),
-    // and with the diagnostic log on (ONE store, which the deferred decode patches: the next run waits for it).
-    if (!c->streams() || c->diag_cap) {
-        c->fold_with_decode = c->fold_pending && c->defer_decode && c->pay() == c->stream;   // (beside the decode, as up to round 5)
-        if ((r = flush_payload(c))) return r;
-        c->fold_with_decode = false;
-        if (c->diag_cap) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
-            if ((r = flush_fold(c))) return r;
-        }
+    c->cur = (int)(&rs - c->sets); c->sel_back = 0;
+    return M17HIP_OK;
+}
+
+// The run's payload work — the frames K5 did not decode itself, then the consumers — is queued when its results are asked for.  At once
+// where that costs nothing or is needed: a context that does not stream (the work goes to the main stream, behind the run, as up to round 5),
+// and with the diagnostic log on (ONE store, which the deferred decode patches: the next run waits for it).
+static int flush_after_run(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
+{
+    if (c->streams() && !c->diag_cap) return M17HIP_OK;
+    const int r = flush_payload(c, false, false, c->fold_pending && c->defer_decode && c->pay() == c->stream);   // (the fold beside the decode, as up to round 5)
+    if (r || !c->diag_cap) return r;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
+    return flush_fold(c);
+}
+
+int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
+{
+    if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
+    GUARD(c);
+    if (c->front_queued || !c->staged) return M17HIP_ESTATE;
+    RunPlan& p = c->front_plan;
+    if (int r = begin_staged(c, p, C, T, flags, RUN_STAGED_FRONT)) return r;
+    c->front_queued = true;
+    // The replay of the staged run's first segment (K2 from K5's state) needs the run in flight only up to its last K5 launch and its
+    // carried tails — not its deferred decode, its consumers, the caller's fetch of its records or the launch of the next run from the
+    // host: queued here, on the replay stream, it runs beside all of those.
+    if (c->gate0_early && c->have_run && c->carryT && !c->profile) {
+        const int q = c->slot;
+        for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &c->ev_fir_[q][0], &c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
+        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
+        HIPCHK(c, hipGetLastError());
+        if (int r = launch_gate_seg(c, p, 0, c->side3, false, false)) return r;
+        HIPCHK(c, hipEventRecord(c->ev_gate_[q][0], c->side3));
+        p.gate0_queued = true;
     }
     return M17HIP_OK;
+}
+
+// The run is processed in segments.  K1 (throughput-bound, the whole chip) and K3 (latency-bound lone waves) of ALL segments
+// are queued on two side streams; the main stream runs K2 -> K5 per segment as soon as that segment's K1 and K3 are done,
+// so the front end of segment k+1 fills the issue slots K5 of segment k leaves idle (its tail above all).
+// Every K2 starts a fresh speculation from K5's own state, so a channel that had to drop it (forced unlock) carries the
+// limit filter itself only until the end of its segment.
+int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
+{
+    if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
+    GUARD(c);
+    int r;
+    RunPlan p;
+    if (c->front_queued) {   // the front end is already on its way (m17hip_demod_front): this call must be the run it was queued for
+        if (C != c->front_plan.C || T != c->front_plan.T || flags != c->front_plan.flags) return M17HIP_ESTATE;
+        c->front_queued = false;
+        p = std::move(c->front_plan);
+    } else if (c->staged) {   // input staged by m17hip_upload_i16_async and friends: swap the slabs, queue the front end
+        if ((r = begin_staged(c, p, C, T, flags, RUN_STAGED))) return r;
+    }
+    if (!c->uploaded) return M17HIP_ESTATE;
+    if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
+    if (!p.staged) p = plan_run(c, C, T, flags, RUN_IN_PLACE);
+    if ((r = p.staged ? carry_staged_prefixes(c, p) : launch_front_all(c, p))) return r;
+    // this run's record set: the one the run before the previous one wrote (its payload work is long through; waited for on the device)
+    m17hip_ctx::RecSet& rs = c->sets[(c->sets[0].valid || c->sets[1].valid || c->have_run) ? (c->cur ^ 1) : c->cur];
+    if ((r = prepare_run(c, p, rs))) return r;
+    if ((r = queue_chain(c, p, rs))) return r;
+    if ((r = end_run(c, p, rs))) return r;
+    return flush_after_run(c, rs);
 }
 
 // The record set the fetch family names (m17hip_frames_select): the latest run's, or the run's before it; nullptr when that run's
@@ -2106,7 +2105,7 @@ int m17hip_diag_fetch(m17hip_ctx* c, m17_diag* diag_host, uint32_t C)
     if (!c || !diag_host || C == 0 || C > c->maxC) return M17HIP_EINVAL;
     GUARD(c);
     if (int fr = flush_fold(c)) return fr;        // m17_diag::evm of the latest run: its last fold pass, if nothing has made it yet
-    if (c->front_pending && c->gate0_queued)      // (... or the replay m17hip_demod_front queued for the next run is making it: wait for that launch)
+    if (c->front_queued && c->front_plan.gate0_queued)   // (... or the replay m17hip_demod_front queued for the next run is making it: wait for that launch)
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
     HIPCHK(c, hipMemcpy2DAsync(diag_host, sizeof(Diag), &c->seq_state[0].cold.diag, sizeof(SeqState), sizeof(Diag), C, hipMemcpyDeviceToHost,
                                c->stream));
@@ -2189,7 +2188,7 @@ int m17hip_sweep_stats(m17hip_ctx* c, uint32_t n_points, m17_chan_stat* host, ui
     if (!c->bert || !c->have_run) return M17HIP_ESTATE;
     // m17hip_diag_fetch's order for `evm`: the latest run's last fold pass on the main stream (or the replay m17hip_demod_front queued is making it)
     if (int fr = flush_fold(c)) return fr;
-    if (c->front_pending && c->gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
+    if (c->front_queued && c->front_plan.gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
     // ... m17hip_bert_stats' order for the PRBS9 state: the payload work of both runs, wherever it was queued
     if (int fr = flush_payload(c)) return fr;
     for (const auto& rs : c->sets)
@@ -2614,7 +2613,7 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
 {
     if (!c) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_pending) return M17HIP_ESTATE;
+    if (c->front_queued) return M17HIP_ESTATE;
     switch (key) {
     // ---- deployment knobs (include/m17hip.h) ----------------------------------------------------------------------------------
     case 3:  // samples per K2+K5 segment of a run (0 = whole run)
