@@ -177,6 +177,31 @@ int m17hip_decode_frames(m17hip_ctx* ctx, const int8_t* llr368_host, uint32_t n_
 /* ---- the full chain ------------------------------------------------------------------------------- */
 /* Fresh demodulators for every channel (M17Demodulator ctor + zero-initialised storage). */
 int m17hip_demod_reset(m17hip_ctx* ctx);
+/* Fresh demodulators for the listed channels only (M17Demodulator ctor, M17Demodulator.h:180-182, + zero-initialised storage, as
+ * m17hip_demod_reset): what the reference does by starting a new m17-demod process for ONE stream — a receiver was retuned, a source
+ * came back, a channel slot goes to another stream — while every other channel of the context keeps its sync, its clock and level
+ * filters and its half-assembled LICH / packets.
+ * channels[n]: LOCAL indices < max_channels (not offset by m17hip_set_channel_base); duplicates are allowed; n == 0 is a successful
+ * no-op.  M17HIP_EINVAL for an index out of range or a NULL list with n > 0 — then nothing is marked.
+ * The call MARKS the channels.  The resets take effect at the start of the NEXT run queued — by m17hip_demod_run, or by the
+ * m17hip_demod_front that begins it — after the previous run's tails have been carried into that run's slab prefixes: from sample 0 of
+ * that run each marked channel behaves as a reference process started there.  Several calls before one run add up;
+ * m17hip_demod_reset clears the marks; so does the run that takes them, once its front end is queued — a m17hip_demod_front / m17hip_demod_run that
+ * fails before that (bad arguments, M17HIP_ESTATE) leaves them pending, one that fails later with M17HIP_EHIP has dropped them.  Between m17hip_demod_front and its m17hip_demod_run: M17HIP_ESTATE, like the other
+ * state-changing calls.  Before the first run after m17hip_demod_reset the call succeeds and changes nothing observable.
+ * Everything the run BEFORE the resets produced stays intact for every channel, the reset ones included: its records in both fetch
+ * orders of a live feed (m17hip_frames_select(ctx, 1) after the next run was queued), its deferred payload frames, its packets and
+ * BERT statistics; its last EVM fold and its m17_diag when they are fetched before the next run is queued (m17hip_demod_run: the
+ * front end m17hip_demod_front queues leaves them alone).
+ * For a reset channel m17_frame_rec.seq and .sample_pos, m17_diag.n_frames / n_diag and the diagnostic log's sample index count
+ * from the channel's own reset, not the context's; its BERT statistics (key 6) and its packet reassembly (key 7) start over — a
+ * half-assembled packet is abandoned, m17_packet_rec.seq restarts.
+ * LIMIT of this version: the carrier-detect tick grid (192 samples) belongs to the context — the carrier-detect table, the
+ * limit-filter replay, the sequential kernel and the gate forecast all find a tick as position / 192 — and a fresh demodulator's
+ * carrier-detect updates fall on the tick ends of ITS stream.  A reset can therefore only take effect where the context's sample
+ * position (the samples run since m17hip_demod_reset) is a multiple of 192: otherwise M17HIP_ESTATE, and nothing is marked.
+ * Cost: list-driven kernels over the marked channels only, O(n); a run with no mark pending queues exactly what it did before. */
+int m17hip_demod_reset_channels(m17hip_ctx* ctx, const uint32_t* channels, uint32_t n);
 /* M17Demodulator<float>::operator() (M17Demodulator.h:657-753) for `samples` new samples of each channel of
  * the uploaded slab; frame callbacks become records, the last diagnostic callback becomes m17_diag. */
 int m17hip_demod_run(m17hip_ctx* ctx, uint32_t channels, uint32_t samples, uint32_t flags);

@@ -91,6 +91,7 @@ struct Cold {  // per-channel state touched a few times per frame (out-of-line h
     uint32_t n_diag_run;        // diagnostic callbacks in the current run (only counted while the diagnostic log is on)
     uint32_t ev_cursor;         // deferred EVM: operations written to the channel's row of SeqParams::ev_ops since the run began
     Diag diag;
+    uint32_t origin_lo, origin_hi;   // context position of the channel's own sample 0 (m17hip_demod_reset_channels): records and the diagnostic log count from there
 };
 struct SeqState {
     Hot hot;

@@ -214,6 +214,12 @@ __global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(Seq
     const uint32_t pos0_ph = (uint32_t)(P.pos0 % TICK), k0 = (uint32_t)(P.pos0 / TICK), k0_mod5 = (uint32_t)((P.pos0 / TICK) % 5u);
     const uint32_t row_k0 = (uint32_t)(P.pos0 / TICK - P.tick_row0);
     FrameRec* rec_base = P.recs + (size_t)c * P.rec_cap;
+    // sample positions in records and log entries count from the channel's own origin: read from the LDS copy where a position is formed
+    // (once per record / callback), so that nothing lives across the main loop
+    auto pos_of = [&](uint32_t te) -> uint64_t {
+        const uint64_t origin = ((uint64_t)SReg<uint32_t>::uni(cd->origin_hi) << 32) | SReg<uint32_t>::uni(cd->origin_lo);
+        return P.pos0 + te - origin;
+    };
     uint32_t t = 0;  // next sample (relative to this run)
     // Loads go through a buffer resource over this channel's row [0, T): the bounds check is the hardware's (a dword at or beyond
     // T reads 0.0) and the eight rows of a granule are one address computation plus instruction offsets.  `avail` is always a
@@ -429,7 +435,7 @@ __global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(Seq
                 wave_lds_sync();
                 const M17_LDS uint32_t* src = reinterpret_cast<const M17_LDS uint32_t*>(&cd->diag);
                 uint32_t* dst = reinterpret_cast<uint32_t*>(P.diag_log + ((size_t)c * P.diag_cap + n));
-                const uint64_t pos = P.pos0 + te;
+                const uint64_t pos = pos_of(te);
                 const int l = cold_lane();
                 if (l < 16) {
                     uint32_t w = src[l];
@@ -1338,7 +1344,7 @@ __global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(Seq
         if (decode_due) {  // decoder(...) and the rest of do_frame (:619-642)
             const unsigned long long d0 = now();
             hpf_ready(); hpf_base = -0x40000000;   // the decoder takes the cost-word array
-            const uint2 r = nf_decode_wave(P.tables, DL, wl, s.sync_word_type, cd, s.viterbi_cost, rec_base, P.rec_cap, P.channel_base + c, P.pos0 + te, P.overflow,
+            const uint2 r = nf_decode_wave(P.tables, DL, wl, s.sync_word_type, cd, s.viterbi_cost, rec_base, P.rec_cap, P.channel_base + c, pos_of(te), P.overflow,
                                            P.defer ? P.defer + (size_t)c * P.rec_cap * 46 : nullptr);
             s.viterbi_cost = r.x;
             s.st = (r.y == 1u || r.y == 0u) ? ST_STREAM_SYNC : (r.y == 4u ? ST_BERT_SYNC : ST_PACKET_SYNC);

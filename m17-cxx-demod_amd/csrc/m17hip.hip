@@ -100,6 +100,7 @@ struct RunPlan {
     bool gate_run = false;        // it is gate-aware (tuning knob 26)
     uint32_t front_segs = 0;      // segments whose front end is queued at once (tuning knob 5)
     bool gate0_queued = false;    // m17hip_demod_front has queued the replay of its first segment (and the prefix copies in front of it)
+    uint32_t n_reset = 0;         // channels that begin it with fresh demodulators (m17hip_demod_reset_channels): entries of the context's reset list in use
     uint32_t t0(uint32_t k) const { return b[std::min<size_t>(k, nseg)]; }
 };
 
@@ -249,6 +250,17 @@ struct m17hip_ctx {
     DevBuf<char> scratch;             // per-operator staging (correlator outputs, viterbi io)
     DcdCoef coef{};
     uint64_t pos = 0;          // samples consumed since reset
+    // m17hip_demod_reset_channels: the channels marked since the latest run was queued, each once (`marked`: [maxC], sized with the first mark).
+    // The run that takes the marks puts them on the device — one of two lists in turn, each staged in pinned host memory and copied on the first
+    // stream that reads it (`ready`: the copy is through; the other readers wait for it), each with an event per stream that read it last
+    // (copy / carrier detect / main / payload): a list is written again only when those have passed.  Nothing of this exists in a context that never marks.
+    std::vector<uint32_t> marks;
+    std::vector<uint8_t> marked;
+    struct ResetList {
+        DevBuf<uint32_t> list; uint32_t* staging = nullptr; hipStream_t first = nullptr; Event ready, used[4]; bool recorded[4] = {false, false, false, false};
+        ~ResetList() { if (staging) (void)hipHostFree(staging); }
+    } rlist[2];
+    int rcur = 0;              // the list of the latest run that took marks
     uint32_t lastC = 0;
     bool have_run = false;     // a run has been made since the last reset (the stream continues)
     bool uploaded = false;
@@ -467,16 +479,14 @@ __global__ void ev_move_kernel(SeqState* st, EvState* es, uint32_t C, int to_def
     if (to_deferred) { es[c].S = st[c].hot.evm_S; es[c].pos = 0; } else st[c].hot.evm_S = es[c].S;
 }
 
-__global__ void seq_reset_kernel(SeqState* st, DcdState* ds, EvState* es, uint32_t C)
+// A fresh channel = the zero-initialised object + the constructors' values (M17Demodulator.h:180-182), its stream beginning at
+// the context's sample `pos` (a multiple of TICK: the carrier-detect ticks are the context's; 0 for m17hip_demod_reset).  The ONE definition
+// of it: seq_reset_kernel (every channel) and the list kernels of m17hip_demod_reset_channels call these two.
+__device__ __forceinline__ void fresh_demod_state(SeqState* st, EvState* es, uint32_t c, uint64_t pos)
 {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
     es[c] = EvState{1.0f, 0.f, 0u, 0u};   // RunningStandardDeviation::S{1.0}
-    // zero-initialised object + the constructors' values
     uint32_t* w = reinterpret_cast<uint32_t*>(st + c);
     for (size_t k = 0; k < sizeof(SeqState) / 4; ++k) w[k] = 0;
-    uint32_t* d = reinterpret_cast<uint32_t*>(ds + c);
-    for (size_t k = 0; k < sizeof(DcdState) / 4; ++k) d[k] = 0;
     Hot& s = st[c].hot;
     Cold& k = st[c].cold;
     s.run_pos = 148;              // the stream start is exact in ybuf (zero history)
@@ -486,6 +496,45 @@ __global__ void seq_reset_kernel(SeqState* st, DcdState* ds, EvState* es, uint32
     s.evm_S = 1.0f;               // RunningStandardDeviation::S{1.0}
     s.initializing = 1920;        // M17Demodulator.h:659 (per channel)
     s.st = ST_UNLOCKED;
+    k.seg_start_tick = (uint32_t)(pos / TICK);   // the first carrier-detect segment begins with the channel's stream
+    k.origin_lo = (uint32_t)pos; k.origin_hi = (uint32_t)(pos >> 32);   // records and log entries count from here
+}
+__device__ __forceinline__ void fresh_dcd_state(DcdState* ds, uint32_t c)
+{
+    uint32_t* d = reinterpret_cast<uint32_t*>(ds + c);
+    for (size_t k = 0; k < sizeof(DcdState) / 4; ++k) d[k] = 0;
+}
+
+__global__ void seq_reset_kernel(SeqState* st, DcdState* ds, EvState* es, uint32_t C)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    fresh_demod_state(st, es, c, 0);
+    fresh_dcd_state(ds, c);
+}
+
+// ---- m17hip_demod_reset_channels: the same over a LIST of n channels (each listed once, every entry < max_channels) -------------------------
+// front end: the channel's 152-sample input prefix (FIR history, DFT delay) and / or its sliding-DFT state; a workgroup per listed channel
+__global__ void front_reset_list_kernel(const uint32_t* list, uint32_t n, int16_t* x, size_t xpitch, DcdState* ds)
+{
+    if (blockIdx.x >= n) return;
+    const uint32_t c = list[blockIdx.x];
+    if (x) for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = 0;
+    if (ds && threadIdx.x == 0) fresh_dcd_state(ds, c);
+}
+// the 96-sample prefixes of the matched-filter output and of the limit-filter history; a workgroup per listed channel
+__global__ void prefix_reset_list_kernel(const uint32_t* list, uint32_t n, float* y, float* h, size_t ypitch)
+{
+    if (blockIdx.x >= n) return;
+    const uint32_t c = list[blockIdx.x];
+    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) { y[(size_t)c * ypitch + k] = 0.f; h[(size_t)c * ypitch + k] = 0.f; }
+}
+// the demodulator and EVM state; a lane per listed channel
+__global__ void seq_reset_list_kernel(const uint32_t* list, uint32_t n, SeqState* st, EvState* es, uint64_t pos)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fresh_demod_state(st, es, list[i], pos);
 }
 
 __global__ void zero_prefix_kernel(int16_t* x, size_t xpitch, float* y, size_t ypitch, uint32_t C)
@@ -657,20 +706,36 @@ __global__ void packet_asm_kernel(const FrameRec* recs, uint32_t rec_cap, const 
     }
     st->size = size; st->counter = counter; st->seq_errors = seq_errors; st->frames = frames; st->completed = completed;
 }
+__device__ __forceinline__ void fresh_packet_state(PacketState* state, uint32_t c)
+{
+    state[c].size = 0; state[c].counter = 0; state[c].seq_errors = 0; state[c].frames = 0; state[c].completed = 0;
+}
 __global__ void packet_reset_kernel(PacketState* state, uint32_t C)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    state[c].size = 0; state[c].counter = 0; state[c].seq_errors = 0; state[c].frames = 0; state[c].completed = 0;
+    fresh_packet_state(state, c);
 }
 
+__device__ __forceinline__ void fresh_bert_state(BertState* state, uint32_t c)
+{
+    BertState b{};
+    b.lfsr = 1;
+    state[c] = b;
+}
 __global__ void bert_reset_kernel(BertState* state, uint32_t C)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    BertState b{};
-    b.lfsr = 1;
-    state[c] = b;
+    fresh_bert_state(state, c);
+}
+// m17hip_demod_reset_channels: the payload consumers of the listed channels start over (pkt == nullptr: packet reassembly is off); a lane per listed channel
+__global__ void consumer_reset_list_kernel(const uint32_t* list, uint32_t n, BertState* bert, PacketState* pkt)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fresh_bert_state(bert, list[i]);
+    if (pkt) fresh_packet_state(pkt, list[i]);
 }
 
 __global__ void copy_prefix_i16_kernel(const int16_t* src, int16_t* dst, size_t xpitch)
@@ -844,7 +909,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 602; }
+int m17hip_version(void) { return 603; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1395,6 +1460,8 @@ int m17hip_demod_reset(m17hip_ctx* c)
         rs.pending = false;
     }
     c->fold_pending = false;   // (the EVM state it would have updated is reset below)
+    for (uint32_t ch : c->marks) c->marked[ch] = 0;   // (m17hip_demod_reset_channels: every channel starts over anyway)
+    c->marks.clear();
     hipLaunchKernelGGL(seq_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->dcd_state, c->ev_state, c->maxC);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, c->maxC);
@@ -1418,6 +1485,22 @@ int m17hip_demod_reset(m17hip_ctx* c)
     c->have_run = false;
     c->inplace_after_run = false;
     c->sel_back = 0;
+    return M17HIP_OK;
+}
+
+int m17hip_demod_reset_channels(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
+{
+    if (!c || (n && !channels)) return M17HIP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if (channels[i] >= c->maxC) return M17HIP_EINVAL;   // (before anything is marked)
+    if (c->front_queued) return M17HIP_ESTATE;   // the run m17hip_demod_front began has taken its marks
+    if (n == 0) return M17HIP_OK;
+    // The carrier-detect tick grid is the context's: K3's table rows, K2's replay, K5 and the gate forecast all find a tick as position / 192.  A fresh
+    // demodulator's update points fall on ITS tick ends, so its stream can only begin where a tick of the context does.
+    if (c->pos % TICK != 0) return M17HIP_ESTATE;
+    if (c->marked.empty()) c->marked.assign(c->maxC, 0);
+    for (uint32_t i = 0; i < n; ++i)
+        if (!c->marked[channels[i]]) { c->marked[channels[i]] = 1; c->marks.push_back(channels[i]); }
     return M17HIP_OK;
 }
 
@@ -1593,6 +1676,62 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
     return M17HIP_OK;
 }
 
+// ---- m17hip_demod_reset_channels: the marked channels begin the run being queued with fresh demodulators ---------------------------------------
+// The marks become a list on the device (n entries; 0: nothing is marked — the caller then queues nothing for them).
+enum { RL_COPY = 0, RL_DCD, RL_MAIN, RL_PAY };
+// `first`: the stream whose kernel reads the list first — the copy is queued there, from pinned memory, so the host waits for nothing that is in flight.
+// The marks themselves stay until the run's front end is queued (commit_marks): a call that fails before that leaves them for the caller's next attempt.
+static int take_marks(m17hip_ctx* c, uint32_t& n, hipStream_t first)
+{
+    n = (uint32_t)c->marks.size();
+    if (!n) return M17HIP_OK;
+    c->rcur ^= 1;
+    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
+    for (int i = 0; i < 4; ++i) {   // (its readers of two marked runs ago; the first of them is behind that run's copy out of `staging`)
+        if (rl.recorded[i]) HIPCHK(c, hipEventSynchronize(rl.used[i]));
+        rl.recorded[i] = false;
+        if (!rl.used[i]) HIPCHK(c, rl.used[i].create());
+    }
+    if (!rl.ready) HIPCHK(c, rl.ready.create());
+    if (!rl.list) HIPCHK(c, rl.list.alloc(c->maxC));
+    if (!rl.staging) HIPCHK(c, hipHostMalloc((void**)&rl.staging, (size_t)c->maxC * 4, hipHostMallocDefault));
+    std::memcpy(rl.staging, c->marks.data(), (size_t)n * 4);
+    HIPCHK(c, hipMemcpyAsync(rl.list, rl.staging, (size_t)n * 4, hipMemcpyHostToDevice, first));
+    HIPCHK(c, hipEventRecord(rl.ready, first));
+    rl.first = first;
+    return M17HIP_OK;
+}
+static void commit_marks(m17hip_ctx* c)
+{
+    for (uint32_t ch : c->marks) c->marked[ch] = 0;
+    c->marks.clear();
+}
+// a kernel on `st` is about to read the list: behind its copy (on the stream that made the copy that is stream order already) ...
+static int reset_list_wait(m17hip_ctx* c, hipStream_t st)
+{
+    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
+    if (st != rl.first) HIPCHK(c, hipStreamWaitEvent(st, rl.ready, 0));
+    return M17HIP_OK;
+}
+// ... and has been queued: the list is not written again before it is through
+static int reset_list_used(m17hip_ctx* c, int which, hipStream_t st)
+{
+    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
+    HIPCHK(c, hipEventRecord(rl.used[which], st));
+    rl.recorded[which] = true;
+    return M17HIP_OK;
+}
+// The FRONT-END state of the listed channels — `x`: the input prefix (K1's FIR history, K3's 120-sample delay), on a stream that has carried the previous
+// input's tail into the prefixes; `dcd`: the sliding-DFT state, on a stream that is behind the previous run's K3 — before K1 / K3 of the run start.
+static int reset_marked_front(m17hip_ctx* c, uint32_t n, hipStream_t st, int which, bool x, bool dcd)
+{
+    if (int r = reset_list_wait(c, st)) return r;
+    hipLaunchKernelGGL(front_reset_list_kernel, dim3(n), dim3(64), 0, st, c->rlist[c->rcur].list.get(), n, x ? c->now().x.get() : (int16_t*)nullptr, c->xpitch,
+                       dcd ? c->dcd_state.get() : (DcdState*)nullptr);
+    HIPCHK(c, hipGetLastError());
+    return reset_list_used(c, which, st);
+}
+
 // A staged run begins: the slab pairs swap, the 152-sample tail of the previous input is carried into the new slab's prefix, and the
 // front end (K1, K3: nothing in them depends on the outcome of the run before) is queued on the side streams — NOT ordered behind
 // the main stream, where K2 / K5 of the previous run may still have a long way to go.  `p`: the run, decided here.
@@ -1614,17 +1753,28 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
         hipLaunchKernelGGL(copy_prefix_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch);
     } else HIPCHK(c, hipMemset2DAsync(c->now().x, c->xpitch * sizeof(int16_t), 0, XPRE * sizeof(int16_t), C, c->copy));
     HIPCHK(c, hipGetLastError());
+    uint32_t n_reset = 0;   // (m17hip_demod_reset_channels: the marked channels' input prefixes, behind the tail copy)
+    if (!c->marks.empty()) {
+        if (int r = take_marks(c, n_reset, c->copy)) return r;
+        if (int r = reset_marked_front(c, n_reset, c->copy, RL_COPY, true, false)) return r;
+    }
     HIPCHK(c, hipEventRecord(c->ev_in_ready, c->copy));
     for (hipStream_t st : {c->side, c->side2}) {
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_in_ready, 0));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_mark, 0));
+    }
+    if (n_reset) {   // (... and their sliding-DFT state, on K3's stream: behind the previous run's K3, in front of this run's)
+        if (int r = reset_marked_front(c, n_reset, c->side, RL_DCD, false, true)) return r;
     }
     if (c->front_k1_after && c->have_run && c->last_nseg) {   // K1 out of the way of the previous run's first (heaviest) K5 launches
         const uint32_t j = std::min(c->front_k1_after, c->last_nseg) - 1u;
         HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[c->slot ^ 1][j], 0));
     }
     p = plan_run(c, C, T, flags, kind);
-    return launch_front_all(c, p);
+    p.n_reset = n_reset;
+    if (int r = launch_front_all(c, p)) return r;
+    if (n_reset) commit_marks(c);
+    return M17HIP_OK;
 }
 
 }  // namespace
@@ -1957,6 +2107,31 @@ static int flush_after_run(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
     return flush_fold(c);
 }
 
+// m17hip_demod_reset_channels, the part of a run that begins with marked channels which waits for the run before it: everything the STATE-MACHINE half
+// reads.  On the main stream, behind the previous run's settle_tail_kernel and the carried / copied y and h prefixes, in front of this run's first replay:
+// the listed channels' SeqState (from the context's position: their tick and their origin) and their 96-sample y / h prefixes; EvState only after the
+// previous run's LAST fold pass has been through them (made here, as m17hip_diag_fetch makes it); the consumers' state on the payload stream, behind the
+// payload work of every earlier run — queued now where it was still to come (flush_payload), so that those runs' statistics and packets are complete.
+static int reset_marked_state(m17hip_ctx* c, const RunPlan& p)
+{
+    const uint32_t n = p.n_reset;
+    const uint32_t* list = c->rlist[c->rcur].list;
+    if (int r = flush_fold(c)) return r;
+    if (int r = flush_payload(c)) return r;
+    for (const auto& rs : c->sets)
+        if (rs.valid)
+            if (int r = pay_after(c, rs)) return r;
+    if (int r = reset_list_wait(c, c->pay())) return r;
+    hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert_state.get(), c->pkt_cap ? c->pkt_state.get() : (PacketState*)nullptr);
+    HIPCHK(c, hipGetLastError());
+    if (int r = reset_list_used(c, RL_PAY, c->pay())) return r;
+    if (int r = reset_list_wait(c, c->stream)) return r;
+    hipLaunchKernelGGL(prefix_reset_list_kernel, dim3(n), dim3(64), 0, c->stream, list, n, c->now().y.get(), c->now().h.get(), c->ypitch);
+    hipLaunchKernelGGL(seq_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, list, n, c->seq_state.get(), c->ev_state.get(), (uint64_t)c->pos);
+    HIPCHK(c, hipGetLastError());
+    return reset_list_used(c, RL_MAIN, c->stream);
+}
+
 int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
@@ -1968,7 +2143,8 @@ int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     // The replay of the staged run's first segment (K2 from K5's state) needs the run in flight only up to its last K5 launch and its
     // carried tails — not its deferred decode, its consumers, the caller's fetch of its records or the launch of the next run from the
     // host: queued here, on the replay stream, it runs beside all of those.
-    if (c->gate0_early && c->have_run && c->carryT && !c->profile) {
+    // (not for a run that begins with marked channels, m17hip_demod_reset_channels: their state is reset by the run call, and this replay reads it)
+    if (c->gate0_early && c->have_run && c->carryT && !c->profile && !p.n_reset) {
         const int q = c->slot;
         for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &c->ev_fir_[q][0], &c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
         hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
@@ -2001,8 +2177,16 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     }
     if (!c->uploaded) return M17HIP_ESTATE;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
-    if (!p.staged) p = plan_run(c, C, T, flags, RUN_IN_PLACE);
+    if (!p.staged) {
+        p = plan_run(c, C, T, flags, RUN_IN_PLACE);
+        if (!c->marks.empty()) {   // (m17hip_demod_reset_channels; in place the main stream is behind the previous run's carried tails and its K3)
+            if ((r = take_marks(c, p.n_reset, c->stream))) return r;
+            if ((r = reset_marked_front(c, p.n_reset, c->stream, RL_COPY, true, true))) return r;
+        }
+    }
     if ((r = p.staged ? carry_staged_prefixes(c, p) : launch_front_all(c, p))) return r;
+    if (!p.staged && p.n_reset) commit_marks(c);
+    if (p.n_reset && (r = reset_marked_state(c, p))) return r;
     // this run's record set: the one the run before the previous one wrote (its payload work is long through; waited for on the device)
     m17hip_ctx::RecSet& rs = c->sets[(c->sets[0].valid || c->sets[1].valid || c->have_run) ? (c->cur ^ 1) : c->cur];
     if ((r = prepare_run(c, p, rs))) return r;

@@ -56,6 +56,9 @@ public:
         channels_ = channels; samples_ = samples;
     }
     void reset() { check(m17hip_demod_reset(ctx_), "m17hip_demod_reset"); }
+    // Fresh demodulators for the listed channels only (local indices), from the start of the NEXT run queued; the others go on
+    // (m17hip_demod_reset_channels: between runs whose lengths are multiples of 192 samples, not between front() and run()).
+    void reset_channels(const uint32_t* channels, uint32_t n) { check(m17hip_demod_reset_channels(ctx_, channels, n), "m17hip_demod_reset_channels"); }
     void run(uint32_t flags = 0) { check(m17hip_demod_run(ctx_, channels_, samples_, flags), "m17hip_demod_run"); }
 
     // records of the last run, ordered by (channel, seq): one compaction and one synchronisation when the guessed capacity suffices

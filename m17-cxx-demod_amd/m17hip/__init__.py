@@ -50,7 +50,7 @@ EXPORTS = [
     "m17hip_set_kalman_order", "m17hip_kalman_trace", "m17hip_set_channel_base", "m17hip_upload_wait", "m17hip_comm_get_id", "m17hip_comm_create",
     "m17hip_comm_destroy", "m17hip_comm_last_error", "m17hip_gather_frames", "m17hip_gather_frames_device", "m17hip_diag_log_fetch",
     "m17hip_upload_i16_device_async", "m17hip_input_alternate", "m17hip_demod_front", "m17hip_advice", "m17hip_replay_drops", "m17hip_frames_select",
-    "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats",
+    "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats", "m17hip_demod_reset_channels",
 ]
 ETRUNC = -6
 EOVERFLOW = -5
@@ -326,6 +326,13 @@ class Context:
 
     def reset(self):
         self._chk(self.lib.m17hip_demod_reset(self.h))
+
+    def reset_channels(self, indices):
+        """Fresh demodulators for the listed channels only (local indices, duplicates allowed), from the start of the NEXT run queued (run(), or
+        the front() that begins it); every other channel goes on.  Between runs whose lengths are multiples of 192 samples, and not between
+        front() and run() (m17hip_demod_reset_channels)."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32).reshape(-1))
+        self._chk(self.lib.m17hip_demod_reset_channels(self.h, _ptr(idx) if idx.size else None, C.c_uint32(idx.size)))
 
     def run(self, flags=0, channels=None, samples=None):
         self._chk(self.lib.m17hip_demod_run(self.h, C.c_uint32(channels or self.C), C.c_uint32(samples or self.T), C.c_uint32(flags)))
