@@ -533,8 +533,11 @@ __global__ __launch_bounds__(64) void limit_kernel(const float* __restrict__ y, 
 //     (p, q) = X*X; n = p + q; the six running sums as three packed adds — 9 VALU instructions per sample for 32 channels.
 //   * the time-parallel part (int16 -> float scaling of x[n] and x[n-120], delta) is done for 64 samples of all 32
 //     channels at once (each lane converts half of its channel's block, 16-byte loads issued one block ahead) and handed
-//     to the recurrence through LDS (row pitch 68: conflict-free 16-byte reads).  x[n-120] comes from the carried prefix
-//     of xbuf (XPRE >= 120), so there is no delay line to maintain.
+//     to the recurrence through LDS (row pitch 68: conflict-free 16-byte reads).  Scaling is dcd_scale2, two samples per
+//     packed f32 instruction and the polarity a template constant: 89 VALU instructions per block and lane where the
+//     double-precision product took 241 (the recurrence itself is 288).  x[n-120] comes from the carried prefix of xbuf
+//     (XPRE >= 120) and is scaled again: a delay line of scaled samples would be 16 KB of LDS per wave (8 KB as int16),
+//     and the workgroup has the 20 KB that four K5 workgroups leave on a CU — the x row in L2 is the delay line.
 // 128 waves for 4096 channels at ~0.42 wave-instructions per channel-sample: the kernel is latency-bound (~17 ms per
 // 480 000 samples) but leaves the SIMDs to the kernels it runs beside; earlier mappings with 16 lanes per channel were
 // faster alone (9.6 ms) and five times as expensive in issue slots.
@@ -542,14 +545,6 @@ __global__ __launch_bounds__(64) void limit_kernel(const float* __restrict__ y, 
 // Table layout: [C][ticks][2 bins][6 sums].  Algorithmic bytes: 2 B/sample read (+ 48 B per 192 samples written).
 // =====================================================================================================
 struct DcdCoef { float c0r, c0i, c1r, c1i; };  // exp(-j 2 pi f/48000), f = 2400, 3600 — computed on the host
-
-// apps/m17-demod.cpp:486-489 through the double-precision product (bit-identical to the division for all int16, see
-// tests/test_oracle_kat.py::test_scale_identities_exhaustive); 3 instructions instead of a division expansion.
-__device__ __forceinline__ float scale_sample_mul(int s, bool invert)
-{
-    if (invert) s = (int)(int16_t)(-s);
-    return (float)((double)s * (1.0 / 41067.0));
-}
 
 constexpr int DCD_BLK = 32;        // samples per block: conversion granule and straight-line length of the recurrence
 constexpr int DCD_CPW = 32;        // channels per wave
@@ -576,6 +571,7 @@ __device__ __forceinline__ void dcd_step(DcdLane& s, float delta)
 // 4096-channel launch take a wave slot on every SIMD of 32 CUs instead of one SIMD on each of 128 CUs — K5 (whose workgroups
 // need a slot on all four SIMDs of a CU) then loses 32 workgroup slots to K3 instead of 128, K1 likewise.
 constexpr int DCD_WPB = 4;
+template <bool INVERT>
 __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
                                                  float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
                                                  uint64_t pos0, DcdCoef k, uint32_t flags)
@@ -587,7 +583,6 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __rest
     uint32_t c = (blockIdx.x * DCD_WPB + (threadIdx.x >> 6)) * DCD_CPW + g;
     const bool live = c < C;   // lanes beyond the last channel shadow it and never store
     if (!live) c = C - 1;
-    const bool invert = flags & 1u;
     const int16_t* xr = x + (size_t)c * xpitch + XPRE;
     DcdState* st = state + c;
     DcdLane s;
@@ -624,10 +619,10 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __rest
         }
         phase = 0; ++tick; ++row;
     };
-    auto conv = [&](int v) { return scale_sample_mul(v, invert); };
-    auto one_sample = [&](uint32_t t) {  // generic path: head / tail of a run
+    auto one_sample = [&](uint32_t t) {  // generic path: head / tail of a run; x[n] and x[n-120] are one packed pair
         if (phase == 0) tick_begin();
-        dcd_step(s, conv((int)xr[t]) - conv((int)xr[(int64_t)t - 120]));
+        const v2f f = dcd_scale2<INVERT>((int)xr[t], (int)xr[(int64_t)t - 120]);
+        dcd_step(s, f.x - f.y);
         if (++phase == TICK) tick_end();
     };
 
@@ -653,13 +648,12 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __rest
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int4 a = pa[q], d = pb[q];
-                float4 u, v;
-                u.x = conv(lo(a.x)) - conv(lo(d.x)); u.y = conv(hi(a.x)) - conv(hi(d.x));
-                u.z = conv(lo(a.y)) - conv(lo(d.y)); u.w = conv(hi(a.y)) - conv(hi(d.y));
-                v.x = conv(lo(a.z)) - conv(lo(d.z)); v.y = conv(hi(a.z)) - conv(hi(d.z));
-                v.z = conv(lo(a.w)) - conv(lo(d.w)); v.w = conv(hi(a.w)) - conv(hi(d.w));
-                *reinterpret_cast<float4*>(wrow + 8 * q) = u;
-                *reinterpret_cast<float4*>(wrow + 8 * q + 4) = v;
+                const v2f u0 = dcd_scale2<INVERT>(lo(a.x), hi(a.x)) - dcd_scale2<INVERT>(lo(d.x), hi(d.x));
+                const v2f u1 = dcd_scale2<INVERT>(lo(a.y), hi(a.y)) - dcd_scale2<INVERT>(lo(d.y), hi(d.y));
+                const v2f u2 = dcd_scale2<INVERT>(lo(a.z), hi(a.z)) - dcd_scale2<INVERT>(lo(d.z), hi(d.z));
+                const v2f u3 = dcd_scale2<INVERT>(lo(a.w), hi(a.w)) - dcd_scale2<INVERT>(lo(d.w), hi(d.w));
+                *reinterpret_cast<float4*>(wrow + 8 * q) = make_float4(u0.x, u0.y, u1.x, u1.y);
+                *reinterpret_cast<float4*>(wrow + 8 * q + 4) = make_float4(u2.x, u2.y, u3.x, u3.y);
             }
             lds_sync();
             if (t + 2 * DCD_BLK <= T) issue(t + DCD_BLK);   // in flight while the recurrence below runs

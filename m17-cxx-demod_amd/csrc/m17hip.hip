@@ -848,10 +848,15 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     // table rows are numbered from the first tick of the RUN: a later segment continues where the previous one stopped
     const uint64_t row0 = (pos + t0) / TICK - pos / TICK;
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
-    if (!latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK)
-        tm.launch(dcd_kernel, dim3((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB)), dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
-    else if (flags & 1u)
+    if (!latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK) {
+        const dim3 grid((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB));
+        if (flags & 1u)
+            tm.launch(dcd_kernel<true>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
+        else
+            tm.launch(dcd_kernel<false>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
+    } else if (flags & 1u)
         tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
                            c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     else
