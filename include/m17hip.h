@@ -202,6 +202,28 @@ int m17hip_demod_reset(m17hip_ctx* ctx);
  * position (the samples run since m17hip_demod_reset) is a multiple of 192: otherwise M17HIP_ESTATE, and nothing is marked.
  * Cost: list-driven kernels over the marked channels only, O(n); a run with no mark pending queues exactly what it did before. */
 int m17hip_demod_reset_channels(m17hip_ctx* ctx, const uint32_t* channels, uint32_t n);
+/* Per-channel input polarity (ABI 604): the reference's -i (apps/m17-demod.cpp:488, sample *= -1 in int16) is a property of ONE receiver — its
+ * discriminator, its sound card, the side of the IF — and each reference process has its own command line.  invert[n], n in 1..max_channels:
+ * entry c is 0 or 1 for LOCAL channel c (not offset by m17hip_set_channel_base); entries >= n keep their value; invert == NULL with n == 0 clears
+ * the whole table.  M17HIP_EINVAL for a NULL context, n > max_channels, NULL with n > 0, non-NULL with n == 0, or an entry other than 0 / 1 —
+ * then nothing changes.
+ * The EFFECTIVE polarity of channel c in a call is table[c] XOR (flags & M17HIP_FLAG_INVERT): in m17hip_demod_run / m17hip_demod_front and in
+ * the per-operator entries that take flags (m17hip_fir_rrc150, m17hip_dcd, m17hip_fir_correlator).
+ * The table belongs to the context and describes the receivers, not the streams: m17hip_demod_reset keeps it; a fresh context has all zeros.
+ * A channel that has RUN since m17hip_demod_reset carries state formed under its old polarity (the raw input prefix, the carrier detect's
+ * sliding DFT, the demodulator), and no reference process corresponds to its continuation: changing its entry marks it exactly as
+ * m17hip_demod_reset_channels does — from the next run queued it is a fresh demodulator under the new polarity, with everything that call
+ * says about records, positions and consumers — and under that call's rule: if the context's position is not a multiple of 192 samples and
+ * at least one CHANGED channel has run, M17HIP_ESTATE, and nothing changes, neither table nor marks.  Entries written with the value they
+ * have mark nothing; before the first run after m17hip_demod_reset any change is free.
+ * Between m17hip_demod_front and its m17hip_demod_run: M17HIP_ESTATE, like the other state-changing calls.  The call waits for no run in
+ * flight and alters none: a run keeps the table it was queued with.
+ * Cost: launches whose channels are of one effective polarity (no table, all 0, all 1) are those of a context without a table; mixed ones
+ * take the per-channel forms of the matched filter and the carrier detect (NOTES.md has their instruction counts).  The call itself never
+ * waits; the wait it saves is paid, if at all, where a mixed run is queued: two device tables take turns, and before one is written again the
+ * host waits for the runs that read it, so m17hip_demod_run / m17hip_demod_front queued after a change may wait for the run before last
+ * (as a marked run does for the reset lists). */
+int m17hip_set_channel_polarity(m17hip_ctx* ctx, const uint8_t* invert, uint32_t n);
 /* M17Demodulator<float>::operator() (M17Demodulator.h:657-753) for `samples` new samples of each channel of
  * the uploaded slab; frame callbacks become records, the last diagnostic callback becomes m17_diag. */
 int m17hip_demod_run(m17hip_ctx* ctx, uint32_t channels, uint32_t samples, uint32_t flags);

@@ -22,6 +22,28 @@ __device__ __forceinline__ v2f dcd_scale2(int a, int b)   // core::scale_i16 on 
     return __builtin_elementwise_fma(r, rcp, q);
 }
 
+// Polarity of a launch of K1 / K3.  Uniform over its channels — plain or inverted, the template constant INVERT of the kernels — or MIXED: per channel, from
+// the context's polarity table (m17hip_set_channel_polarity: pol[c] = 0 / 1, XOR the call's M17HIP_FLAG_INVERT).  The mixed forms negate in int16, where
+// the reference does (-(-32768) wraps to -32768), under a mask m = 0 (plain) / -1 (inverted): (s ^ m) - m, two samples per instruction on the packed
+// word the loads deliver; the scaling behind it is the plain form's, so every value is core::scale_i16's (tests/test_scale_newton_exhaustive.py).
+// A uniform and a mixed kernel are ONE text (the *_body.inc files, included into both), so that the uniform instantiations compile to what they were
+// before the mixed ones existed.
+__device__ __forceinline__ int pol_mask(const uint32_t* __restrict__ pol, uint32_t c, uint32_t flip) { return -(int)((pol[c] ^ flip) & 1u); }
+__device__ __forceinline__ int pol_word(int w, int m)   // a word of two int16 samples
+{
+    typedef short v2s __attribute__((ext_vector_type(2)));
+    const int x = w ^ m;
+    v2s a, b;
+    __builtin_memcpy(&a, &x, 4);
+    __builtin_memcpy(&b, &m, 4);
+    a = a - b;
+    int r;
+    __builtin_memcpy(&r, &a, 4);
+    return r;
+}
+__device__ __forceinline__ int4 pol_word4(int4 v, int m) { return make_int4(pol_word(v.x, m), pol_word(v.y, m), pol_word(v.z, m), pol_word(v.w, m)); }
+__device__ __forceinline__ int pol_i16(int s, int m) { return (int)(int16_t)((s ^ m) - m); }   // one sample
+
 // hand-over between the roles of the pipeline kernels: LDS only.  (__syncthreads() would also fence GLOBAL memory, i.e. wait for the producer's prefetches
 // of the blocks to come — vmcnt(0) at every barrier — and expose a full HBM round trip per block.)  Every role executes the
 // same number of these, each in its own loop: the hardware counts arrivals per workgroup, not program counters.
@@ -230,128 +252,17 @@ __global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_kernel(const in
                                                                        uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
                                                                        const uint32_t* __restrict__ first_needed)
 {
-    // first_needed (may be null): per channel, the first sample of this slab the carrier can be on for (gate_forecast_kernel): tiles that end
-    // before it are skipped
-    __shared__ __attribute__((aligned(16))) float win[FS_LDS_FLOATS];
-    const int tid = threadIdx.x;
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    constexpr int NCH = (FS_WIN + 7) / 8;             // 531 chunks of eight samples
-    constexpr int CPT = (NCH + FS_THREADS - 1) / FS_THREADS;   // 3 per thread (the third for 19 threads only)
-    v4i pre[CPT];
-    // the int16 input of an item: chunk k <-> window samples 8k .. 8k + 7 <-> times t0 - 152 + 8k ...; beyond the slab's end: zero
-    auto fetch = [&](uint32_t item) {
-        const uint32_t c = item / tiles, tile = item - c * tiles;
-        const int16_t* xr = x + (size_t)c * xpitch + XPRE;
-        const int64_t w0 = (int64_t)tile * FS_TILE - FS_WOFF;
-#pragma unroll
-        for (int q = 0; q < CPT; ++q) {
-            const int k = tid + q * FS_THREADS;
-            const int64_t t = w0 + 8 * k;
-            v4i v = {0, 0, 0, 0};
-            if (k < NCH) {
-                if (t + 8 <= (int64_t)T) v = *reinterpret_cast<const v4i*>(xr + t);
-                else {                                // the slab ends inside this chunk (once per channel at most): sample by sample
-                    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll 1
-                    for (int h = 0; h < 8; ++h)
-                        if (t + h < (int64_t)T) w[h >> 1] |= (uint32_t)(uint16_t)xr[t + h] << (16 * (h & 1));
-                    v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-                }
-            }
-            pre[q] = v;
-        }
-    };
-    auto stage = [&] {
-#pragma unroll
-        for (int q = 0; q < CPT; ++q) {
-            const int k = tid + q * FS_THREADS;
-            if (k < NCH) {
-                float* dst = win + FS_PADF + 8 * k + 2 * (k >> 1);   // sample j = 8k at word j + 2 (j >> 4)
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int w = pre[q][h];
-                    const v2f f = dcd_scale2<INVERT>((int)(int16_t)(w & 0xFFFF), w >> 16);
-                    *reinterpret_cast<v2f*>(dst + 2 * h) = f;
-                }
-            }
-        }
-    };
-    auto next_item = [&](uint32_t it) {               // the first item from `it` on (stride = the grid) that is not skipped
-        if (first_needed) {
-            while (it < items) {
-                const uint32_t c = it / tiles, tile = it - c * tiles;
-                if ((uint64_t)(tile + 1u) * FS_TILE > (uint64_t)first_needed[c]) break;
-                it += gridDim.x;
-            }
-        }
-        return it;
-    };
-    uint32_t item = next_item(blockIdx.x);
-    if (item < items) fetch(item);
-    const float* lbase = win + FS_PADF + 18 * tid;    // lane-relative element e at lbase[fs_off(e)]
-    while (item < items) {
-        const uint32_t c = item / tiles, tile = item - c * tiles;
-        const uint32_t following = next_item(item + gridDim.x);
-        stage();
-        dp_handover();                                // (LDS only: no wait for the stores of the item before)
-        if (following < items) fetch(following);      // in flight during the tap loop
-        v2f acc[8], ring[16];
-        v2f late = {0.0f, 0.0f};                      // pair 7's product of the step before (added one step late: +0 first, harmless)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] = v2f{0.0f, 0.0f};
-        // the ring before step 0: the pairs that positions in front of the entry point would have loaded (elements 142 .. 167)
-        static_for<0, 13>([&](auto kc) {
-            constexpr int e = 142 + 2 * decltype(kc)::value;
-            ring[(e & 31) >> 1] = *reinterpret_cast<const v2f*>(lbase + fs_off(e));
-        });
-        const float* lb = lbase + 36;                 // body b reads from lbase - 36 b: b = -1 first
-#pragma unroll 1
-        for (int bi = 0; bi < FS_NBODY; ++bi) {
-            const float* tb = tab + bi * FS_TAB;      // wave-uniform: scalar loads
-            auto half = [&](auto lo_c, auto hi_c) {
-                static_for<decltype(lo_c)::value, decltype(hi_c)::value>([&](auto pc) {
-                    constexpr int p = decltype(pc)::value;
-                    // step s = 32 b + 22 + p; pair q reads element e = 153 + 2q - s = 131 - 32 b + 2q - p: slot (131 + 2q - p) mod 32
-                    if constexpr ((p & 1) == 0) {     // the pair of elements first needed twelve steps from now
-                        constexpr int e = 118 - p;    // (minus 32 b: folded into lb)
-                        ring[(e & 31) >> 1] = *reinterpret_cast<const v2f*>(lb + fs_off(e));
-                    }
-                    const v2f tp = (p & 1) ? *reinterpret_cast<const v2f*>(tb + 32 + p - 1) : *reinterpret_cast<const v2f*>(tb + p);
-                    v2f pr[8];                        // the eight products first, then the eight additions: no dependent neighbours
-                    static_for<0, 8>([&](auto qc) {
-                        constexpr int q = decltype(qc)::value;
-                        constexpr int slot = (131 + 2 * q - p) & 31;
-                        pr[q] = fs_tap_pair_times<slot & 1>(tp, ring[slot >> 1]);
-                    });
-                    // (the compiler counts an asm statement as no wait state at all and pads a reader of ANY asm result that follows a run of
-                    //  them with an s_nop: pair 7's addition of the step before goes first — its product is eight real instructions old)
-                    acc[7] = acc[7] + late;
-#pragma unroll
-                    for (int q = 0; q < 7; ++q) acc[q] = acc[q] + pr[q];
-                    late = pr[7];
-                });
-            };
-            if (bi > 0) half(std::integral_constant<int, 0>{}, std::integral_constant<int, FS_ENTRY>{});
-            half(std::integral_constant<int, FS_ENTRY>{}, std::integral_constant<int, FS_BODY>{});
-            lb -= 36;
-        }
-        acc[7] = acc[7] + late;
-        // outputs 16 tid .. 16 tid + 15 of the tile, from the registers
-        const uint32_t t = tile * FS_TILE + 16u * (uint32_t)tid;
-        float* yo = y + (size_t)c * ypitch + YPRE + t;
-        if (t + 16 <= T) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(yo + 4 * g) = make_float4(acc[2 * g].x, acc[2 * g].y, acc[2 * g + 1].x, acc[2 * g + 1].y);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                if (t + 2 * q < T) yo[2 * q] = acc[q].x;
-                if (t + 2 * q + 1 < T) yo[2 * q + 1] = acc[q].y;
-            }
-        }
-        dp_handover();                                // every wave is through with the window before the next item is staged
-        item = following;
-    }
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr; const uint32_t flip = 0u;
+#include "m17_fir_skew_body.inc"
+}
+// the same with the polarity per channel: pol[c] XOR flip (bit 0)
+__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
+                                                                             uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
+                                                                             const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
+{
+    constexpr bool INVERT = false, MIXED = true;
+#include "m17_fir_skew_body.inc"
 }
 
 // =====================================================================================================
@@ -576,107 +487,17 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __rest
                                                  float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
                                                  uint64_t pos0, DcdCoef k, uint32_t flags)
 {
-    __shared__ __attribute__((aligned(16))) float dl_all[DCD_WPB][DCD_CPW][DCD_PITCH];
-    float (*dl)[DCD_PITCH] = dl_all[threadIdx.x >> 6];
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 1, bin = lane & 1;
-    uint32_t c = (blockIdx.x * DCD_WPB + (threadIdx.x >> 6)) * DCD_CPW + g;
-    const bool live = c < C;   // lanes beyond the last channel shadow it and never store
-    if (!live) c = C - 1;
-    const int16_t* xr = x + (size_t)c * xpitch + XPRE;
-    DcdState* st = state + c;
-    DcdLane s;
-    s.X = v2f{st->xr[bin], st->xi[bin]};
-    s.cc = bin ? v2f{k.c1r, k.c1i} : v2f{k.c0r, k.c0i};
-    s.cs = v2f{-s.cc.y, s.cc.x};
-    s.a01 = v2f{st->acc[0][bin], st->acc[1][bin]};
-    s.a23 = v2f{st->acc[2][bin], st->acc[3][bin]};
-    s.a45 = v2f{st->acc[4][bin], st->acc[5][bin]};
-    float* tab = table + (size_t)c * ticks_cap * 12 + bin * 6;
-    const float* mydl = dl[g];
-    uint32_t phase = (uint32_t)(pos0 % TICK);  // position inside the current tick (wave-uniform)
-    uint64_t tick = pos0 / TICK;
-    uint32_t row = 0;
-    auto lds_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    };
-    auto tick_begin = [&] {  // the sum that restarts with this tick
-        const uint32_t j = (uint32_t)(tick % 5);
-        if (j == 0) s.a01.x = 0.f;
-        if (j == 1) s.a01.y = 0.f;
-        if (j == 2) s.a23.x = 0.f;
-        if (j == 3) s.a23.y = 0.f;
-        if (j == 4) s.a45.x = 0.f;
-    };
-    auto tick_end = [&] {
-        if (live) {
-            float* o = tab + (size_t)row * 12;
-            *reinterpret_cast<float2*>(o) = make_float2(s.a01.x, s.a01.y);
-            *reinterpret_cast<float2*>(o + 2) = make_float2(s.a23.x, s.a23.y);
-            *reinterpret_cast<float2*>(o + 4) = make_float2(s.a45.x, s.a45.y);
-        }
-        phase = 0; ++tick; ++row;
-    };
-    auto one_sample = [&](uint32_t t) {  // generic path: head / tail of a run; x[n] and x[n-120] are one packed pair
-        if (phase == 0) tick_begin();
-        const v2f f = dcd_scale2<INVERT>((int)xr[t], (int)xr[(int64_t)t - 120]);
-        dcd_step(s, f.x - f.y);
-        if (++phase == TICK) tick_end();
-    };
-
-    uint32_t t = 0;
-    while (t < T && (phase % DCD_BLK) != 0) { one_sample(t); ++t; }   // head: up to a block boundary of the tick
-    // whole blocks: lane (g, bin) converts samples [HALF bin, HALF bin + HALF) of its channel's block
-    if (t + DCD_BLK <= T) {
-        constexpr int HALF = DCD_BLK / 2, NQ = HALF / 8;
-        int4 pa[NQ], pb[NQ];
-        auto issue = [&](uint32_t t0) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int16_t* p = xr + (size_t)t0 + HALF * bin + 8 * q;
-                pa[q] = *reinterpret_cast<const int4*>(p);
-                pb[q] = *reinterpret_cast<const int4*>(p - 120);
-            }
-        };
-        auto lo = [](int w) { return (int)(int16_t)(w & 0xFFFF); };
-        auto hi = [](int w) { return w >> 16; };
-        issue(t);
-        for (; t + DCD_BLK <= T; t += DCD_BLK) {
-            float* wrow = dl[g] + HALF * bin;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int4 a = pa[q], d = pb[q];
-                const v2f u0 = dcd_scale2<INVERT>(lo(a.x), hi(a.x)) - dcd_scale2<INVERT>(lo(d.x), hi(d.x));
-                const v2f u1 = dcd_scale2<INVERT>(lo(a.y), hi(a.y)) - dcd_scale2<INVERT>(lo(d.y), hi(d.y));
-                const v2f u2 = dcd_scale2<INVERT>(lo(a.z), hi(a.z)) - dcd_scale2<INVERT>(lo(d.z), hi(d.z));
-                const v2f u3 = dcd_scale2<INVERT>(lo(a.w), hi(a.w)) - dcd_scale2<INVERT>(lo(d.w), hi(d.w));
-                *reinterpret_cast<float4*>(wrow + 8 * q) = make_float4(u0.x, u0.y, u1.x, u1.y);
-                *reinterpret_cast<float4*>(wrow + 8 * q + 4) = make_float4(u2.x, u2.y, u3.x, u3.y);
-            }
-            lds_sync();
-            if (t + 2 * DCD_BLK <= T) issue(t + DCD_BLK);   // in flight while the recurrence below runs
-            if (phase == 0) tick_begin();
-            float d[DCD_BLK];
-#pragma unroll
-            for (int u = 0; u < DCD_BLK / 4; ++u) {
-                const float4 v = *reinterpret_cast<const float4*>(mydl + 4 * u);
-                d[4 * u] = v.x; d[4 * u + 1] = v.y; d[4 * u + 2] = v.z; d[4 * u + 3] = v.w;
-            }
-#pragma unroll
-            for (int u = 0; u < DCD_BLK; ++u) dcd_step(s, d[u]);
-            phase += DCD_BLK;
-            if (phase == TICK) tick_end();
-            lds_sync();
-        }
-    }
-    for (; t < T; ++t) one_sample(t);  // tail
-    if (live) {
-        st->xr[bin] = s.X.x; st->xi[bin] = s.X.y;
-        st->acc[0][bin] = s.a01.x; st->acc[1][bin] = s.a01.y; st->acc[2][bin] = s.a23.x;
-        st->acc[3][bin] = s.a23.y; st->acc[4][bin] = s.a45.x; st->acc[5][bin] = s.a45.y;
-    }
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr;
+#include "m17_dcd_body.inc"
+}
+// the same with the polarity per channel (one channel per lane pair: a per-lane mask): pol[c] XOR bit 0 of flags
+__global__ __launch_bounds__(64 * DCD_WPB) void dcd_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                       float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                       uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
+{
+    constexpr bool INVERT = false, MIXED = true;
+#include "m17_dcd_body.inc"
 }
 
 
@@ -711,151 +532,16 @@ __global__ __launch_bounds__(256) void dcd_pipe_kernel(const int16_t* __restrict
                                                        float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
                                                        uint64_t pos0, DcdCoef k, uint32_t flags)
 {
-    __shared__ __attribute__((aligned(16))) float dbuf[2][DP_CPB][DP_DPITCH];
-    __shared__ __attribute__((aligned(16))) float4 xb[2][DP_BLK / 2][64];
-    const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 1, bin = lane & 1;
-    uint32_t c = blockIdx.x * DP_CPB + g;
-    const bool live = c < C;   // lanes beyond the last channel shadow it and never store
-    if (!live) c = C - 1;
-    const int16_t* xr = x + (size_t)c * xpitch + XPRE;
-    DcdState* st = state + c;
-    const uint32_t NB = T / DP_BLK;       // blocks
-    // every role runs NI hand-overs: NB + 2 for pipeline fill and drain, rounded up to a multiple of DP_PF so that the
-    // producer's unrolled loop has no early exit (its registers stay in fixed slots and its waits stay partial)
-    const uint32_t NI = (NB + 2u + DP_PF - 1u) / DP_PF * DP_PF;
-
-    if (role == 0) {
-        // ---- P: scaling and delta.  A block lasts ~0.5 us, an HBM round trip twice that: the loads of block b are issued DP_PF
-        // blocks ahead (slot = b % DP_PF is a compile-time constant: the loop is unrolled DP_PF times and every body issues the
-        // same loads — past the end the last block again — so the wait for a slot leaves the other slots in flight).
-        int4 pa[DP_PF][2], pb[DP_PF][2];
-        auto issue = [&](uint32_t b, int slot) {   // lane (g, bin) converts samples [16 bin, 16 bin + 16) of its channel's block
-            const int16_t* p = xr + (size_t)min(b, NB - 1u) * DP_BLK + 16 * bin;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                pa[slot][q] = *reinterpret_cast<const int4*>(p + 8 * q);
-                pb[slot][q] = *reinterpret_cast<const int4*>(p + 8 * q - 120);
-            }
-        };
-#pragma unroll
-        for (int j = 0; j < DP_PF; ++j) issue((uint32_t)j, j);
-        auto lo = [](int w) { return (int)(int16_t)(w & 0xFFFF); };
-        auto hi = [](int w) { return w >> 16; };
-        for (uint32_t i0 = 0; i0 < NI; i0 += DP_PF) {
-#pragma unroll
-            for (int slot = 0; slot < DP_PF; ++slot) {
-                const uint32_t i = i0 + (uint32_t)slot;
-                {
-                    float4 o[4];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const int4 a = pa[slot][q], d = pb[slot][q];
-                        const v2f u0 = dcd_scale2<INVERT>(lo(a.x), hi(a.x)) - dcd_scale2<INVERT>(lo(d.x), hi(d.x));
-                        const v2f u1 = dcd_scale2<INVERT>(lo(a.y), hi(a.y)) - dcd_scale2<INVERT>(lo(d.y), hi(d.y));
-                        const v2f u2 = dcd_scale2<INVERT>(lo(a.z), hi(a.z)) - dcd_scale2<INVERT>(lo(d.z), hi(d.z));
-                        const v2f u3 = dcd_scale2<INVERT>(lo(a.w), hi(a.w)) - dcd_scale2<INVERT>(lo(d.w), hi(d.w));
-                        o[2 * q] = make_float4(u0.x, u0.y, u1.x, u1.y);
-                        o[2 * q + 1] = make_float4(u2.x, u2.y, u3.x, u3.y);
-                    }
-                    issue(i + DP_PF, slot);   // this slot's registers are free again: block i + DP_PF goes in flight
-                    if (i < NB && !(flags & 16u)) {
-                        float* wrow = &dbuf[i & 1u][g][16 * bin];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(wrow + 4 * q) = o[q];
-                    }
-                    dp_handover();
-                }
-            }
-        }
-    } else if (role == 1) {
-        // ---- R: the recurrence and nothing else
-        v2f X = v2f{st->xr[bin], st->xi[bin]};
-        const v2f cc = bin ? v2f{k.c1r, k.c1i} : v2f{k.c0r, k.c0i};
-        const v2f cs = v2f{-cc.y, cc.x};
-        auto step = [&](float delta) {
-            const float a = X.x + delta;
-            const v2f m1 = v2f{a, a} * cc;          // (ac, ad)
-            const v2f m2 = v2f{X.y, X.y} * cs;      // (-bd, bc)
-            X = m1 + m2;                            // (ac - bd, ad + bc)
-        };
-        for (uint32_t i = 0; i < NI; ++i) {
-            if (i >= 1u && i <= NB && !(flags & 32u)) {
-                const uint32_t b = i - 1u;
-                const float* drow = &dbuf[b & 1u][g][0];
-                float4* out = &xb[b & 1u][0][lane];
-                float d[DP_BLK];
-#pragma unroll
-                for (int u = 0; u < DP_BLK / 4; ++u) {
-                    const float4 v = *reinterpret_cast<const float4*>(drow + 4 * u);
-                    d[4 * u] = v.x; d[4 * u + 1] = v.y; d[4 * u + 2] = v.z; d[4 * u + 3] = v.w;
-                }
-#pragma unroll
-                for (int u = 0; u < DP_BLK; u += 2) {
-                    step(d[u]); const v2f x0 = X;
-                    step(d[u + 1]);
-                    out[(u / 2) * 64] = make_float4(x0.x, x0.y, X.x, X.y);
-                }
-            }
-            dp_handover();
-        }
-        if (live) { st->xr[bin] = X.x; st->xi[bin] = X.y; }
-    } else {
-        // ---- A0 / A1: norms and running sums; A0 (role 2) owns the sums restarted at ticks = 0..3 (mod 5), A1 the one restarted
-        // at ticks = 4 (mod 5) and the one that runs from the stream start
-        const bool a0 = role == 2;
-        v2f s01 = a0 ? v2f{st->acc[0][bin], st->acc[1][bin]} : v2f{st->acc[4][bin], st->acc[5][bin]};
-        v2f s23 = a0 ? v2f{st->acc[2][bin], st->acc[3][bin]} : v2f{0.f, 0.f};
-        uint32_t phase = (uint32_t)(pos0 % TICK);
-        uint64_t tick = pos0 / TICK;
-        uint32_t row = 0;
-        float* tab = table + (size_t)c * ticks_cap * 12 + bin * 6;
-        const bool skip = flags & (a0 ? 64u : 128u);
-        for (uint32_t i = 0; i < NI; ++i) {
-            if (i >= 2u && i < NB + 2u && !skip) {
-                const uint32_t b = i - 2u;
-                const float4* in = &xb[b & 1u][0][lane];
-                if (phase == 0) {   // the sum that restarts with this tick
-                    const uint32_t j = (uint32_t)(tick % 5);
-                    if (a0) { if (j == 0) s01.x = 0.f; if (j == 1) s01.y = 0.f; if (j == 2) s23.x = 0.f; if (j == 3) s23.y = 0.f; }
-                    else if (j == 4) s01.x = 0.f;
-                }
-                auto acc = [&](float re, float im) {
-                    const v2f xx = {re, im};
-                    const v2f p = xx * xx;
-                    const float nrm = p.x + p.y;
-                    const v2f nn = {nrm, nrm};
-                    s01 = s01 + nn;
-                    if (a0) s23 = s23 + nn;
-                };
-#pragma unroll
-                for (int u = 0; u < DP_BLK / 2; ++u) {
-                    const float4 v = in[u * 64];
-                    acc(v.x, v.y);
-                    acc(v.z, v.w);
-                }
-                phase += DP_BLK;
-                if (phase == TICK) {
-                    if (live) {
-                        float* o = tab + (size_t)row * 12;
-                        if (a0) {
-                            *reinterpret_cast<float2*>(o) = make_float2(s01.x, s01.y);
-                            *reinterpret_cast<float2*>(o + 2) = make_float2(s23.x, s23.y);
-                        } else {
-                            *reinterpret_cast<float2*>(o + 4) = make_float2(s01.x, s01.y);
-                        }
-                    }
-                    phase = 0; ++tick; ++row;
-                }
-            }
-            dp_handover();
-        }
-        if (live) {
-            if (a0) { st->acc[0][bin] = s01.x; st->acc[1][bin] = s01.y; st->acc[2][bin] = s23.x; st->acc[3][bin] = s23.y; }
-            else { st->acc[4][bin] = s01.x; st->acc[5][bin] = s01.y; }
-        }
-    }
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr;
+#include "m17_dcd_pipe_body.inc"
+}
+__global__ __launch_bounds__(256) void dcd_pipe_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                             float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                             uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
+{
+    constexpr bool INVERT = false, MIXED = true;
+#include "m17_dcd_pipe_body.inc"
 }
 
 

@@ -64,6 +64,7 @@ struct GateParams {
     uint32_t flags;
     uint32_t nblk;            // workgroups of the replay itself; the ones behind them fold deferred EVM operations (m17_state.hpp, evm_fold_pass)
     EvParams ev;
+    const uint32_t* pol;      // optional [C]: the channels' polarity entries, 0 / 1 (m17hip_set_channel_polarity), XOR flags bit 0
 };
 
 constexpr int GT_LPC = 4;             // lanes per channel (cooperative loads / stores; the recurrence runs on the first of them)
@@ -96,7 +97,7 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
     float (&pw)[298] = *reinterpret_cast<float (*)[298]>(lds_base + GT_CPW * GT_ROW + GT_CPW * 148);      // patch window: 149 snapshot + 148 run samples
     const int lane = threadIdx.x;
     const int g = lane % GT_CPW, r = lane / GT_CPW;
-    const bool invert = P.flags & 1u;
+    const bool invert = ((P.flags ^ (P.pol ? P.pol[c] : 0u)) & 1u) != 0u;   // this lane's channel: the run's flag XOR its polarity table entry
     // flags bit 1: a replay whose history values nobody will read (the channels K5 serves itself, m17_wave_kernel.hpp): only the
     // replay's end state is wanted, hbuf is left alone (K5 is writing those very rows)
     const bool store = !state_only;
@@ -253,15 +254,16 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
                 const int32_t rs = (int32_t)t - rp;           // relative index of the run's first sample (>= -148)
                 const bool eir = __shfl((int)end_in_run, src);
                 const int32_t et = __shfl(end_t, src);
+                const bool inv_cc = __shfl((int)invert, src) != 0;   // the whole wave works for channel cc here: ITS polarity, not each lane's own channel's
                 const int16_t* xrc = P.x + (size_t)cc * P.xpitch + XPRE + t0;
                 const Boundary* bsrc = (!from_chain && bnd_base) ? bnd_base + cc : nullptr;   // (both wave-uniform)
                 const int16_t* hist = bsrc ? bsrc->hist : P.state[cc].hist;
                 for (int k = lane; k < 149; k += 64) {
                     const int sv = eir ? (int)xrc[(int64_t)et - 148 + k] : (int)hist[k];
-                    pw[k] = scale_sample(sv, invert);
+                    pw[k] = scale_sample(sv, inv_cc);
                 }
                 for (int k = lane; k < 148; k += 64)
-                    if ((int64_t)rs + k < (int64_t)segT) pw[149 + k] = scale_sample((int)xrc[(int64_t)rs + k], invert);
+                    if ((int64_t)rs + k < (int64_t)segT) pw[149 + k] = scale_sample((int)xrc[(int64_t)rs + k], inv_cc);
                 lds_sync();
                 for (int j = rp + lane; j < 148; j += 64) {
                     if ((int64_t)rs + j >= (int64_t)segT) break;

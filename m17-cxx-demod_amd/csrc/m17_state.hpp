@@ -139,7 +139,7 @@ struct SeqParams {
     uint32_t C, T;
     uint64_t pos0;            // absolute index of sample 0 of this (segment of a) run
     uint64_t tick_row0;       // absolute tick stored in row 0 of the DCD table
-    uint32_t flags;           // bit 0 invert, bit 1 continuation segment of a run
+    uint32_t flags;           // bit 0 invert (XOR the channel's entry of `pol`), bit 1 continuation segment of a run
     unsigned long long* dbg;  // optional [channels][24] counters (diagnostics)
     const float* h;           // K2's limit-filter history (hbuf), pitch ypitch
     const float* final_h;     // [C][4] K2's filter history after the last fed sample of the run
@@ -157,6 +157,7 @@ struct SeqParams {
     uint32_t ev_pitch;
     uint32_t* ev_cursor_out;  // [C] the channel's operation cursor at the end of this segment
     GateTruth* truth_out;     // optional [C]: the gate state at the end of this segment (gate-aware front end); overflow[3] counts the channels whose carrier is off there
+    const uint32_t* pol;      // optional [C]: the channels' polarity entries, 0 / 1 (m17hip_set_channel_polarity), XOR flags bit 0; nullptr: flags bit 0 for every channel
 };
 
 // ---- the running EVM, deferred ------------------------------------------------------------------------------------------------------

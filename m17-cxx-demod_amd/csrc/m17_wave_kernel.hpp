@@ -173,7 +173,7 @@ __global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(Seq
     }
     uint16_t* llr16 = reinterpret_cast<uint16_t*>(DL.llr);
 
-    const bool invert = P.flags & 1u;
+    const bool invert = ((P.flags ^ (P.pol ? SReg<uint32_t>::uni(P.pol[c]) : 0u)) & 1u) != 0u;   // the channel's polarity: the run's flag XOR its table entry (one wave = one channel)
     SeqState* gs = P.state + c;
     // ... and so does the cold state (Kalman filters, decoder registers, diagnostics): its users are out-of-line helpers whose
     // global round trips (~1 us each, several in a row) made a single-sample step cost 6 us

@@ -101,6 +101,10 @@ struct RunPlan {
     uint32_t front_segs = 0;      // segments whose front end is queued at once (tuning knob 5)
     bool gate0_queued = false;    // m17hip_demod_front has queued the replay of its first segment (and the prefix copies in front of it)
     uint32_t n_reset = 0;         // channels that begin it with fresh demodulators (m17hip_demod_reset_channels): entries of the context's reset list in use
+    // The polarity of its channels (m17hip_set_channel_polarity; resolve_polarity): uniform — bit 0 of kflags says it, pol == nullptr, the launches are those
+    // of a context without a table — or mixed: pol = the device table the run reads to its end (entry XOR bit 0 of kflags), whatever is set meanwhile.
+    uint32_t kflags = 0;          // `flags` as the kernels get them
+    const uint32_t* pol = nullptr;
     uint32_t t0(uint32_t k) const { return b[std::min<size_t>(k, nseg)]; }
 };
 
@@ -261,6 +265,20 @@ struct m17hip_ctx {
         ~ResetList() { if (staging) (void)hipHostFree(staging); }
     } rlist[2];
     int rcur = 0;              // the list of the latest run that took marks
+    // m17hip_set_channel_polarity: entry c = 1: channel c's samples are negated (XOR M17HIP_FLAG_INVERT of the call).  The table is the host's (`pol_host`,
+    // [maxC], sized by the first call that sets a 1; `pol_ones` of its entries are 1); a launch whose channels are of one polarity never needs it on the
+    // device.  One that does (resolve_polarity) finds it in one of two device tables that take turns, as the reset lists do: staged in pinned memory and
+    // copied on the first stream that reads it when the host's has changed (`pol_dirty`), every other reading stream (main, K3's, K1's, the replay's)
+    // put behind `ready`; when the turn passes to the other table an event per reading stream is recorded for this one, and they are waited for before
+    // it is written again — so a run in flight keeps the table it was queued with.  Nothing of this exists in a context that never sets a 1.
+    std::vector<uint8_t> pol_host;
+    uint32_t pol_ones = 0;
+    bool pol_dirty = false;
+    struct PolTable {
+        DevBuf<uint32_t> dev; uint32_t* staging = nullptr; Event ready, used[4]; bool copied = false, recorded = false;
+        ~PolTable() { if (staging) (void)hipHostFree(staging); }
+    } ptab[2];
+    int pcur = 0;              // the table of the latest launch that read one
     uint32_t lastC = 0;
     bool have_run = false;     // a run has been made since the last reset (the stream continues)
     bool uploaded = false;
@@ -816,10 +834,13 @@ constexpr size_t SEQ_LDS_BYTES_4 = 34816;   // see the K5 launch
 // items per workgroup for the runs that get the latency form of K3 (a continued stream, or nothing else in flight), eight for the others, and
 // never fewer workgroups than a CU can hold of them five times over.
 constexpr uint32_t FIR_GRID_PER_CU = 5, FIR_ITEMS_LATENCY = 3, FIR_ITEMS_THROUGHPUT = 8;
-int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool latency, hipStream_t st, uint32_t t0 = 0, const uint32_t* first_needed = nullptr)
+// `flags` / `pol`: the channels' polarity as resolve_polarity gave it (pol == nullptr: uniform, bit 0 of flags — today's two instantiations)
+int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool latency, hipStream_t st, uint32_t t0 = 0, const uint32_t* first_needed = nullptr,
+               const uint32_t* pol = nullptr)
 {
     TimedK tm(c, KT_FIR);
 #ifdef M17_TOOLS
+    if (c->fir_form == 0 && pol) return M17HIP_EINVAL;   // (round 4's kernel has no per-channel form: refused, not computed under the flag alone)
     if (c->fir_form == 0) {   // round 4's kernel: the measurement build keeps it for same-box comparisons (tools/k1_forms.py, the clk_k1 pass of tools/profile_round.sh)
         dim3 grid((T + FIR_TILE - 1) / FIR_TILE, C);
         tm.launch((fir_rrc150_rolled_kernel<FIR_R, 4>), grid, dim3(FIR_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, flags, c->taps);
@@ -833,7 +854,9 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
         const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
-        if (flags & 1u)
+        if (pol)
+            tm.launch(fir_rrc150_skew_mixed_kernel, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, pol, flags & 1u);
+        else if (flags & 1u)
             tm.launch(fir_rrc150_skew_kernel<true>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
         else
             tm.launch(fir_rrc150_skew_kernel<false>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
@@ -842,7 +865,7 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
     return M17HIP_OK;
 }
 // `pos`: the stream position of the slab's first sample (of the run, where t0 names a segment); `latency`: the four-wave pipeline where the piece allows it
-int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t pos, bool latency, hipStream_t st, uint32_t t0 = 0)
+int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t pos, bool latency, hipStream_t st, uint32_t t0 = 0, const uint32_t* pol = nullptr)
 {
     TimedK tm(c, KT_DCD);
     // table rows are numbered from the first tick of the RUN: a later segment continues where the previous one stopped
@@ -850,19 +873,67 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
     if (!latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK) {
         const dim3 grid((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB));
-        if (flags & 1u)
+        if (pol)
+            tm.launch(dcd_mixed_kernel, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, pol);
+        else if (flags & 1u)
             tm.launch(dcd_kernel<true>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
                                c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
         else
             tm.launch(dcd_kernel<false>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
                                c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
-    } else if (flags & 1u)
+    } else if (pol)
+        tm.launch(dcd_pipe_mixed_kernel, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
+                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, pol);
+    else if (flags & 1u)
         tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
                            c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     else
         tm.launch(dcd_pipe_kernel<false>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
                            c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
     HIPCHK(c, hipGetLastError());
+    return M17HIP_OK;
+}
+
+// The polarity of channels [0, C) in a call made with `flags`: entry XOR bit 0 of flags (m17hip_set_channel_polarity).  Of one polarity (no table, all
+// 0, all 1): kflags carries it in bit 0 and pol stays nullptr — what a context without a table passes.  Mixed: kflags = flags, pol = the device table,
+// brought up to date first where the host's has changed: the copy goes to `first`, the stream whose kernels read it first (or that they are ordered behind).
+int resolve_polarity(m17hip_ctx* c, uint32_t C, uint32_t flags, hipStream_t first, uint32_t& kflags, const uint32_t*& pol)
+{
+    kflags = flags; pol = nullptr;
+    if (!c->pol_ones) return M17HIP_OK;
+    const uint32_t ones = (uint32_t)std::count(c->pol_host.begin(), c->pol_host.begin() + C, (uint8_t)1);
+    if (ones == 0) return M17HIP_OK;
+    if (ones == C) { kflags = flags ^ 1u; return M17HIP_OK; }
+    if (c->pol_dirty || !c->ptab[c->pcur].copied) {
+        const hipStream_t readers[4] = {c->stream, c->side, c->side2, c->side3};
+        m17hip_ctx::PolTable& old = c->ptab[c->pcur];
+        if (old.copied) {   // whatever reads it has been queued by now
+            for (int i = 0; i < 4; ++i) {
+                if (!old.used[i]) HIPCHK(c, old.used[i].create());
+                HIPCHK(c, hipEventRecord(old.used[i], readers[i]));
+            }
+            old.recorded = true;
+            c->pcur ^= 1;
+        }
+        m17hip_ctx::PolTable& t = c->ptab[c->pcur];
+        if (t.recorded) {   // (its readers, up to the change before last; they are behind its copy out of `staging`)
+            for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventSynchronize(t.used[i]));
+            t.recorded = false;
+        }
+        if (!t.ready) HIPCHK(c, t.ready.create());
+        else if (t.copied) HIPCHK(c, hipEventSynchronize(t.ready));
+        if (!t.dev) HIPCHK(c, t.dev.alloc(c->maxC));
+        if (!t.staging) HIPCHK(c, hipHostMalloc((void**)&t.staging, (size_t)c->maxC * 4, hipHostMallocDefault));
+        for (uint32_t ch = 0; ch < c->maxC; ++ch) t.staging[ch] = c->pol_host[ch];
+        HIPCHK(c, hipMemcpyAsync(t.dev, t.staging, (size_t)c->maxC * 4, hipMemcpyHostToDevice, first));
+        HIPCHK(c, hipEventRecord(t.ready, first));
+        for (hipStream_t st : readers)
+            if (st != first) HIPCHK(c, hipStreamWaitEvent(st, t.ready, 0));
+        t.copied = true;
+        c->pol_dirty = false;
+    }
+    pol = c->ptab[c->pcur].dev;
     return M17HIP_OK;
 }
 
@@ -914,7 +985,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 603; }
+int m17hip_version(void) { return 604; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1305,7 +1376,9 @@ int m17hip_fir_rrc150(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, flo
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
     if (!c->uploaded) return M17HIP_ESTATE;
-    if (int r = launch_fir(c, C, T, flags, false, c->stream)) return r;   // (an operator call: the whole chip is its own)
+    uint32_t kflags; const uint32_t* pol;
+    if (int r = resolve_polarity(c, C, flags, c->stream, kflags, pol)) return r;
+    if (int r = launch_fir(c, C, T, kflags, false, c->stream, 0, nullptr, pol)) return r;   // (an operator call: the whole chip is its own)
     if (out_host) {
         HIPCHK(c, hipMemcpy2DAsync(out_host, (size_t)T * sizeof(float), c->now().y + YPRE, c->ypitch * sizeof(float), (size_t)T * sizeof(float), C,
                                    hipMemcpyDeviceToHost, c->stream));
@@ -1359,7 +1432,9 @@ int m17hip_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, float* sum
     if (!c->uploaded) return M17HIP_ESTATE;
     // operator-level call: always from a fresh DFT state at stream position 0
     HIPCHK(c, hipMemsetAsync(c->dcd_state, 0, (size_t)C * sizeof(DcdState), c->stream));
-    if (int r = launch_dcd(c, C, T, flags, 0, c->dcd_form == 1, c->stream)) return r;
+    uint32_t kflags; const uint32_t* pol;
+    if (int r = resolve_polarity(c, C, flags, c->stream, kflags, pol)) return r;
+    if (int r = launch_dcd(c, C, T, kflags, 0, c->dcd_form == 1, c->stream, 0, pol)) return r;
     const uint32_t ticks = T / TICK;
     if (ticks_out) *ticks_out = ticks;
     if (sums_host && ticks)
@@ -1493,6 +1568,14 @@ int m17hip_demod_reset(m17hip_ctx* c)
     return M17HIP_OK;
 }
 
+// the marks of m17hip_demod_reset_channels (and of a polarity change of a channel that has run): every entry < maxC
+static void mark_channels(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
+{
+    if (c->marked.empty()) c->marked.assign(c->maxC, 0);
+    for (uint32_t i = 0; i < n; ++i)
+        if (!c->marked[channels[i]]) { c->marked[channels[i]] = 1; c->marks.push_back(channels[i]); }
+}
+
 int m17hip_demod_reset_channels(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
 {
     if (!c || (n && !channels)) return M17HIP_EINVAL;
@@ -1503,9 +1586,36 @@ int m17hip_demod_reset_channels(m17hip_ctx* c, const uint32_t* channels, uint32_
     // The carrier-detect tick grid is the context's: K3's table rows, K2's replay, K5 and the gate forecast all find a tick as position / 192.  A fresh
     // demodulator's update points fall on ITS tick ends, so its stream can only begin where a tick of the context does.
     if (c->pos % TICK != 0) return M17HIP_ESTATE;
-    if (c->marked.empty()) c->marked.assign(c->maxC, 0);
+    mark_channels(c, channels, n);
+    return M17HIP_OK;
+}
+
+int m17hip_set_channel_polarity(m17hip_ctx* c, const uint8_t* invert, uint32_t n)
+{
+    if (!c || n > c->maxC || (invert == nullptr) != (n == 0)) return M17HIP_EINVAL;
     for (uint32_t i = 0; i < n; ++i)
-        if (!c->marked[channels[i]]) { c->marked[channels[i]] = 1; c->marks.push_back(channels[i]); }
+        if (invert[i] > 1) return M17HIP_EINVAL;   // (before anything changes)
+    if (c->front_queued) return M17HIP_ESTATE;   // the run m17hip_demod_front began has its table
+    // the entries that change: [0, n) against the call's values, or every 1 when the table is cleared
+    std::vector<uint32_t> changed;
+    const uint32_t span = c->pol_host.empty() ? 0u : (n ? n : c->maxC);
+    for (uint32_t i = 0; i < span; ++i)
+        if (c->pol_host[i] != (n ? invert[i] : 0)) changed.push_back(i);
+    if (c->pol_host.empty())
+        for (uint32_t i = 0; i < n; ++i)
+            if (invert[i]) changed.push_back(i);
+    if (changed.empty()) return M17HIP_OK;
+    // A channel that has run carries state formed under its old polarity (the raw input prefix, the sliding DFT, the demodulator): it starts over, as
+    // m17hip_demod_reset_channels starts it — and where that call can (the tick grid is the context's).  The channels of a continued stream are [0, lastC).
+    std::vector<uint32_t> restart;
+    if (c->have_run)
+        for (uint32_t ch : changed)
+            if (ch < c->lastC) restart.push_back(ch);
+    if (!restart.empty() && c->pos % TICK != 0) return M17HIP_ESTATE;
+    if (c->pol_host.empty()) c->pol_host.assign(c->maxC, 0);
+    for (uint32_t ch : changed) { c->pol_host[ch] ^= 1u; if (c->pol_host[ch]) ++c->pol_ones; else --c->pol_ones; }
+    c->pol_dirty = true;
+    if (!restart.empty()) mark_channels(c, restart.data(), (uint32_t)restart.size());
     return M17HIP_OK;
 }
 
@@ -1545,7 +1655,7 @@ enum RunKind { RUN_IN_PLACE, RUN_STAGED, RUN_STAGED_FRONT };
 static RunPlan plan_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, RunKind kind)
 {
     RunPlan p;
-    p.C = C; p.T = T; p.flags = flags; p.staged = kind != RUN_IN_PLACE; p.from_front = kind == RUN_STAGED_FRONT;
+    p.C = C; p.T = T; p.flags = p.kflags = flags; p.staged = kind != RUN_IN_PLACE; p.from_front = kind == RUN_STAGED_FRONT;
     // kind              runs_overlap is asked                    ramp where key 33 = -1
     // in place          always                                   AUTO_RAMP when chain-bound
     // staged (run)      where key 10 = -1 leaves K3 to the run   none: as a rule a continued stream, where the extra launches of a ramp
@@ -1595,10 +1705,10 @@ static int launch_front_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k)
         HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k - ahead], 0));
     }
     if (k == 1) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fir_[q][0], 0));   // segment 0's front end first: K2/K5 wait for it
-    if (int r = launch_dcd(c, p.C, len, p.flags, c->pos, p.dcd_latency, c->side, t0)) return r;
+    if (int r = launch_dcd(c, p.C, len, p.kflags, c->pos, p.dcd_latency, c->side, t0, p.pol)) return r;
     HIPCHK(c, hipEventRecord(c->ev_dcd_[q][k], c->side));
     if (p.gate_run && k >= 2u) return M17HIP_OK;
-    if (int r = launch_fir(c, p.C, len, p.flags, p.fir_latency, c->side2, t0)) return r;
+    if (int r = launch_fir(c, p.C, len, p.kflags, p.fir_latency, c->side2, t0, nullptr, p.pol)) return r;
     HIPCHK(c, hipEventRecord(c->ev_fir_[q][k], c->side2));
     return M17HIP_OK;
 }
@@ -1631,7 +1741,7 @@ static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
     hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, c->truth + (size_t)(k & 1u) * c->maxC, c->now().dcd, c->ticks_cap,
                        (uint64_t)(c->pos / TICK), (uint64_t)(c->pos + t1), t2 - t1, t3 - t1, c->first_needed, C);
     HIPCHK(c, hipGetLastError());
-    if (int r = launch_fir(c, C, t3 - t2, p.flags, p.fir_latency, c->side2, t2, c->first_needed)) return r;
+    if (int r = launch_fir(c, C, t3 - t2, p.kflags, p.fir_latency, c->side2, t2, c->first_needed, p.pol)) return r;
     HIPCHK(c, hipEventRecord(c->ev_fir_[q][k + 2u], c->side2));
     return M17HIP_OK;
 }
@@ -1659,7 +1769,7 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
     G.only = redo ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (flags by segment parity)
     G.bnd = redo ? c->bnd + (size_t)(k & 1u) * c->maxC : nullptr;   // (written by K5 of segment k - 1)
-    G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.flags | ((redo && !redo_stores) ? 2u : 0u);
+    G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.kflags | ((redo && !redo_stores) ? 2u : 0u); G.pol = p.pol;
     G.nblk = (C + GT_CPW - 1) / GT_CPW;
     uint32_t fold_blocks = 0;
     if (ahead && k >= 2 && c->defer_evm && c->ev_ops2[c->ev_par]) {   // (K5 of segment k - 2 is through: its EVM operations ride along, sixteen channels per block)
@@ -1763,6 +1873,8 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
         if (int r = take_marks(c, n_reset, c->copy)) return r;
         if (int r = reset_marked_front(c, n_reset, c->copy, RL_COPY, true, false)) return r;
     }
+    uint32_t kflags; const uint32_t* pol;   // (m17hip_set_channel_polarity: a changed table goes up behind the staged input, in front of everything that reads it)
+    if (int r = resolve_polarity(c, C, flags, c->copy, kflags, pol)) return r;
     HIPCHK(c, hipEventRecord(c->ev_in_ready, c->copy));
     for (hipStream_t st : {c->side, c->side2}) {
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_in_ready, 0));
@@ -1776,7 +1888,7 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
         HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[c->slot ^ 1][j], 0));
     }
     p = plan_run(c, C, T, flags, kind);
-    p.n_reset = n_reset;
+    p.n_reset = n_reset; p.kflags = kflags; p.pol = pol;
     if (int r = launch_front_all(c, p)) return r;
     if (n_reset) commit_marks(c);
     return M17HIP_OK;
@@ -1873,6 +1985,8 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     if (tiled && npieces > 1 && T - (npieces - 1) * piece < 4 * LP_TILE) --npieces;   // (a last piece of fewer than four tiles joins the one before it)
     int r = ensure_seg_events(c, c->slot, npieces);
     if (r) return r;
+    uint32_t kflags; const uint32_t* pol;
+    if ((r = resolve_polarity(c, C, flags, c->stream, kflags, pol))) return r;
     auto& ev_fir = c->ev_fir_[c->slot];
     // (Tried: the chain on compute units of its own — hipExtStreamCreateWithCUMask, a quarter of the chip — with the two throughput kernels on
     //  the rest: the chain's pieces 0.79 -> 0.74 ms, the call 8.2 -> 9.0 ms.  What stretches the chain beside them is not its SIMD: NOTES 5.4.)
@@ -1884,7 +1998,7 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     if (tiled) HIPCHK(c, hipMemsetAsync(lstate, 0, (size_t)C * 4 * sizeof(float), st_chain));
     for (uint32_t k = 0; k < npieces; ++k) {
         const uint32_t t0 = k * piece, len = k + 1 < npieces ? piece : T - t0;
-        if ((r = launch_fir(c, C, len, flags, false, st_fir, t0))) return r;
+        if ((r = launch_fir(c, C, len, kflags, false, st_fir, t0, nullptr, pol))) return r;
         HIPCHK(c, hipEventRecord(ev_fir[k], st_fir));
         HIPCHK(c, hipStreamWaitEvent(st_corr, ev_fir[k], 0));
         HIPCHK(c, hipStreamWaitEvent(st_chain, ev_fir[k], 0));
@@ -1984,7 +2098,7 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
     P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
     P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
-    P.C = p.C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (p.flags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8);
+    P.C = p.C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (p.kflags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8); P.pol = p.pol;
     P.kalman_order = c->kalman_order; P.channel_base = c->channel_base;
     P.level_gain = c->level_gain + (size_t)(c->kalman_order & 7u) * core::LEVEL_SCHED_N;
     P.diag_log = c->diag_cap ? c->diag_log : nullptr; P.diag_cap = c->diag_cap; P.diag_count = c->diag_count;
@@ -2184,6 +2298,7 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
     if (!p.staged) {
         p = plan_run(c, C, T, flags, RUN_IN_PLACE);
+        if ((r = resolve_polarity(c, C, flags, c->stream, p.kflags, p.pol))) return r;
         if (!c->marks.empty()) {   // (m17hip_demod_reset_channels; in place the main stream is behind the previous run's carried tails and its K3)
             if ((r = take_marks(c, p.n_reset, c->stream))) return r;
             if ((r = reset_marked_front(c, p.n_reset, c->stream, RL_COPY, true, true))) return r;

@@ -59,6 +59,9 @@ public:
     // Fresh demodulators for the listed channels only (local indices), from the start of the NEXT run queued; the others go on
     // (m17hip_demod_reset_channels: between runs whose lengths are multiples of 192 samples, not between front() and run()).
     void reset_channels(const uint32_t* channels, uint32_t n) { check(m17hip_demod_reset_channels(ctx_, channels, n), "m17hip_demod_reset_channels"); }
+    // Per-channel input polarity (the reference's -i, per receiver): invert[n] of 0 / 1 for local channels 0 .. n - 1, nullptr with n == 0 clears;
+    // XOR the flags of run() (m17hip_set_channel_polarity: changing a channel that has run restarts it, as reset_channels does).
+    void set_channel_polarity(const uint8_t* invert, uint32_t n) { check(m17hip_set_channel_polarity(ctx_, invert, n), "m17hip_set_channel_polarity"); }
     void run(uint32_t flags = 0) { check(m17hip_demod_run(ctx_, channels_, samples_, flags), "m17hip_demod_run"); }
 
     // records of the last run, ordered by (channel, seq): one compaction and one synchronisation when the guessed capacity suffices

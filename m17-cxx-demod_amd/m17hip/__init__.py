@@ -51,6 +51,7 @@ EXPORTS = [
     "m17hip_comm_destroy", "m17hip_comm_last_error", "m17hip_gather_frames", "m17hip_gather_frames_device", "m17hip_diag_log_fetch",
     "m17hip_upload_i16_device_async", "m17hip_input_alternate", "m17hip_demod_front", "m17hip_advice", "m17hip_replay_drops", "m17hip_frames_select",
     "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats", "m17hip_demod_reset_channels",
+    "m17hip_set_channel_polarity",
 ]
 ETRUNC = -6
 EOVERFLOW = -5
@@ -333,6 +334,19 @@ class Context:
         front() and run() (m17hip_demod_reset_channels)."""
         idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32).reshape(-1))
         self._chk(self.lib.m17hip_demod_reset_channels(self.h, _ptr(idx) if idx.size else None, C.c_uint32(idx.size)))
+
+    def set_channel_polarity(self, invert):
+        """Per-channel input polarity: `invert` is an array-like of 0 / 1 for local channels 0 .. len - 1 (later entries keep their value), or None
+        to clear the table.  A channel's effective polarity in a call is its entry XOR the call's FLAG_INVERT.  Changing the entry of a channel
+        that has run restarts it as reset_channels does, under that call's rule (m17hip_set_channel_polarity)."""
+        if invert is None:
+            self._chk(self.lib.m17hip_set_channel_polarity(self.h, None, C.c_uint32(0)))
+            return
+        a = np.asarray(invert).reshape(-1)
+        if a.size == 0 or not np.all((a == 0) | (a == 1)):   # (an empty table is not "clear": that is None)
+            self._chk(-1)
+        tab = np.ascontiguousarray(a.astype(np.uint8))
+        self._chk(self.lib.m17hip_set_channel_polarity(self.h, _ptr(tab), C.c_uint32(tab.size)))
 
     def run(self, flags=0, channels=None, samples=None):
         self._chk(self.lib.m17hip_demod_run(self.h, C.c_uint32(channels or self.C), C.c_uint32(samples or self.T), C.c_uint32(flags)))
