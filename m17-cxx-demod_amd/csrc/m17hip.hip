@@ -85,6 +85,61 @@ private:
     hipEvent_t e_ = nullptr;
 };
 
+// A small table of words that the host writes and kernels on several streams read (the reset lists, the polarity table).  Two device copies take turns, so
+// a write never touches the copy that queued work reads, and the host waits for nothing that is in flight:
+//   begin_write   passes the turn to the other copy, waits ON THE HOST for the readers recorded for that one — those of two turns ago — and for its earlier
+//                 upload, and hands out its pinned staging buffer; events and buffers (`cap` words) are made the first time a copy is written
+//   publish       queues the upload of the first n words on `first`, the stream whose kernels read the table first, and records `ready` there
+//   before_read   a kernel on `st` is about to read the table: `st` goes behind `ready` (on `first` that is stream order already)
+//   after_read    a kernel of reader `which` has been queued on `st`: `used[which]` is recorded, what the write after next waits for
+// An object that is never written owns nothing and waits for nothing.
+enum Reader { RD_MAIN = 0, RD_DCD, RD_FIR, RD_REPLAY, RD_FRONT, RD_PAY, RD_N };   // main stream; K3's, K1's, the replay's; a reset list's first kernel; the payload stream
+class TurnTable {
+public:
+    bool live() const { return t_[cur_].live; }                // the current copy holds a published table
+    const uint32_t* dev() const { return t_[cur_].dev; }       // (the current copy, on the device)
+    hipError_t begin_write(size_t cap, uint32_t** staging)
+    {
+        if (live()) cur_ ^= 1;   // (a write that failed half way is made again into the same copy)
+        Copy& t = t_[cur_];
+        t.live = false;
+        for (int i = 0; i < RD_N; ++i) {
+            if (!t.recorded[i]) continue;
+            if (const hipError_t e = hipEventSynchronize(t.used[i])) return e;
+            t.recorded[i] = false;
+        }
+        if (const hipError_t e = t.ready ? hipEventSynchronize(t.ready) : t.ready.create()) return e;   // (the staging buffer is the upload's source)
+        if (!t.dev) if (const hipError_t e = t.dev.alloc(cap)) return e;
+        if (!t.staging) if (const hipError_t e = hipHostMalloc((void**)&t.staging, cap * 4, hipHostMallocDefault)) return e;
+        *staging = t.staging;
+        return hipSuccess;
+    }
+    hipError_t publish(size_t n, hipStream_t first)
+    {
+        Copy& t = t_[cur_];
+        if (const hipError_t e = hipMemcpyAsync(t.dev, t.staging, n * 4, hipMemcpyHostToDevice, first)) return e;
+        if (const hipError_t e = hipEventRecord(t.ready, first)) return e;
+        t.first = first;
+        t.live = true;
+        return hipSuccess;
+    }
+    hipError_t before_read(hipStream_t st) { return st == t_[cur_].first ? hipSuccess : hipStreamWaitEvent(st, t_[cur_].ready, 0); }
+    hipError_t after_read(Reader which, hipStream_t st)
+    {
+        Copy& t = t_[cur_];
+        if (!t.used[which]) if (const hipError_t e = t.used[which].create()) return e;
+        if (const hipError_t e = hipEventRecord(t.used[which], st)) return e;
+        t.recorded[which] = true;
+        return hipSuccess;
+    }
+private:
+    struct Copy {
+        DevBuf<uint32_t> dev; uint32_t* staging = nullptr; hipStream_t first = nullptr; Event ready, used[RD_N]; bool recorded[RD_N] = {}; bool live = false;
+        ~Copy() { if (staging) (void)hipHostFree(staging); }
+    } t_[2];
+    int cur_ = 0;
+};
+
 struct TimedLaunch { Event a, b; int which; };
 
 struct BertState; struct ChanStat; struct PacketState; struct PacketRec;   // (with the host layer's kernels, below)
@@ -255,30 +310,20 @@ struct m17hip_ctx {
     DcdCoef coef{};
     uint64_t pos = 0;          // samples consumed since reset
     // m17hip_demod_reset_channels: the channels marked since the latest run was queued, each once (`marked`: [maxC], sized with the first mark).
-    // The run that takes the marks puts them on the device — one of two lists in turn, each staged in pinned host memory and copied on the first
-    // stream that reads it (`ready`: the copy is through; the other readers wait for it), each with an event per stream that read it last
-    // (copy / carrier detect / main / payload): a list is written again only when those have passed.  Nothing of this exists in a context that never marks.
+    // The run that takes the marks puts them on the device as a list (TurnTable; take_marks); each kernel that reads it records its reader's event as it
+    // is queued (front / carrier detect / main / payload).  A context that never marks never writes one.
     std::vector<uint32_t> marks;
     std::vector<uint8_t> marked;
-    struct ResetList {
-        DevBuf<uint32_t> list; uint32_t* staging = nullptr; hipStream_t first = nullptr; Event ready, used[4]; bool recorded[4] = {false, false, false, false};
-        ~ResetList() { if (staging) (void)hipHostFree(staging); }
-    } rlist[2];
-    int rcur = 0;              // the list of the latest run that took marks
+    TurnTable reset_list;      // the list of the latest run that took marks
     // m17hip_set_channel_polarity: entry c = 1: channel c's samples are negated (XOR M17HIP_FLAG_INVERT of the call).  The table is the host's (`pol_host`,
     // [maxC], sized by the first call that sets a 1; `pol_ones` of its entries are 1); a launch whose channels are of one polarity never needs it on the
-    // device.  One that does (resolve_polarity) finds it in one of two device tables that take turns, as the reset lists do: staged in pinned memory and
-    // copied on the first stream that reads it when the host's has changed (`pol_dirty`), every other reading stream (main, K3's, K1's, the replay's)
-    // put behind `ready`; when the turn passes to the other table an event per reading stream is recorded for this one, and they are waited for before
-    // it is written again — so a run in flight keeps the table it was queued with.  Nothing of this exists in a context that never sets a 1.
+    // device.  One that does (resolve_polarity) finds it in a TurnTable, written when the host's has changed (`pol_dirty`).  Its readers are every launch of
+    // every run queued until the next change: their events are recorded on all four reading streams (main, K3's, K1's, the replay's) when the turn passes
+    // on — so a run in flight keeps the table it was queued with.  A context that never sets a 1 never writes one.
     std::vector<uint8_t> pol_host;
     uint32_t pol_ones = 0;
     bool pol_dirty = false;
-    struct PolTable {
-        DevBuf<uint32_t> dev; uint32_t* staging = nullptr; Event ready, used[4]; bool copied = false, recorded = false;
-        ~PolTable() { if (staging) (void)hipHostFree(staging); }
-    } ptab[2];
-    int pcur = 0;              // the table of the latest launch that read one
+    TurnTable pol_table;       // the table of the latest launch that read one
     uint32_t lastC = 0;
     bool have_run = false;     // a run has been made since the last reset (the stream continues)
     bool uploaded = false;
@@ -854,12 +899,12 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
         const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
-        if (pol)
-            tm.launch(fir_rrc150_skew_mixed_kernel, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, pol, flags & 1u);
-        else if (flags & 1u)
-            tm.launch(fir_rrc150_skew_kernel<true>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
-        else
-            tm.launch(fir_rrc150_skew_kernel<false>, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed);
+        const auto go = [&](auto kernel, auto... mixed) {
+            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
+        };
+        if (pol) go(fir_rrc150_skew_mixed_kernel, pol, flags & 1u);
+        else if (flags & 1u) go(fir_rrc150_skew_kernel<true>);
+        else go(fir_rrc150_skew_kernel<false>);
     }
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
@@ -871,26 +916,18 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     // table rows are numbered from the first tick of the RUN: a later segment continues where the previous one stopped
     const uint64_t row0 = (pos + t0) / TICK - pos / TICK;
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
-    if (!latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK) {
-        const dim3 grid((C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB));
-        if (pol)
-            tm.launch(dcd_mixed_kernel, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, pol);
-        else if (flags & 1u)
-            tm.launch(dcd_kernel<true>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
-        else
-            tm.launch(dcd_kernel<false>, grid, dim3(64 * DCD_WPB), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                               c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
-    } else if (pol)
-        tm.launch(dcd_pipe_mixed_kernel, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, pol);
-    else if (flags & 1u)
-        tm.launch(dcd_pipe_kernel<true>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
-    else
-        tm.launch(dcd_pipe_kernel<false>, dim3((C + DP_CPB - 1) / DP_CPB), dim3(256), 0, st, c->now().x + t0, c->xpitch, c->dcd_state,
-                           c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags);
+    const bool one_wave = !latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK;
+    const dim3 grid(one_wave ? (C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB) : (C + DP_CPB - 1) / DP_CPB), block(one_wave ? 64 * DCD_WPB : 256);
+    const auto go = [&](auto kernel, auto... mixed) {   // (both forms take the same arguments)
+        tm.launch(kernel, grid, block, 0, st, c->now().x + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
+    };
+    if (one_wave) {
+        if (pol) go(dcd_mixed_kernel, pol);
+        else if (flags & 1u) go(dcd_kernel<true>);
+        else go(dcd_kernel<false>);
+    } else if (pol) go(dcd_pipe_mixed_kernel, pol);
+    else if (flags & 1u) go(dcd_pipe_kernel<true>);
+    else go(dcd_pipe_kernel<false>);
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -905,35 +942,18 @@ int resolve_polarity(m17hip_ctx* c, uint32_t C, uint32_t flags, hipStream_t firs
     const uint32_t ones = (uint32_t)std::count(c->pol_host.begin(), c->pol_host.begin() + C, (uint8_t)1);
     if (ones == 0) return M17HIP_OK;
     if (ones == C) { kflags = flags ^ 1u; return M17HIP_OK; }
-    if (c->pol_dirty || !c->ptab[c->pcur].copied) {
-        const hipStream_t readers[4] = {c->stream, c->side, c->side2, c->side3};
-        m17hip_ctx::PolTable& old = c->ptab[c->pcur];
-        if (old.copied) {   // whatever reads it has been queued by now
-            for (int i = 0; i < 4; ++i) {
-                if (!old.used[i]) HIPCHK(c, old.used[i].create());
-                HIPCHK(c, hipEventRecord(old.used[i], readers[i]));
-            }
-            old.recorded = true;
-            c->pcur ^= 1;
-        }
-        m17hip_ctx::PolTable& t = c->ptab[c->pcur];
-        if (t.recorded) {   // (its readers, up to the change before last; they are behind its copy out of `staging`)
-            for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventSynchronize(t.used[i]));
-            t.recorded = false;
-        }
-        if (!t.ready) HIPCHK(c, t.ready.create());
-        else if (t.copied) HIPCHK(c, hipEventSynchronize(t.ready));
-        if (!t.dev) HIPCHK(c, t.dev.alloc(c->maxC));
-        if (!t.staging) HIPCHK(c, hipHostMalloc((void**)&t.staging, (size_t)c->maxC * 4, hipHostMallocDefault));
-        for (uint32_t ch = 0; ch < c->maxC; ++ch) t.staging[ch] = c->pol_host[ch];
-        HIPCHK(c, hipMemcpyAsync(t.dev, t.staging, (size_t)c->maxC * 4, hipMemcpyHostToDevice, first));
-        HIPCHK(c, hipEventRecord(t.ready, first));
-        for (hipStream_t st : readers)
-            if (st != first) HIPCHK(c, hipStreamWaitEvent(st, t.ready, 0));
-        t.copied = true;
+    if (c->pol_dirty || !c->pol_table.live()) {
+        const struct { Reader which; hipStream_t st; } readers[4] = {{RD_MAIN, c->stream}, {RD_DCD, c->side}, {RD_FIR, c->side2}, {RD_REPLAY, c->side3}};
+        if (c->pol_table.live())   // the turn passes on: whatever reads the table in use has been queued by now
+            for (const auto& rd : readers) HIPCHK(c, c->pol_table.after_read(rd.which, rd.st));
+        uint32_t* staging;
+        HIPCHK(c, c->pol_table.begin_write(c->maxC, &staging));
+        for (uint32_t ch = 0; ch < c->maxC; ++ch) staging[ch] = c->pol_host[ch];
+        HIPCHK(c, c->pol_table.publish(c->maxC, first));
+        for (const auto& rd : readers) HIPCHK(c, c->pol_table.before_read(rd.st));
         c->pol_dirty = false;
     }
-    pol = c->ptab[c->pcur].dev;
+    pol = c->pol_table.dev();
     return M17HIP_OK;
 }
 
@@ -1793,27 +1813,16 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
 
 // ---- m17hip_demod_reset_channels: the marked channels begin the run being queued with fresh demodulators ---------------------------------------
 // The marks become a list on the device (n entries; 0: nothing is marked — the caller then queues nothing for them).
-enum { RL_COPY = 0, RL_DCD, RL_MAIN, RL_PAY };
-// `first`: the stream whose kernel reads the list first — the copy is queued there, from pinned memory, so the host waits for nothing that is in flight.
+// `first`: the stream whose kernel reads the list first (TurnTable::publish).
 // The marks themselves stay until the run's front end is queued (commit_marks): a call that fails before that leaves them for the caller's next attempt.
 static int take_marks(m17hip_ctx* c, uint32_t& n, hipStream_t first)
 {
     n = (uint32_t)c->marks.size();
     if (!n) return M17HIP_OK;
-    c->rcur ^= 1;
-    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
-    for (int i = 0; i < 4; ++i) {   // (its readers of two marked runs ago; the first of them is behind that run's copy out of `staging`)
-        if (rl.recorded[i]) HIPCHK(c, hipEventSynchronize(rl.used[i]));
-        rl.recorded[i] = false;
-        if (!rl.used[i]) HIPCHK(c, rl.used[i].create());
-    }
-    if (!rl.ready) HIPCHK(c, rl.ready.create());
-    if (!rl.list) HIPCHK(c, rl.list.alloc(c->maxC));
-    if (!rl.staging) HIPCHK(c, hipHostMalloc((void**)&rl.staging, (size_t)c->maxC * 4, hipHostMallocDefault));
-    std::memcpy(rl.staging, c->marks.data(), (size_t)n * 4);
-    HIPCHK(c, hipMemcpyAsync(rl.list, rl.staging, (size_t)n * 4, hipMemcpyHostToDevice, first));
-    HIPCHK(c, hipEventRecord(rl.ready, first));
-    rl.first = first;
+    uint32_t* staging;
+    HIPCHK(c, c->reset_list.begin_write(c->maxC, &staging));
+    std::memcpy(staging, c->marks.data(), (size_t)n * 4);
+    HIPCHK(c, c->reset_list.publish(n, first));
     return M17HIP_OK;
 }
 static void commit_marks(m17hip_ctx* c)
@@ -1821,30 +1830,16 @@ static void commit_marks(m17hip_ctx* c)
     for (uint32_t ch : c->marks) c->marked[ch] = 0;
     c->marks.clear();
 }
-// a kernel on `st` is about to read the list: behind its copy (on the stream that made the copy that is stream order already) ...
-static int reset_list_wait(m17hip_ctx* c, hipStream_t st)
-{
-    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
-    if (st != rl.first) HIPCHK(c, hipStreamWaitEvent(st, rl.ready, 0));
-    return M17HIP_OK;
-}
-// ... and has been queued: the list is not written again before it is through
-static int reset_list_used(m17hip_ctx* c, int which, hipStream_t st)
-{
-    m17hip_ctx::ResetList& rl = c->rlist[c->rcur];
-    HIPCHK(c, hipEventRecord(rl.used[which], st));
-    rl.recorded[which] = true;
-    return M17HIP_OK;
-}
 // The FRONT-END state of the listed channels — `x`: the input prefix (K1's FIR history, K3's 120-sample delay), on a stream that has carried the previous
 // input's tail into the prefixes; `dcd`: the sliding-DFT state, on a stream that is behind the previous run's K3 — before K1 / K3 of the run start.
-static int reset_marked_front(m17hip_ctx* c, uint32_t n, hipStream_t st, int which, bool x, bool dcd)
+static int reset_marked_front(m17hip_ctx* c, uint32_t n, hipStream_t st, Reader which, bool x, bool dcd)
 {
-    if (int r = reset_list_wait(c, st)) return r;
-    hipLaunchKernelGGL(front_reset_list_kernel, dim3(n), dim3(64), 0, st, c->rlist[c->rcur].list.get(), n, x ? c->now().x.get() : (int16_t*)nullptr, c->xpitch,
+    HIPCHK(c, c->reset_list.before_read(st));
+    hipLaunchKernelGGL(front_reset_list_kernel, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? c->now().x.get() : (int16_t*)nullptr, c->xpitch,
                        dcd ? c->dcd_state.get() : (DcdState*)nullptr);
     HIPCHK(c, hipGetLastError());
-    return reset_list_used(c, which, st);
+    HIPCHK(c, c->reset_list.after_read(which, st));
+    return M17HIP_OK;
 }
 
 // A staged run begins: the slab pairs swap, the 152-sample tail of the previous input is carried into the new slab's prefix, and the
@@ -1871,7 +1866,7 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
     uint32_t n_reset = 0;   // (m17hip_demod_reset_channels: the marked channels' input prefixes, behind the tail copy)
     if (!c->marks.empty()) {
         if (int r = take_marks(c, n_reset, c->copy)) return r;
-        if (int r = reset_marked_front(c, n_reset, c->copy, RL_COPY, true, false)) return r;
+        if (int r = reset_marked_front(c, n_reset, c->copy, RD_FRONT, true, false)) return r;
     }
     uint32_t kflags; const uint32_t* pol;   // (m17hip_set_channel_polarity: a changed table goes up behind the staged input, in front of everything that reads it)
     if (int r = resolve_polarity(c, C, flags, c->copy, kflags, pol)) return r;
@@ -1881,7 +1876,7 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_mark, 0));
     }
     if (n_reset) {   // (... and their sliding-DFT state, on K3's stream: behind the previous run's K3, in front of this run's)
-        if (int r = reset_marked_front(c, n_reset, c->side, RL_DCD, false, true)) return r;
+        if (int r = reset_marked_front(c, n_reset, c->side, RD_DCD, false, true)) return r;
     }
     if (c->front_k1_after && c->have_run && c->last_nseg) {   // K1 out of the way of the previous run's first (heaviest) K5 launches
         const uint32_t j = std::min(c->front_k1_after, c->last_nseg) - 1u;
@@ -2234,21 +2229,22 @@ static int flush_after_run(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
 static int reset_marked_state(m17hip_ctx* c, const RunPlan& p)
 {
     const uint32_t n = p.n_reset;
-    const uint32_t* list = c->rlist[c->rcur].list;
+    const uint32_t* list = c->reset_list.dev();
     if (int r = flush_fold(c)) return r;
     if (int r = flush_payload(c)) return r;
     for (const auto& rs : c->sets)
         if (rs.valid)
             if (int r = pay_after(c, rs)) return r;
-    if (int r = reset_list_wait(c, c->pay())) return r;
+    HIPCHK(c, c->reset_list.before_read(c->pay()));
     hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert_state.get(), c->pkt_cap ? c->pkt_state.get() : (PacketState*)nullptr);
     HIPCHK(c, hipGetLastError());
-    if (int r = reset_list_used(c, RL_PAY, c->pay())) return r;
-    if (int r = reset_list_wait(c, c->stream)) return r;
+    HIPCHK(c, c->reset_list.after_read(RD_PAY, c->pay()));
+    HIPCHK(c, c->reset_list.before_read(c->stream));
     hipLaunchKernelGGL(prefix_reset_list_kernel, dim3(n), dim3(64), 0, c->stream, list, n, c->now().y.get(), c->now().h.get(), c->ypitch);
     hipLaunchKernelGGL(seq_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, list, n, c->seq_state.get(), c->ev_state.get(), (uint64_t)c->pos);
     HIPCHK(c, hipGetLastError());
-    return reset_list_used(c, RL_MAIN, c->stream);
+    HIPCHK(c, c->reset_list.after_read(RD_MAIN, c->stream));
+    return M17HIP_OK;
 }
 
 int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
@@ -2301,7 +2297,7 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
         if ((r = resolve_polarity(c, C, flags, c->stream, p.kflags, p.pol))) return r;
         if (!c->marks.empty()) {   // (m17hip_demod_reset_channels; in place the main stream is behind the previous run's carried tails and its K3)
             if ((r = take_marks(c, p.n_reset, c->stream))) return r;
-            if ((r = reset_marked_front(c, p.n_reset, c->stream, RL_COPY, true, true))) return r;
+            if ((r = reset_marked_front(c, p.n_reset, c->stream, RD_FRONT, true, true))) return r;
         }
     }
     if ((r = p.staged ? carry_staged_prefixes(c, p) : launch_front_all(c, p))) return r;

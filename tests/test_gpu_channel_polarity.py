@@ -400,6 +400,77 @@ def test_a_run_in_flight_keeps_the_table_it_was_queued_with():
         ctx.close()
 
 
+# ---- 7b: a device copy written again after a run has read it --------------------------------------------------------------------------------
+RE_T, RE_RUNS, RE_SEED = 19200, 5, 6051
+RE_FLIPS = {1: [2, 5], 2: [0], 3: [5, 7], 4: [3]}   # run: the receivers that change sides in front of it
+
+
+@pytest.fixture(scope="module")
+def reuse_case():
+    """Five runs, a different table in front of each of runs 1 to 4, the changed channels' input negated from that run on: four tables and four reset
+    lists go up, so each of the two device copies of either is written a second time after a run has read it."""
+    Cn, T = 8, RE_T
+    x = _stream8(T, RE_RUNS, seed=RE_SEED).copy()
+    pols = [np.zeros(Cn, dtype=np.uint8)]
+    for r in range(1, RE_RUNS):
+        pol = pols[-1].copy()
+        pol[RE_FLIPS[r]] ^= 1
+        assert 0 < pol.sum() < Cn, "a mixed table: only that one is put on the device"
+        pols.append(pol)
+        x[RE_FLIPS[r], r * T:] = -x[RE_FLIPS[r], r * T:]
+    exp = _expect(x, T, pols, restarts=RE_FLIPS)
+    for r in range(RE_RUNS):   # (on the oracle alone)
+        assert sum(rows.size for rows in exp[r][0]) > 0, r
+    for r, chs in RE_FLIPS.items():   # a restarted channel reports again, counted from its restart, before it is restarted again or the stream ends
+        for c in chs:
+            end = min([q for q, cc in RE_FLIPS.items() if q > r and c in cc] + [RE_RUNS])
+            later = np.concatenate([exp[q][0][c] for q in range(r, end)])
+            assert later.size > 0 and later["seq"][0] == 0 and 0 < later["sample_pos"][0] <= (end - r) * T, (r, c)
+    x.setflags(write=False)
+    return x, pols, exp
+
+
+def test_copies_written_again_after_a_run_has_read_them_in_place(reuse_case):
+    x, pols, exp = reuse_case
+    Cn, T = 8, RE_T
+    ctx = m17hip.Context(Cn, T)
+    try:
+        ctx.reset()
+        for r in range(RE_RUNS):
+            if r:
+                ctx.set_channel_polarity(pols[r])
+            ctx.upload(x[:, r * T:(r + 1) * T]); ctx.run()
+            _assert_run(ctx.frames().copy(), ctx.diag(Cn), exp[r], f"in place, run {r}")
+    finally:
+        ctx.close()
+
+
+def test_copies_written_again_after_a_run_has_read_them_staged_live_feed(reuse_case):
+    import torch
+    x, pols, exp = reuse_case
+    Cn, T = 8, RE_T
+    pins = [torch.from_numpy(np.ascontiguousarray(x[:, r * T:(r + 1) * T])).pin_memory() for r in range(RE_RUNS)]
+    ctx = m17hip.Context(Cn, T)
+    try:
+        ctx.reset()
+        ctx.upload_async(pins[0].data_ptr(), Cn, T)
+        ctx.run(channels=Cn, samples=T)
+        for r in range(RE_RUNS):
+            if r + 1 < RE_RUNS:
+                ctx.set_channel_polarity(pols[r + 1])   # at once: run r is in flight
+            d = ctx.diag(Cn)                            # (m17_diag is the latest run's: read before the next one is queued)
+            if r + 1 < RE_RUNS:
+                ctx.upload_async(pins[r + 1].data_ptr(), Cn, T)
+                ctx.run(channels=Cn, samples=T)
+                ctx.frames_select(1)
+            got = ctx.frames().copy()
+            ctx.frames_select(0)
+            _assert_run(got, d, exp[r], f"live feed, run {r}")
+        ctx.upload_wait()
+    finally:
+        ctx.close()
+
+
 # ---- 8: refusals ----------------------------------------------------------------------------------------------------------------------------
 def test_refusals_change_nothing():
     import torch
