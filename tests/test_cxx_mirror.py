@@ -266,6 +266,23 @@ def test_scalar_cpu_demodulator_delivers_the_reference_callback_sequence(exe, tm
     assert lines == exp
 
 
+@pytest.mark.parametrize("ppm", [500.0, -500.0, 1000.0])
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_scalar_cpu_demodulator_delivers_the_reference_callback_sequence_off_clock(exe, tmp_path, kind, ppm):
+    """The same program and comparison on a BERT, a voice and a packet burst of 40 000 samples from a transmitter whose symbol clock is 500 ppm
+    fast, 500 ppm slow and 1000 ppm fast (tests/off_clock.py): the scalar classes' ClockRecovery moves sample_index about once per frame (twice
+    at 1000 ppm) where the on-clock cases above move it hardly ever — every callback, in order, bit for bit."""
+    import off_clock as oc
+    x = oc.burst(240 + kind, kind, 40000, sigma=300.0, ppm=ppm)
+    x.tofile(tmp_path / "x.i16")
+    lines = run(exe, "cpu_demod", tmp_path / "x.i16").strip().split("\n")
+    exp, n_recs, n_diag = _expected_callback_lines(x)
+    assert n_diag > 30 and n_recs >= 5
+    # (on the oracle alone: the case does move the clock — at 1000 ppm a BERT receiver follows only in part, 13 of 15 frames and 3 moves)
+    assert oc.index_moves(ol.demod_diag_log(x)) >= (10 if abs(ppm) == 500.0 else 2)
+    assert lines == exp
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,block", [(0, 1920), (1, 1920), (2, 5000), (1, 9600)])
 def test_gpu_backed_demodulator_delivers_the_reference_callback_sequence(exe, tmp_path, kind, block):

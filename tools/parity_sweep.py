@@ -1,11 +1,19 @@
 """Randomised parity sweep on the GPU box: the scenario generator of tests/test_gpu_parity.py::test_full_chain_random_scenarios over
 many seeds, both decode placements, several segment lengths (with and without a ramp), run boundaries at random samples, pipelined runs in both call orders; prints the channels whose records or diagnostics differ from the oracle.
-Usage: parity_sweep.py <first seed> <n seeds>"""
+Usage: parity_sweep.py <first seed> <n seeds> [dump] [--ppm v1,v2,...]
+--ppm: every channel of every scenario is re-read at a clock offset drawn from the list (tests/off_clock.py: a transmitter whose symbol clock is
+that many parts per million off); without it the inputs are what they always were."""
 import sys, os, numpy as np
+PPM = None
+if '--ppm' in sys.argv:
+    k = sys.argv.index('--ppm')
+    PPM = [float(v) for v in sys.argv[k + 1].split(',')]
+    del sys.argv[k:k + 2]
 os.environ.setdefault('GPU_MAX_HW_QUEUES', '16')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'm17-cxx-demod_amd')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import oracle_lib as ol
+import off_clock
 C, T = 64, 96000
 DUMP = len(sys.argv) > 3 and sys.argv[3] == 'dump'   # write the input of the first seed to tools/x_dbg.npy (no GPU needed) and stop
 if not DUMP:
@@ -26,6 +34,9 @@ for seed in range(int(sys.argv[1]), int(sys.argv[1]) + int(sys.argv[2])):
                               dc_offset=float(rng.choice([0.0, 0.0, 300.0, -2000.0, 6000.0])), gain=float(rng.choice([1.0, 0.3, 0.7, 1.6])),
                               phase=int(rng.integers(-1, 10)), invert=0, total=n)
             x[c, pos:pos + n] = ol.generate(p)[:n]; pos += n
+    if PPM:   # (drawn after the scenario: the scenario of a seed is the same with and without the option)
+        ppm = np.random.default_rng([seed, 0x99]).choice(PPM, C)
+        x = off_clock.resample_clock(x, ppm)   # (a fast transmitter is read past the end of its array: up to 190 zeros close the stream)
     inv = seed & 1
     if DUMP:
         np.save(os.path.join(ROOT, 'tools', 'x_dbg.npy'), x); print('wrote tools/x_dbg.npy, invert =', inv); sys.exit(0)
@@ -69,5 +80,5 @@ for seed in range(int(sys.argv[1]), int(sys.argv[1]) + int(sys.argv[2])):
         bad = [c for c in range(C) if got[got['channel'] == c].tobytes() != recs[c, :counts[c]].tobytes()
                or any(not np.array_equal(d[f][c:c + 1], diags[f][c:c + 1], equal_nan=True) for f in d.dtype.names if f in diags.dtype.names)]
         total_bad += len(bad)
-        print(f'seed {seed} invert={inv} deferred_decode={spec} seg={seg} piped={piped} runs={"1" if pieces is None else pieces}: frames {int(counts.sum())}, bad channels {bad}', flush=True)
+        print(f'seed {seed}{" ppm=" + ",".join(str(int(v)) for v in sorted(set(ppm))) if PPM else ""} invert={inv} deferred_decode={spec} seg={seg} piped={piped} runs={"1" if pieces is None else pieces}: frames {int(counts.sum())}, bad channels {bad}', flush=True)
 print('TOTAL bad channel-runs:', total_bad, ' replay drops since the last reset:', ctx.replay_drops())
