@@ -71,6 +71,8 @@ private:
     T* p_ = nullptr;
     size_t n_ = 0;
 };
+// The half that segment k's parity names of a buffer doubled by segment parity: [2][maxC] entries of `per` elements
+template <typename T> T* by_parity(const DevBuf<T>& b, uint32_t k, uint32_t maxC, size_t per = 1) { return b.get() + (size_t)(k & 1u) * maxC * per; }
 
 // A HIP event that destroys itself; reads as the hipEvent_t it holds (nullptr until created).  Movable: the timing pool hands them round.
 class Event {
@@ -140,6 +142,44 @@ private:
     int cur_ = 0;
 };
 
+// The running EVM folded OUTSIDE K5, one lane per channel (m17_state.hpp, evm_fold_pass; m17hip_tune key 17).  K5 writes a run's operations into one row per
+// channel and leaves its cursor at the end of every segment; the fold follows in passes.  Segment k's operations ride the limit-filter replay that runs ahead
+// for segment k + 2 (ahead).  The LAST pass of a run, the operations of its last two segments, is OWED once the run is queued (end_run); whoever comes first
+// takes it (take) and makes it: the next run's first replay (which K5 of that run waits for anyway), the run's own deferred decode, somebody who asks for
+// m17_diag (flush_fold), or the end of the next run.  A run that begins while a pass is owed writes the other row buffer and leaves its end-of-run cursors
+// in the other row of `cur_`: the owed pass keeps what it works on.  EvParams::last says which pass a kernel is making:
+enum EvLast : uint32_t {
+    EV_MORE = 0, EV_SETTLES = 1,   // not a run's last pass; its last pass, behind the run or in front of what K5 waits for: m17_diag is settled as always
+    EV_BESIDE_K5 = 2   // its last pass beside K5 of the NEXT run's first segment: m17_diag is NOT settled by this pass — that K5 has the state in its hands meanwhile; found by the sweep: a run whose last segment fires no callback kept the value this pass had put over the first segment's mark (NOTES 6.3.4)
+};
+class EvmFold {
+public:
+    struct Pass { const float* ops = nullptr; uint32_t C = 0; const uint32_t* upto = nullptr; uint32_t blocks() const { return ev_fold_blocks(C); } };
+    DevBuf<EvState> state;                                   // [maxC]
+    hipError_t alloc(size_t maxC) { maxC_ = (uint32_t)maxC; return cur_.alloc(4 * maxC); }   // (the cursors; the rows come with the first run that needs them)
+    float* ops() const { return ops_[par_]; } uint32_t pitch() const { return pitch_; }   // the rows of the current / latest run (nullptr: none yet), floats per row
+    void set_pitch(uint32_t floats) { pitch_override_ = floats; }   // tuning knob 18 (tests): floats per row instead of ev_row_floats(maxT); for rows still to be allocated
+    bool owed() const { return owed_.ops != nullptr; }       // the latest run's last pass is still to be made
+    hipError_t begin_run(uint32_t maxT)                      // the run before keeps its rows while its last pass is owed; rows of 4 B per symbol of the longest run
+    {
+        if (owed()) par_ ^= 1;
+        if (!ops_[par_]) pitch_ = pitch_override_ ? pitch_override_ : ev_row_floats(maxT);
+        return ops_[par_] ? hipSuccess : ops_[par_].alloc((size_t)maxC_ * pitch_);
+    }
+    uint32_t* cursor_out(uint32_t k, uint32_t nseg) const { return k + 1u == nseg ? end_cursors() : by_parity(cur_, k, maxC_); }   // where K5 of segment k of nseg leaves its cursor
+    Pass ahead(uint32_t k, uint32_t C) const { return Pass{ops_[par_], C, by_parity(cur_, k - 2u, maxC_)}; }   // beside the replay ahead for segment k: up to K5's cursor of segment k - 2
+    Pass take() { const Pass f = owed_; owed_ = Pass{}; return f; }   // the owed pass (ops == nullptr: none), which is the caller's to launch now
+    void end_run(uint32_t C, bool deferred) { owed_ = deferred ? Pass{ops_[par_], C, end_cursors()} : Pass{}; }   // the run's rows, channels and end cursors
+    void forget() { owed_ = Pass{}; }                        // (the state the pass would have updated is reset)
+    void release(int* last_hip) { ops_[0].release(last_hip); ops_[1].release(last_hip); forget(); }   // the rows; nothing queued may still use them
+private:
+    uint32_t* end_cursors() const { return cur_.get() + (2 + (size_t)par_) * maxC_; }
+    DevBuf<float> ops_[2];     // [maxC][pitch_] operations of a run
+    int par_ = 0;              // the buffer of the current / latest run
+    Pass owed_; uint32_t pitch_ = 0, pitch_override_ = 0, maxC_ = 0;
+    DevBuf<uint32_t> cur_;     // [4][maxC] K5's operation cursor at the end of a segment: [0], [1] by segment parity; [2], [3] at the end of a run's LAST segment, by the run's buffer (par_)
+};
+
 struct TimedLaunch { Event a, b; int which; };
 
 struct BertState; struct ChanStat; struct PacketState; struct PacketRec;   // (with the host layer's kernels, below)
@@ -175,8 +215,6 @@ struct m17hip_ctx {
     hipStream_t side2 = nullptr;       // K1 of the segments of a run
     hipStream_t side3 = nullptr;       // K2 of segment k+1 while K5 works on segment k
     Event ev_fork, ev_join;
-    // per segment: K1 / K3 / K2 (ahead) done, K2 redo done, K5 done — one set per slab pair (consecutive staged runs alternate)
-    std::vector<Event> ev_fir_[2], ev_dcd_[2], ev_gate_[2], ev_redo_[2], ev_seq_[2];
     uint32_t front_ahead = 0;         // tuning knob 5: segments the front end (K1, K3) may run ahead of K5 (0 = unlimited, measured best)
     uint32_t maxC = 0, maxT = 0;
     size_t xpitch = 0, ypitch = 0;
@@ -186,9 +224,20 @@ struct m17hip_ctx {
     // Streaming: a second pair.  The input of the NEXT run is staged in other().x while the current run computes; that
     // run's front end (K1 -> other().y, K3 -> other().dcd) may start before the current run's K2/K5 chain has ended (m17hip_demod_front),
     // and K2 / K5 of the next run then work on other().y / .h.  The pairs change roles (slot ^= 1) when a staged run begins.
+    struct SegEvents { Event fir, dcd, gate, redo, seq; };   // of one segment: K1 / K3 / K2 (ahead) done, K2 redo done, K5 done
     struct Slab {
         DevBuf<int16_t> x;
         DevBuf<float> y, h, dcd;
+        uint32_t C = 0, T = 0;        // what the input slab holds (m17hip_input_alternate)
+        Event end; bool used = false; // the last run on this pair is done with its slabs, if there has been one
+        std::vector<SegEvents> seg;   // one set per slab pair (consecutive staged runs alternate)
+        hipError_t wait_free(hipStream_t st) const { return used ? hipStreamWaitEvent(st, end, 0) : hipSuccess; }
+        hipError_t ensure_seg_events(uint32_t nseg)
+        {
+            for (SegEvents s; seg.size() < nseg; seg.push_back(std::move(s)))   // (what an Event is moved out of is empty again)
+                for (Event* e : {&s.fir, &s.dcd, &s.gate, &s.redo, &s.seq}) if (const hipError_t r = e->create()) return r;
+            return hipSuccess;
+        }
     } slab[2];                        // [1]: allocated the first time input is staged (stage_prepare)
     Slab& now() { return slab[slot]; }         // the current / latest run's
     Slab& other() { return slab[slot ^ 1]; }   // the staging pair (the run before the latest one's)
@@ -196,9 +245,7 @@ struct m17hip_ctx {
     hipStream_t copy = nullptr;       // host -> device copies of staged input only
     Event ev_copy;                    // the staged copy has left its source buffer
     Event ev_in_ready;                // the staged slab and its carried 152-sample prefix are complete
-    Event ev_end[2];                  // the last run on slab pair 0 / 1 is done with its slabs
     Event ev_mark;                    // last main-stream operation a front end must not overtake (reset)
-    bool slot_used[2] = {false, false};
     bool inplace_after_run = false;   // the current input slab was overwritten in place after its last run: its data region no longer holds that run's tail
     int slot = 0;                     // the slab pair now() names (0 until the first staged run begins)
     bool staged = false;
@@ -207,18 +254,17 @@ struct m17hip_ctx {
     uint32_t runT = 0;                // samples of the latest run
     Event ev_tail;                    // the latest run has carried its tails into its prefixes (K5 is done with its last segment)
     int gate0_early = 1;              // tuning knob 25: 1 = it does so
-    DevBuf<Boundary> bnd;             // [2][maxC] boundary records (by segment parity): K5 -> the redo of K2 (m17_state.hpp)
+    DevBuf<Boundary> bnd;             // [2][maxC] boundary records (by segment parity, as every [2][maxC] below: by_parity): K5 -> the redo of K2 (m17_state.hpp)
     uint32_t front_k1_after = 0;      // tuning knob 21: the matched filter of a staged run starts after K5 of this segment (1-based) of the run before it; 0 = at once
     uint32_t last_nseg = 0;           // segments of the latest run
     bool wave_times = false;          // tuning knob 19: K5 writes each wave's working time per segment (m17hip_debug_counters)
     uint32_t stagedC = 0, stagedT = 0;
-    uint32_t slabC[2] = {0, 0}, slabT[2] = {0, 0};   // what the input slab of each pair holds (m17hip_input_alternate)
     bool front_queued = false;        // m17hip_demod_front has queued the front end of the run that must follow:
     RunPlan front_plan;               // that run, as m17hip_demod_run will make it
     uint32_t carryT = 0;              // length of the run whose tail those prefixes come from (0 = none since the reset)
     DevBuf<float> final_h;            // [2][maxC][4], by segment parity
     DevBuf<GateExport> gate_exp;      // [maxC] K2's own state at the end of a segment
-    DevBuf<uint32_t> dropped;         // [maxC] K5: the segment dropped the speculation
+    DevBuf<uint32_t> dropped;         // [2][maxC] K5: the segment dropped the speculation
     DevBuf<BertState> bert_state;     // [maxC] (tuning knob 6)
     bool bert = false;
     DevBuf<ChanStat> chan_words;      // m17hip_sweep_stats' words on their way out / a rank's words on their way into m17hip_gather_sweep_stats (payload stream)
@@ -239,7 +285,7 @@ struct m17hip_ctx {
     int redo_form = 0;                // tuning knob 20: the replay's redo beside K5, state only (0, default), or in front of K5 with the history stored (1)
     int dcd_form = -1;                // tuning knob 10: K3 as one wave per 32 channels (0), as the four-wave latency pipeline (1), or chosen per run (-1: the pipeline for runs queued by m17hip_demod_front)
     uint64_t seen_overlap = 0;        // (run registry below) the overlap count this context's previous run saw
-    hipEvent_t last_end = nullptr;    // ev_end of the run queued last (not owned)
+    hipEvent_t last_end = nullptr;    // Slab::end of the run queued last (not owned)
     uint32_t seg_len = 48000;         // tuning knob 3: samples per K2+K5 segment of a run (0 = the whole run)
     uint32_t seg0_len = 0;            // tuning knob 4: samples of the FIRST segment (a short one starts K5 early; 0 = like the others; measured neutral)
     int64_t seg_ramp = -1;            // tuning knob 33: first segment of a ramp r, 2 r, 4 r, ... up to seg_len (0 = none; -1 = per run: AUTO_RAMP when the run is the only thing in flight)
@@ -289,20 +335,8 @@ struct m17hip_ctx {
     uint32_t n_cu = 256;
     DevBuf<uint32_t> defer_hist;     // [maxC][101][64]: decode_deferred_kernel's decision words (one launch at a time: payload stream)
     bool defer_decode = true;
-    // the running EVM folded outside K5, one lane per channel (m17_state.hpp, evm_fold_pass; tune 17)
-    bool defer_evm = true;
-    DevBuf<float> ev_ops2[2];        // [maxC][ev_pitch] operations of a run (lazily allocated); the second one where a run begins while the last fold pass of the run before is still to come
-    int ev_par = 0;                  // the buffer of the current / latest run
-    const float* fold_ops = nullptr; // what the pending last fold pass works on: the run's buffer, its channels, its end-of-run cursors
-    uint32_t fold_C = 0;
-    const uint32_t* fold_end = nullptr;
-    uint32_t ev_pitch = 0;
-    uint32_t ev_pitch_override = 0;  // tuning knob 18 (tests): floats per operation row instead of ev_row_floats(maxT)
-    DevBuf<uint32_t> ev_cur;         // [4][maxC] K5's operation cursor at the end of a segment: [0], [1] by segment parity; [2], [3] at the end of a run's
-                                     // LAST segment, by the run's buffer (ev_par)
-    bool fold_pending = false;       // the last EVM fold pass of the latest run (the operations of its last two segments) is still to be made: it rides the next
-                                     // run's first limit-filter replay (which K5 of that run waits for anyway), or is made when somebody asks for m17_diag (flush_fold)
-    DevBuf<EvState> ev_state;        // [maxC]
+    bool defer_evm = true;           // tuning knob 17: the running EVM folded outside K5 ...
+    EvmFold evm;                     // ... its state, its operation rows and the pass that is still owed
     uint32_t seq_lds_bytes = 0; // tune 14: LDS bytes a workgroup of the sequential kernel asks for (0 = SEQ_LDS_BYTES_4 for four waves)
     DevBuf<float> llr_edges;
     DevBuf<core::Kalman2Gain> level_gain;   // [8 orders][LEVEL_SCHED_N] gain schedules of the level filters (core.h)
@@ -1046,8 +1080,8 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     alloc(s.dcd, C * c->ticks_cap * 12);
     alloc(c->dcd_state, C);
     alloc(c->seq_state, C);
-    alloc(c->ev_state, C);
-    alloc(c->ev_cur, 4 * C);
+    alloc(c->evm.state, C);
+    alloc(c->evm, C);
     alloc(c->sets[0].recs, C * c->rec_cap);      // (the second set: with the second run, m17hip_demod_run)
     alloc(c->sets[0].rec_count, C);
     alloc(c->rec_offsets, C + 1);
@@ -1125,7 +1159,7 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
         //  process: four rank processes on one GPU, 32 + queues in all, ran tests/test_gpu_gather_ranks.py twice as long.  Not kept: NOTES 6.6)
     }
     if (c->own_main) c->stream = c->own_main;
-    for (Event* e : {&c->ev_fork, &c->ev_join, &c->ev_mark, &c->ev_tail, &c->ev_end[0], &c->ev_end[1]})
+    for (Event* e : {&c->ev_fork, &c->ev_join, &c->ev_mark, &c->ev_tail, &c->slab[0].end, &c->slab[1].end})
         if (e->create() != hipSuccess) return fail(M17HIP_EHIP);
     if (hipFuncSetAttribute((const void*)viterbi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (122 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
@@ -1226,20 +1260,18 @@ static int input_target(m17hip_ctx* c, InputTarget& t)
     if (!c->stage_inputs) { t.x = c->now().x; t.st = c->stream; t.stage = false; return M17HIP_OK; }
     const int r = stage_prepare(c);
     if (r) return r;
-    const int other = c->slot ^ 1;
-    if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
+    HIPCHK(c, c->other().wait_free(c->copy));
     t.x = c->other().x; t.st = c->copy; t.stage = true;
     return M17HIP_OK;
 }
 static void input_done(m17hip_ctx* c, const InputTarget& t, uint32_t C, uint32_t T)
 {
     if (t.stage) {
-        c->staged = true; c->stagedC = C; c->stagedT = T;
-        c->slabC[c->slot ^ 1] = C; c->slabT[c->slot ^ 1] = T;
+        c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
         return;
     }
     c->uploaded = true;
-    c->slabC[c->slot] = C; c->slabT[c->slot] = T;
+    c->now().C = C; c->now().T = T;
     c->lastC = C;
     if (c->have_run) c->inplace_after_run = true;
 }
@@ -1267,13 +1299,11 @@ int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint
     int r = stage_prepare(c);
     if (r) return r;
     // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
-    const int other = c->slot ^ 1;
-    if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
+    HIPCHK(c, c->other().wait_free(c->copy));
     HIPCHK(c, hipMemcpy2DAsync(c->other().x + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
                                hipMemcpyHostToDevice, c->copy));
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->stagedC = C; c->stagedT = T;
-    c->slabC[other] = C; c->slabT[other] = T;
+    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
     return M17HIP_OK;
 }
 
@@ -1284,14 +1314,12 @@ int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C
     if (c->front_queued) return M17HIP_ESTATE;
     int r = stage_prepare(c);
     if (r) return r;
-    const int other = c->slot ^ 1;
-    if (c->slot_used[other]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[other], 0));
+    HIPCHK(c, c->other().wait_free(c->copy));
     dim3 grid(((T + 7) / 8 + 255) / 256, C);
     hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, c->copy, dev, pitch, c->other().x, c->xpitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->stagedC = C; c->stagedT = T;
-    c->slabC[other] = C; c->slabT[other] = T;
+    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
     return M17HIP_OK;
 }
 
@@ -1300,8 +1328,7 @@ int m17hip_input_alternate(m17hip_ctx* c, uint32_t C, uint32_t T)
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
-    const int other = c->slot ^ 1;
-    if (!c->other().x || c->slabC[other] != C || c->slabT[other] != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
+    if (!c->other().x || c->other().C != C || c->other().T != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
     c->staged = true; c->stagedC = C; c->stagedT = T;
     return M17HIP_OK;
 }
@@ -1559,10 +1586,10 @@ int m17hip_demod_reset(m17hip_ctx* c)
         HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));   // (never recorded: no wait)
         rs.pending = false;
     }
-    c->fold_pending = false;   // (the EVM state it would have updated is reset below)
+    c->evm.forget();   // (the EVM state the owed pass would have updated is reset below)
     for (uint32_t ch : c->marks) c->marked[ch] = 0;   // (m17hip_demod_reset_channels: every channel starts over anyway)
     c->marks.clear();
-    hipLaunchKernelGGL(seq_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->dcd_state, c->ev_state, c->maxC);
+    hipLaunchKernelGGL(seq_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->dcd_state, c->evm.state, c->maxC);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, c->maxC);
     HIPCHK(c, hipGetLastError());
@@ -1698,18 +1725,6 @@ static RunPlan plan_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, R
     return p;
 }
 
-static int ensure_seg_events(m17hip_ctx* c, int q, uint32_t nseg)
-{
-    while (c->ev_fir_[q].size() < nseg) {
-        for (auto* v : {&c->ev_fir_[q], &c->ev_dcd_[q], &c->ev_gate_[q], &c->ev_redo_[q], &c->ev_seq_[q]}) {
-            Event e;
-            HIPCHK(c, e.create());
-            v->push_back(std::move(e));
-        }
-    }
-    return M17HIP_OK;
-}
-
 // K3 and K1 of segment k of the run being queued (slab pair c->slot), on the two side streams.
 // The front end of segment k may be held back until K5 of segment k - front_ahead is done (tuning knob 5), to spread it over
 // the step; measured, letting it run ahead freely is faster (K3 is a latency chain of 1.7 ms per segment: held back, it is
@@ -1718,18 +1733,18 @@ static int ensure_seg_events(m17hip_ctx* c, int q, uint32_t nseg)
 static int launch_front_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 {
     if (k >= p.nseg) return M17HIP_OK;
-    const int q = c->slot;
+    auto& seg = c->now().seg;
     const uint32_t ahead = p.front_segs, t0 = p.t0(k), len = p.t0(k + 1) - t0;
     if (k >= ahead) {   // (tuning knob 5 is set)
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_seq_[q][k - ahead], 0));
-        HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k - ahead], 0));
+        HIPCHK(c, hipStreamWaitEvent(c->side, seg[k - ahead].seq, 0));
+        HIPCHK(c, hipStreamWaitEvent(c->side2, seg[k - ahead].seq, 0));
     }
-    if (k == 1) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fir_[q][0], 0));   // segment 0's front end first: K2/K5 wait for it
+    if (k == 1) HIPCHK(c, hipStreamWaitEvent(c->side, seg[0].fir, 0));   // segment 0's front end first: K2/K5 wait for it
     if (int r = launch_dcd(c, p.C, len, p.kflags, c->pos, p.dcd_latency, c->side, t0, p.pol)) return r;
-    HIPCHK(c, hipEventRecord(c->ev_dcd_[q][k], c->side));
+    HIPCHK(c, hipEventRecord(seg[k].dcd, c->side));
     if (p.gate_run && k >= 2u) return M17HIP_OK;
     if (int r = launch_fir(c, p.C, len, p.kflags, p.fir_latency, c->side2, t0, nullptr, p.pol)) return r;
-    HIPCHK(c, hipEventRecord(c->ev_fir_[q][k], c->side2));
+    HIPCHK(c, hipEventRecord(seg[k].fir, c->side2));
     return M17HIP_OK;
 }
 
@@ -1738,7 +1753,7 @@ static int launch_front_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 // A run in place: behind what the main stream holds so far (its input); a staged one is ordered by begin_staged.
 static int launch_front_all(m17hip_ctx* c, const RunPlan& p)
 {
-    if (int r = ensure_seg_events(c, c->slot, p.nseg)) return r;
+    HIPCHK(c, c->now().ensure_seg_events(p.nseg));
     if (!p.staged) {
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -1754,22 +1769,20 @@ static int launch_front_all(m17hip_ctx* c, const RunPlan& p)
 static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 {
     if (k + 2u >= p.nseg) return M17HIP_OK;
-    const int q = c->slot;
+    auto& seg = c->now().seg;
     const uint32_t C = p.C, t1 = p.t0(k + 1u), t2 = p.t0(k + 2u), t3 = p.t0(k + 3u);
-    HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[q][k], 0));
-    HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_dcd_[q][k + 2u], 0));
-    hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, c->truth + (size_t)(k & 1u) * c->maxC, c->now().dcd, c->ticks_cap,
+    HIPCHK(c, hipStreamWaitEvent(c->side2, seg[k].seq, 0));
+    HIPCHK(c, hipStreamWaitEvent(c->side2, seg[k + 2u].dcd, 0));
+    hipLaunchKernelGGL(gate_forecast_kernel, dim3((C + 63) / 64), dim3(64), 0, c->side2, by_parity(c->truth, k, c->maxC), c->now().dcd, c->ticks_cap,
                        (uint64_t)(c->pos / TICK), (uint64_t)(c->pos + t1), t2 - t1, t3 - t1, c->first_needed, C);
     HIPCHK(c, hipGetLastError());
     if (int r = launch_fir(c, C, t3 - t2, p.kflags, p.fir_latency, c->side2, t2, c->first_needed, p.pol)) return r;
-    HIPCHK(c, hipEventRecord(c->ev_fir_[q][k + 2u], c->side2));
+    HIPCHK(c, hipEventRecord(seg[k + 2u].fir, c->side2));
     return M17HIP_OK;
 }
 
-// A fold pass of the deferred EVM over `C` channels' operation rows `ops` up to the cursors `upto` (`last`: m17_state.hpp); the pending last
-// pass of the latest run (fold_pending); and none — what a kernel that can take a pass along is given when there is nothing to fold.
-static EvParams ev_fold(const m17hip_ctx* c, const float* ops, uint32_t C, const uint32_t* upto, uint32_t last) { return EvParams{ops, c->ev_pitch, c->ev_state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, C, upto, last}; }
-static EvParams ev_last_fold(const m17hip_ctx* c, uint32_t last) { return ev_fold(c, c->fold_ops, c->fold_C, c->fold_end, last); }
+// A fold pass of the deferred EVM (EvmFold) as a kernel gets it; and none — what a kernel that can take a pass along is given when there is nothing to fold.
+static EvParams ev_fold(const m17hip_ctx* c, const EvmFold::Pass& f, EvLast last) { return EvParams{f.ops, c->evm.pitch(), c->evm.state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, f.C, f.upto, last}; }
 static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}; }
 
 // One launch of K2 over segment k of the run whose slabs the context names: the whole segment from K5's state (first segment), ahead of
@@ -1777,7 +1790,7 @@ static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nu
 static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStream_t st, bool ahead, bool redo, bool redo_stores = false)
 {
     if (k == 0 && p.gate0_queued) {   // m17hip_demod_front has queued this one on the replay stream, behind the prefix copies
-        HIPCHK(c, hipStreamWaitEvent(st, c->ev_gate_[c->slot][0], 0));
+        HIPCHK(c, hipStreamWaitEvent(st, c->now().seg[0].gate, 0));
         return M17HIP_OK;
     }
     const uint32_t C = p.C, t0 = p.t0(k), len = p.t0(k + 1) - t0;
@@ -1785,26 +1798,23 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
     GateParams G{};
     G.x = c->now().x + t0; G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
     G.dcd_table = c->now().dcd; G.ticks_cap = c->ticks_cap; G.state = c->seq_state;
-    G.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
+    G.final_h = by_parity(c->final_h, k, c->maxC, 4);
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
-    G.only = redo ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (flags by segment parity)
-    G.bnd = redo ? c->bnd + (size_t)(k & 1u) * c->maxC : nullptr;   // (written by K5 of segment k - 1)
+    G.only = redo ? by_parity(c->dropped, k - 1u, c->maxC) : nullptr;   // (flags by segment parity)
+    G.bnd = redo ? by_parity(c->bnd, k, c->maxC) : nullptr;   // (written by K5 of segment k - 1)
     G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.kflags | ((redo && !redo_stores) ? 2u : 0u); G.pol = p.pol;
     G.nblk = (C + GT_CPW - 1) / GT_CPW;
     uint32_t fold_blocks = 0;
-    if (ahead && k >= 2 && c->defer_evm && c->ev_ops2[c->ev_par]) {   // (K5 of segment k - 2 is through: its EVM operations ride along, sixteen channels per block)
-        G.ev = ev_fold(c, c->ev_ops2[c->ev_par], C, c->ev_cur + (size_t)((k - 2u) & 1u) * c->maxC, 0u);
+    if (ahead && k >= 2 && c->defer_evm && c->evm.ops()) {   // (K5 of segment k - 2 is through: its EVM operations ride along, sixteen channels per block)
+        G.ev = ev_fold(c, c->evm.ahead(k, C), EV_MORE);
         fold_blocks = ev_fold_blocks(C);
     }
     // The LAST pass of the run before (its buffer is not this run's): beside K5 of this run's first segment, with the replay that runs ahead for the
     // second one — or, for a run of one segment, with this replay, which K5 waits for (that K5 is the one that moves the end-of-run cursors on)
-    if (!redo && c->fold_pending && c->fold_ops && ((p.nseg >= 2 && ahead && k == 1) || (p.nseg < 2 && k == 0))) {
-        // (beside the replay, last = 2: m17_diag is NOT settled by this pass — K5 of this run's first segment has the state in its hands meanwhile; found by the
-        //  sweep: a run whose last segment fires no callback kept the value this pass had put over the first segment's mark.  In front of segment 0, which K5
-        //  waits for, it is settled as always)
-        G.ev = ev_last_fold(c, k == 0 ? 1u : 2u);
-        fold_blocks = ev_fold_blocks(c->fold_C);
-        c->fold_pending = false;
+    if (!redo && c->evm.owed() && ((p.nseg >= 2 && ahead && k == 1) || (p.nseg < 2 && k == 0))) {
+        const EvmFold::Pass f = c->evm.take();
+        G.ev = ev_fold(c, f, k == 0 ? EV_SETTLES : EV_BESIDE_K5);   // (in front of segment 0, which K5 waits for: settled; beside the replay ahead: not)
+        fold_blocks = f.blocks();
     }
     tm.launch(limit_track_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
     HIPCHK(c, hipGetLastError());
@@ -1853,13 +1863,13 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
     c->slot ^= 1;   // (the staged input's pair becomes now(), the previous run's other())
     c->staged = false; c->uploaded = true;
     c->carryT = c->have_run ? c->runT : 0;
-    // the new slab's prefix, behind the staged copy on the copy stream; the slab pair itself is free since ev_end[slot] (the copy
+    // the new slab's prefix, behind the staged copy on the copy stream; the slab pair itself is free since now().end (the copy
     // stream waited for it when the input was staged — m17hip_input_alternate stages without a copy, so wait here as well)
-    if (c->slot_used[c->slot]) HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[c->slot], 0));
+    HIPCHK(c, c->now().wait_free(c->copy));
     if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)   // the tail of the previous input, where it lies (that slab is only read while its run is in flight)
         hipLaunchKernelGGL(copy_tail_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch, c->carryT);
     else if (c->carryT) {              // (or its data region was overwritten in place since: the tail its last kernel carried into its prefix)              // a run shorter than the prefix: its tail reaches into its own prefix, which its last kernel rewrites — wait for that
-        HIPCHK(c, hipStreamWaitEvent(c->copy, c->ev_end[c->slot ^ 1], 0));
+        HIPCHK(c, hipStreamWaitEvent(c->copy, c->other().end, 0));
         hipLaunchKernelGGL(copy_prefix_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch);
     } else HIPCHK(c, hipMemset2DAsync(c->now().x, c->xpitch * sizeof(int16_t), 0, XPRE * sizeof(int16_t), C, c->copy));
     HIPCHK(c, hipGetLastError());
@@ -1880,7 +1890,7 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
     }
     if (c->front_k1_after && c->have_run && c->last_nseg) {   // K1 out of the way of the previous run's first (heaviest) K5 launches
         const uint32_t j = std::min(c->front_k1_after, c->last_nseg) - 1u;
-        HIPCHK(c, hipStreamWaitEvent(c->side2, c->ev_seq_[c->slot ^ 1][j], 0));
+        HIPCHK(c, hipStreamWaitEvent(c->side2, c->other().seg[j].seq, 0));
     }
     p = plan_run(c, C, T, flags, kind);
     p.n_reset = n_reset; p.kflags = kflags; p.pol = pol;
@@ -1894,10 +1904,9 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
 // The latest run's last EVM fold pass on the main stream (behind that run), if nothing has taken it along yet.
 static int flush_fold(m17hip_ctx* c)
 {
-    if (!c->fold_pending) return M17HIP_OK;
-    c->fold_pending = false;
-    if (!c->fold_ops) return M17HIP_OK;
-    hipLaunchKernelGGL(evm_deferred_kernel, dim3(ev_fold_blocks(c->fold_C)), dim3(64), 0, c->stream, ev_last_fold(c, 1u));
+    const EvmFold::Pass f = c->evm.take();
+    if (!f.ops) return M17HIP_OK;
+    hipLaunchKernelGGL(evm_deferred_kernel, dim3(f.blocks()), dim3(64), 0, c->stream, ev_fold(c, f, EV_SETTLES));
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1925,10 +1934,10 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
             D.state = c->seq_state; D.diag_log = c->diag_cap ? c->diag_log : nullptr; D.diag_cap = c->diag_cap; D.diag_count = c->diag_count; D.C = C;
             D.ev = ev_no_fold(C);
             uint32_t fold_blocks = 0;
-            if (fold_beside_decode && c->fold_pending && i == c->cur && c->fold_ops) {   // (the latest run's last fold pass, beside its decode on the main stream)
-                D.ev = ev_last_fold(c, 1u);
-                fold_blocks = ev_fold_blocks(C);
-                c->fold_pending = false;
+            if (fold_beside_decode && c->evm.owed() && i == c->cur) {   // (the latest run's last fold pass, beside its decode on the main stream)
+                const EvmFold::Pass f = c->evm.take();
+                D.ev = ev_fold(c, f, EV_SETTLES);
+                fold_blocks = f.blocks();
             }
             TimedK tm(c, KT_DEC);
             tm.launch(decode_deferred_kernel, dim3(defer_blocks(C) + fold_blocks), dim3(64 * DEFER_CPB), DEFER_LDS_BYTES, ps, D);
@@ -1978,11 +1987,11 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     const uint32_t piece = tiled ? std::max<uint32_t>((uint32_t)round_up((T + 9) / 10, LP_TILE), 4 * LP_TILE) : T;
     uint32_t npieces = (T + piece - 1) / piece;
     if (tiled && npieces > 1 && T - (npieces - 1) * piece < 4 * LP_TILE) --npieces;   // (a last piece of fewer than four tiles joins the one before it)
-    int r = ensure_seg_events(c, c->slot, npieces);
-    if (r) return r;
+    HIPCHK(c, c->now().ensure_seg_events(npieces));   // (it borrows the current pair's `fir` events)
+    int r;
     uint32_t kflags; const uint32_t* pol;
     if ((r = resolve_polarity(c, C, flags, c->stream, kflags, pol))) return r;
-    auto& ev_fir = c->ev_fir_[c->slot];
+    auto& seg = c->now().seg;
     // (Tried: the chain on compute units of its own — hipExtStreamCreateWithCUMask, a quarter of the chip — with the two throughput kernels on
     //  the rest: the chain's pieces 0.79 -> 0.74 ms, the call 8.2 -> 9.0 ms.  What stretches the chain beside them is not its SIMD: NOTES 5.4.)
     const hipStream_t st_chain = c->stream, st_fir = c->side2, st_corr = c->side;
@@ -1994,9 +2003,9 @@ int m17hip_fir_correlator(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags,
     for (uint32_t k = 0; k < npieces; ++k) {
         const uint32_t t0 = k * piece, len = k + 1 < npieces ? piece : T - t0;
         if ((r = launch_fir(c, C, len, kflags, false, st_fir, t0, nullptr, pol))) return r;
-        HIPCHK(c, hipEventRecord(ev_fir[k], st_fir));
-        HIPCHK(c, hipStreamWaitEvent(st_corr, ev_fir[k], 0));
-        HIPCHK(c, hipStreamWaitEvent(st_chain, ev_fir[k], 0));
+        HIPCHK(c, hipEventRecord(seg[k].fir, st_fir));
+        HIPCHK(c, hipStreamWaitEvent(st_corr, seg[k].fir, 0));
+        HIPCHK(c, hipStreamWaitEvent(st_chain, seg[k].fir, 0));
         {   // each kernel timed on the stream it runs on, under its own key: the correlations as "correlator", the limit chain as "limit_track"
             Timed tc(c, KT_CORR, st_corr);
             if (T % 4 == 0 && t0 % 4 == 0 && len % 4 == 0)
@@ -2063,13 +2072,7 @@ static int prepare_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
         HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
     }
     rs.valid = false;
-    if (c->defer_evm) {   // the operation rows of the deferred EVM: 4 B per symbol of the longest run
-        if (c->fold_pending) c->ev_par ^= 1;   // (the run before still has a fold pass to come: it keeps its rows, this run writes the other buffer)
-        if (!c->ev_ops2[c->ev_par]) {
-            c->ev_pitch = c->ev_pitch_override ? c->ev_pitch_override : ev_row_floats(c->maxT);
-            HIPCHK(c, c->ev_ops2[c->ev_par].alloc((size_t)c->maxC * c->ev_pitch));
-        }
-    }
+    if (c->defer_evm) HIPCHK(c, c->evm.begin_run(c->maxT));   // (the operation rows of the deferred EVM)
     c->dbg_waves = (c->profile || c->wave_times) ? p.C : 0;
     if (!c->bnd) {
         HIPCHK(c, c->bnd.alloc(2 * (size_t)c->maxC));
@@ -2087,8 +2090,8 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
 {
     const uint32_t t0 = p.t0(k), len = p.t0(k + 1) - t0;
     SeqParams P{};
-    P.h = c->now().h + t0; P.final_h = c->final_h + (size_t)(k & 1u) * c->maxC * 4;
-    P.dropped = c->dropped + (size_t)(k & 1u) * c->maxC;   // (by segment parity)
+    P.h = c->now().h + t0; P.final_h = by_parity(c->final_h, k, c->maxC, 4);
+    P.dropped = by_parity(c->dropped, k, c->maxC);
     P.x = c->now().x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
     P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
     P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
@@ -2098,11 +2101,11 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     P.level_gain = c->level_gain + (size_t)(c->kalman_order & 7u) * core::LEVEL_SCHED_N;
     P.diag_log = c->diag_cap ? c->diag_log : nullptr; P.diag_cap = c->diag_cap; P.diag_count = c->diag_count;
     P.defer = c->defer_decode ? rs.defer_llr : nullptr;
-    if (c->defer_evm) { P.ev_ops = c->ev_ops2[c->ev_par]; P.ev_pitch = c->ev_pitch; P.ev_cursor_out = c->ev_cur + (size_t)(k + 1u == p.nseg ? 2u + (uint32_t)c->ev_par : (k & 1u)) * c->maxC; }
-    P.bnd_out = c->bnd + (size_t)((k + 1u) & 1u) * c->maxC;
-    P.truth_out = c->truth ? c->truth + (size_t)(k & 1u) * c->maxC : nullptr;
+    if (c->defer_evm) { P.ev_ops = c->evm.ops(); P.ev_pitch = c->evm.pitch(); P.ev_cursor_out = c->evm.cursor_out(k, p.nseg); }
+    P.bnd_out = by_parity(c->bnd, k + 1u, c->maxC);
+    P.truth_out = c->truth ? by_parity(c->truth, k, c->maxC) : nullptr;
     P.dbg = (c->profile || c->wave_times) ? c->dbg : nullptr;
-    P.dropped_in = (k > 0 && c->redo_form != 1) ? c->dropped + (size_t)((k - 1u) & 1u) * c->maxC : nullptr;   // (redo in front: nobody starts a segment off the replay)
+    P.dropped_in = (k > 0 && c->redo_form != 1) ? by_parity(c->dropped, k - 1u, c->maxC) : nullptr;   // (redo in front: nobody starts a segment off the replay)
     return P;
 }
 
@@ -2115,9 +2118,8 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
 static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet& rs)
 {
     int r;
-    const int q = c->slot;
     const uint32_t nseg = p.nseg, ahead = p.front_segs;   // (ahead < nseg: tuning knob 5 is set)
-    auto& ev_fir = c->ev_fir_[q]; auto& ev_dcd = c->ev_dcd_[q]; auto& ev_gate = c->ev_gate_[q]; auto& ev_redo = c->ev_redo_[q]; auto& ev_seq = c->ev_seq_[q];
+    auto& seg = c->now().seg;
     // Redo policy (m17hip_tune key 20).  IN FRONT of K5: the redo stores the history of segment k for the channels that left the replay in
     // k - 1 before K5(k) starts — sixteen channels per instruction instead of one wave each carrying the filter itself through segment k
     // (3 dependent instructions per sample): fewer instructions, but 1-2 ms of replay latency on the K5 chain of every segment that follows
@@ -2134,28 +2136,28 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
     HIPCHK(c, hipMemsetAsync(rs.ovf, 0, 4, c->stream));       // record overflow of THIS run
     HIPCHK(c, hipMemsetAsync(rs.ovf + 3, 0, 4, c->stream));   // channel-segments of THIS run that end with the carrier off (K5 counts)
     for (uint32_t k = 0; k < nseg; ++k) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream, ev_fir[k], 0));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, ev_dcd[k], 0));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, seg[k].fir, 0));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, seg[k].dcd, 0));
         if (k == 0 && c->front_first > 1 && ahead >= nseg) {   // the matched filter of the first `front_first` segments has the chip to itself
             const uint32_t last = std::min(c->front_first, nseg) - 1u;
-            HIPCHK(c, hipStreamWaitEvent(c->stream, ev_fir[last], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, seg[last].fir, 0));
         }
         // replay stream: ahead(k) -> redo(k) [after K5(k - 1): its flags and its state] -> ahead(k + 1) -> ...; the main stream only
         // ever waits for an `ahead`
-        if (k > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_gate[k], 0));
+        if (k > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, seg[k].gate, 0));
         if (k == 0 || redo_front) {   // the first segment whole; a redo in front: flagged channels only, from their boundary records, history stored
             if ((r = launch_gate_seg(c, p, k, c->stream, false, k > 0, k > 0))) return r;
-            HIPCHK(c, hipEventRecord(ev_redo[k], c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_redo[k], 0));
+            HIPCHK(c, hipEventRecord(seg[k].redo, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, seg[k].redo, 0));
         } else if (k + 1 < nseg) {
-            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_seq[k - 1], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, seg[k - 1].seq, 0));
             if ((r = launch_gate_seg(c, p, k, c->side3, false, true))) return r;
         }
         if (k + 1 < nseg) {
-            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_fir[k + 1], 0));
-            HIPCHK(c, hipStreamWaitEvent(c->side3, ev_dcd[k + 1], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, seg[k + 1].fir, 0));
+            HIPCHK(c, hipStreamWaitEvent(c->side3, seg[k + 1].dcd, 0));
             if ((r = launch_gate_seg(c, p, k + 1, c->side3, true, false))) return r;
-            HIPCHK(c, hipEventRecord(ev_gate[k + 1], c->side3));
+            HIPCHK(c, hipEventRecord(seg[k + 1].gate, c->side3));
         }
         TimedK tm(c, KT_SEQ);
         const SeqParams P = seq_params(c, p, rs, k);
@@ -2167,7 +2169,7 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
         if (c->kalman_order == 3u) tm.launch((demod_wave_kernel<4, false, false, 3>), grid, block, lds, c->stream, P);   // (the default order: no call in the kernel)
         else tm.launch(demod_wave_kernel<4>, grid, block, lds, c->stream, P);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(ev_seq[k], c->stream));
+        HIPCHK(c, hipEventRecord(seg[k].seq, c->stream));
         if (k + ahead < nseg && (r = launch_front_seg(c, p, k + ahead))) return r;
         if (p.gate_run && (r = launch_gated_fir(c, p, k))) return r;
     }
@@ -2179,7 +2181,6 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
 static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
 {
     int r;
-    const int q = c->slot;
     const uint32_t C = p.C, T = p.T;
     // the tails a run that continues in THESE slabs (input uploaded in place) will find as its prefixes; a staged run takes them from
     // here into the other slab pair itself.  (Before the deferred decode: the next staged run's first replay waits for these, not for that.)
@@ -2189,19 +2190,18 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     HIPCHK(c, hipEventRecord(c->ev_tail, c->stream));
     // ---- the end of the run on the MAIN stream: what the next run's chain needs of this one — the one or two deferred costs the state still
     //      names (settle_tail_kernel).  The rest of the run's EVM fold (the operations of its last two segments: 0.8 ms of one dependent chain
-    //      per channel that nothing in the demodulator reads) is NOT made here: see fold_pending
+    //      per channel that nothing in the demodulator reads) is NOT made here: it is owed (EvmFold)
     if (c->defer_decode) {
         SettleParams S{rs.recs, c->rec_cap, rs.defer_llr, c->tables, c->seq_state, C, ev_no_fold(C)};
         hipLaunchKernelGGL(settle_tail_kernel, dim3(C), dim3(64), SETTLE_LDS_BYTES, c->stream, S);
         HIPCHK(c, hipGetLastError());
     }
-    if (c->fold_pending && (r = flush_fold(c))) return r;   // (the run before: nothing of this run took its last pass along — one segment, no replay ahead)
-    c->fold_pending = c->defer_evm;
-    c->fold_ops = c->ev_ops2[c->ev_par]; c->fold_C = C; c->fold_end = c->ev_cur + (2 + (size_t)c->ev_par) * c->maxC;
+    if ((r = flush_fold(c))) return r;   // (the run before: nothing of this run took its last pass along — one segment, no replay ahead)
+    c->evm.end_run(C, c->defer_evm);
     HIPCHK(c, hipEventRecord(rs.chain, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_end[q], c->stream));
-    { std::lock_guard<std::mutex> lk(g_runs.mu); c->last_end = c->ev_end[q]; }
-    c->slot_used[q] = true; c->pos += T; c->inplace_after_run = false; c->have_run = true;
+    HIPCHK(c, hipEventRecord(c->now().end, c->stream));
+    { std::lock_guard<std::mutex> lk(g_runs.mu); c->last_end = c->now().end; }
+    c->now().used = true; c->pos += T; c->inplace_after_run = false; c->have_run = true;
     c->lastC = C; c->runT = T; c->last_nseg = p.nseg;
     rs.valid = true; rs.C = C; rs.rec_cap = c->rec_cap; rs.nseg = p.nseg;
     rs.pending = true; rs.bert = c->bert; rs.pkt = c->pkt_cap != 0;
@@ -2215,7 +2215,7 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
 static int flush_after_run(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
 {
     if (c->streams() && !c->diag_cap) return M17HIP_OK;
-    const int r = flush_payload(c, false, false, c->fold_pending && c->defer_decode && c->pay() == c->stream);   // (the fold beside the decode, as up to round 5)
+    const int r = flush_payload(c, false, false, c->evm.owed() && c->defer_decode && c->pay() == c->stream);   // (the fold beside the decode, as up to round 5)
     if (r || !c->diag_cap) return r;
     HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
     return flush_fold(c);
@@ -2241,7 +2241,7 @@ static int reset_marked_state(m17hip_ctx* c, const RunPlan& p)
     HIPCHK(c, c->reset_list.after_read(RD_PAY, c->pay()));
     HIPCHK(c, c->reset_list.before_read(c->stream));
     hipLaunchKernelGGL(prefix_reset_list_kernel, dim3(n), dim3(64), 0, c->stream, list, n, c->now().y.get(), c->now().h.get(), c->ypitch);
-    hipLaunchKernelGGL(seq_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, list, n, c->seq_state.get(), c->ev_state.get(), (uint64_t)c->pos);
+    hipLaunchKernelGGL(seq_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, list, n, c->seq_state.get(), c->evm.state.get(), (uint64_t)c->pos);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->reset_list.after_read(RD_MAIN, c->stream));
     return M17HIP_OK;
@@ -2260,13 +2260,13 @@ int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     // host: queued here, on the replay stream, it runs beside all of those.
     // (not for a run that begins with marked channels, m17hip_demod_reset_channels: their state is reset by the run call, and this replay reads it)
     if (c->gate0_early && c->have_run && c->carryT && !c->profile && !p.n_reset) {
-        const int q = c->slot;
-        for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &c->ev_fir_[q][0], &c->ev_dcd_[q][0]}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
+        m17hip_ctx::SegEvents& seg0 = c->now().seg[0];
+        for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &seg0.fir, &seg0.dcd}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
         hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
         hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
         HIPCHK(c, hipGetLastError());
         if (int r = launch_gate_seg(c, p, 0, c->side3, false, false)) return r;
-        HIPCHK(c, hipEventRecord(c->ev_gate_[q][0], c->side3));
+        HIPCHK(c, hipEventRecord(seg0.gate, c->side3));
         p.gate0_queued = true;
     }
     return M17HIP_OK;
@@ -2406,7 +2406,7 @@ int m17hip_diag_fetch(m17hip_ctx* c, m17_diag* diag_host, uint32_t C)
     GUARD(c);
     if (int fr = flush_fold(c)) return fr;        // m17_diag::evm of the latest run: its last fold pass, if nothing has made it yet
     if (c->front_queued && c->front_plan.gate0_queued)   // (... or the replay m17hip_demod_front queued for the next run is making it: wait for that launch)
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->now().seg[0].gate, 0));
     HIPCHK(c, hipMemcpy2DAsync(diag_host, sizeof(Diag), &c->seq_state[0].cold.diag, sizeof(SeqState), sizeof(Diag), C, hipMemcpyDeviceToHost,
                                c->stream));
     uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2488,7 +2488,7 @@ int m17hip_sweep_stats(m17hip_ctx* c, uint32_t n_points, m17_chan_stat* host, ui
     if (!c->bert || !c->have_run) return M17HIP_ESTATE;
     // m17hip_diag_fetch's order for `evm`: the latest run's last fold pass on the main stream (or the replay m17hip_demod_front queued is making it)
     if (int fr = flush_fold(c)) return fr;
-    if (c->front_queued && c->front_plan.gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gate_[c->slot][0], 0));
+    if (c->front_queued && c->front_plan.gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->now().seg[0].gate, 0));
     // ... m17hip_bert_stats' order for the PRBS9 state: the payload work of both runs, wherever it was queued
     if (int fr = flush_payload(c)) return fr;
     for (const auto& rs : c->sets)
@@ -2973,17 +2973,16 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
             if (int fr = flush_fold(c)) return fr;
             HIPCHK(c, hipStreamSynchronize(c->stream));
             c->defer_evm = value != 0;
-            hipLaunchKernelGGL(ev_move_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->ev_state, c->maxC, c->defer_evm ? 1 : 0);
+            hipLaunchKernelGGL(ev_move_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->evm.state, c->maxC, c->defer_evm ? 1 : 0);
             HIPCHK(c, hipGetLastError());
-            if (!c->defer_evm) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->ev_ops2[0].release(&c->last_hip); c->ev_ops2[1].release(&c->last_hip); c->fold_ops = nullptr; }
+            if (!c->defer_evm) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->evm.release(&c->last_hip); }
         }
         return M17HIP_OK;
     case 18:  // (tests) floats per channel row of deferred EVM operations, 0 = what a run of max_samples can produce: a smaller value makes the overflow flag reachable
         if (value < 0 || value > (1 << 28) || (value & 3)) return M17HIP_EINVAL;
         if (int fr = flush_fold(c)) return fr;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ev_ops2[0].release(&c->last_hip); c->ev_ops2[1].release(&c->last_hip); c->fold_ops = nullptr;
-        c->ev_pitch_override = (uint32_t)value;
+        c->evm.release(&c->last_hip); c->evm.set_pitch((uint32_t)value);
         return M17HIP_OK;
     case 15:  // payload frames of running stream / BERT transmissions decoded after the run, one lane per frame (1, default), or in K5 (0)
         c->defer_decode = value != 0;
