@@ -309,6 +309,32 @@ typedef struct m17_impairment {   /* one point of a sweep grid */
 #define M17HIP_MAX_SWEEP_POINTS 4096u
 int m17hip_synth_sweep_i16(m17hip_ctx* ctx, const m17_synth_params* base, const m17_impairment* points, uint32_t n_points,
                            uint32_t channels, uint32_t samples, uint32_t chan0);
+/* Caller-supplied transmissions (ABI 605): the same framing (apps/m17-mod.cpp:264-504, 509-564), shaping and impairments as
+ * m17hip_synth_i16, with the CONTENT given by the caller — channel c sends transmission tx[c]:
+ *   kind 1 (stream)  preamble(s), the LSF, n_frames stream frames, EOT + 40 zero symbols;
+ *   kind 2 (packet)  preamble(s), the LSF, n_frames packet frames, EOT + 40 zero symbols;
+ *   kind 0 (BERT)    preambles, n_frames BERT frames.
+ * lsf30[c] is channel c's 30-byte LSF, sent as given: its CRC is NOT recomputed, so a broken one can be sent.  Payload frame i of
+ * channel c is rows[tx[c].first_row + i], 32 bytes laid out as the frame records' payloads are: a stream frame takes bytes 0..17 (frame
+ * number, with the caller's end-of-stream bit, and 16 payload bytes) and carries segment i % 6 of the channel's LSF as its LICH; a packet
+ * frame takes bytes 0..25 of which 206 bits are carried; a BERT frame takes bytes 0..24 of which 197 bits are carried.  The rest of a row
+ * is ignored and nothing outside rows[first_row .. first_row + n_frames) is read.
+ * From `base`: seed (noise, the derived phase; per channel with chan0 as for m17hip_synth_i16), lead_in, phase, invert, n_preamble (0 = as
+ * m17-mod does for the channel's kind), the sigmas, dc_offset and gain; base->kind and base->n_frames are ignored.  With the content the
+ * built-in generator would have chosen, every int16 equals m17hip_synth_i16's.  A burst longer than `samples` is cut off.  Tuning knob 16
+ * (staging) applies; M17HIP_ESTATE between m17hip_demod_front and its run; complete when it returns.
+ * M17HIP_EINVAL, with nothing written: ctx, base, tx or rows NULL; lsf30 NULL with a kind other than 0; a kind > 2; reserved != 0;
+ * first_row + n_frames > n_rows; n_frames > samples / 1920 + 1; and whatever m17hip_synth_i16 refuses for channels / samples. */
+typedef struct m17_tx {      /* one transmission = one channel; 16 bytes */
+    uint32_t kind;           /* 0 BERT, 1 stream, 2 packet */
+    uint32_t n_frames;       /* payload frames */
+    uint32_t first_row;      /* index of its first row in `rows` */
+    uint32_t reserved;       /* 0 */
+} m17_tx;
+int m17hip_synth_tx_i16(m17hip_ctx* ctx, const m17_synth_params* base, const m17_tx* tx,
+                        const uint8_t* lsf30,   /* [channels][30], NULL allowed when every kind is 0 */
+                        const uint8_t* rows,    /* [n_rows][32] */
+                        uint32_t n_rows, uint32_t channels, uint32_t samples, uint32_t chan0);
 /* Read the input slab back: out[channels][samples] (row pitch in samples). */
 int m17hip_download_i16(m17hip_ctx* ctx, int16_t* host, uint32_t channels, uint32_t samples, size_t pitch);
 
@@ -480,7 +506,7 @@ int m17hip_gather_sweep_stats(m17hip_ctx* ctx, m17hip_comm* comm, int root, cons
  * key 18 (tests): floats per channel row of deferred EVM operations (key 17), 0 (default) = what a run of max_samples can produce; with a
  *        smaller row a channel outruns it, the operations beyond are dropped and m17hip_diag_fetch / m17hip_diag_log_fetch return
  *        M17HIP_EOVERFLOW (every diagnostic field but `evm` is still right; the frame records are not affected).
- * key 16: 1 = m17hip_upload_i16, m17hip_upload_i16_device, m17hip_synth_i16 and m17hip_synth_sweep_i16 write the context's STAGING slab (as
+ * key 16: 1 = m17hip_upload_i16, m17hip_upload_i16_device, m17hip_synth_i16, m17hip_synth_sweep_i16 and m17hip_synth_tx_i16 write the context's STAGING slab (as
  *        m17hip_upload_i16_async does, but complete when they return) and stage it for the next run; 0 (default) = the current slab.
  * key 30 (tests): fault injection for m17hip_gather_frames* and m17hip_gather_sweep_stats: 1 = this rank's compaction (its upload of
  *        the words) fails inside the call, 2 = the root's staging

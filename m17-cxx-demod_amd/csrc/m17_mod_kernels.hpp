@@ -236,6 +236,122 @@ __global__ __launch_bounds__(64) void mod_symbols_kernel(ModParams base, uint32_
     nsym_out[c] = ss.n;
 }
 
+// ---- caller-supplied transmissions (m17hip_synth_tx_i16) ---------------------------------------------------------------------------------
+// The same symbol stream as mod_symbols_kernel writes, with the LSF and the payload rows given by the caller, so nothing is carried from one
+// frame to the next: one wave per (channel, frame), a frame's place is 192 x (preambles + slot), and — the encoder being linear — on-air bit p
+// of a frame is the parity of one generator polynomial over five message bits, found through a table:
+//   p -> k = the interleaver's inverse (set_interleaved: (45 k + 92 k^2) % 368 = p) -> coded bit ci = the k-th bit the puncture keeps
+//   (mod_encode's `keep`) -> poly (ci & 1 ? 027 : 031) over message bits (ci >> 1) - 4 .. ci >> 1.
+struct ModTx {   // layout of m17_tx (include/m17hip.h)
+    uint32_t kind, n_frames, first_row, reserved;
+};
+
+// src[t][p] for frame type t (0 LSF: P1, 1 stream: 96 LICH bits then P2, 2 packet: P3, 3 BERT: P2): the coded bit behind on-air bit p, or
+// 0x8000 | LICH bit number.  Built from the two formulas above when the library is compiled.
+struct ModTxTables {
+    uint16_t src[4][368];
+};
+constexpr ModTxTables mod_tx_tables()
+{
+    ModTxTables t{};
+    uint16_t inv[368] = {};
+    for (uint32_t k = 0; k < 368; ++k) inv[(45u * k + 92u * k * k) % 368u] = (uint16_t)k;
+    uint16_t kept[3][368] = {};
+    for (int which = 1; which <= 3; ++which) {
+        const uint32_t plen = which == 1 ? 61u : (which == 2 ? 12u : 8u);
+        uint32_t pidx = 0, k = 0;
+        for (uint32_t ci = 0; k < 368; ++ci) {
+            const bool keep = which == 1 ? !((pidx & 3u) == 2u && pidx <= 58u) : (which == 2 ? pidx != 11u : pidx != 7u);
+            if (keep) kept[which - 1][k++] = (uint16_t)ci;
+            if (++pidx == plen) pidx = 0;
+        }
+    }
+    for (uint32_t p = 0; p < 368; ++p) {
+        const uint32_t k = inv[p];
+        t.src[0][p] = kept[0][k];
+        t.src[1][p] = k < 96u ? (uint16_t)(0x8000u | k) : kept[1][k - 96u];
+        t.src[2][p] = kept[2][k];
+        t.src[3][p] = kept[1][k];
+    }
+    return t;
+}
+__device__ __constant__ const ModTxTables MOD_TX = mod_tx_tables();
+
+// grid (1 + the largest slot count, channels), one wave each.  Item 0 of a channel writes its preambles, its EOT + 40 zeros and nsym[c]; item
+// 1 + s writes frame slot s (slot 0 is the LSF frame for kinds 1 and 2): lanes 0..47 four symbols each, one dword store.  Every index comes
+// from a descriptor the host has checked (m17hip_synth_tx_i16): kind <= 2, first_row + n_frames <= n_rows, n_frames and n_preamble within
+// what sym_pitch was sized for.
+__global__ __launch_bounds__(64) void mod_symbols_tx_kernel(const ModTx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_preamble,
+                                                            int8_t* sym, size_t sym_pitch, uint32_t* nsym_out)
+{
+    __shared__ uint8_t msg[40];   // msg[0] = 0 (message bits -4..-1), the frame's message bytes from msg[1] on, zeros behind them (the flush bits)
+    __shared__ uint32_t gol[4];   // a stream frame's four Golay words
+    const uint32_t c = blockIdx.y, lane = threadIdx.x;
+    const ModTx t = tx[c];
+    const uint32_t has_lsf = t.kind != 0u ? 1u : 0u;
+    const uint32_t npre = n_preamble ? n_preamble : (t.kind == 0u ? 2u : 1u);
+    uint32_t* out = reinterpret_cast<uint32_t*>(sym + (size_t)c * sym_pitch);   // (sym_pitch is a multiple of 16)
+    if (blockIdx.x == 0) {
+        for (uint32_t i = lane; i < 48u * npre; i += 64u) out[i] = 0xFD03FD03u;   // 0x77 = +3 -3 +3 -3 (m17-mod.cpp:264-280)
+        const uint32_t body = 192u * (npre + has_lsf + t.n_frames);
+        if (has_lsf && lane < 12u) out[body / 4u + lane] = lane == 0u ? 0x03030303u : (lane == 1u ? 0x03FD0303u : 0u);   // 0x55 0x5D + 40 zeros (m17-mod.cpp:289-308)
+        if (lane == 0u) nsym_out[c] = body + 48u * has_lsf;
+        return;
+    }
+    const uint32_t slot = blockIdx.x - 1u;
+    if (slot >= has_lsf + t.n_frames) return;
+    const bool is_lsf = has_lsf && slot == 0u;
+    const uint32_t fi = slot - has_lsf;
+    const uint32_t type = is_lsf ? 0u : (t.kind == 1u ? 1u : (t.kind == 2u ? 2u : 3u));
+    const uint32_t nbits = type == 0u ? 240u : (type == 1u ? 144u : (type == 2u ? 206u : 197u));
+    const uint32_t sync = type == 0u ? 0x55F7u : (type == 1u ? 0xFF5Du : (type == 2u ? 0x75FFu : 0xDF55u));
+    const uint8_t* lsf = lsf30 + (size_t)c * 30u;   // (formed, not read, when kind is 0)
+    const uint8_t* src = is_lsf ? lsf : rows + ((size_t)t.first_row + fi) * 32u;
+    const uint32_t nbytes = (nbits + 7u) >> 3;
+    if (lane < 40u) {
+        uint32_t v = 0;
+        if (lane >= 1u && lane <= nbytes) {
+            v = src[lane - 1u];
+            if (lane == nbytes) v &= 0xFFu & (0xFF00u >> (((nbits - 1u) & 7u) + 1u));   // only nbits bits are carried
+        }
+        msg[lane] = (uint8_t)v;
+    }
+    if (type == 1u && lane < 4u) {   // LICH: Golay(24,12) of LSF segment fi % 6 (m17-mod.cpp:509-548)
+        const uint32_t n = fi % 6u;
+        const uint8_t* seg = lsf + 5u * n;
+        const uint32_t s0 = seg[0], s1 = seg[1], s2 = seg[2], s3 = seg[3], s4 = seg[4];
+        const uint32_t w = lane == 0u ? (s0 << 4) | (s1 >> 4) : (lane == 1u ? ((s1 & 15u) << 8) | s2 : (lane == 2u ? (s3 << 4) | (s4 >> 4) : ((s4 & 15u) << 8) | (n << 5)));
+        gol[lane] = mod_golay24(w);
+    }
+    __syncthreads();
+    if (lane >= 48u) return;
+    uint32_t word = 0;
+    for (uint32_t s = 0; s < 4u; ++s) {
+        const uint32_t j = 4u * lane + s;   // symbol of the frame: 0..7 the sync word, then the 184 dibits
+        uint32_t d;
+        if (lane < 2u) {
+            d = (sync >> (14u - 2u * j)) & 3u;
+        } else {
+            d = 0;
+            for (uint32_t h = 0; h < 2u; ++h) {
+                const uint32_t p = 2u * (j - 8u) + h;
+                const uint32_t e = MOD_TX.src[type][p];
+                const uint32_t lb = e & 0x7FFFu;   // LICH bit (stream frames only)
+                const uint32_t lich = (gol[(lb / 24u) & 3u] >> (23u - lb % 24u)) & 1u;
+                const uint32_t ci = e & 0x7FFFu, pos = (ci >> 1) + 4u;   // bit pos of msg[] is message bit (ci >> 1) - 4
+                const uint32_t v16 = ((uint32_t)msg[(pos >> 3) & 31u] << 8) | msg[((pos >> 3) & 31u) + 1u];
+                const uint32_t mem = (v16 >> (11u - (pos & 7u))) & 31u;
+                const uint32_t coded = (uint32_t)__popc(mem & ((ci & 1u) ? 027u : 031u)) & 1u;
+                const uint32_t bit = ((e & 0x8000u) ? lich : coded) ^ ((MOD_DC_SEQ[p >> 3] >> (7u - (p & 7u))) & 1u);   // M17Randomizer.h:51-57
+                d = (d << 1) | bit;
+            }
+        }
+        const uint32_t a = (d & 1u) ? 3u : 1u;   // m17-mod.cpp:164-174: 0 -> +1, 1 -> +3, 2 -> -1, 3 -> -3
+        word |= (((d & 2u) ? 0u - a : a) & 0xFFu) << (8u * s);
+    }
+    out[48u * (npre + slot) + lane] = word;
+}
+
 // Zero-mean unit-variance noise for (stream, n): sum of 8 uniform u16 from two splitmix64 words, exact in double
 __device__ inline double mod_unit_noise(uint64_t stream, uint64_t n)
 {

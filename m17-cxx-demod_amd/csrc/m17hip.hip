@@ -1039,7 +1039,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 604; }
+int m17hip_version(void) { return 605; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1388,6 +1388,57 @@ int m17hip_synth_sweep_i16(m17hip_ctx* c, const m17_synth_params* base, const m1
         if (!std::isfinite(p.dc_offset) || !std::isfinite(p.gain)) return M17HIP_EINVAL;
     }
     return synth_impl(c, base, points, n_points, C, T, chan0);
+}
+
+// Caller-supplied transmissions: mod_symbols_tx_kernel fills the symbol staging mod_symbols_kernel would have filled, mod_shape_kernel runs as
+// for m17hip_synth_i16.  Every index the symbols kernel forms is bounded HERE (it re-checks nothing).
+int m17hip_synth_tx_i16(m17hip_ctx* c, const m17_synth_params* base, const m17_tx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_rows,
+                        uint32_t C, uint32_t T, uint32_t chan0)
+{
+    if (!c || !base || !tx || !rows || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
+    static_assert(sizeof(ModTx) == sizeof(m17_tx) && sizeof(ModTx) == 16, "m17_tx layout");
+    uint32_t max_frames = 0, max_slots = 0;
+    for (uint32_t i = 0; i < C; ++i) {
+        const m17_tx& t = tx[i];
+        if (t.kind > 2u || t.reserved != 0u || (t.kind != 0u && !lsf30)) return M17HIP_EINVAL;
+        if (t.n_frames > T / 1920u + 1u || (uint64_t)t.first_row + t.n_frames > n_rows) return M17HIP_EINVAL;
+        max_frames = std::max(max_frames, t.n_frames);
+        max_slots = std::max(max_slots, t.n_frames + (t.kind != 0u ? 1u : 0u));
+    }
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    ModParams mp;
+    std::memcpy(&mp, base, sizeof(mp));
+    mp.kind = 1;        // (the shaper asks only whether this is 3)
+    mp.n_frames = 0;
+    // preambles past the end of the slab are cut off whatever their number: bounding it bounds the staging
+    const uint32_t n_pre = mp.n_preamble > 0 ? std::min((uint32_t)mp.n_preamble, T / 1920u + 2u) : 0u;
+    const size_t sym_pitch = round_up((size_t)mod_max_symbols((int)max_frames, (int)n_pre), 16);
+    const size_t sym_bytes = round_up((size_t)C * sym_pitch, 256);
+    const size_t tx_at = sym_bytes + round_up((size_t)C * 4, 256);
+    const size_t lsf_at = tx_at + round_up((size_t)C * sizeof(ModTx), 256);
+    const size_t rows_at = lsf_at + round_up((size_t)C * 30, 256);
+    const size_t need = rows_at + std::max<size_t>((size_t)n_rows * 32, 32);
+    InputTarget in;
+    int r = input_target(c, in);
+    if (r) return r;
+    if (need > c->synth_scratch.size() && c->synth_scratch) HIPCHK(c, hipDeviceSynchronize());   // (nothing still reads the one it outgrew)
+    HIPCHK(c, c->synth_scratch.grow(need, &c->last_hip));
+    int8_t* sym = reinterpret_cast<int8_t*>(c->synth_scratch.get());
+    uint32_t* nsym = reinterpret_cast<uint32_t*>(c->synth_scratch + sym_bytes);
+    ModTx* dtx = reinterpret_cast<ModTx*>(c->synth_scratch + tx_at);
+    uint8_t* dlsf = reinterpret_cast<uint8_t*>(c->synth_scratch + lsf_at);
+    uint8_t* drows = reinterpret_cast<uint8_t*>(c->synth_scratch + rows_at);
+    HIPCHK(c, hipMemcpyAsync(dtx, tx, (size_t)C * sizeof(ModTx), hipMemcpyHostToDevice, in.st));
+    if (lsf30) HIPCHK(c, hipMemcpyAsync(dlsf, lsf30, (size_t)C * 30, hipMemcpyHostToDevice, in.st));
+    if (n_rows) HIPCHK(c, hipMemcpyAsync(drows, rows, (size_t)n_rows * 32, hipMemcpyHostToDevice, in.st));
+    hipLaunchKernelGGL(mod_symbols_tx_kernel, dim3(1 + max_slots, C), dim3(64), 0, in.st, dtx, dlsf, drows, n_pre, sym, sym_pitch, nsym);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(mod_shape_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, C, T, chan0, sym, sym_pitch, nsym, in.x, c->xpitch);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(in.st));
+    input_done(c, in, C, T);
+    return M17HIP_OK;
 }
 
 int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch)

@@ -55,6 +55,14 @@ public:
         check(m17hip_upload_i16(ctx_, host, channels, samples, pitch), "m17hip_upload_i16");
         channels_ = channels; samples_ = samples;
     }
+    // The input generated on the device from the caller's own transmissions, one per channel (m17hip_synth_tx_i16: the framing of
+    // apps/m17-mod.cpp:264-504, 509-564 around lsf30[channels][30] and rows[n_rows][32]; impairments and seeding from `base`)
+    void synth_tx(const m17_synth_params& base, const m17_tx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_rows, uint32_t channels,
+                  uint32_t samples, uint32_t chan0 = 0)
+    {
+        check(m17hip_synth_tx_i16(ctx_, &base, tx, lsf30, rows, n_rows, channels, samples, chan0), "m17hip_synth_tx_i16");
+        channels_ = channels; samples_ = samples;
+    }
     void reset() { check(m17hip_demod_reset(ctx_), "m17hip_demod_reset"); }
     // Fresh demodulators for the listed channels only (local indices), from the start of the NEXT run queued; the others go on
     // (m17hip_demod_reset_channels: between runs whose lengths are multiples of 192 samples, not between front() and run()).

@@ -41,6 +41,8 @@ CHAN_STAT_DTYPE = np.dtype([("channel", "<u4"), ("point", "<u4"), ("bits", "<u4"
                             ("evm", "<f4"), ("flags", "<u4")])   # m17_chan_stat; flags bit 0: evm is valid
 assert IMPAIRMENT_DTYPE.itemsize == 32 and CHAN_STAT_DTYPE.itemsize == 32
 MAX_SWEEP_POINTS = 4096
+TX_DTYPE = np.dtype([("kind", "<u4"), ("n_frames", "<u4"), ("first_row", "<u4"), ("reserved", "<u4")])   # m17_tx
+TX_BERT, TX_STREAM, TX_PACKET = 0, 1, 2
 
 EXPORTS = [
     "m17hip_strerror", "m17hip_last_hip_error", "m17hip_version", "m17hip_ctx_create", "m17hip_ctx_destroy", "m17hip_set_stream", "m17hip_get_stream",
@@ -51,7 +53,7 @@ EXPORTS = [
     "m17hip_comm_destroy", "m17hip_comm_last_error", "m17hip_gather_frames", "m17hip_gather_frames_device", "m17hip_diag_log_fetch",
     "m17hip_upload_i16_device_async", "m17hip_input_alternate", "m17hip_demod_front", "m17hip_advice", "m17hip_replay_drops", "m17hip_frames_select",
     "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats", "m17hip_demod_reset_channels",
-    "m17hip_set_channel_polarity",
+    "m17hip_set_channel_polarity", "m17hip_synth_tx_i16",
 ]
 ETRUNC = -6
 EOVERFLOW = -5
@@ -60,6 +62,48 @@ COMM_ID_BYTES = 128
 
 class M17HipError(RuntimeError):
     pass
+
+
+# ---- content of a caller-supplied transmission (Context.synth_tx), pure Python ------------------------------------------------------------
+_CALLSIGN_ALPHABET = " ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789-/."
+
+
+def encode_callsign(call):
+    """Up to 9 characters of A-Z 0-9 - / . as the 6-byte big-endian base-40 address of LinkSetupFrame.h:46-86 (first character least
+    significant; any other character counts as a blank)."""
+    enc = 0
+    for ch in reversed(call[:9]):
+        enc = enc * 40 + max(_CALLSIGN_ALPHABET.find(ch), 0)
+    return enc.to_bytes(6, "big")
+
+
+def crc16_m17(data):
+    """CRC16<0x5935, 0xFFFF> of CRC16.h:12-70 over `data`."""
+    reg = 0xFFFF
+    for byte in bytes(data):
+        reg ^= byte << 8
+        for _ in range(8):
+            reg = ((reg << 1) ^ 0x5935 if reg & 0x8000 else reg << 1) & 0xFFFF
+    return reg
+
+
+def make_lsf(dst, src, type_field, meta=b""):
+    """The 30 bytes of a link setup frame as apps/m17-mod.cpp:310-347 fills them: destination (base 40; "" = the broadcast address FF x 6) and
+    source callsigns, the 16-bit type field, up to 14 bytes of META (zero padded) and the CRC-16 over the first 28 bytes, big-endian."""
+    meta = bytes(meta)
+    if len(meta) > 14:
+        raise ValueError("META is 14 bytes at the most")
+    body = (encode_callsign(dst) if dst != "" else b"\xff" * 6) + encode_callsign(src) + int(type_field & 0xFFFF).to_bytes(2, "big") + meta.ljust(14, b"\0")
+    return body + crc16_m17(body).to_bytes(2, "big")
+
+
+def stream_row(fn, payload16, last=False):
+    """The 32-byte row of one stream frame (apps/m17-mod.cpp:407-440): the 15-bit frame number with the end-of-stream bit, then 16 payload
+    bytes; the rest is padding."""
+    payload16 = bytes(payload16)
+    if len(payload16) != 16:
+        raise ValueError("a stream frame carries 16 payload bytes")
+    return (((fn & 0x7FFF) | (0x8000 if last else 0)).to_bytes(2, "big") + payload16).ljust(32, b"\0")
 
 
 _lib = None
@@ -202,6 +246,31 @@ class Context:
         self.C, self.T = int(channels), int(samples)
         self._chk(self.lib.m17hip_synth_sweep_i16(self.h, C.byref(base), _ptr(pts), C.c_uint32(pts.size), C.c_uint32(self.C), C.c_uint32(self.T),
                                                   C.c_uint32(chan0)))
+
+    def synth_tx(self, base, transmissions, samples, chan0=0):
+        """Generate the input slab on the device from the caller's own transmissions, one per channel (m17hip_synth_tx_i16: the framing of
+        apps/m17-mod.cpp:264-504, 509-564 with the content supplied).  A transmission is (kind, lsf_bytes_or_None, [row_bytes, ...]): kind
+        TX_BERT / TX_STREAM / TX_PACKET, the 30-byte LSF sent as given (make_lsf; None for BERT), and one row of up to 32 bytes per payload
+        frame (stream_row; 26 bytes of a packet frame; 25 of a BERT frame).  `base` = an m17_synth_params block: seed, lead_in, phase, invert,
+        n_preamble and the impairments; its kind and n_frames are ignored."""
+        tx = np.zeros(len(transmissions), dtype=TX_DTYPE)
+        lsf = np.zeros((len(transmissions), 30), dtype=np.uint8)
+        rows = []
+        for i, (kind, lsf_bytes, frames) in enumerate(transmissions):
+            tx[i] = (kind, len(frames), len(rows), 0)
+            if lsf_bytes is not None:
+                lsf[i] = np.frombuffer(bytes(lsf_bytes), dtype=np.uint8)   # (exactly 30 bytes)
+            elif kind != TX_BERT:
+                raise ValueError("a stream or packet transmission needs its LSF")
+            for row in frames:
+                row = bytes(row)
+                if len(row) > 32:
+                    raise ValueError("a row is 32 bytes at the most")
+                rows.append(row.ljust(32, b"\0"))
+        rows_arr = np.frombuffer(b"".join(rows), dtype=np.uint8) if rows else np.zeros(32, dtype=np.uint8)
+        self._chk(self.lib.m17hip_synth_tx_i16(self.h, C.byref(base), _ptr(tx), _ptr(lsf), _ptr(rows_arr), C.c_uint32(len(rows)),
+                                               C.c_uint32(len(transmissions)), C.c_uint32(int(samples)), C.c_uint32(chan0)))
+        self.C, self.T = len(transmissions), int(samples)
 
     def download(self, channels=None):
         """The input slab's first `channels` rows (default: all of the last input)."""
