@@ -392,6 +392,68 @@ int m17hip_packets_fetch(m17hip_ctx* ctx, m17_packet_rec* recs_host, uint32_t ca
  * exactly as it does at the end of a run; the packets completed are then returned by m17hip_packets_fetch. */
 int m17hip_packets_feed(m17hip_ctx* ctx, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t channels, uint32_t pitch);
 
+/* Payload consumer (ABI 606): the voice of stream transmissions — FrameType::STREAM -> demodulate_audio
+ * (apps/m17-demod.cpp:178-205, 321-323) — without codec2, which stays host work: per channel and run the 16 payload bytes of every
+ * stream record (payload[2..17]: two codec2 3200 frames, :198-200) next to each other in arrival order, one MARK byte per slot, and a
+ * log of the CALLS the run closed.  Enabled with m17hip_tune(ctx, 34, room) BEFORE the runs to be consumed: room = voice slots per
+ * channel and run (a run of T samples carries at most T / 1920 + 1 stream frames per channel).  The consumer is defined on the frame
+ * records of a run in (channel, seq) order, with per-channel state carried from run to run:
+ *   1. a record with frame_type == M17_FRAME_LSF (an LSF frame, or one assembled from LICH, M17FrameDecoder.h:247-254) closes the
+ *      channel's open call, if any (close = 2), and opens a new one: has_lsf = 1, lsf = payload[0..29], start_pos = its sample_pos
+ *      (dump_lsf, :316);
+ *   2. a record with frame_type == M17_FRAME_STREAM opens a call if none is open (has_lsf = 0, lsf all zero, start_pos = its sample_pos:
+ *      a late join, or the frames that follow an end of stream) and takes the channel's next voice slot of the run: the payload is ALWAYS
+ *      copied — blanking is the host's decision — with the mark bits
+ *          bit 0 (M17HIP_MARK_BLANK)  cost > 80: what -b would silence (:190)
+ *          bit 1 (M17HIP_MARK_EOS)    cost < 70 && (payload[0] & 0x80): an accepted end of stream (:184)
+ *          bit 2 (M17HIP_MARK_FIRST)  the first voice frame of its call
+ *          bit 3 (M17HIP_MARK_GAP)    its frame number ((payload[0] << 8 | payload[1]) & 0x7fff) is not the call's previous frame number
+ *                                     + 1 mod 0x8000 (never set together with bit 2: a first frame has no predecessor)
+ *      and the call's frames, blanked (bit 0), cost_sum (mod 2^32) and end_pos (= its sample_pos) advance; with bit 3 set `lost` grows by
+ *      (frame number - previous frame number - 1) mod 0x8000.  Mark bit 1 closes the call (close = 1);
+ *   3. every other record is ignored.
+ * m17hip_demod_reset starts every channel over (no open call, seq 0); m17hip_demod_reset_channels, or a polarity change that marks a
+ * channel, does so for the marked channels — an open call is abandoned, as a half-assembled packet is.
+ * A call is reported ONCE, by the run that closes it.  Room for call records: M17HIP_CALLS_PER_CHANNEL(room) per channel and run (one
+ * row per channel in the store, max_channels x that in all — nothing but (channel, seq) ever orders it); a channel that closes more in
+ * one run keeps the first ones and m17hip_calls_fetch returns M17HIP_EOVERFLOW.  A channel with more stream records than `room` in one
+ * run: the slots that fit are written, the call accounting goes on over every record, m17hip_voice_fetch returns M17HIP_EOVERFLOW. */
+#define M17HIP_MARK_BLANK 1u
+#define M17HIP_MARK_EOS 2u
+#define M17HIP_MARK_FIRST 4u
+#define M17HIP_MARK_GAP 8u
+#define M17HIP_CALLS_PER_CHANNEL(room) ((room) / 8u + 2u)
+typedef struct m17_call_rec {   /* 72 bytes */
+    uint32_t channel;           /* channel_base + local index */
+    uint32_t seq;               /* calls this channel closed before this one, since reset */
+    uint64_t start_pos, end_pos;/* sample_pos of the opening record / of the last voice frame (= start_pos when there was none) */
+    uint32_t cost_sum, frames, blanked, lost;
+    uint8_t  has_lsf, close;    /* close: 1 accepted EOS, 2 the next LSF record */
+    uint8_t  lsf[30];
+} m17_call_rec;
+/* The planes of the selected run (m17hip_frames_select; ordered as the fetch family is: behind that run's payload work, whatever was
+ * queued since): audio_host[channels][slots][16], marks_host[channels][slots], counts_host[channels] = stream records of the channel in
+ * that run.  slots < room is allowed: rows are cut (slots beyond the room are not written; slots == 0 fetches the counts alone, the two
+ * plane pointers may then be NULL).  M17HIP_EOVERFLOW if a count exceeds room, else M17HIP_ETRUNC if one exceeds `slots` — the rows are
+ * written as far as they go either way.  M17HIP_ESTATE with the key off or with no run made (nor m17hip_voice_feed) since the reset;
+ * M17HIP_EINVAL for NULL where a pointer is needed, channels == 0 or more channels than the run had.
+ * Replaces the loop a host runs over the fetched records: apps/m17-demod.cpp:178-205. */
+int m17hip_voice_fetch(m17hip_ctx* ctx, uint8_t* audio_host, uint8_t* marks_host, uint32_t* counts_host, uint32_t channels, uint32_t slots);
+/* The same planes where they lie, for a consumer on the GPU (a torch tensor view): DEVICE pointers of the selected run's
+ * audio[max_channels][*pitch_slots][16], marks[max_channels][*pitch_slots], counts[max_channels] (*pitch_slots = room).  The call waits
+ * for the payload work of that run; the memory is valid until the run after the next is queued (as the record sets are), or key 34 is
+ * set again.  Replaces apps/m17-demod.cpp:198-200 (the payload handed to codec2). */
+int m17hip_voice_device(m17hip_ctx* ctx, const uint8_t** audio_dev, const uint8_t** marks_dev, const uint32_t** counts_dev, uint32_t* pitch_slots);
+/* The calls the selected run closed, ordered by (channel, seq): *count = how many there were, min(*count, capacity) are written
+ * (the truncation rule of m17hip_packets_fetch); M17HIP_EOVERFLOW if a channel closed more than M17HIP_CALLS_PER_CHANNEL(room).
+ * Replaces what an operator reads off dump_lsf's and demodulate_audio's output (apps/m17-demod.cpp:124-205, 316). */
+int m17hip_calls_fetch(m17hip_ctx* ctx, m17_call_rec* host, uint32_t capacity, uint32_t* count);
+/* The same consumer over frame records supplied by the caller (fetched earlier, gathered from other GPUs, or made by a test) instead of
+ * a run's: recs_host[channels][pitch] with counts_host[c] records used in row c (cut at pitch).  The per-channel state advances exactly
+ * as at the end of a run; the results are then what the three calls above return (they take the place of the latest run's).
+ * M17HIP_ESTATE with the key off and between m17hip_demod_front and its run.  (apps/m17-demod.cpp:321-323 over a record list.) */
+int m17hip_voice_feed(m17hip_ctx* ctx, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t channels, uint32_t pitch);
+
 /* Payload consumer: link setup frames as text — LinkSetupFrame::decode_callsign (LinkSetupFrame.h:95-121: 6 bytes
  * big-endian base 40 -> up to 9 characters, all ones = "BROADCAST"), the 16-bit type field and the CRC check of dump_lsf
  * (apps/m17-demod.cpp:124-200), for a batch of n 30-byte LSFs (e.g. the payloads of the frame_type 0 records). */
@@ -460,6 +522,10 @@ int m17hip_gather_sweep_stats(m17hip_ctx* ctx, m17hip_comm* comm, int root, cons
  *        segments bound how long a channel that lost sync computes its own limit-filter history, longer ones mean fewer launches.
  * key 6: BERT statistics on/off (m17hip_bert_stats; default off).
  * key 7: packet reassembly, value = packets of room per run (m17hip_packets_fetch; default 0 = off).
+ * key 34: voice consumer, value = voice slots of room per channel and run (m17hip_voice_fetch, m17hip_calls_fetch; default 0 = off;
+ *        at most 65536).  Set before the runs to be consumed, like keys 6 and 7; it allocates the per-channel call state, two sets of planes
+ *        (max_channels x room x 17 bytes each) that alternate with the record sets, and max_channels x M17HIP_CALLS_PER_CHANNEL(room)
+ *        call records per set.  With the key off a run queues exactly what it queues without it.
  * key 8: record slots per channel and run actually used, 0 = all that were allocated (2 per 1920 samples + 8, which a run cannot
  *        outgrow) — a smaller value makes M17HIP_EOVERFLOW reachable for tests.
  * key 9: diagnostic log, value = diagnostic callbacks of room per channel and run (m17hip_diag_log_fetch; default 0 = off).
@@ -533,7 +599,8 @@ int m17hip_debug_counters(m17hip_ctx* ctx, uint64_t* host, uint32_t max_waves, u
 int m17hip_timing_enable(m17hip_ctx* ctx, int on);
 /* Accumulated device time (ms) and launch count per kernel since the last m17hip_timing_reset:
  * which: 0 = fir_rrc150, 1 = dcd, 2 = demod_seq, 3 = viterbi/decode_frames, 4 = correlator, 5 = compaction,
- * 6 = limit_track (the limit filter run ahead of demod_seq; in m17hip_fir_correlator the limit filter's chain, 4 = its correlations). */
+ * 6 = limit_track (the limit filter run ahead of demod_seq; in m17hip_fir_correlator the limit filter's chain, 4 = its correlations),
+ * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -11,6 +11,7 @@
 #include "m17_gate_kernel.hpp"
 #include "m17_mod_kernels.hpp"
 #include "m17_parity_kernels.hpp"
+#include "m17_voice_kernel.hpp"
 #include "m17_gather.hpp"
 
 #include <hip/hip_ext.h>
@@ -30,7 +31,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -273,6 +274,17 @@ struct m17hip_ctx {
     DevBuf<uint32_t> pkt_count2;      // [2]
     uint32_t pkt_cap = 0;
     bool pkt_fed = false;
+    // The voice consumer (tuning knob 34; m17_voice_kernel.hpp): per-channel call state, and per record set the planes of a run — payloads,
+    // marks, counts — and the calls it closed, a row of call_room slots per channel (nothing but (channel, seq) orders them).
+    DevBuf<VoiceState> voice_state;   // [maxC]
+    DevBuf<uint8_t> voice_audio2[2];  // [maxC][voice_room][16]
+    DevBuf<uint8_t> voice_marks2[2];  // [maxC][voice_room]
+    DevBuf<uint32_t> voice_counts2;   // [2][maxC] voice records of the run (not cut at voice_room)
+    DevBuf<CallRec> call_recs2[2];    // [maxC][call_room]
+    DevBuf<uint32_t> call_counts2;    // [2][maxC] calls closed in the run (not cut at call_room)
+    uint32_t voice_room = 0, call_room = 0;
+    uint32_t voice_C[2] = {0, 0};     // channels whose rows of a store the consumer has written (a run's, or m17hip_voice_feed's)
+    bool voice_fed = false;
     DevBuf<Diag> diag_log;            // [maxC][diag_cap] one entry per diagnostic callback of the last run (tuning knob 9)
     DevBuf<uint32_t> diag_count;      // [maxC]
     uint32_t diag_cap = 0;
@@ -305,7 +317,7 @@ struct m17hip_ctx {
         uint32_t C = 0, rec_cap = 0, nseg = 0;
         bool valid = false;               // holds a finished run's records in the layout (rec_cap) they were written with
         bool pending = false;             // its payload work (deferred decode, consumers) is not queued yet (flush_payload)
-        bool bert = false, pkt = false;   // the consumers that were on when the run was made
+        bool bert = false, pkt = false, voice = false;   // the consumers that were on when the run was made
     } sets[2];
     int cur = 0;                      // the set of the latest run
     uint32_t sel_back = 0;            // m17hip_frames_select: 0 = the latest run's records, 1 = the run's before it
@@ -826,13 +838,14 @@ __global__ void bert_reset_kernel(BertState* state, uint32_t C)
     if (c >= C) return;
     fresh_bert_state(state, c);
 }
-// m17hip_demod_reset_channels: the payload consumers of the listed channels start over (pkt == nullptr: packet reassembly is off); a lane per listed channel
-__global__ void consumer_reset_list_kernel(const uint32_t* list, uint32_t n, BertState* bert, PacketState* pkt)
+// m17hip_demod_reset_channels: the payload consumers of the listed channels start over (pkt / voice == nullptr: that consumer is off); a lane per listed channel
+__global__ void consumer_reset_list_kernel(const uint32_t* list, uint32_t n, BertState* bert, PacketState* pkt, VoiceState* voice)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     fresh_bert_state(bert, list[i]);
     if (pkt) fresh_packet_state(pkt, list[i]);
+    if (voice) fresh_voice_state(voice, list[i]);   // (an open call is abandoned, as a half-assembled packet is; its seq restarts)
 }
 
 __global__ void copy_prefix_i16_kernel(const int16_t* src, int16_t* dst, size_t xpitch)
@@ -1039,7 +1052,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 605; }
+int m17hip_version(void) { return 606; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1652,6 +1665,13 @@ int m17hip_demod_reset(m17hip_ctx* c)
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
     }
+    if (c->voice_room) {   // no open call, seq back to 0; nothing of the runs before is left to fetch
+        hipLaunchKernelGGL(voice_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->voice_state, c->maxC);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemsetAsync(c->voice_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->call_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
+        c->voice_fed = false;
+    }
     for (auto& rs : c->sets) {
         if (rs.rec_count) HIPCHK(c, hipMemsetAsync(rs.rec_count, 0, (size_t)c->maxC * 4, c->stream));
         rs.valid = false;
@@ -1962,6 +1982,19 @@ static int flush_fold(m17hip_ctx* c)
     return M17HIP_OK;
 }
 
+// The voice consumer over `C` rows of records, into the planes and the call store of record set `set` (payload stream: the state goes from run to run)
+static void launch_voice(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set)
+{
+    VoiceParams V{};
+    V.recs = recs; V.rec_cap = rec_cap; V.rec_count = rec_count; V.state = c->voice_state; V.C = C;
+    V.audio = c->voice_audio2[set]; V.marks = c->voice_marks2[set]; V.counts = c->voice_counts2 + (size_t)set * c->maxC; V.room = c->voice_room;
+    V.calls = c->call_recs2[set]; V.call_counts = c->call_counts2 + (size_t)set * c->maxC; V.call_room = c->call_room;
+    V.channel_base = c->channel_base;
+    TimedK tm(c, KT_VOICE);
+    tm.launch(voice_log_kernel, dim3((C + VOICE_CPB - 1) / VOICE_CPB), dim3(64 * VOICE_CPB), 0, ps, V);
+    c->voice_C[set] = C;
+}
+
 // Queue the payload work of the runs whose results nobody has asked for yet, in run order, on the payload stream: the frames K5 left to
 // decode_deferred_kernel (one lane per frame), then the consumers (their state goes from run to run), then `done`.
 // `selected_only`: up to the run the fetch family names (m17hip_frames_select) — a fetch of run k must not queue the work of run k + 1, whose
@@ -2001,6 +2034,8 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
             hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->pkt_state, C,
                                c->pkt_recs2[i], c->pkt_cap, c->pkt_count2 + i, c->channel_base);
         }
+        if (rs.voice && c->voice_room)   // payload consumer: codec2 payload planes and the call log over this run's stream records (behind their deferred decode)
+            launch_voice(c, ps, rs.recs, rs.rec_cap, rs.rec_count, C, i);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(rs.done, ps));
         rs.pending = false;
@@ -2255,7 +2290,7 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     c->now().used = true; c->pos += T; c->inplace_after_run = false; c->have_run = true;
     c->lastC = C; c->runT = T; c->last_nseg = p.nseg;
     rs.valid = true; rs.C = C; rs.rec_cap = c->rec_cap; rs.nseg = p.nseg;
-    rs.pending = true; rs.bert = c->bert; rs.pkt = c->pkt_cap != 0;
+    rs.pending = true; rs.bert = c->bert; rs.pkt = c->pkt_cap != 0; rs.voice = c->voice_room != 0;
     c->cur = (int)(&rs - c->sets); c->sel_back = 0;
     return M17HIP_OK;
 }
@@ -2287,7 +2322,8 @@ static int reset_marked_state(m17hip_ctx* c, const RunPlan& p)
         if (rs.valid)
             if (int r = pay_after(c, rs)) return r;
     HIPCHK(c, c->reset_list.before_read(c->pay()));
-    hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert_state.get(), c->pkt_cap ? c->pkt_state.get() : (PacketState*)nullptr);
+    hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert_state.get(), c->pkt_cap ? c->pkt_state.get() : (PacketState*)nullptr,
+                       c->voice_room ? c->voice_state.get() : (VoiceState*)nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->reset_list.after_read(RD_PAY, c->pay()));
     HIPCHK(c, c->reset_list.before_read(c->stream));
@@ -2606,6 +2642,99 @@ int m17hip_packets_fetch(m17hip_ctx* c, m17_packet_rec* recs_host, uint32_t capa
     const uint32_t n = std::min(stored, capacity);
     if (n) std::memcpy(recs_host, tmp.data(), (size_t)n * sizeof(PacketRec));
     return total > c->pkt_cap ? M17HIP_EOVERFLOW : M17HIP_OK;
+}
+
+// The store of the run the fetch family names (m17hip_frames_select), ordered behind that run's payload work wherever it was queued
+static int voice_select(m17hip_ctx* c, int& ps)
+{
+    if (!c->voice_room || !(c->have_run || c->voice_fed)) return M17HIP_ESTATE;
+    ps = c->cur ^ (int)(c->sel_back & 1u);
+    if (c->sel_back && !c->sets[ps].valid) return M17HIP_ESTATE;
+    if (int fr = flush_payload(c, true)) return fr;
+    if (c->sets[ps].valid)
+        if (int fr = pay_after(c, c->sets[ps])) return fr;
+    return M17HIP_OK;
+}
+
+int m17hip_voice_fetch(m17hip_ctx* c, uint8_t* audio_host, uint8_t* marks_host, uint32_t* counts_host, uint32_t C, uint32_t slots)
+{
+    if (!c || !counts_host || C == 0 || C > c->maxC || (slots && (!audio_host || !marks_host))) return M17HIP_EINVAL;
+    GUARD(c);
+    int ps = 0;
+    if (int r = voice_select(c, ps)) return r;
+    if (C > c->voice_C[ps]) return M17HIP_EINVAL;   // (rows the consumer has not written)
+    const uint32_t room = c->voice_room, w = std::min(slots, room);
+    HIPCHK(c, hipMemcpyAsync(counts_host, c->voice_counts2 + (size_t)ps * c->maxC, (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
+    if (w) {   // rows cut at `slots` (slots beyond the room are not written)
+        HIPCHK(c, hipMemcpy2DAsync(audio_host, (size_t)slots * 16, c->voice_audio2[ps], (size_t)room * 16, (size_t)w * 16, C, hipMemcpyDeviceToHost, c->pay()));
+        HIPCHK(c, hipMemcpy2DAsync(marks_host, slots, c->voice_marks2[ps], room, w, C, hipMemcpyDeviceToHost, c->pay()));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
+    bool over = false, trunc = false;
+    for (uint32_t i = 0; i < C; ++i) { over = over || counts_host[i] > room; trunc = trunc || counts_host[i] > slots; }
+    return over ? M17HIP_EOVERFLOW : (trunc ? M17HIP_ETRUNC : M17HIP_OK);
+}
+
+int m17hip_voice_device(m17hip_ctx* c, const uint8_t** audio_dev, const uint8_t** marks_dev, const uint32_t** counts_dev, uint32_t* pitch_slots)
+{
+    if (!c || !audio_dev || !marks_dev || !counts_dev || !pitch_slots) return M17HIP_EINVAL;
+    GUARD(c);
+    int ps = 0;
+    if (int r = voice_select(c, ps)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
+    *audio_dev = c->voice_audio2[ps]; *marks_dev = c->voice_marks2[ps]; *counts_dev = c->voice_counts2 + (size_t)ps * c->maxC;
+    *pitch_slots = c->voice_room;
+    return M17HIP_OK;
+}
+
+int m17hip_calls_fetch(m17hip_ctx* c, m17_call_rec* host, uint32_t capacity, uint32_t* count)
+{
+    if (!c || !count || (capacity && !host)) return M17HIP_EINVAL;
+    GUARD(c);
+    static_assert(sizeof(CallRec) == sizeof(m17_call_rec) && sizeof(CallRec) == 72, "m17_call_rec layout");
+    int ps = 0;
+    if (int r = voice_select(c, ps)) return r;
+    const uint32_t C = c->voice_C[ps], room = c->call_room;
+    std::vector<uint32_t> cnt(C);
+    if (C) HIPCHK(c, hipMemcpyAsync(cnt.data(), c->call_counts2 + (size_t)ps * c->maxC, (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
+    uint64_t total = 0; uint32_t most = 0; bool over = false;
+    for (uint32_t n : cnt) { total += n; most = std::max(most, std::min(n, room)); over = over || n > room; }
+    *count = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFu);
+    if (most && capacity) {   // the columns in use of every channel's row, then row after row: (channel, seq) order
+        std::vector<CallRec> tmp((size_t)C * most);
+        HIPCHK(c, hipMemcpy2D(tmp.data(), (size_t)most * sizeof(CallRec), c->call_recs2[ps], (size_t)room * sizeof(CallRec), (size_t)most * sizeof(CallRec), C,
+                              hipMemcpyDeviceToHost));
+        uint32_t written = 0;
+        for (uint32_t ch = 0; ch < C && written < capacity; ++ch) {
+            const uint32_t k = std::min(std::min(cnt[ch], room), capacity - written);
+            if (k) std::memcpy(host + written, tmp.data() + (size_t)ch * most, (size_t)k * sizeof(CallRec));
+            written += k;
+        }
+    }
+    return over ? M17HIP_EOVERFLOW : M17HIP_OK;
+}
+
+int m17hip_voice_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t C, uint32_t pitch)
+{
+    if (!c || !recs_host || !counts_host || C == 0 || C > c->maxC || pitch == 0) return M17HIP_EINVAL;
+    GUARD(c);
+    if (c->front_queued || !c->voice_room) return M17HIP_ESTATE;
+    if (int fr = flush_payload(c)) return fr;
+    for (const auto& rs : c->sets)   // (the consumer's state goes from run to run: behind both runs, wherever their payload work was queued)
+        if (rs.valid)
+            if (int fr = pay_after(c, rs)) return fr;
+    const size_t rec_b = round_up((size_t)C * pitch * sizeof(FrameRec), 256);
+    HIPCHK(c, c->scratch.grow(rec_b + (size_t)C * 4, &c->last_hip));
+    FrameRec* drec = reinterpret_cast<FrameRec*>(c->scratch.get());
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(c->scratch + rec_b);
+    HIPCHK(c, hipMemcpyAsync(drec, recs_host, (size_t)C * pitch * sizeof(FrameRec), hipMemcpyHostToDevice, c->pay()));
+    HIPCHK(c, hipMemcpyAsync(dcnt, counts_host, (size_t)C * 4, hipMemcpyHostToDevice, c->pay()));
+    launch_voice(c, c->pay(), drec, pitch, dcnt, C, c->cur);   // (the store of the latest run's set, as m17hip_packets_feed)
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->pay()));   // the host buffers may go away
+    c->voice_fed = true;
+    return M17HIP_OK;
 }
 
 int m17hip_set_kalman_order(m17hip_ctx* c, int order)
@@ -2991,6 +3120,36 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
         hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->pkt_state, c->maxC);
         HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
         HIPCHK(c, hipGetLastError());
+        return M17HIP_OK;
+    }
+    case 34: {  // voice consumer (m17hip_voice_fetch, m17hip_calls_fetch): `value` voice slots per channel and run, 0 = off
+        if (value < 0 || value > 65536) return M17HIP_EINVAL;
+        if (int fr = flush_payload(c)) return fr;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->pay()));
+        for (int i = 0; i < 2; ++i) {
+            c->voice_audio2[i].release(&c->last_hip); c->voice_marks2[i].release(&c->last_hip); c->call_recs2[i].release(&c->last_hip);
+            c->voice_C[i] = 0;
+        }
+        c->voice_room = 0; c->call_room = 0; c->voice_fed = false;
+        if (value == 0) return M17HIP_OK;
+        const uint32_t room = (uint32_t)value, call_room = M17HIP_CALLS_PER_CHANNEL(room);
+        if (!c->voice_state) {
+            HIPCHK(c, c->voice_state.alloc(c->maxC));
+            HIPCHK(c, c->voice_counts2.alloc((size_t)2 * c->maxC));
+            HIPCHK(c, c->call_counts2.alloc((size_t)2 * c->maxC));
+        }
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, c->voice_audio2[i].alloc((size_t)c->maxC * room * 16));
+            HIPCHK(c, c->voice_marks2[i].alloc((size_t)c->maxC * room));
+            HIPCHK(c, c->call_recs2[i].alloc((size_t)c->maxC * call_room));
+        }
+        hipLaunchKernelGGL(voice_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->voice_state, c->maxC);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemsetAsync(c->voice_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->call_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (the payload stream, where the consumer works, may be another one)
+        c->voice_room = room; c->call_room = call_room;
         return M17HIP_OK;
     }
     case 8:  // record slots per channel and run actually used (0 = all that were allocated): exercises M17HIP_EOVERFLOW

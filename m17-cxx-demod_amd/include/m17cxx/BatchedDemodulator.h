@@ -18,7 +18,7 @@ namespace mobilinkd
 class BatchedDemodulator
 {
     m17hip_ctx* ctx_ = nullptr;
-    uint32_t channels_ = 0, samples_ = 0, room_ = 0, diag_room_ = 0;
+    uint32_t channels_ = 0, samples_ = 0, room_ = 0, diag_room_ = 0, voice_room_ = 0;
     uint64_t last_frames_ = 0;
 
     static void check(int code, const char* what)
@@ -88,7 +88,7 @@ public:
         last_frames_ = got;
         return out;
     }
-    // Which run's records frames() / packets() name: 0 = the latest run (every run() selects it again), 1 = the run before it — what a live
+    // Which run's records frames() / packets() / voice() / calls() name: 0 = the latest run (every run() selects it again), 1 = the run before it — what a live
     // feed asks for after it has queued the next run (m17hip_frames_select).
     void select(uint32_t back) { check(m17hip_frames_select(ctx_, back), "m17hip_frames_select"); }
     // Streaming (include/m17hip.h, m17hip_demod_front): stage the next run's input from pinned host memory while the current run
@@ -118,6 +118,37 @@ public:
         uint32_t n = 0;
         check(m17hip_packets_fetch(ctx_, out.data(), room_, &n), "m17hip_packets_fetch");
         out.resize(n < room_ ? n : room_);
+        return out;
+    }
+    // The voice of stream transmissions (demodulate_audio, apps/m17-demod.cpp:178-205, without codec2): enable with room for `room` voice
+    // frames per channel and run (0 = off; samples / 1920 + 1 is always enough), then voice() returns the 16 payload bytes (two codec2 3200
+    // frames) of every stream frame of the selected run per channel, in arrival order, with one mark byte each (M17HIP_MARK_*: bit 0 = what
+    // -b would silence), and calls() the calls that run closed, ordered by (channel, seq).
+    struct Voice {
+        uint32_t slots = 0;              // row pitch of audio / marks
+        std::vector<uint8_t> audio;      // [channels][slots][16]
+        std::vector<uint8_t> marks;      // [channels][slots]
+        std::vector<uint32_t> counts;    // [channels] slots in use
+        const uint8_t* frame(uint32_t channel, uint32_t slot) const { return audio.data() + ((size_t)channel * slots + slot) * 16; }
+        uint8_t mark(uint32_t channel, uint32_t slot) const { return marks[(size_t)channel * slots + slot]; }
+    };
+    void enable_voice(uint32_t room) { check(m17hip_tune(ctx_, 34, room), "m17hip_tune"); voice_room_ = room; }
+    Voice voice()
+    {
+        Voice v;
+        v.slots = voice_room_;
+        v.audio.resize((size_t)channels_ * voice_room_ * 16);
+        v.marks.resize((size_t)channels_ * voice_room_);
+        v.counts.resize(channels_);
+        check(m17hip_voice_fetch(ctx_, v.audio.data(), v.marks.data(), v.counts.data(), channels_, voice_room_), "m17hip_voice_fetch");
+        return v;
+    }
+    std::vector<m17_call_rec> calls()
+    {
+        std::vector<m17_call_rec> out((size_t)channels_ * M17HIP_CALLS_PER_CHANNEL(voice_room_));
+        uint32_t n = 0;
+        check(m17hip_calls_fetch(ctx_, out.data(), (uint32_t)out.size(), &n), "m17hip_calls_fetch");
+        out.resize(n < out.size() ? n : out.size());
         return out;
     }
     std::vector<m17_diag> diagnostics()

@@ -29,12 +29,23 @@ DIAG = np.dtype(
 assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
-KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6}
+KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
                        ("frames", "u1"), ("seq_errors", "u1"), ("reserved", "u1"), ("data", "u1", (840,))])
 assert PACKET_REC.itemsize == 864
+CALL_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("start_pos", "<u8"), ("end_pos", "<u8"), ("cost_sum", "<u4"), ("frames", "<u4"),
+                     ("blanked", "<u4"), ("lost", "<u4"), ("has_lsf", "u1"), ("close", "u1"), ("lsf", "u1", (30,))])   # m17_call_rec
+assert CALL_REC.itemsize == 72
+MARK_BLANK, MARK_EOS, MARK_FIRST, MARK_GAP = 1, 2, 4, 8   # mark bits of a voice slot (M17HIP_MARK_*)
+CALL_CLOSE_EOS, CALL_CLOSE_LSF = 1, 2
+
+
+def calls_per_channel(room):
+    """M17HIP_CALLS_PER_CHANNEL: call records of room per channel and run for a voice room of `room` slots."""
+    return int(room) // 8 + 2
+
 VITERBI_SHAPES = {0: (488, 240), 1: (296, 144), 2: (420, 206), 3: (402, 197)}
 IMPAIRMENT_DTYPE = np.dtype([("noise_sigma", "<f8"), ("tail_sigma", "<f8"), ("dc_offset", "<f8"), ("gain", "<f8")])   # m17_impairment
 CHAN_STAT_DTYPE = np.dtype([("channel", "<u4"), ("point", "<u4"), ("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4"),
@@ -54,6 +65,7 @@ EXPORTS = [
     "m17hip_upload_i16_device_async", "m17hip_input_alternate", "m17hip_demod_front", "m17hip_advice", "m17hip_replay_drops", "m17hip_frames_select",
     "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats", "m17hip_demod_reset_channels",
     "m17hip_set_channel_polarity", "m17hip_synth_tx_i16",
+    "m17hip_voice_fetch", "m17hip_voice_device", "m17hip_calls_fetch", "m17hip_voice_feed",
 ]
 ETRUNC = -6
 EOVERFLOW = -5
@@ -418,6 +430,7 @@ class Context:
         self._chk(self.lib.m17hip_set_channel_polarity(self.h, _ptr(tab), C.c_uint32(tab.size)))
 
     def run(self, flags=0, channels=None, samples=None):
+        self._fed_channels = None
         self._chk(self.lib.m17hip_demod_run(self.h, C.c_uint32(channels or self.C), C.c_uint32(samples or self.T), C.c_uint32(flags)))
 
     def frames_select(self, back):
@@ -517,6 +530,48 @@ class Context:
         r = np.ascontiguousarray(recs2d, dtype=FRAME_REC)
         n = np.ascontiguousarray(counts, dtype=np.uint32)
         self._chk(self.lib.m17hip_packets_feed(self.h, _ptr(r), _ptr(n), C.c_uint32(r.shape[0]), C.c_uint32(r.shape[1])))
+
+    # ---- the voice consumer (tune(34, room) before the runs) ---------------------------------------------------------
+    def voice(self, slots=None, channels=None):
+        """The codec2 payload planes of the selected run: (audio uint8[C, n, 16], marks uint8[C, n], counts uint32[C]).  counts[c] stream
+        records of channel c, in arrival order; marks: MARK_BLANK / MARK_EOS / MARK_FIRST / MARK_GAP.  n = `slots`, by default the largest
+        count (cut at the room).  More records than the room (M17HIP_EOVERFLOW) or than `slots` (M17HIP_ETRUNC) raise; the C entry point
+        (m17hip_voice_fetch) returns the rows as far as they go."""
+        C_ = channels or getattr(self, "_fed_channels", None) or self.C
+        counts = np.zeros(C_, dtype=np.uint32)
+        if slots is None:   # the counts first: the planes are then fetched as wide as they are used
+            code = self.lib.m17hip_voice_fetch(self.h, None, None, _ptr(counts), C.c_uint32(C_), C.c_uint32(0))
+            if code != ETRUNC:
+                self._chk(code)
+            slots = int(counts.max()) if C_ else 0
+        n = int(slots)
+        audio = np.zeros((C_, n, 16), dtype=np.uint8)
+        marks = np.zeros((C_, n), dtype=np.uint8)
+        self._chk(self.lib.m17hip_voice_fetch(self.h, _ptr(audio) if n else None, _ptr(marks) if n else None, _ptr(counts), C.c_uint32(C_), C.c_uint32(n)))
+        return audio, marks, counts
+
+    def voice_device(self):
+        """Raw DEVICE pointers of the selected run's planes, (audio, marks, counts, pitch_slots): audio[max_channels][pitch_slots][16] uint8,
+        marks[max_channels][pitch_slots] uint8, counts[max_channels] uint32 — valid until the run after the next is queued
+        (m17hip_voice_device); the payload work of that run is complete when this returns."""
+        a, m, n, pitch = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        self._chk(self.lib.m17hip_voice_device(self.h, C.byref(a), C.byref(m), C.byref(n), C.byref(pitch)))
+        return a.value or 0, m.value or 0, n.value or 0, pitch.value
+
+    def calls(self, capacity=4096):
+        """Calls the selected run closed, ordered by (channel, seq): a CALL_REC array (m17hip_calls_fetch)."""
+        out = np.zeros(capacity, dtype=CALL_REC)
+        n = C.c_uint32(0)
+        self._chk(self.lib.m17hip_calls_fetch(self.h, _ptr(out) if capacity else None, C.c_uint32(capacity), C.byref(n)))
+        return out[: min(n.value, capacity)]
+
+    def voice_feed(self, recs2d, counts):
+        """Run the voice consumer over caller-supplied frame records [channels][pitch] (counts[c] used per row); voice() and calls() then
+        return what it made of them."""
+        r = np.ascontiguousarray(recs2d, dtype=FRAME_REC)
+        n = np.ascontiguousarray(counts, dtype=np.uint32)
+        self._chk(self.lib.m17hip_voice_feed(self.h, _ptr(r), _ptr(n), C.c_uint32(r.shape[0]), C.c_uint32(r.shape[1])))
+        self._fed_channels = r.shape[0]   # (what voice() names by default until the next run)
 
     def replay_drops(self):
         """Times a channel left the limit-filter replay since the last reset (m17hip_replay_drops)."""
