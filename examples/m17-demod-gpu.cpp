@@ -1,10 +1,12 @@
-// A reference-style demodulator front end on the GPU path: 48 kSPS s16le mono on stdin, one line per frame callback on
+// A reference-style demodulator front end on the GPU path: 48 kSPS s16le mono on stdin (with -f / --float32: raw float32 in the
+// reference's units — a discriminator's output, taken as it is: a float stream, nothing rounded), one line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
 #include "m17cxx/M17Demodulator.h"
 
 #include <cstdio>
+#include <cstring>
 #include <iostream>
 
 bool display_lsf = false;  // the reference's M17FrameDecoder.h:19 expects the application to define this
@@ -27,12 +29,23 @@ static bool handle_frame(mobilinkd::M17FrameDecoder::output_buffer_t const& fram
     return true;
 }
 
-int main()
+int main(int argc, char** argv)
 {
     using namespace mobilinkd;
+    bool float_input = false;
+    for (int i = 1; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
+        else { std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32] < samples\n"); return 2; }
+    }
     M17Demodulator<float> demod(handle_frame);
     demod.diagnostics([](bool, float, float, float, bool, float, int, int, int, int) {});
-    while (std::cin) {
+    while (float_input && std::cin) {   // raw float32, native byte order: the value IS the demodulator's sample
+        float sample;
+        std::cin.read(reinterpret_cast<char*>(&sample), 4);
+        if (!std::cin) break;
+        demod(sample);
+    }
+    while (!float_input && std::cin) {
         int16_t sample;
         std::cin.read(reinterpret_cast<char*>(&sample), 2);
         if (!std::cin) break;

@@ -139,6 +139,40 @@ int m17hip_upload_i16_device_async(m17hip_ctx* ctx, const int16_t* dev, uint32_t
  * that alternate, e.g. a replayed capture).  M17HIP_ESTATE if that slab holds no input of this shape. */
 int m17hip_input_alternate(m17hip_ctx* ctx, uint32_t channels, uint32_t samples);
 
+/* ---- float32 input (ABI 607) ---------------------------------------------------------------------
+ * A second sample format for a context's input: IEEE float32 IN THE REFERENCE'S UNITS — a value is what M17Demodulator<float>::operator()
+ * receives (apps/m17-demod.cpp:489 makes it from an int16 as sample / 41067.0; a discriminator or a channeliser delivers it as it is).
+ * Nothing is scaled and nothing is rounded; under M17HIP_FLAG_INVERT / m17hip_set_channel_polarity the float is negated, which is exact (there is
+ * no -32768 wrap); values beyond +-1 are samples like any other.  Every kernel that reads the input has a float form, and records, m17_diag
+ * and the diagnostic log are bit-identical to the reference algorithm stepped on those floats (tests/test_gpu_f32_input.py); on floats of
+ * the form float(s / 41067.0) they are what the int16 path gives on s.
+ * The four entry points are the int16 ones with `const float*` (pitch in samples; the same staging-pair semantics, m17hip_input_alternate,
+ * m17hip_demod_front and m17hip_upload_wait).  The float slabs are allocated with the first float input: a context that never sees one holds
+ * nothing more than before (m17hip_input_format).
+ * THE FORMAT BELONGS TO THE STREAM: the first upload or synthesis after m17hip_ctx_create or m17hip_demod_reset fixes it (synthesis is int16);
+ * an upload of the other format, m17hip_synth_* on a float stream and a run on a slab that holds the other format return M17HIP_ESTATE, with
+ * nothing changed; m17hip_demod_reset frees the choice again.  m17hip_download_i16 / m17hip_download_f32 return M17HIP_ESTATE when the current
+ * slab holds the other format.  Everything else — m17hip_demod_run / _front, m17hip_frames_*, m17hip_diag_*, the consumers and gathers,
+ * m17hip_demod_reset_channels, the polarity table, the gate-aware front end, both carrier-detect forms, m17hip_fir_rrc150,
+ * m17hip_fir_correlator and m17hip_dcd — works on a float stream exactly as on an int16 one.
+ * m17hip_tune keys that select among kernels reading the input: 10, 13, 20 and 26 are honoured; the measurement build's keys 1, 19 (the
+ * instrumented sequential kernels) and 11 = 0 (round 4's matched filter) have no float form: a float run under them returns M17HIP_ESTATE
+ * (no int16 kernel is ever launched on float memory).
+ * Non-finite samples are legal input: a NaN or an infinity stays in its channel (whose results from there on are whatever IEEE arithmetic
+ * makes of it); the other channels and the call are not affected. */
+#define M17HIP_FORMAT_I16 1
+#define M17HIP_FORMAT_F32 2
+int m17hip_upload_f32(m17hip_ctx* ctx, const float* host, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_f32_device(m17hip_ctx* ctx, const float* dev, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_f32_async(m17hip_ctx* ctx, const float* host, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_f32_device_async(m17hip_ctx* ctx, const float* dev, uint32_t channels, uint32_t samples, size_t pitch);
+/* Read the float input slab back: out[channels][samples] (row pitch in samples), byte for byte what was uploaded. */
+int m17hip_download_f32(m17hip_ctx* ctx, float* host, uint32_t channels, uint32_t samples, size_t pitch);
+/* *stream_format: the sample format the stream is fixed to (M17HIP_FORMAT_I16 / M17HIP_FORMAT_F32; 0 = free: nothing uploaded or synthesised
+ * since the creation or the last m17hip_demod_reset).  *f32_bytes: device memory the context holds for float input (slabs and history
+ * arrays): 0 for a context that has never seen a float.  Either pointer may be NULL. */
+int m17hip_input_format(m17hip_ctx* ctx, int* stream_format, uint64_t* f32_bytes);
+
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
  * (apps/m17-demod.cpp:489 scaling; FirFilter.h:28-43; taps M17Demodulator.h:79-118).
@@ -335,7 +369,7 @@ int m17hip_synth_tx_i16(m17hip_ctx* ctx, const m17_synth_params* base, const m17
                         const uint8_t* lsf30,   /* [channels][30], NULL allowed when every kind is 0 */
                         const uint8_t* rows,    /* [n_rows][32] */
                         uint32_t n_rows, uint32_t channels, uint32_t samples, uint32_t chan0);
-/* Read the input slab back: out[channels][samples] (row pitch in samples). */
+/* Read the input slab back: out[channels][samples] (row pitch in samples).  M17HIP_ESTATE when the slab holds float input (m17hip_download_f32). */
 int m17hip_download_i16(m17hip_ctx* ctx, int16_t* host, uint32_t channels, uint32_t samples, size_t pitch);
 
 /* Payload consumer: BERT statistics — decode_bert + PRBS9::validate (apps/m17-demod.cpp:286-304,

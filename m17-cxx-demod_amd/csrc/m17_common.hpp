@@ -16,7 +16,7 @@ namespace m17 {
 namespace core = ::mobilinkd::core;
 
 // ---- slab geometry ---------------------------------------------------------------------------
-// xbuf row:  [XPRE samples carried from the previous run | T new samples]   (int16)
+// xbuf row:  [XPRE samples carried from the previous run | T new samples]   (int16, or float32 for a float stream)
 // ybuf row:  [YPRE samples carried from the previous run | T new samples]   (float)
 constexpr int XPRE = 152;  // >= 148 (FIR history), >= 120 (sliding-DFT delay line), >= 149 (history snapshot); multiple of 8
 constexpr int YPRE = 96;   // >= 80 (correlator ring); multiple of 4
@@ -32,6 +32,9 @@ using core::rrc_tap;
 // remainder, fma(r, 1/41067, q) the correctly rounded quotient — 3 instructions instead of the 10 of an IEEE division.
 // Exhaustive: tests/test_oracle_kat.py::test_scale_identities_exhaustive (host), tests/test_gpu_parity.py::test_scale_exhaustive.
 __device__ __forceinline__ float scale_sample(int s, bool invert) { return core::scale_i16(s, invert); }
+// The same for either sample format of a context's input (int16, or float32 in the reference's units: core::scale_f32).
+__device__ __forceinline__ float scale_sample(int16_t s, bool invert) { return core::scale_i16((int)s, invert); }
+__device__ __forceinline__ float scale_sample(float v, bool invert) { return core::scale_f32(v, invert); }
 
 // Sync words M17Demodulator.h:154-157: preamble, LSF(/stream), packet(/BERT), EOT — symbol signs (x3).
 // The same words as sign masks (bit i set = symbol i is -3): (float)(-3) * x == -(3.0f * x) exactly, and r + (-p) is what

@@ -1,5 +1,7 @@
 // The body of dcd_kernel<INVERT> and dcd_mixed_kernel (m17_frontend_kernels.hpp): included into both, inside the kernel's braces.
-// The including kernel names: INVERT, MIXED (constants); pol (MIXED only: the polarity table; a channel's polarity is its entry XOR bit 0 of flags).
+// The including kernel names: INVERT, MIXED (constants); pol (MIXED only: the polarity table; a channel's polarity is its entry XOR bit 0 of flags); XT, the
+// sample type of the input slab: int16_t, or float (a float stream: nothing is scaled, negation is a sign-bit XOR, under the lane's mask in the mixed form).
+    constexpr bool F32 = std::is_same<XT, float>::value;
     __shared__ __attribute__((aligned(16))) float dl_all[DCD_WPB][DCD_CPW][DCD_PITCH];
     float (*dl)[DCD_PITCH] = dl_all[threadIdx.x >> 6];
     const int lane = threadIdx.x & 63;
@@ -7,7 +9,7 @@
     uint32_t c = (blockIdx.x * DCD_WPB + (threadIdx.x >> 6)) * DCD_CPW + g;
     const bool live = c < C;   // lanes beyond the last channel shadow it and never store
     if (!live) c = C - 1;
-    const int16_t* xr = x + (size_t)c * xpitch + XPRE;
+    const XT* xr = x + (size_t)c * xpitch + XPRE;
     DcdState* st = state + c;
     // MIXED: the channels' polarities as a LANE MASK in a scalar pair; the per-lane mask (0 / -1) is formed from it where samples are converted — a
     // register kept across the recurrence cost the kernel its seventh wave per SIMD (74 VGPRs against 72)
@@ -54,10 +56,17 @@
     };
     auto one_sample = [&](uint32_t t) {  // generic path: head / tail of a run; x[n] and x[n-120] are one packed pair
         if (phase == 0) tick_begin();
+        if constexpr (F32) {
+            int sm = INVERT ? (int)0x80000000u : 0;
+            if constexpr (MIXED) sm = lane_mask() & (int)0x80000000u;
+            const float fn = __int_as_float(__float_as_int(xr[t]) ^ sm), fd = __int_as_float(__float_as_int(xr[(int64_t)t - 120]) ^ sm);
+            dcd_step(s, fn - fd);
+        } else {
         int xn = (int)xr[t], xd = (int)xr[(int64_t)t - 120];
         if constexpr (MIXED) { const int m = lane_mask(); xn = pol_i16(xn, m); xd = pol_i16(xd, m); }
         const v2f f = dcd_scale2<INVERT>(xn, xd);
         dcd_step(s, f.x - f.y);
+        }
         if (++phase == TICK) tick_end();
     };
 
@@ -66,11 +75,13 @@
     // whole blocks: lane (g, bin) converts samples [HALF bin, HALF bin + HALF) of its channel's block
     if (t + DCD_BLK <= T) {
         constexpr int HALF = DCD_BLK / 2, NQ = HALF / 8;
-        int4 pa[NQ], pb[NQ];
+        constexpr int NV = F32 ? 2 * NQ : NQ;   // 16-byte registers per half block
+        int4 pa[NV], pb[NV];
         auto issue = [&](uint32_t t0) {
+            constexpr int SPV = F32 ? 4 : 8;    // samples per 16-byte register
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int16_t* p = xr + (size_t)t0 + HALF * bin + 8 * q;
+            for (int q = 0; q < NV; ++q) {
+                const XT* p = xr + (size_t)t0 + HALF * bin + SPV * q;
                 pa[q] = *reinterpret_cast<const int4*>(p);
                 pb[q] = *reinterpret_cast<const int4*>(p - 120);
             }
@@ -82,6 +93,15 @@
             float* wrow = dl[g] + HALF * bin;
             int m = 0;
             if constexpr (MIXED) m = lane_mask();
+            if constexpr (F32) {
+                const int sm = MIXED ? (m & (int)0x80000000u) : (INVERT ? (int)0x80000000u : 0);
+                auto neg = [&](int w) { return __int_as_float(w ^ sm); };
+#pragma unroll
+                for (int q = 0; q < NV; ++q) {
+                    const int4 a = pa[q], d = pb[q];
+                    *reinterpret_cast<float4*>(wrow + 4 * q) = make_float4(neg(a.x) - neg(d.x), neg(a.y) - neg(d.y), neg(a.z) - neg(d.z), neg(a.w) - neg(d.w));
+                }
+            } else
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 int4 a = pa[q], d = pb[q];

@@ -1,5 +1,7 @@
 // The body of dcd_pipe_kernel<INVERT> and dcd_pipe_mixed_kernel (m17_frontend_kernels.hpp): included into both, inside the kernel's braces.
-// The including kernel names: INVERT, MIXED (constants); pol (MIXED only: the polarity table; the producer's per-lane mask is its entry XOR bit 0 of flags).
+// The including kernel names: INVERT, MIXED (constants); pol (MIXED only: the polarity table; the producer's per-lane mask is its entry XOR bit 0 of flags);
+// XT, the sample type of the input slab: int16_t, or float (a float stream: nothing is scaled, negation is a sign-bit XOR, under the lane's mask when MIXED).
+    constexpr bool F32 = std::is_same<XT, float>::value;
     __shared__ __attribute__((aligned(16))) float dbuf[2][DP_CPB][DP_DPITCH];
     __shared__ __attribute__((aligned(16))) float4 xb[2][DP_BLK / 2][64];
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -8,7 +10,7 @@
     uint32_t c = blockIdx.x * DP_CPB + g;
     const bool live = c < C;   // lanes beyond the last channel shadow it and never store
     if (!live) c = C - 1;
-    const int16_t* xr = x + (size_t)c * xpitch + XPRE;
+    const XT* xr = x + (size_t)c * xpitch + XPRE;
     DcdState* st = state + c;
     const uint32_t NB = T / DP_BLK;       // blocks
     // every role runs NI hand-overs: NB + 2 for pipeline fill and drain, rounded up to a multiple of DP_PF so that the
@@ -21,13 +23,14 @@
         // same loads — past the end the last block again — so the wait for a slot leaves the other slots in flight).
         int m = 0;             // MIXED: this lane's channel's polarity mask
         if constexpr (MIXED) m = pol_mask(pol, c, flags);
-        int4 pa[DP_PF][2], pb[DP_PF][2];
+        constexpr int NV = F32 ? 4 : 2, SPV = F32 ? 4 : 8;   // 16-byte registers per sixteen samples; samples per register
+        int4 pa[DP_PF][NV], pb[DP_PF][NV];
         auto issue = [&](uint32_t b, int slot) {   // lane (g, bin) converts samples [16 bin, 16 bin + 16) of its channel's block
-            const int16_t* p = xr + (size_t)min(b, NB - 1u) * DP_BLK + 16 * bin;
+            const XT* p = xr + (size_t)min(b, NB - 1u) * DP_BLK + 16 * bin;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                pa[slot][q] = *reinterpret_cast<const int4*>(p + 8 * q);
-                pb[slot][q] = *reinterpret_cast<const int4*>(p + 8 * q - 120);
+            for (int q = 0; q < NV; ++q) {
+                pa[slot][q] = *reinterpret_cast<const int4*>(p + SPV * q);
+                pb[slot][q] = *reinterpret_cast<const int4*>(p + SPV * q - 120);
             }
         };
 #pragma unroll
@@ -40,6 +43,15 @@
                 const uint32_t i = i0 + (uint32_t)slot;
                 {
                     float4 o[4];
+                    if constexpr (F32) {
+                        const int sm = MIXED ? (m & (int)0x80000000u) : (INVERT ? (int)0x80000000u : 0);
+                        auto neg = [&](int w) { return __int_as_float(w ^ sm); };
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int4 a = pa[slot][q], d = pb[slot][q];
+                            o[q] = make_float4(neg(a.x) - neg(d.x), neg(a.y) - neg(d.y), neg(a.z) - neg(d.z), neg(a.w) - neg(d.w));
+                        }
+                    } else
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         int4 a = pa[slot][q], d = pb[slot][q];

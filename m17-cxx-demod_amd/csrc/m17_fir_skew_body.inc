@@ -1,5 +1,7 @@
 // The body of fir_rrc150_skew_kernel<INVERT> and fir_rrc150_skew_mixed_kernel (m17_frontend_kernels.hpp): included into both, inside the kernel's braces.
-// The including kernel names: INVERT, MIXED (constants); pol, flip (MIXED only: the polarity table and bit 0 of the call's flags).
+// The including kernel names: INVERT, MIXED (constants); pol, flip (MIXED only: the polarity table and bit 0 of the call's flags); XT, the sample type of
+// the input slab: int16_t, or float (a float stream: samples in the reference's units, 32 bytes per eight-sample chunk, staged as they are, negated by a
+// sign-bit XOR — under the item's mask in the mixed form; no dcd_scale2).
     // first_needed (may be null): per channel, the first sample of this slab the carrier can be on for (gate_forecast_kernel): tiles that end
     // before it are skipped
     __shared__ __attribute__((aligned(16))) float win[FS_LDS_FLOATS];
@@ -7,18 +9,43 @@
     typedef int v4i __attribute__((ext_vector_type(4)));
     constexpr int NCH = (FS_WIN + 7) / 8;             // 531 chunks of eight samples
     constexpr int CPT = (NCH + FS_THREADS - 1) / FS_THREADS;   // 3 per thread (the third for 19 threads only)
-    v4i pre[CPT];
+    constexpr bool F32 = std::is_same<XT, float>::value;
+    // float rows: the two whole chunks of a lane are 32 bytes each; the last 152 samples of the window (chunks 512 .. 530, which the int16 form gives
+    // to nineteen lanes as a third chunk) go one sample per lane — 17 registers in flight instead of 24, which the 128 of four workgroups per CU do not hold
+    constexpr int FS_LAST = FS_WIN - 16 * FS_THREADS; // 152
+    static_assert(FS_LAST > 0 && FS_LAST <= FS_THREADS && CPT == 3, "the float form's split of the window");
+    v4i pre[F32 ? 4 : CPT];
+    int pre_last = 0;
     int m = 0;                                        // MIXED: the polarity mask of the item being staged
     // the int16 input of an item: chunk k <-> window samples 8k .. 8k + 7 <-> times t0 - 152 + 8k ...; beyond the slab's end: zero
     auto fetch = [&](uint32_t item) {
         const uint32_t c = item / tiles, tile = item - c * tiles;
-        const int16_t* xr = x + (size_t)c * xpitch + XPRE;
+        const XT* xr = x + (size_t)c * xpitch + XPRE;
         const int64_t w0 = (int64_t)tile * FS_TILE - FS_WOFF;
 #pragma unroll
         for (int q = 0; q < CPT; ++q) {
             const int k = tid + q * FS_THREADS;
             const int64_t t = w0 + 8 * k;
             v4i v = {0, 0, 0, 0};
+            if constexpr (F32) {
+                if (q < 2) {                          // (k < NCH for both)
+                    v4i v2 = {0, 0, 0, 0};
+                    if (t + 8 <= (int64_t)T) {
+                        v = *reinterpret_cast<const v4i*>(xr + t);
+                        v2 = *reinterpret_cast<const v4i*>(xr + t + 4);
+                    } else {                          // the slab ends inside this chunk (once per channel at most): sample by sample
+                        uint32_t w[8];
+#pragma unroll
+                        for (int h = 0; h < 8; ++h) w[h] = t + h < (int64_t)T ? __float_as_uint(xr[t + h]) : 0u;
+                        v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+                        v2 = v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+                    }
+                    pre[2 * q] = v; pre[2 * q + 1] = v2;
+                } else {
+                    const int64_t tl = w0 + 16 * FS_THREADS + tid;
+                    pre_last = (tid < FS_LAST && tl < (int64_t)T) ? (int)__float_as_uint(xr[tl]) : 0;
+                }
+            } else {
             if (k < NCH) {
                 if (t + 8 <= (int64_t)T) v = *reinterpret_cast<const v4i*>(xr + t);
                 else {                                // the slab ends inside this chunk (once per channel at most): sample by sample
@@ -30,14 +57,30 @@
                 }
             }
             pre[q] = v;
+            }
         }
     };
     auto stage = [&] {
 #pragma unroll
         for (int q = 0; q < CPT; ++q) {
             const int k = tid + q * FS_THREADS;
+            int sm = INVERT ? (int)0x80000000u : 0;   // (float rows) the sign bit where the sample is negated
+            if constexpr (F32 && MIXED) sm = m & (int)0x80000000u;
+            if constexpr (F32) if (q == 2) {          // the window's last 152 samples, one per lane
+                const int j = 16 * FS_THREADS + tid;
+                if (tid < FS_LAST) win[FS_PADF + j + 2 * (j >> 4)] = __int_as_float(pre_last ^ sm);
+                continue;
+            }
             if (k < NCH) {
                 float* dst = win + FS_PADF + 8 * k + 2 * (k >> 1);   // sample j = 8k at word j + 2 (j >> 4)
+                if constexpr (F32) {
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) {
+                        const v4i r = pre[2 * q + (h >> 1)];
+                        const int a = ((h & 1) ? r[2] : r[0]) ^ sm, b = ((h & 1) ? r[3] : r[1]) ^ sm;
+                        *reinterpret_cast<v2f*>(dst + 2 * h) = v2f{__int_as_float(a), __int_as_float(b)};
+                    }
+                } else
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     int w = pre[q][h];

@@ -254,6 +254,7 @@ __global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_kernel(const in
 {
     constexpr bool MIXED = false;
     const uint32_t* pol = nullptr; const uint32_t flip = 0u;
+    typedef int16_t XT;
 #include "m17_fir_skew_body.inc"
 }
 // the same with the polarity per channel: pol[c] XOR flip (bit 0)
@@ -262,6 +263,27 @@ __global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_mixed_kernel(co
                                                                              const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
 {
     constexpr bool INVERT = false, MIXED = true;
+    typedef int16_t XT;
+#include "m17_fir_skew_body.inc"
+}
+// The float forms (a float stream, m17hip_upload_f32: samples in the reference's units): the same text over float rows.  The input of an item in flight is
+// 24 registers instead of 12; still four workgroups per CU without scratch (NOTES 2026-10-18).
+template <bool INVERT>
+__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_f32_kernel(const float* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
+                                                                           uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
+                                                                           const uint32_t* __restrict__ first_needed)
+{
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr; const uint32_t flip = 0u;
+    typedef float XT;
+#include "m17_fir_skew_body.inc"
+}
+__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
+                                                                                 uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
+                                                                                 const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
+{
+    constexpr bool INVERT = false, MIXED = true;
+    typedef float XT;
 #include "m17_fir_skew_body.inc"
 }
 
@@ -489,6 +511,7 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __rest
 {
     constexpr bool MIXED = false;
     const uint32_t* pol = nullptr;
+    typedef int16_t XT;
 #include "m17_dcd_body.inc"
 }
 // the same with the polarity per channel (one channel per lane pair: a per-lane mask): pol[c] XOR bit 0 of flags
@@ -497,6 +520,26 @@ __global__ __launch_bounds__(64 * DCD_WPB) void dcd_mixed_kernel(const int16_t* 
                                                        uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
 {
     constexpr bool INVERT = false, MIXED = true;
+    typedef int16_t XT;
+#include "m17_dcd_body.inc"
+}
+// the float forms (a float stream): the same text over float rows — nothing is scaled, the recurrence is the same
+template <bool INVERT>
+__global__ __launch_bounds__(64 * DCD_WPB) void dcd_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                     float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                     uint64_t pos0, DcdCoef k, uint32_t flags)
+{
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr;
+    typedef float XT;
+#include "m17_dcd_body.inc"
+}
+__global__ __launch_bounds__(64 * DCD_WPB) void dcd_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                           float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                           uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
+{
+    constexpr bool INVERT = false, MIXED = true;
+    typedef float XT;
 #include "m17_dcd_body.inc"
 }
 
@@ -534,6 +577,7 @@ __global__ __launch_bounds__(256) void dcd_pipe_kernel(const int16_t* __restrict
 {
     constexpr bool MIXED = false;
     const uint32_t* pol = nullptr;
+    typedef int16_t XT;
 #include "m17_dcd_pipe_body.inc"
 }
 __global__ __launch_bounds__(256) void dcd_pipe_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
@@ -541,6 +585,26 @@ __global__ __launch_bounds__(256) void dcd_pipe_mixed_kernel(const int16_t* __re
                                                              uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
 {
     constexpr bool INVERT = false, MIXED = true;
+    typedef int16_t XT;
+#include "m17_dcd_pipe_body.inc"
+}
+// the float forms (a float stream)
+template <bool INVERT>
+__global__ __launch_bounds__(256) void dcd_pipe_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                           float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                           uint64_t pos0, DcdCoef k, uint32_t flags)
+{
+    constexpr bool MIXED = false;
+    const uint32_t* pol = nullptr;
+    typedef float XT;
+#include "m17_dcd_pipe_body.inc"
+}
+__global__ __launch_bounds__(256) void dcd_pipe_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+                                                                 float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
+                                                                 uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
+{
+    constexpr bool INVERT = false, MIXED = true;
+    typedef float XT;
 #include "m17_dcd_pipe_body.inc"
 }
 

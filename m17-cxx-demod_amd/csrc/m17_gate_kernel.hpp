@@ -65,6 +65,9 @@ struct GateParams {
     uint32_t nblk;            // workgroups of the replay itself; the ones behind them fold deferred EVM operations (m17_state.hpp, evm_fold_pass)
     EvParams ev;
     const uint32_t* pol;      // optional [C]: the channels' polarity entries, 0 / 1 (m17hip_set_channel_polarity), XOR flags bit 0
+    // a float stream (limit_track_f32_kernel only; nullptr for int16): x names float rows, and the patch window's snapshots are floats
+    const float* hist_f;      // [C][HISTF_PITCH] SeqState::hist's twin
+    const float* bnd_hist_f;  // [C][HISTF_PITCH] the twin of bnd's Boundary::hist
 };
 
 constexpr int GT_LPC = 4;             // lanes per channel (cooperative loads / stores; the recurrence runs on the first of them)
@@ -81,6 +84,8 @@ constexpr int GT_LDS_FLOATS = GT_CPW * GT_ROW + GT_CPW * 148 + 298;   // 23.2 KB
 // One pass over the segment P names for the sixteen channels of a wave.  Per lane: `valid` = the channel takes part (stores, exports its
 // end state); a lane that does not idles.  `from_chain` (wave-uniform) = the pass starts from the replay's own state, else from K5's:
 // P.state, or the boundary record `bnd_base[c]` (the redo).  `state_only`: no history value is stored (the redo).
+// XT: the sample type of the input slab (int16_t, or float for a float stream): only the patch window reads raw samples.
+template <typename XT>
 __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state_only, uint32_t c, bool valid, bool from_chain, const Boundary* bnd_base,
                                                  float* lds_base)
 {
@@ -102,7 +107,6 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
     // replay's end state is wanted, hbuf is left alone (K5 is writing those very rows)
     const bool store = !state_only;
     const SeqState* gs = P.state + c;
-    const int16_t* xr = P.x + (size_t)c * P.xpitch + XPRE + t0;
     const float* yr = P.y + (size_t)c * P.ypitch + YPRE + t0;
     float* hr = P.h + (size_t)c * P.ypitch + YPRE + t0;
     const float* tab = P.dcd_table + (size_t)c * P.ticks_cap * 12;
@@ -255,15 +259,17 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
                 const bool eir = __shfl((int)end_in_run, src);
                 const int32_t et = __shfl(end_t, src);
                 const bool inv_cc = __shfl((int)invert, src) != 0;   // the whole wave works for channel cc here: ITS polarity, not each lane's own channel's
-                const int16_t* xrc = P.x + (size_t)cc * P.xpitch + XPRE + t0;
+                const XT* xrc = reinterpret_cast<const XT*>(P.x) + (size_t)cc * P.xpitch + XPRE + t0;
                 const Boundary* bsrc = (!from_chain && bnd_base) ? bnd_base + cc : nullptr;   // (both wave-uniform)
-                const int16_t* hist = bsrc ? bsrc->hist : P.state[cc].hist;
+                const XT* hist;
+                if constexpr (std::is_same<XT, float>::value) hist = (bsrc ? P.bnd_hist_f : P.hist_f) + (size_t)cc * HISTF_PITCH;
+                else hist = bsrc ? bsrc->hist : P.state[cc].hist;
                 for (int k = lane; k < 149; k += 64) {
-                    const int sv = eir ? (int)xrc[(int64_t)et - 148 + k] : (int)hist[k];
+                    const XT sv = eir ? xrc[(int64_t)et - 148 + k] : hist[k];
                     pw[k] = scale_sample(sv, inv_cc);
                 }
                 for (int k = lane; k < 148; k += 64)
-                    if ((int64_t)rs + k < (int64_t)segT) pw[149 + k] = scale_sample((int)xrc[(int64_t)rs + k], inv_cc);
+                    if ((int64_t)rs + k < (int64_t)segT) pw[149 + k] = scale_sample(xrc[(int64_t)rs + k], inv_cc);
                 lds_sync();
                 for (int j = rp + lane; j < 148; j += 64) {
                     if ((int64_t)rs + j >= (int64_t)segT) break;
@@ -379,7 +385,8 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
 }
 
 // (at most 128 VGPRs: a wave of it has to fit into what four K5 waves leave of a SIMD)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_kernel(GateParams P)
+template <typename XT>
+__device__ __forceinline__ void limit_track_body(const GateParams& P)
 {
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     if (blockIdx.x >= P.nblk) {   // (a launch that runs beside K5 takes an earlier segment's EVM operations along: 64 channels per block)
@@ -397,8 +404,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     }
     // (dynamic LDS, GT_LDS_FLOATS floats: with a static allocation the compiler sizes the register budget for the LDS-limited occupancy and
     //  ignores the waves-per-SIMD attribute above)
-    limit_track_pass(P, (P.flags & 2u) != 0, c, valid, P.chain_in != nullptr, P.only ? P.bnd : nullptr, lds_dyn);
+    limit_track_pass<XT>(P, (P.flags & 2u) != 0, c, valid, P.chain_in != nullptr, P.only ? P.bnd : nullptr, lds_dyn);
 }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_kernel(GateParams P) { limit_track_body<int16_t>(P); }
+// a float stream: P.x names float rows, P.hist_f / P.bnd_hist_f the snapshots
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_f32_kernel(GateParams P) { limit_track_body<float>(P); }
 
 // =====================================================================================================
 // Gate-aware front end (m17hip_tune key 26): which samples of segment k + 2 can the carrier be ON for?

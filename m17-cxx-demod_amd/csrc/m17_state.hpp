@@ -100,8 +100,11 @@ struct SeqState {
     float sw_samples[4][10];
     uint32_t llr[92];
     uint32_t lsf[8];
-    int16_t hist[150];          // last 149 gated FIR inputs (raw int16) at the end of the previous run
+    int16_t hist[150];          // last 149 gated FIR inputs (raw int16) at the end of the previous run (a float stream keeps them in SeqParams::hist_f)
 };
+// A float stream (m17hip_upload_f32) keeps the 149 raw samples of SeqState::hist and of Boundary::hist in side arrays of floats, a row of
+// HISTF_PITCH per channel: the structs stay as they are, and a context that never sees a float allocates neither array.
+constexpr int HISTF_PITCH = 152;
 
 // What a replay needs of a channel's state at a segment boundary, written by K5 where the channel left the replay in the segment that ends
 // there (a copy: the replay that takes the channel up again runs beside K5 of the next segment, which goes on changing the state itself)
@@ -158,6 +161,9 @@ struct SeqParams {
     uint32_t* ev_cursor_out;  // [C] the channel's operation cursor at the end of this segment
     GateTruth* truth_out;     // optional [C]: the gate state at the end of this segment (gate-aware front end); overflow[3] counts the channels whose carrier is off there
     const uint32_t* pol;      // optional [C]: the channels' polarity entries, 0 / 1 (m17hip_set_channel_polarity), XOR flags bit 0; nullptr: flags bit 0 for every channel
+    // a float stream (the float instantiations only; nullptr for int16): x names float rows, and the raw-sample histories live here
+    float* hist_f;            // [C][HISTF_PITCH] SeqState::hist's twin
+    float* bnd_hist_f;        // [C][HISTF_PITCH] the twin of bnd_out's Boundary::hist
 };
 
 // ---- the running EVM, deferred ------------------------------------------------------------------------------------------------------
@@ -406,7 +412,8 @@ __device__ __forceinline__ void nf_fire_diag(M17_LDS Cold* cd, uint32_t dcd_on, 
     }
 }
 // the 149 raw samples that end with sample te: the FIR history a later gated run splices in front of its own samples (lane-parallel)
-__device__ __forceinline__ void nf_snapshot_hist(int16_t* hist, const int16_t* xr, uint32_t te, int lane)
+template <typename XT>
+__device__ __forceinline__ void nf_snapshot_hist(XT* hist, const XT* xr, uint32_t te, int lane)
 {
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
     for (int k = lane; k < 149; k += 64) hist[k] = xr[(int64_t)te - 148 + k];

@@ -240,6 +240,24 @@ struct m17hip_ctx {
             return hipSuccess;
         }
     } slab[2];                        // [1]: allocated the first time input is staged (stage_prepare)
+    // A FLOAT STREAM (m17hip_upload_f32): its input rows are float32 in the reference's units, in a pair of their own — same pitch in samples, same
+    // XPRE prefix, named by the same slot as the int16 pair.  Allocated lazily: a slab with the first float input that goes to its slot, and with the
+    // first of them the float twins of the 149-sample histories (SeqState::hist -> hist_f; Boundary::hist -> bnd_hist_f, by segment parity).
+    // A context that never sees a float holds none of it (m17hip_input_format reports the bytes) and its launches are what they always were.
+    struct FloatSlab {
+        DevBuf<float> x;
+        size_t bytes() const { return x.size() * sizeof(float); }
+    } fslab[2];
+    DevBuf<float> hist_f, bnd_hist_f; // [maxC][HISTF_PITCH]; [2][maxC][HISTF_PITCH]
+    // The sample format belongs to the stream: the first input after the creation or m17hip_demod_reset fixes it (synthesis is int16), input of the
+    // other format is refused until the next reset.  Each slab pair remembers the format of the input it holds; a run takes its slab's.
+    int stream_fmt = 0;               // M17HIP_FORMAT_*; 0: free
+    int slab_fmt[2] = {0, 0};
+    bool f32_now() const { return slab_fmt[slot] == M17HIP_FORMAT_F32; }
+    const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
+    {
+        return f32_now() ? reinterpret_cast<const int16_t*>(fslab[slot].x + t0) : slab[slot].x + t0;
+    }
     Slab& now() { return slab[slot]; }         // the current / latest run's
     Slab& other() { return slab[slot ^ 1]; }   // the staging pair (the run before the latest one's)
     bool foreign_streams[4] = {false, false, false, false};   // tools build, keys 40-43: side / side2 / side3 / copy belong to the experiment, not to the context
@@ -646,6 +664,15 @@ __global__ void seq_reset_list_kernel(const uint32_t* list, uint32_t n, SeqState
     fresh_demod_state(st, es, list[i], pos);
 }
 
+// the same for the rows of a float stream
+__global__ void front_reset_list_xf32_kernel(const uint32_t* list, uint32_t n, float* x, size_t xpitch, DcdState* ds)
+{
+    if (blockIdx.x >= n) return;
+    const uint32_t c = list[blockIdx.x];
+    if (x) for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = 0.f;
+    if (ds && threadIdx.x == 0) fresh_dcd_state(ds, c);
+}
+
 __global__ void zero_prefix_kernel(int16_t* x, size_t xpitch, float* y, size_t ypitch, uint32_t C)
 {
     const uint32_t c = blockIdx.x;
@@ -666,6 +693,42 @@ __global__ void carry_tail_kernel(int16_t* x, size_t xpitch, float* y, size_t yp
     __syncthreads();
     for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xr[k] = xs[k];
     for (int k = threadIdx.x; k < YPRE; k += blockDim.x) yr[k] = ys[k];
+}
+
+// The input rows of a float stream: the same helpers over float samples (pitch and prefix in samples, as for int16).
+__global__ void zero_prefix_xf32_kernel(float* x, size_t xpitch)
+{
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)blockIdx.x * xpitch + k] = 0.f;
+}
+__global__ void carry_tail_xf32_kernel(float* x, size_t xpitch, uint32_t T)
+{
+    __shared__ float xs[XPRE];
+    float* xr = x + (size_t)blockIdx.x * xpitch;
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xs[k] = xr[(size_t)T + k];
+    __syncthreads();
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xr[k] = xs[k];
+}
+__global__ void copy_prefix_xf32_kernel(const float* src, float* dst, size_t xpitch)
+{
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + k];
+}
+__global__ void copy_tail_xf32_kernel(const float* src, float* dst, size_t xpitch, uint32_t T)
+{
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + T + k];
+}
+// rows of T floats (pitch spitch) into the data region of the slab's rows: four samples per lane
+__global__ void copy_rows_xf32_kernel(const float* src, size_t spitch, float* dst, size_t dpitch, uint32_t T)
+{
+    const uint32_t c = blockIdx.y;
+    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (t >= T) return;
+    const float* s = src + (size_t)c * spitch + t;
+    float* d = dst + (size_t)c * dpitch + XPRE + t;
+    if (t + 4 <= T && (((uintptr_t)s) & 15) == 0) {
+        *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
+    } else {
+        for (uint32_t q = 0; q < 4 && t + q < T; ++q) d[q] = s[q];
+    }
 }
 
 // PRBS9 receiver state per channel (Util.h:320-441), carried between runs
@@ -932,6 +995,7 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
 {
     TimedK tm(c, KT_FIR);
 #ifdef M17_TOOLS
+    if (c->fir_form == 0 && c->f32_now()) return M17HIP_ESTATE;   // (round 4's kernel reads int16 rows only: a float stream is refused, m17hip_tune key 11)
     if (c->fir_form == 0 && pol) return M17HIP_EINVAL;   // (round 4's kernel has no per-channel form: refused, not computed under the flag alone)
     if (c->fir_form == 0) {   // round 4's kernel: the measurement build keeps it for same-box comparisons (tools/k1_forms.py, the clk_k1 pass of tools/profile_round.sh)
         dim3 grid((T + FIR_TILE - 1) / FIR_TILE, C);
@@ -946,12 +1010,20 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
         const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
-        const auto go = [&](auto kernel, auto... mixed) {
-            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
+        const auto go = [&](auto kernel, const auto* xin, auto... mixed) {
+            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, xin + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
         };
-        if (pol) go(fir_rrc150_skew_mixed_kernel, pol, flags & 1u);
-        else if (flags & 1u) go(fir_rrc150_skew_kernel<true>);
-        else go(fir_rrc150_skew_kernel<false>);
+        if (c->f32_now()) {   // a float stream: the float forms over the float pair
+            const float* xf = c->fslab[c->slot].x;
+            if (pol) go(fir_rrc150_skew_mixed_f32_kernel, xf, pol, flags & 1u);
+            else if (flags & 1u) go(fir_rrc150_skew_f32_kernel<true>, xf);
+            else go(fir_rrc150_skew_f32_kernel<false>, xf);
+        } else {
+            const int16_t* xi = c->now().x;
+            if (pol) go(fir_rrc150_skew_mixed_kernel, xi, pol, flags & 1u);
+            else if (flags & 1u) go(fir_rrc150_skew_kernel<true>, xi);
+            else go(fir_rrc150_skew_kernel<false>, xi);
+        }
     }
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
@@ -965,16 +1037,28 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
     const bool one_wave = !latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK;
     const dim3 grid(one_wave ? (C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB) : (C + DP_CPB - 1) / DP_CPB), block(one_wave ? 64 * DCD_WPB : 256);
-    const auto go = [&](auto kernel, auto... mixed) {   // (both forms take the same arguments)
-        tm.launch(kernel, grid, block, 0, st, c->now().x + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
+    const auto go = [&](auto kernel, const auto* xin, auto... mixed) {   // (both forms take the same arguments)
+        tm.launch(kernel, grid, block, 0, st, xin + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
     };
-    if (one_wave) {
-        if (pol) go(dcd_mixed_kernel, pol);
-        else if (flags & 1u) go(dcd_kernel<true>);
-        else go(dcd_kernel<false>);
-    } else if (pol) go(dcd_pipe_mixed_kernel, pol);
-    else if (flags & 1u) go(dcd_pipe_kernel<true>);
-    else go(dcd_pipe_kernel<false>);
+    if (c->f32_now()) {   // a float stream: the float forms over the float pair
+        const float* xf = c->fslab[c->slot].x;
+        if (one_wave) {
+            if (pol) go(dcd_mixed_f32_kernel, xf, pol);
+            else if (flags & 1u) go(dcd_f32_kernel<true>, xf);
+            else go(dcd_f32_kernel<false>, xf);
+        } else if (pol) go(dcd_pipe_mixed_f32_kernel, xf, pol);
+        else if (flags & 1u) go(dcd_pipe_f32_kernel<true>, xf);
+        else go(dcd_pipe_f32_kernel<false>, xf);
+    } else {
+        const int16_t* xi = c->now().x;
+        if (one_wave) {
+            if (pol) go(dcd_mixed_kernel, xi, pol);
+            else if (flags & 1u) go(dcd_kernel<true>, xi);
+            else go(dcd_kernel<false>, xi);
+        } else if (pol) go(dcd_pipe_mixed_kernel, xi, pol);
+        else if (flags & 1u) go(dcd_pipe_kernel<true>, xi);
+        else go(dcd_pipe_kernel<false>, xi);
+    }
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1052,7 +1136,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 606; }
+int m17hip_version(void) { return 607; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1265,20 +1349,59 @@ static int stage_prepare(m17hip_ctx* c)
     return alloc_code(c, s.x.alloc((size_t)c->maxC * c->xpitch));   // last: its presence says "all of it is there"
 }
 
-// Where an in-place producer (m17hip_upload_i16, m17hip_upload_i16_device, m17hip_synth_i16) writes: the current input slab on the
-// main stream, or — tuning knob 16 — the STAGING slab on the copy stream, as soon as the run before the latest one has released it.
-struct InputTarget { int16_t* x = nullptr; hipStream_t st = nullptr; bool stage = false; };
-static int input_target(m17hip_ctx* c, InputTarget& t)
+extern "C++" {   // (templates)
+// ---- the sample format of the input (int16, or float32 in the reference's units) ---------------------------------------------------------
+template <typename XT> constexpr int fmt_of() { return std::is_same<XT, float>::value ? M17HIP_FORMAT_F32 : M17HIP_FORMAT_I16; }
+// the input rows of slab pair `slot` in that format (nullptr: not allocated)
+template <typename XT> static XT* slab_x(m17hip_ctx* c, int slot)
 {
-    if (!c->stage_inputs) { t.x = c->now().x; t.st = c->stream; t.stage = false; return M17HIP_OK; }
-    const int r = stage_prepare(c);
-    if (r) return r;
-    HIPCHK(c, c->other().wait_free(c->copy));
-    t.x = c->other().x; t.st = c->copy; t.stage = true;
+    if constexpr (std::is_same<XT, float>::value) return c->fslab[slot].x;
+    else return c->slab[slot].x;
+}
+// The float pair's slab of `slot` and the float history arrays, the first time they are needed.  A fresh slab's prefix is zeroed on `st` (the stream
+// its input is written on): what a stream that begins in it finds where an int16 stream finds the prefix m17hip_demod_reset cleared.
+static int ensure_f32(m17hip_ctx* c, int slot, hipStream_t st)
+{
+    int r;
+    if (!c->hist_f || !c->bnd_hist_f) {
+        if (!c->hist_f && (r = alloc_code(c, c->hist_f.alloc((size_t)c->maxC * HISTF_PITCH)))) return r;
+        if (!c->bnd_hist_f && (r = alloc_code(c, c->bnd_hist_f.alloc(2 * (size_t)c->maxC * HISTF_PITCH)))) return r;
+        HIPCHK(c, hipMemsetAsync(c->hist_f, 0, c->hist_f.size() * sizeof(float), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->bnd_hist_f, 0, c->bnd_hist_f.size() * sizeof(float), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (once per context: the replay reads them on a stream of its own)
+    }
+    if (!c->fslab[slot].x) {
+        if ((r = alloc_code(c, c->fslab[slot].x.alloc((size_t)c->maxC * c->xpitch)))) return r;
+        HIPCHK(c, hipMemset2DAsync(c->fslab[slot].x, c->xpitch * sizeof(float), 0, XPRE * sizeof(float), c->maxC, st));
+    }
     return M17HIP_OK;
 }
-static void input_done(m17hip_ctx* c, const InputTarget& t, uint32_t C, uint32_t T)
+// input of format `fmt` is about to be written: refused on a stream of the other format
+static int claim_format(const m17hip_ctx* c, int fmt) { return (c->stream_fmt && c->stream_fmt != fmt) ? M17HIP_ESTATE : M17HIP_OK; }
+
+// Where an in-place producer (m17hip_upload_i16 / _f32, m17hip_upload_i16_device / _f32_device, m17hip_synth_i16) writes: the current input slab on the
+// main stream, or — tuning knob 16 — the STAGING slab on the copy stream, as soon as the run before the latest one has released it.
+template <typename XT> struct InputTargetT { XT* x = nullptr; hipStream_t st = nullptr; bool stage = false; int slot = 0; };
+using InputTarget = InputTargetT<int16_t>;
+template <typename XT>
+static int input_target(m17hip_ctx* c, InputTargetT<XT>& t)
 {
+    int r;
+    if ((r = claim_format(c, fmt_of<XT>()))) return r;
+    if (!c->stage_inputs) { t.slot = c->slot; t.st = c->stream; t.stage = false; }
+    else {
+        if ((r = stage_prepare(c))) return r;
+        HIPCHK(c, c->other().wait_free(c->copy));
+        t.slot = c->slot ^ 1; t.st = c->copy; t.stage = true;
+    }
+    if constexpr (std::is_same<XT, float>::value) if ((r = ensure_f32(c, t.slot, t.st))) return r;
+    t.x = slab_x<XT>(c, t.slot);
+    return M17HIP_OK;
+}
+template <typename XT>
+static void input_done(m17hip_ctx* c, const InputTargetT<XT>& t, uint32_t C, uint32_t T)
+{
+    c->stream_fmt = c->slab_fmt[t.slot] = fmt_of<XT>();
     if (t.stage) {
         c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
         return;
@@ -1288,51 +1411,122 @@ static void input_done(m17hip_ctx* c, const InputTarget& t, uint32_t C, uint32_t
     c->lastC = C;
     if (c->have_run) c->inplace_after_run = true;
 }
+// the staging slab of that format, free for the next input (the copy stream has waited for the run that read it)
+template <typename XT>
+static int staging_target(m17hip_ctx* c, XT*& x)
+{
+    int r;
+    if ((r = claim_format(c, fmt_of<XT>()))) return r;
+    if ((r = stage_prepare(c))) return r;
+    // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
+    HIPCHK(c, c->other().wait_free(c->copy));
+    if constexpr (std::is_same<XT, float>::value) if ((r = ensure_f32(c, c->slot ^ 1, c->copy))) return r;
+    x = slab_x<XT>(c, c->slot ^ 1);
+    return M17HIP_OK;
+}
+static void staged_done(m17hip_ctx* c, int fmt, uint32_t C, uint32_t T)
+{
+    c->stream_fmt = c->slab_fmt[c->slot ^ 1] = fmt;
+    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
+}
+static void launch_copy_rows(const int16_t* dev, size_t pitch, int16_t* x, size_t xpitch, uint32_t C, uint32_t T, hipStream_t st)
+{
+    hipLaunchKernelGGL(copy_rows_i16_kernel, dim3(((T + 7) / 8 + 255) / 256, C), dim3(256), 0, st, dev, pitch, x, xpitch, T);
+}
+static void launch_copy_rows(const float* dev, size_t pitch, float* x, size_t xpitch, uint32_t C, uint32_t T, hipStream_t st)
+{
+    hipLaunchKernelGGL(copy_rows_xf32_kernel, dim3(((T + 3) / 4 + 255) / 256, C), dim3(256), 0, st, dev, pitch, x, xpitch, T);
+}
 
-int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch)
+// The four ways in, for either format (the C entry points below name the instantiations).
+template <typename XT>
+static int upload_host(m17hip_ctx* c, const XT* host, uint32_t C, uint32_t T, size_t pitch)
 {
     if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    InputTarget in;
+    InputTargetT<XT> in;
     int r = input_target(c, in);
     if (r) return r;
-    HIPCHK(c, hipMemcpy2DAsync(in.x + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
-                               hipMemcpyHostToDevice, in.st));
+    HIPCHK(c, hipMemcpy2DAsync(in.x + XPRE, c->xpitch * sizeof(XT), host, pitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyHostToDevice, in.st));
     HIPCHK(c, hipStreamSynchronize(in.st));
     input_done(c, in, C, T);
     return M17HIP_OK;
 }
-
-int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch)
+template <typename XT>
+static int upload_host_async(m17hip_ctx* c, const XT* host, uint32_t C, uint32_t T, size_t pitch)
 {
     if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
-    int r = stage_prepare(c);
+    XT* x;
+    int r = staging_target(c, x);
     if (r) return r;
-    // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
-    HIPCHK(c, c->other().wait_free(c->copy));
-    HIPCHK(c, hipMemcpy2DAsync(c->other().x + XPRE, c->xpitch * sizeof(int16_t), host, pitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
-                               hipMemcpyHostToDevice, c->copy));
+    HIPCHK(c, hipMemcpy2DAsync(x + XPRE, c->xpitch * sizeof(XT), host, pitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyHostToDevice, c->copy));
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
+    staged_done(c, fmt_of<XT>(), C, T);
     return M17HIP_OK;
 }
-
-int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch)
+template <typename XT>
+static int upload_dev_async(m17hip_ctx* c, const XT* dev, uint32_t C, uint32_t T, size_t pitch)
 {
     if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
-    int r = stage_prepare(c);
+    XT* x;
+    int r = staging_target(c, x);
     if (r) return r;
-    HIPCHK(c, c->other().wait_free(c->copy));
-    dim3 grid(((T + 7) / 8 + 255) / 256, C);
-    hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, c->copy, dev, pitch, c->other().x, c->xpitch, T);
+    launch_copy_rows(dev, pitch, x, c->xpitch, C, T, c->copy);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
+    staged_done(c, fmt_of<XT>(), C, T);
+    return M17HIP_OK;
+}
+template <typename XT>
+static int upload_dev(m17hip_ctx* c, const XT* dev, uint32_t C, uint32_t T, size_t pitch)
+{
+    if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    InputTargetT<XT> in;
+    int r = input_target(c, in);
+    if (r) return r;
+    launch_copy_rows(dev, pitch, in.x, c->xpitch, C, T, in.st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(in.st));   // `dev` belongs to the caller again when this returns
+    input_done(c, in, C, T);
+    return M17HIP_OK;
+}
+template <typename XT>
+static int download_host(m17hip_ctx* c, XT* host, uint32_t C, uint32_t T, size_t pitch)
+{
+    if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
+    GUARD(c);
+    if (!c->uploaded || c->slab_fmt[c->slot] != fmt_of<XT>()) return M17HIP_ESTATE;   // (nothing there, or input of the other format)
+    HIPCHK(c, hipMemcpy2DAsync(host, pitch * sizeof(XT), slab_x<XT>(c, c->slot) + XPRE, c->xpitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyDeviceToHost,
+                               c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return M17HIP_OK;
+}
+
+}  // extern "C++"
+
+int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
+int m17hip_upload_f32(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
+int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host_async(c, host, C, T, pitch); }
+int m17hip_upload_f32_async(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host_async(c, host, C, T, pitch); }
+int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev_async(c, dev, C, T, pitch); }
+int m17hip_upload_f32_device_async(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev_async(c, dev, C, T, pitch); }
+int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch); }
+int m17hip_upload_f32_device(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch); }
+int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
+int m17hip_download_f32(m17hip_ctx* c, float* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
+
+int m17hip_input_format(m17hip_ctx* c, int* stream_format, uint64_t* f32_bytes)
+{
+    if (!c) return M17HIP_EINVAL;
+    if (stream_format) *stream_format = c->stream_fmt;
+    if (f32_bytes) *f32_bytes = c->fslab[0].bytes() + c->fslab[1].bytes() + (c->hist_f.size() + c->bnd_hist_f.size()) * sizeof(float);
     return M17HIP_OK;
 }
 
@@ -1342,6 +1536,7 @@ int m17hip_input_alternate(m17hip_ctx* c, uint32_t C, uint32_t T)
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
     if (!c->other().x || c->other().C != C || c->other().T != T) return M17HIP_ESTATE;   // the other slab does not hold such an input
+    if (!c->slab_fmt[c->slot ^ 1] || (c->stream_fmt && c->slab_fmt[c->slot ^ 1] != c->stream_fmt)) return M17HIP_ESTATE;   // (... of the stream's format)
     c->staged = true; c->stagedC = C; c->stagedT = T;
     return M17HIP_OK;
 }
@@ -1450,33 +1645,6 @@ int m17hip_synth_tx_i16(m17hip_ctx* c, const m17_synth_params* base, const m17_t
     hipLaunchKernelGGL(mod_shape_kernel, dim3((T + 255) / 256, C), dim3(256), 0, in.st, mp, C, T, chan0, sym, sym_pitch, nsym, in.x, c->xpitch);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(in.st));
-    input_done(c, in, C, T);
-    return M17HIP_OK;
-}
-
-int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch)
-{
-    if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (!c->uploaded) return M17HIP_ESTATE;
-    HIPCHK(c, hipMemcpy2DAsync(host, pitch * sizeof(int16_t), c->now().x + XPRE, c->xpitch * sizeof(int16_t), (size_t)T * sizeof(int16_t), C,
-                               hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return M17HIP_OK;
-}
-
-int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch)
-{
-    if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    InputTarget in;
-    int r = input_target(c, in);
-    if (r) return r;
-    dim3 grid(((T + 7) / 8 + 255) / 256, C);
-    hipLaunchKernelGGL(copy_rows_i16_kernel, grid, dim3(256), 0, in.st, dev, pitch, in.x, c->xpitch, T);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(in.st));   // `dev` belongs to the caller again when this returns
     input_done(c, in, C, T);
     return M17HIP_OK;
 }
@@ -1657,6 +1825,11 @@ int m17hip_demod_reset(m17hip_ctx* c)
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, c->maxC);
     HIPCHK(c, hipGetLastError());
+    if (c->fslab[c->slot].x) {   // (a context that has seen a float stream: the float pair's prefix and the float histories as well)
+        hipLaunchKernelGGL(zero_prefix_xf32_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->fslab[c->slot].x.get(), c->xpitch);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemsetAsync(c->hist_f, 0, c->hist_f.size() * sizeof(float), c->stream));
+    }
     HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
     hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->bert_state, c->maxC);
     HIPCHK(c, hipGetLastError());
@@ -1683,6 +1856,7 @@ int m17hip_demod_reset(m17hip_ctx* c)
     c->have_run = false;
     c->inplace_after_run = false;
     c->sel_back = 0;
+    c->stream_fmt = 0;   // the next input chooses the stream's sample format again (what the slabs hold keeps its own)
     return M17HIP_OK;
 }
 
@@ -1867,12 +2041,14 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
     const uint32_t C = p.C, t0 = p.t0(k), len = p.t0(k + 1) - t0;
     TimedK tm(c, KT_GATE);
     GateParams G{};
-    G.x = c->now().x + t0; G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
+    G.x = c->x_now(t0); G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
     G.dcd_table = c->now().dcd; G.ticks_cap = c->ticks_cap; G.state = c->seq_state;
     G.final_h = by_parity(c->final_h, k, c->maxC, 4);
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
     G.only = redo ? by_parity(c->dropped, k - 1u, c->maxC) : nullptr;   // (flags by segment parity)
     G.bnd = redo ? by_parity(c->bnd, k, c->maxC) : nullptr;   // (written by K5 of segment k - 1)
+    const bool f32 = c->f32_now();
+    if (f32) { G.hist_f = c->hist_f; G.bnd_hist_f = redo ? by_parity(c->bnd_hist_f, k, c->maxC, HISTF_PITCH) : nullptr; }
     G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.kflags | ((redo && !redo_stores) ? 2u : 0u); G.pol = p.pol;
     G.nblk = (C + GT_CPW - 1) / GT_CPW;
     uint32_t fold_blocks = 0;
@@ -1887,7 +2063,8 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
         G.ev = ev_fold(c, f, k == 0 ? EV_SETTLES : EV_BESIDE_K5);   // (in front of segment 0, which K5 waits for: settled; beside the replay ahead: not)
         fold_blocks = f.blocks();
     }
-    tm.launch(limit_track_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
+    if (f32) tm.launch(limit_track_f32_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
+    else tm.launch(limit_track_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1916,10 +2093,26 @@ static void commit_marks(m17hip_ctx* c)
 static int reset_marked_front(m17hip_ctx* c, uint32_t n, hipStream_t st, Reader which, bool x, bool dcd)
 {
     HIPCHK(c, c->reset_list.before_read(st));
+    if (c->f32_now())
+        hipLaunchKernelGGL(front_reset_list_xf32_kernel, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? c->fslab[c->slot].x.get() : (float*)nullptr, c->xpitch,
+                           dcd ? c->dcd_state.get() : (DcdState*)nullptr);
+    else
     hipLaunchKernelGGL(front_reset_list_kernel, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? c->now().x.get() : (int16_t*)nullptr, c->xpitch,
                        dcd ? c->dcd_state.get() : (DcdState*)nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->reset_list.after_read(which, st));
+    return M17HIP_OK;
+}
+
+// A run is about to read the input slab pair `slot` holds: its format must be the stream's (it becomes the stream's where a reset has freed the
+// choice since the input was written), and the kernels a tuning key selects must exist for it — the tools-only instantiations of the
+// sequential kernel (keys 1, 19) and round 4's matched filter (key 11 = 0) read int16 rows only: refused, never launched on float memory.
+static int run_format_check(m17hip_ctx* c, int slot)
+{
+    const int fmt = c->slab_fmt[slot];
+    if (c->stream_fmt && fmt && fmt != c->stream_fmt) return M17HIP_ESTATE;
+    if (fmt == M17HIP_FORMAT_F32 && (c->profile || c->wave_times || c->fir_form == 0)) return M17HIP_ESTATE;
+    if (fmt) c->stream_fmt = fmt;
     return M17HIP_OK;
 }
 
@@ -1930,13 +2123,25 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
 {
     if (C != c->stagedC || T != c->stagedT) return M17HIP_EINVAL;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
+    if (int r = run_format_check(c, c->slot ^ 1)) return r;
     const int16_t* xprev = c->now().x;
+    const float* xprev_f = c->fslab[c->slot].x;
     c->slot ^= 1;   // (the staged input's pair becomes now(), the previous run's other())
     c->staged = false; c->uploaded = true;
     c->carryT = c->have_run ? c->runT : 0;
     // the new slab's prefix, behind the staged copy on the copy stream; the slab pair itself is free since now().end (the copy
     // stream waited for it when the input was staged — m17hip_input_alternate stages without a copy, so wait here as well)
     HIPCHK(c, c->now().wait_free(c->copy));
+    if (c->f32_now()) {   // a float stream: the same three cases over the float pair
+        float* xf = c->fslab[c->slot].x;
+        if (c->carryT && !xprev_f) return M17HIP_ESTATE;   // (cannot be: a continued float stream has run on a float slab)
+        if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)
+            hipLaunchKernelGGL(copy_tail_xf32_kernel, dim3(C), dim3(64), 0, c->copy, xprev_f, xf, c->xpitch, c->carryT);
+        else if (c->carryT) {
+            HIPCHK(c, hipStreamWaitEvent(c->copy, c->other().end, 0));
+            hipLaunchKernelGGL(copy_prefix_xf32_kernel, dim3(C), dim3(64), 0, c->copy, xprev_f, xf, c->xpitch);
+        } else HIPCHK(c, hipMemset2DAsync(xf, c->xpitch * sizeof(float), 0, XPRE * sizeof(float), C, c->copy));
+    } else
     if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)   // the tail of the previous input, where it lies (that slab is only read while its run is in flight)
         hipLaunchKernelGGL(copy_tail_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch, c->carryT);
     else if (c->carryT) {              // (or its data region was overwritten in place since: the tail its last kernel carried into its prefix)              // a run shorter than the prefix: its tail reaches into its own prefix, which its last kernel rewrites — wait for that
@@ -2178,7 +2383,8 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     SeqParams P{};
     P.h = c->now().h + t0; P.final_h = by_parity(c->final_h, k, c->maxC, 4);
     P.dropped = by_parity(c->dropped, k, c->maxC);
-    P.x = c->now().x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+    P.x = c->x_now(t0); P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+    if (c->f32_now()) { P.hist_f = c->hist_f; P.bnd_hist_f = by_parity(c->bnd_hist_f, k + 1u, c->maxC, HISTF_PITCH); }
     P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
     P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
     P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
@@ -2252,6 +2458,10 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
         else if (c->wave_times) tm.launch((demod_wave_kernel<4, false, true>), grid, block, lds, c->stream, P);
         else
 #endif
+        if (c->f32_now()) {   // a float stream (run_format_check has refused the tools-only instantiations above)
+            if (c->kalman_order == 3u) tm.launch((demod_wave_f32_kernel<4, 3>), grid, block, lds, c->stream, P);
+            else tm.launch(demod_wave_f32_kernel<4>, grid, block, lds, c->stream, P);
+        } else
         if (c->kalman_order == 3u) tm.launch((demod_wave_kernel<4, false, false, 3>), grid, block, lds, c->stream, P);   // (the default order: no call in the kernel)
         else tm.launch(demod_wave_kernel<4>, grid, block, lds, c->stream, P);
         HIPCHK(c, hipGetLastError());
@@ -2270,6 +2480,10 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     const uint32_t C = p.C, T = p.T;
     // the tails a run that continues in THESE slabs (input uploaded in place) will find as its prefixes; a staged run takes them from
     // here into the other slab pair itself.  (Before the deferred decode: the next staged run's first replay waits for these, not for that.)
+    if (c->f32_now()) {
+        hipLaunchKernelGGL(carry_tail_xf32_kernel, dim3(C), dim3(64), 0, c->stream, c->fslab[c->slot].x.get(), c->xpitch, T);
+        hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().y.get(), c->ypitch, T);
+    } else
     hipLaunchKernelGGL(carry_tail_kernel, dim3(C), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, C, T);
     hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().h, c->ypitch, T);
     HIPCHK(c, hipGetLastError());
@@ -2380,6 +2594,7 @@ int m17hip_demod_run(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     if (!c->uploaded) return M17HIP_ESTATE;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
     if (!p.staged) {
+        if ((r = run_format_check(c, c->slot))) return r;
         p = plan_run(c, C, T, flags, RUN_IN_PLACE);
         if ((r = resolve_polarity(c, C, flags, c->stream, p.kflags, p.pol))) return r;
         if (!c->marks.empty()) {   // (m17hip_demod_reset_channels; in place the main stream is behind the previous run's carried tails and its K3)

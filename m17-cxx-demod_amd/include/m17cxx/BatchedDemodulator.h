@@ -55,6 +55,13 @@ public:
         check(m17hip_upload_i16(ctx_, host, channels, samples, pitch), "m17hip_upload_i16");
         channels_ = channels; samples_ = samples;
     }
+    // float32 input in the reference's units (what M17Demodulator<float>::operator() receives), taken as it is: a float stream
+    // (m17hip_upload_f32; the format belongs to the stream until the next reset())
+    void upload(const float* host, uint32_t channels, uint32_t samples, size_t pitch)
+    {
+        check(m17hip_upload_f32(ctx_, host, channels, samples, pitch), "m17hip_upload_f32");
+        channels_ = channels; samples_ = samples;
+    }
     // The input generated on the device from the caller's own transmissions, one per channel (m17hip_synth_tx_i16: the framing of
     // apps/m17-mod.cpp:264-504, 509-564 around lsf30[channels][30] and rows[n_rows][32]; impairments and seeding from `base`)
     void synth_tx(const m17_synth_params& base, const m17_tx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_rows, uint32_t channels,
@@ -97,6 +104,11 @@ public:
     void stage(const int16_t* pinned_host, uint32_t channels, uint32_t samples, size_t pitch)
     {
         check(m17hip_upload_i16_async(ctx_, pinned_host, channels, samples, pitch), "m17hip_upload_i16_async");
+        channels_ = channels; samples_ = samples;
+    }
+    void stage(const float* pinned_host, uint32_t channels, uint32_t samples, size_t pitch)
+    {
+        check(m17hip_upload_f32_async(ctx_, pinned_host, channels, samples, pitch), "m17hip_upload_f32_async");
         channels_ = channels; samples_ = samples;
     }
     void front(uint32_t flags = 0) { check(m17hip_demod_front(ctx_, channels_, samples_, flags), "m17hip_demod_front"); }

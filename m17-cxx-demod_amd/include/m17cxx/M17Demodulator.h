@@ -112,7 +112,9 @@ struct M17Demodulator
         try { flush(); } catch (...) {}
     }
 
-    // The reference takes sample / 41067.0 (apps/m17-demod.cpp:489); the int16 the GPU path scales itself is recovered exactly.
+    // The sample is what the reference's operator() receives (apps/m17-demod.cpp:489 makes it sample / 41067.0; a discriminator delivers it as it
+    // is): the GPU path buffers it as float32 and uploads it as a float stream (m17hip_upload_f32) — nothing is rounded, nothing is clipped, and the
+    // callbacks are those of the host form on the same samples.
     void operator()(const FloatType input)
     {
         if (cpu_) {   // the host form: this very sample, callbacks before the call returns
@@ -120,7 +122,7 @@ struct M17Demodulator
             demodState = (DemodState)cpu_->state();
             return;
         }
-        buffer_.push_back((int16_t)std::lrint((double)input * 41067.0));
+        buffer_.push_back((float)input);
         if (buffer_.size() == block_) run_block();
     }
 
@@ -194,7 +196,7 @@ private:
     std::unique_ptr<BatchedDemodulator> gpu_;                        // one of the two
     std::unique_ptr<detail::ScalarDemodulator<FloatType>> cpu_;
     callback_t callback_;
-    std::vector<int16_t> buffer_;
+    std::vector<float> buffer_;
     uint32_t block_;
     bool dcd_ = false;
     bool passall_ = false;

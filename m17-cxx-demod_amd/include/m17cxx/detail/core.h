@@ -35,6 +35,9 @@ M17_HD float scale_i16(int s, bool invert)
     const float r = __builtin_fmaf(-q, 41067.0f, fs);
     return __builtin_fmaf(r, rcp, q);
 }
+// The float twin: a float32 input sample is already what the reference's M17Demodulator<float>::operator() receives — nothing is scaled.
+// Under invert it is negated, which is exact (a sign-bit flip, NaNs and zeroes included); there is no -32768 wrap.
+M17_HD float scale_f32(float v, bool invert) { return invert ? -v : v; }
 
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).

@@ -66,7 +66,10 @@ EXPORTS = [
     "m17hip_synth_sweep_i16", "m17hip_sweep_stats", "m17hip_gather_sweep_stats", "m17hip_demod_reset_channels",
     "m17hip_set_channel_polarity", "m17hip_synth_tx_i16",
     "m17hip_voice_fetch", "m17hip_voice_device", "m17hip_calls_fetch", "m17hip_voice_feed",
+    "m17hip_upload_f32", "m17hip_upload_f32_device", "m17hip_upload_f32_async", "m17hip_upload_f32_device_async", "m17hip_download_f32",
+    "m17hip_input_format",
 ]
+FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 ETRUNC = -6
 EOVERFLOW = -5
 COMM_ID_BYTES = 128
@@ -215,23 +218,37 @@ class Context:
 
     # ---- input -------------------------------------------------------------------------------------------------
     def upload(self, samples):
-        s = np.ascontiguousarray(samples, dtype=np.int16)
+        """The input of the next run.  A float32 array is a float stream's input — samples in the reference's units, taken as they are
+        (m17hip_upload_f32); anything else is int16 input, as ever."""
+        if getattr(samples, "dtype", None) == np.float32:
+            s = np.ascontiguousarray(samples)
+            fn = self.lib.m17hip_upload_f32
+        else:
+            s = np.ascontiguousarray(samples, dtype=np.int16)
+            fn = self.lib.m17hip_upload_i16
         if s.ndim == 1:
             s = s[None, :]
         self.C, self.T = s.shape
-        self._chk(self.lib.m17hip_upload_i16(self.h, _ptr(s), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(self.T)))
+        self._chk(fn(self.h, _ptr(s), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(self.T)))
 
-    def upload_async(self, host_ptr, channels, samples, pitch=None):
+    def _by_dtype(self, stem, dtype):
+        """The entry point `m17hip_upload_<i16|f32><stem>` for samples of `dtype` (int16, the default, or float32)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int16), np.dtype(np.float32)):
+            raise TypeError(f"input samples are int16 or float32, not {dt}")
+        return getattr(self.lib, f"m17hip_upload_{'f32' if dt == np.float32 else 'i16'}{stem}")
+
+    def upload_async(self, host_ptr, channels, samples, pitch=None, dtype=np.int16):
         """Stage the input of the NEXT run (pinned host memory at `host_ptr`, kept alive by the caller) while the current run computes."""
         self.C, self.T = int(channels), int(samples)
-        self._chk(self.lib.m17hip_upload_i16_async(self.h, C.c_void_p(int(host_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
-                                                   C.c_size_t(self.T if pitch is None else pitch)))
+        self._chk(self._by_dtype("_async", dtype)(self.h, C.c_void_p(int(host_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
+                                                  C.c_size_t(self.T if pitch is None else pitch)))
 
-    def upload_device_async(self, dev_ptr, channels, samples, pitch=None):
+    def upload_device_async(self, dev_ptr, channels, samples, pitch=None, dtype=np.int16):
         """Stage the input of the NEXT run from device memory at `dev_ptr` (kept alive and unmodified by the caller until upload_wait)."""
         self.C, self.T = int(channels), int(samples)
-        self._chk(self.lib.m17hip_upload_i16_device_async(self.h, C.c_void_p(int(dev_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
-                                                          C.c_size_t(self.T if pitch is None else pitch)))
+        self._chk(self._by_dtype("_device_async", dtype)(self.h, C.c_void_p(int(dev_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
+                                                         C.c_size_t(self.T if pitch is None else pitch)))
 
     def input_alternate(self, channels=None, samples=None):
         """Stage, without a copy, the input the context's second slab still holds (two resident slabs that alternate)."""
@@ -291,10 +308,23 @@ class Context:
         self._chk(self.lib.m17hip_download_i16(self.h, _ptr(out), C.c_uint32(n), C.c_uint32(self.T), C.c_size_t(self.T)))
         return out
 
-    def upload_device(self, dev_ptr, channels, samples, pitch=None):
+    def download_f32(self, channels=None):
+        """The float input slab's first `channels` rows (a float stream), byte for byte what was uploaded."""
+        n = channels or self.C
+        out = np.empty((n, self.T), dtype=np.float32)
+        self._chk(self.lib.m17hip_download_f32(self.h, _ptr(out), C.c_uint32(n), C.c_uint32(self.T), C.c_size_t(self.T)))
+        return out
+
+    def input_format(self):
+        """(the stream's sample format: 0 free / FORMAT_I16 / FORMAT_F32, device bytes held for float input) — m17hip_input_format."""
+        fmt, nbytes = C.c_int(0), C.c_uint64(0)
+        self._chk(self.lib.m17hip_input_format(self.h, C.byref(fmt), C.byref(nbytes)))
+        return fmt.value, nbytes.value
+
+    def upload_device(self, dev_ptr, channels, samples, pitch=None, dtype=np.int16):
         self.C, self.T = int(channels), int(samples)
-        self._chk(self.lib.m17hip_upload_i16_device(self.h, C.c_void_p(int(dev_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
-                                                    C.c_size_t(self.T if pitch is None else pitch)))
+        self._chk(self._by_dtype("_device", dtype)(self.h, C.c_void_p(int(dev_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
+                                                  C.c_size_t(self.T if pitch is None else pitch)))
 
     # ---- per-operator entry points --------------------------------------------------------------------------------
     def fir(self, flags=0, fetch=True):
