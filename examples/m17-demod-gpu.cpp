@@ -1,11 +1,14 @@
 // A reference-style demodulator front end on the GPU path: 48 kSPS s16le mono on stdin (with -f / --float32: raw float32 in the
-// reference's units — a discriminator's output, taken as it is: a float stream, nothing rounded), one line per frame callback on
+// reference's units — a discriminator's output, taken as it is: a float stream, nothing rounded; with --iq-i16 / --iq-f32: interleaved
+// I,Q of the narrowband FM channel, int16 or float32, discriminated on the device with --iq-gain G, default 1), one line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
 #include "m17cxx/M17Demodulator.h"
 
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 
@@ -33,12 +36,32 @@ int main(int argc, char** argv)
 {
     using namespace mobilinkd;
     bool float_input = false;
+    int iq = 0;   // 1: int16 I,Q; 2: float32 I,Q
+    float iq_gain = 1.0f;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
-        else { std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32] < samples\n"); return 2; }
+        else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
+        else if (!std::strcmp(argv[i], "--iq-f32")) iq = 2;
+        else if (!std::strcmp(argv[i], "--iq-gain") && i + 1 < argc) iq_gain = std::strtof(argv[++i], nullptr);
+        else { std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32] [--iq-gain G] < samples\n"); return 2; }
     }
+    if ((iq && float_input) || !(iq_gain > 0.0f) || !std::isfinite(iq_gain)) { std::fprintf(stderr, "m17-demod-gpu: one input format, and a finite gain > 0\n"); return 2; }
     M17Demodulator<float> demod(handle_frame);
     demod.diagnostics([](bool, float, float, float, bool, float, int, int, int, int) {});
+    demod.iq_gain(iq_gain);
+    while (iq == 1 && std::cin) {   // interleaved int16 I,Q at 48 kSPS: the discriminator runs on the device
+        int16_t s[2];
+        std::cin.read(reinterpret_cast<char*>(s), 4);
+        if (!std::cin) break;
+        demod.iq((float)s[0], (float)s[1]);
+    }
+    while (iq == 2 && std::cin) {
+        float s[2];
+        std::cin.read(reinterpret_cast<char*>(s), 8);
+        if (!std::cin) break;
+        demod.iq(s[0], s[1]);
+    }
+    if (iq) return 0;
     while (float_input && std::cin) {   // raw float32, native byte order: the value IS the demodulator's sample
         float sample;
         std::cin.read(reinterpret_cast<char*>(&sample), 4);

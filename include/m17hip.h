@@ -173,6 +173,41 @@ int m17hip_download_f32(m17hip_ctx* ctx, float* host, uint32_t channels, uint32_
  * arrays): 0 for a context that has never seen a float.  Either pointer may be NULL. */
 int m17hip_input_format(m17hip_ctx* ctx, int* stream_format, uint64_t* f32_bytes);
 
+/* ---- complex IQ input: the FM discriminator on the device (ABI 608) -----------------------------------
+ * The radios that deliver thousands of channels deliver complex IQ, one narrowband stream per channel at 48 kSPS.  These entry points take it and put
+ *     y[n] = gain * arg(x[n] * conj(x[n-1]))        (radians per sample at gain 1)
+ * into the context's float input slab, where m17hip_upload_f32 would have put the caller's floats: behind them the stream is a FLOAT STREAM and nothing
+ * else in the chain knows the difference (m17hip_download_f32 returns the discriminated floats, m17hip_input_format says M17HIP_FORMAT_F32; on an int16
+ * stream they return M17HIP_ESTATE with nothing changed; m17hip_synth_* on the stream they made returns M17HIP_ESTATE).  The arithmetic is the project's
+ * own, defined once for host and device (m17cxx/detail/core.h: fm_cross, fm_phase, fm_discriminate — a float32 four-quadrant arctangent within 2^-20 rad
+ * of atan2, odd in Q to the bit, +0 for a zero product), so a host can compute the very words the device computes.  The demodulator normalises by its own
+ * deviation estimate: any finite gain > 0 decodes.  A spectrum-flipped (conjugated) input is the exact negation: M17HIP_FLAG_INVERT / the polarity table.
+ * iq_format: M17HIP_IQ_I16 — interleaved int16 I,Q (converted to float, exact) — or M17HIP_IQ_F32 — interleaved float32 I,Q; no scaling in either, and
+ * the format may change from one call to the next.  `samples` counts COMPLEX samples (= float baseband samples produced), and so does `pitch`.
+ * The four functions are the four m17hip_upload_f32 ways in, with the same staging-pair semantics (m17hip_input_alternate, m17hip_demod_front and
+ * m17hip_upload_wait work as for floats).  The device forms read the caller's memory directly (a sample aligned to its own size; rows that are 16-byte
+ * aligned take the 16-byte loads, others go sample by sample).  As for m17hip_upload_i16_device_async, `dev` must be COMPLETE when the call is made: the
+ * context's streams are non-blocking and do not wait for the producer's stream (the producer synchronised, or the hand-over ordered by the caller);
+ * the _async form's memory stays valid and unmodified until m17hip_upload_wait has returned.  The host forms copy the raw IQ into a device buffer the
+ * context owns (allocated with the first host IQ block, grown when a later one is larger), then discriminate on the same stream.
+ * THE FEED: IQ blocks continue one another in call order, per channel, whether or not a run consumed the slab in between: the sample in front of a
+ * block's first one is the last sample of the IQ block uploaded before it (one float2 per channel, kept on the device).  It is zero — the first output is
+ * +0 — after m17hip_ctx_create, after m17hip_demod_reset, and for the listed channels after m17hip_demod_reset_channels: a channel reset applies to the IQ
+ * blocks uploaded AFTER it (not to a block already staged).
+ * M17HIP_EINVAL: a NULL context or pointer, channels or samples of 0 or beyond the context's limits, pitch < samples, an unknown iq_format, a gain that is
+ * not finite and > 0.  M17HIP_ESTATE: while a front end queued by m17hip_demod_front is waiting for its run, as for every upload.
+ * Non-finite IQ samples stay in their channel (and reach the following block's first output through the carry).
+ * m17hip_timing_get index 8 is the discriminator kernel.
+ * Out of scope: a channeliser (wideband IQ -> channels), resampling to 48 kSPS, 8-bit IQ, de-emphasis and squelch. */
+#define M17HIP_IQ_I16 1   /* interleaved int16 I,Q */
+#define M17HIP_IQ_F32 2   /* interleaved float32 I,Q */
+int m17hip_upload_iq(m17hip_ctx* ctx, const void* host, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_iq_device(m17hip_ctx* ctx, const void* dev, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_iq_async(m17hip_ctx* ctx, const void* host, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_iq_device_async(m17hip_ctx* ctx, const void* dev, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+/* Device memory the context holds for IQ input: the carry and the host forms' raw-IQ buffer.  0 for a context that has never seen IQ. */
+int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
+
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
  * (apps/m17-demod.cpp:489 scaling; FirFilter.h:28-43; taps M17Demodulator.h:79-118).
@@ -234,7 +269,9 @@ int m17hip_demod_reset(m17hip_ctx* ctx);
  * limit-filter replay, the sequential kernel and the gate forecast all find a tick as position / 192 — and a fresh demodulator's
  * carrier-detect updates fall on the tick ends of ITS stream.  A reset can therefore only take effect where the context's sample
  * position (the samples run since m17hip_demod_reset) is a multiple of 192: otherwise M17HIP_ESTATE, and nothing is marked.
- * Cost: list-driven kernels over the marked channels only, O(n); a run with no mark pending queues exactly what it did before. */
+ * Cost: list-driven kernels over the marked channels only, O(n); a run with no mark pending queues exactly what it did before.
+ * Complex IQ input (m17hip_upload_iq*): the listed channels' IQ feeds start over as well — AT ONCE, not with the next run: the reset applies to the IQ
+ * blocks uploaded after this call (their first discriminated sample is +0), not to a block that is already staged. */
 int m17hip_demod_reset_channels(m17hip_ctx* ctx, const uint32_t* channels, uint32_t n);
 /* Per-channel input polarity (ABI 604): the reference's -i (apps/m17-demod.cpp:488, sample *= -1 in int16) is a property of ONE receiver — its
  * discriminator, its sound card, the side of the IF — and each reference process has its own command line.  invert[n], n in 1..max_channels:
@@ -634,7 +671,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
 /* Accumulated device time (ms) and launch count per kernel since the last m17hip_timing_reset:
  * which: 0 = fir_rrc150, 1 = dcd, 2 = demod_seq, 3 = viterbi/decode_frames, 4 = correlator, 5 = compaction,
  * 6 = limit_track (the limit filter run ahead of demod_seq; in m17hip_fir_correlator the limit filter's chain, 4 = its correlations),
- * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode). */
+ * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode),
+ * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

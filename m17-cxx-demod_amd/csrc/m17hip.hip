@@ -6,6 +6,7 @@
 #include "m17_common.hpp"
 #include "m17_decode_device.hpp"
 #include "m17_frontend_kernels.hpp"
+#include "m17_iq_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -31,7 +32,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -254,6 +255,14 @@ struct m17hip_ctx {
     int stream_fmt = 0;               // M17HIP_FORMAT_*; 0: free
     int slab_fmt[2] = {0, 0};
     bool f32_now() const { return slab_fmt[slot] == M17HIP_FORMAT_F32; }
+    // COMPLEX IQ INPUT (m17hip_upload_iq): the discriminator writes the float pair's slabs, so behind it the stream is a float stream.  What it holds of its
+    // own, allocated with the first IQ input: the carry — one float2 per channel, the last IQ sample of the previous IQ block, zero for a fresh feed — and,
+    // for the host forms, a buffer for the raw IQ of one block (grown when a later block is larger).  In-place blocks run on the main stream and staged ones
+    // on the copy stream: `ev_iq` follows every launch that reads or writes the carry (or reads iq_raw), a launch on the other stream goes behind it.
+    DevBuf<float2> iq_carry;          // [maxC]
+    DevBuf<char> iq_raw;              // rows of round_up(T, 4) samples of the latest host block's format
+    Event ev_iq;
+    hipStream_t iq_last = nullptr;    // the stream ev_iq was recorded on (nullptr: never)
     const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
     {
         return f32_now() ? reinterpret_cast<const int16_t*>(fslab[slot].x + t0) : slab[slot].x + t0;
@@ -1136,7 +1145,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 607; }
+int m17hip_version(void) { return 608; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1509,6 +1518,102 @@ static int download_host(m17hip_ctx* c, XT* host, uint32_t C, uint32_t T, size_t
     return M17HIP_OK;
 }
 
+// ---- complex IQ input (ABI 608): the FM discriminator in front of the float slab -----------------------------------------------------------
+// `st` is about to read or write the IQ carry (or the raw-IQ buffer): behind the latest launch that did, where that was on the other stream
+static int iq_order(m17hip_ctx* c, hipStream_t st)
+{
+    if (c->iq_last && c->iq_last != st) HIPCHK(c, hipStreamWaitEvent(st, c->ev_iq, 0));
+    return M17HIP_OK;
+}
+static int iq_mark(m17hip_ctx* c, hipStream_t st)
+{
+    HIPCHK(c, hipEventRecord(c->ev_iq, st));
+    c->iq_last = st;
+    return M17HIP_OK;
+}
+// the carry, the first time an IQ block arrives: zeroed on the stream that block's discriminator runs on
+static int ensure_iq(m17hip_ctx* c, hipStream_t st)
+{
+    if (c->iq_carry) return M17HIP_OK;
+    if (!c->ev_iq) HIPCHK(c, c->ev_iq.create());
+    if (int r = alloc_code(c, c->iq_carry.alloc(c->maxC))) return r;
+    HIPCHK(c, hipMemsetAsync(c->iq_carry, 0, (size_t)c->maxC * sizeof(float2), st));
+    return iq_mark(c, st);
+}
+// A fresh feed for every channel (m17hip_demod_reset) or for the listed ones (m17hip_demod_reset_channels: one memset per run of consecutive channels;
+// nothing is copied to the device and the host waits for nothing).  On the stream of the latest IQ launch: IQ blocks uploaded from here on find the zeroes.
+static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
+{
+    if (!c->iq_carry) return M17HIP_OK;
+    const hipStream_t st = c->iq_last;
+    if (!channels) HIPCHK(c, hipMemsetAsync(c->iq_carry, 0, (size_t)c->maxC * sizeof(float2), st));
+    else {
+        std::vector<uint32_t> v(channels, channels + n);
+        std::sort(v.begin(), v.end());
+        for (size_t i = 0; i < v.size();) {
+            size_t j = i + 1;
+            while (j < v.size() && v[j] <= v[j - 1] + 1u) ++j;
+            HIPCHK(c, hipMemsetAsync(c->iq_carry.get() + v[i], 0, (size_t)(v[j - 1] - v[i] + 1u) * sizeof(float2), st));
+            i = j;
+        }
+    }
+    return iq_mark(c, st);
+}
+template <typename IQT>
+static int launch_discriminate(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
+{
+    const IQT* src = static_cast<const IQT*>(dev);
+    {
+        TimedK tm(c, KT_IQ);
+        tm.launch(discriminate_kernel<IQT>, dim3(((T + IQ_LANE - 1) / IQ_LANE + IQ_THREADS - 1) / IQ_THREADS, C), dim3(IQ_THREADS), 0, st, src, pitch, x, c->xpitch, T,
+                  c->iq_carry.get(), gain);
+    }
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(iq_carry_kernel<IQT>, dim3((C + 63) / 64), dim3(64), 0, st, src, pitch, T, c->iq_carry.get(), C);   // (behind it: the next block's carry)
+    HIPCHK(c, hipGetLastError());
+    return iq_mark(c, st);
+}
+// The four ways in (`how`: from host memory / staged for the next run), as upload_host, upload_dev and their _async forms have them for floats: the
+// discriminator takes the place of the copy.
+enum { IQ_FROM_HOST = 1, IQ_STAGED = 2 };
+static int upload_iq(m17hip_ctx* c, const void* p, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
+{
+    if (!c || !p || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32) return M17HIP_EINVAL;
+    if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    int r;
+    InputTargetT<float> in;
+    float* x = nullptr;
+    hipStream_t st = nullptr;
+    if (how & IQ_STAGED) { if ((r = staging_target(c, x))) return r; st = c->copy; }
+    else { if ((r = input_target(c, in))) return r; x = in.x; st = in.st; }
+    if ((r = ensure_iq(c, st))) return r;
+    if ((r = iq_order(c, st))) return r;
+    const size_t sb = iq_format == M17HIP_IQ_I16 ? sizeof(short2) : sizeof(float2);
+    const void* dev = p;
+    if (how & IQ_FROM_HOST) {   // the raw IQ into the context's own buffer first, rows of a multiple of four samples (16-byte loads)
+        const size_t rp = round_up(T, IQ_LANE);
+        if (c->iq_raw.size() < (size_t)C * rp * sb) {
+            HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be read)
+            if ((r = alloc_code(c, c->iq_raw.grow((size_t)C * rp * sb, &c->last_hip)))) return r;
+        }
+        HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, p, pitch * sb, (size_t)T * sb, C, hipMemcpyHostToDevice, st));
+        dev = c->iq_raw; pitch = rp;
+    }
+    r = iq_format == M17HIP_IQ_I16 ? launch_discriminate<short2>(c, dev, pitch, x, C, T, gain, st) : launch_discriminate<float2>(c, dev, pitch, x, C, T, gain, st);
+    if (r) return r;
+    if (how & IQ_STAGED) {
+        HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
+        staged_done(c, M17HIP_FORMAT_F32, C, T);
+    } else {
+        HIPCHK(c, hipStreamSynchronize(st));   // the caller's memory belongs to the caller again when this returns
+        input_done(c, in, C, T);
+    }
+    return M17HIP_OK;
+}
+
 }  // extern "C++"
 
 int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
@@ -1521,6 +1626,29 @@ int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint
 int m17hip_upload_f32_device(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch); }
 int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
 int m17hip_download_f32(m17hip_ctx* c, float* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
+
+int m17hip_upload_iq(m17hip_ctx* c, const void* host, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_iq(c, host, iq_format, gain, C, T, pitch, IQ_FROM_HOST);
+}
+int m17hip_upload_iq_device(m17hip_ctx* c, const void* dev, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_iq(c, dev, iq_format, gain, C, T, pitch, 0);
+}
+int m17hip_upload_iq_async(m17hip_ctx* c, const void* host, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_iq(c, host, iq_format, gain, C, T, pitch, IQ_FROM_HOST | IQ_STAGED);
+}
+int m17hip_upload_iq_device_async(m17hip_ctx* c, const void* dev, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_iq(c, dev, iq_format, gain, C, T, pitch, IQ_STAGED);
+}
+int m17hip_iq_bytes(m17hip_ctx* c, uint64_t* bytes)
+{
+    if (!c || !bytes) return M17HIP_EINVAL;
+    *bytes = c->iq_carry.size() * sizeof(float2) + c->iq_raw.size();
+    return M17HIP_OK;
+}
 
 int m17hip_input_format(m17hip_ctx* c, int* stream_format, uint64_t* f32_bytes)
 {
@@ -1830,6 +1958,7 @@ int m17hip_demod_reset(m17hip_ctx* c)
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(c->hist_f, 0, c->hist_f.size() * sizeof(float), c->stream));
     }
+    if (int r = iq_fresh_feed(c, nullptr, 0)) return r;   // (a context that has seen IQ input: every channel's feed starts over)
     HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
     hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->bert_state, c->maxC);
     HIPCHK(c, hipGetLastError());
@@ -1878,6 +2007,10 @@ int m17hip_demod_reset_channels(m17hip_ctx* c, const uint32_t* channels, uint32_
     // The carrier-detect tick grid is the context's: K3's table rows, K2's replay, K5 and the gate forecast all find a tick as position / 192.  A fresh
     // demodulator's update points fall on ITS tick ends, so its stream can only begin where a tick of the context does.
     if (c->pos % TICK != 0) return M17HIP_ESTATE;
+    if (c->iq_carry) {   // (a context that has seen IQ input: the listed channels' feeds start over with the next IQ block uploaded)
+        GUARD(c);
+        if (int r = iq_fresh_feed(c, channels, n)) return r;
+    }
     mark_channels(c, channels, n);
     return M17HIP_OK;
 }

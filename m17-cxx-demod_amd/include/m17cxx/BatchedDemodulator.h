@@ -5,6 +5,7 @@
 
 #include "../../../include/m17hip.h"
 
+#include <complex>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +63,19 @@ public:
         check(m17hip_upload_f32(ctx_, host, channels, samples, pitch), "m17hip_upload_f32");
         channels_ = channels; samples_ = samples;
     }
+    // Complex IQ input, one narrowband 48 kSPS stream per channel (m17hip_upload_iq): gain * arg(x[n] conj(x[n-1])) is computed on the device into
+    // the float input slab — a float stream from there on.  [channels][samples] interleaved I,Q as complex<float> or as int16 pairs, row pitch in
+    // complex samples.  IQ blocks continue one another per channel in call order; reset() / reset_channels() start a feed over.
+    void upload_iq(const std::complex<float>* host, uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_iq(ctx_, host, M17HIP_IQ_F32, gain, channels, samples, pitch), "m17hip_upload_iq");
+        channels_ = channels; samples_ = samples;
+    }
+    void upload_iq(const int16_t (*host)[2], uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_iq(ctx_, host, M17HIP_IQ_I16, gain, channels, samples, pitch), "m17hip_upload_iq");
+        channels_ = channels; samples_ = samples;
+    }
     // The input generated on the device from the caller's own transmissions, one per channel (m17hip_synth_tx_i16: the framing of
     // apps/m17-mod.cpp:264-504, 509-564 around lsf30[channels][30] and rows[n_rows][32]; impairments and seeding from `base`)
     void synth_tx(const m17_synth_params& base, const m17_tx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_rows, uint32_t channels,
@@ -109,6 +123,16 @@ public:
     void stage(const float* pinned_host, uint32_t channels, uint32_t samples, size_t pitch)
     {
         check(m17hip_upload_f32_async(ctx_, pinned_host, channels, samples, pitch), "m17hip_upload_f32_async");
+        channels_ = channels; samples_ = samples;
+    }
+    void stage_iq(const std::complex<float>* pinned_host, uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_iq_async(ctx_, pinned_host, M17HIP_IQ_F32, gain, channels, samples, pitch), "m17hip_upload_iq_async");
+        channels_ = channels; samples_ = samples;
+    }
+    void stage_iq(const int16_t (*pinned_host)[2], uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_iq_async(ctx_, pinned_host, M17HIP_IQ_I16, gain, channels, samples, pitch), "m17hip_upload_iq_async");
         channels_ = channels; samples_ = samples;
     }
     void front(uint32_t flags = 0) { check(m17hip_demod_front(ctx_, channels_, samples_, flags), "m17hip_demod_front"); }

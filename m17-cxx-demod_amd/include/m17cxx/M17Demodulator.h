@@ -122,12 +122,35 @@ struct M17Demodulator
             demodState = (DemodState)cpu_->state();
             return;
         }
+        if (!iq_buffer_.empty()) run_iq_block();   // (IQ pushed before this sample comes before it)
         buffer_.push_back((float)input);
         if (buffer_.size() == block_) run_block();
     }
 
+    // One complex IQ sample of a narrowband FM channel at 48 kSPS in front of the demodulator: gain * arg(x[n] conj(x[n-1])) is the sample the
+    // demodulator receives (detail/core.h fm_discriminate; an int16 pair converts exactly).  The GPU path buffers the IQ and discriminates it on the device
+    // (m17hip_upload_iq); the host form computes the same words here.  The feed begins from a zero sample: the first output is +0.
+    void iq(float i, float q)
+    {
+        if (cpu_) {
+            const float y = core::fm_discriminate(i, q, iq_prev_[0], iq_prev_[1], iq_gain_);
+            iq_prev_[0] = i; iq_prev_[1] = q;
+            cpu_->step((FloatType)y);
+            demodState = (DemodState)cpu_->state();
+            return;
+        }
+        if (!buffer_.empty()) run_block();
+        iq_buffer_.push_back({i, q});
+        if (iq_buffer_.size() == block_) run_iq_block();
+    }
+    void iq_gain(float gain) { iq_gain_ = gain; }   // finite and > 0; 1 = radians per sample (the demodulator normalises by its own deviation estimate)
+
     // demodulate what is buffered (end of input); safe to call at any time
-    void flush() { if (gpu_ && !buffer_.empty()) run_block(); }
+    void flush()
+    {
+        if (gpu_ && !buffer_.empty()) run_block();
+        if (gpu_ && !iq_buffer_.empty()) run_iq_block();
+    }
     bool on_gpu() const { return gpu_ != nullptr; }
 
     bool locked() const { return dcd_; }
@@ -176,8 +199,19 @@ private:
     }
     void run_block()
     {
+        gpu_->upload(buffer_.data(), 1, (uint32_t)buffer_.size(), buffer_.size());
+        buffer_.clear();
+        run_uploaded();
+    }
+    void run_iq_block()
+    {
+        gpu_->upload_iq(iq_buffer_.data(), 1, (uint32_t)iq_buffer_.size(), iq_buffer_.size(), iq_gain_);
+        iq_buffer_.clear();
+        run_uploaded();
+    }
+    void run_uploaded()
+    {
         auto& gpu_ = *this->gpu_;
-        gpu_.upload(buffer_.data(), 1, (uint32_t)buffer_.size(), buffer_.size());
         gpu_.run();
         const auto frames = gpu_.frames();
         const auto diags = gpu_.diag_log();
@@ -190,13 +224,14 @@ private:
             else deliver(diags[g++]);
         }
         demodState = (DemodState)gpu_.diagnostics()[0].demod_state;
-        buffer_.clear();
     }
 
     std::unique_ptr<BatchedDemodulator> gpu_;                        // one of the two
     std::unique_ptr<detail::ScalarDemodulator<FloatType>> cpu_;
     callback_t callback_;
     std::vector<float> buffer_;
+    std::vector<std::complex<float>> iq_buffer_;   // (one of the two holds samples at a time)
+    float iq_gain_ = 1.0f, iq_prev_[2] = {0.0f, 0.0f};
     uint32_t block_;
     bool dcd_ = false;
     bool passall_ = false;

@@ -29,7 +29,7 @@ DIAG = np.dtype(
 assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
-KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7}
+KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -68,8 +68,10 @@ EXPORTS = [
     "m17hip_voice_fetch", "m17hip_voice_device", "m17hip_calls_fetch", "m17hip_voice_feed",
     "m17hip_upload_f32", "m17hip_upload_f32_device", "m17hip_upload_f32_async", "m17hip_upload_f32_device_async", "m17hip_download_f32",
     "m17hip_input_format",
+    "m17hip_upload_iq", "m17hip_upload_iq_device", "m17hip_upload_iq_async", "m17hip_upload_iq_device_async", "m17hip_iq_bytes",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
+IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
 ETRUNC = -6
 EOVERFLOW = -5
 COMM_ID_BYTES = 128
@@ -249,6 +251,70 @@ class Context:
         self.C, self.T = int(channels), int(samples)
         self._chk(self._by_dtype("_device_async", dtype)(self.h, C.c_void_p(int(dev_ptr)), C.c_uint32(self.C), C.c_uint32(self.T),
                                                          C.c_size_t(self.T if pitch is None else pitch)))
+
+    # ---- complex IQ input: the FM discriminator on the device (m17hip_upload_iq*) ---------------------------------
+    def upload_iq(self, samples, gain=1.0):
+        """The input of the next run as complex IQ, one narrowband 48 kSPS stream per channel: gain * arg(x[n] conj(x[n-1])) goes into the float
+        input slab (a float stream from there on; download_f32 returns it).  `samples`: numpy complex64 [C][T], numpy int16 [C][T][2] (I, Q), or a
+        torch tensor of either ON THE DEVICE, which is read where it lies (m17hip_upload_iq_device).  The context's streams are non-blocking and do
+        not wait for the stream that produced the tensor: it must be COMPLETE when this is called (torch.cuda.synchronize(), or the producer's
+        stream synchronised).  IQ blocks continue one another per channel in call order; reset() / reset_channels() start a feed over."""
+        if hasattr(samples, "data_ptr"):   # a torch tensor
+            t = samples
+            if not t.is_cuda:
+                return self.upload_iq(t.numpy(), gain)
+            if t.is_complex():
+                if str(t.dtype) != "torch.complex64":
+                    raise TypeError(f"IQ samples are complex64 or int16 pairs, not {t.dtype}")
+                if t.dim() == 1:
+                    t = t[None, :]
+                fmt = IQ_F32
+            else:
+                if str(t.dtype) != "torch.int16" or t.shape[-1] != 2:
+                    raise TypeError("IQ samples are complex64 [C][T] or int16 [C][T][2]")
+                if t.dim() == 2:
+                    t = t[None, :, :]
+                fmt = IQ_I16
+            t = t.contiguous()   # (the call below has read it when it returns)
+            return self.upload_iq_device(t.data_ptr(), int(t.shape[0]), int(t.shape[1]), iq_format=fmt, gain=gain)
+        a = np.asarray(samples)
+        if a.dtype == np.complex64:
+            a = np.ascontiguousarray(a)
+            if a.ndim == 1:
+                a = a[None, :]
+            fmt = IQ_F32
+        elif a.dtype == np.int16 and a.ndim >= 2 and a.shape[-1] == 2:
+            a = np.ascontiguousarray(a)
+            if a.ndim == 2:
+                a = a[None, :, :]
+            fmt = IQ_I16
+        else:
+            raise TypeError("IQ samples are complex64 [C][T] or int16 [C][T][2]")
+        self.C, self.T = int(a.shape[0]), int(a.shape[1])
+        self._chk(self.lib.m17hip_upload_iq(self.h, _ptr(a), C.c_int(fmt), C.c_float(gain), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(self.T)))
+
+    def _upload_iq_raw(self, name, ptr, channels, samples, pitch, iq_format, gain):
+        self.C, self.T = int(channels), int(samples)
+        self._chk(getattr(self.lib, name)(self.h, C.c_void_p(int(ptr)), C.c_int(iq_format), C.c_float(gain), C.c_uint32(self.C), C.c_uint32(self.T),
+                                          C.c_size_t(self.T if pitch is None else pitch)))
+
+    def upload_iq_async(self, host_ptr, channels, samples, pitch=None, iq_format=IQ_F32, gain=1.0):
+        """Stage the NEXT run's input from IQ in pinned host memory (pitch in complex samples; kept alive and unmodified until upload_wait)."""
+        self._upload_iq_raw("m17hip_upload_iq_async", host_ptr, channels, samples, pitch, iq_format, gain)
+
+    def upload_iq_device(self, dev_ptr, channels, samples, pitch=None, iq_format=IQ_F32, gain=1.0):
+        """IQ in device memory, complete when the call is made; the discriminator has read it when this returns."""
+        self._upload_iq_raw("m17hip_upload_iq_device", dev_ptr, channels, samples, pitch, iq_format, gain)
+
+    def upload_iq_device_async(self, dev_ptr, channels, samples, pitch=None, iq_format=IQ_F32, gain=1.0):
+        """Stage the NEXT run's input from IQ in device memory (complete when the call is made; kept alive and unmodified until upload_wait)."""
+        self._upload_iq_raw("m17hip_upload_iq_device_async", dev_ptr, channels, samples, pitch, iq_format, gain)
+
+    def iq_bytes(self):
+        """Device bytes the context holds for IQ input (the carry and the host forms' raw buffer); 0 if it has never seen IQ — m17hip_iq_bytes."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.m17hip_iq_bytes(self.h, C.byref(n)))
+        return n.value
 
     def input_alternate(self, channels=None, samples=None):
         """Stage, without a copy, the input the context's second slab still holds (two resident slabs that alternate)."""
@@ -442,7 +508,7 @@ class Context:
     def reset_channels(self, indices):
         """Fresh demodulators for the listed channels only (local indices, duplicates allowed), from the start of the NEXT run queued (run(), or
         the front() that begins it); every other channel goes on.  Between runs whose lengths are multiples of 192 samples, and not between
-        front() and run() (m17hip_demod_reset_channels)."""
+        front() and run() (m17hip_demod_reset_channels).  Their IQ feeds (upload_iq*) start over with the IQ blocks uploaded after this call."""
         idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32).reshape(-1))
         self._chk(self.lib.m17hip_demod_reset_channels(self.h, _ptr(idx) if idx.size else None, C.c_uint32(idx.size)))
 
