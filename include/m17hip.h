@@ -198,15 +198,64 @@ int m17hip_input_format(m17hip_ctx* ctx, int* stream_format, uint64_t* f32_bytes
  * not finite and > 0.  M17HIP_ESTATE: while a front end queued by m17hip_demod_front is waiting for its run, as for every upload.
  * Non-finite IQ samples stay in their channel (and reach the following block's first output through the carry).
  * m17hip_timing_get index 8 is the discriminator kernel.
- * Out of scope: a channeliser (wideband IQ -> channels), resampling to 48 kSPS, 8-bit IQ, de-emphasis and squelch. */
+ * Out of scope: de-emphasis and squelch (tuning channels out of wideband IQ by an integer decimation, 8-bit IQ included: ABI 609, below). */
 #define M17HIP_IQ_I16 1   /* interleaved int16 I,Q */
 #define M17HIP_IQ_F32 2   /* interleaved float32 I,Q */
 int m17hip_upload_iq(m17hip_ctx* ctx, const void* host, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 int m17hip_upload_iq_device(m17hip_ctx* ctx, const void* dev, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 int m17hip_upload_iq_async(m17hip_ctx* ctx, const void* host, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 int m17hip_upload_iq_device_async(m17hip_ctx* ctx, const void* dev, int iq_format, float gain, uint32_t channels, uint32_t samples, size_t pitch);
-/* Device memory the context holds for IQ input: the carry and the host forms' raw-IQ buffer.  0 for a context that has never seen IQ. */
+/* Device memory the context holds for IQ input: the carry and the host forms' raw-IQ buffer, and for wideband input (m17hip_wide_config) the taps, the
+ * sources' histories and the channel tables.  0 for a context that has never seen IQ. */
 int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
+
+/* ---- wideband IQ input: tune and decimate channels on the device (ABI 609) ----------------------------
+ * A receiver that covers thousands of channels delivers a few WIDE IQ streams at a multiple of 48 kSPS.  These entry points take S such sources at
+ * 48000 * decim samples per second; each of the context's channels names a source and a frequency offset, and one kernel (csrc/m17_wide_kernels.hpp) mixes,
+ * low-pass filters, keeps every decim-th sample and discriminates straight into the float input slab:
+ *     mixed[m] = x[m] * conj(nco(fcw * m))                             (m counts the source's samples since the feed began; the product is taken mod 2^32)
+ *     z[n]     = sum_{i < ntaps} taps[i] * mixed[n decim + decim - 1 - i]
+ *     y[n]     = gain * arg(z[n] * conj(z[n-1]))
+ * Behind it the stream is a FLOAT STREAM exactly as after m17hip_upload_iq.  There is no reference file to cite: this is the stage the reference's users run
+ * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
+ * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
+ * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
+ * Out of scope, for a later pull request: polyphase / FFT channelisers, non-integer resampling, multi-stage decimation, per-source sample counts,
+ * squelch / RSSI. */
+#define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
+/* The filter m17hip_wide_config takes by default — what a user of rtl_fm leaves to its built-in low-pass: ntaps = 32 * decim + 1, a Blackman-windowed
+ * sinc with its cutoff at 5500 Hz of 48000 * decim, computed in double, scaled to unit DC gain and rounded to float.  No context is needed.  *ntaps is set
+ * whenever decim is valid (1..16); M17HIP_EINVAL if it is not, if ntaps is NULL, or if taps is NULL or capacity < *ntaps (nothing written to taps). */
+int m17hip_wide_default_taps(uint32_t decim, float* taps, uint32_t capacity, uint32_t* ntaps);
+/* What the command line of rtl_sdr / rtl_fm says once per receiver: `sources` wide streams (1..256) at 48000 * decim (decim 1..16) in iq_format
+ * (M17HIP_IQ_I16, M17HIP_IQ_F32 or M17HIP_IQ_U8), low-passed with taps[ntaps] (1..1024, finite; taps == NULL with ntaps == 0: the default taps).  It starts
+ * every source's feed over (history zero, sample count 0) and may be called again to reconfigure (it waits for the tuner's launches in flight, not for a
+ * demodulation run; a channel whose source no longer exists goes back to source 0, offset 0).  The channels' carries are left as they are.
+ * M17HIP_EINVAL outside those limits; M17HIP_ESTATE between m17hip_demod_front and its run. */
+int m17hip_wide_config(m17hip_ctx* ctx, uint32_t sources, uint32_t decim, int iq_format, const float* taps, uint32_t ntaps);
+/* What rtl_fm's -f says per process: local channel c < n listens to source[c] at fcw[c] / 2^32 * 48000 * decim Hz from that source's centre (a signed
+ * 32-bit frequency word).  Entries at n and above keep their value; a fresh table is all (0, 0).  It applies to the blocks uploaded AFTER the call — a
+ * block already staged keeps the table it was tuned with — and it never waits for anything in flight (two device copies take turns, as for
+ * m17hip_set_channel_polarity).  A retuned channel's carry (the last z) belongs to its OLD frequency: the first output behind a retune is one sample of
+ * that mismatch; m17hip_demod_reset_channels is the clean cut.
+ * M17HIP_EINVAL, with nothing changed: n > max_channels, a source at or above `sources`, NULL with n > 0.  M17HIP_ESTATE before m17hip_wide_config. */
+int m17hip_wide_channels(m17hip_ctx* ctx, const uint32_t* source, const int32_t* fcw, uint32_t n);
+/* The input of `channels` channels from one block of every source: what the pipe from rtl_sdr delivers.  p: [sources][pitch] interleaved I,Q of the
+ * configured format; `samples` counts OUTPUTS per channel at 48 kSPS, every source row holds samples * decim complex samples, and pitch counts complex
+ * samples (>= samples * decim).  The four functions are the four ways in of m17hip_upload_iq with its staging-pair semantics (m17hip_input_alternate,
+ * m17hip_demod_front and m17hip_upload_wait work as for floats); the device forms read the caller's memory directly (a sample aligned to its own size),
+ * under the completeness rule stated for m17hip_upload_iq_device*; the host forms copy the raw block into the buffer m17hip_upload_iq's host forms use.
+ * They make a float stream: on an int16 stream M17HIP_ESTATE, as for m17hip_upload_iq; M17HIP_ESTATE also before m17hip_wide_config and between
+ * m17hip_demod_front and its run.  M17HIP_EINVAL as for m17hip_upload_iq, the gain rule included.
+ * THE FEED: blocks continue one another in call order.  Per source the last ntaps - 1 converted samples are carried on the device, and the context keeps
+ * ONE running sample count: all sources advance together.  Per channel the carry is the float2 of ABI 608, here the last z (zero: the first output is +0).
+ * m17hip_demod_reset zeroes histories, count and carries; m17hip_demod_reset_channels zeroes the listed channels' carries at once and leaves the sources
+ * alone — they are not the channel's.  A context may use this family and m17hip_upload_iq* on one stream: the carry is then whatever the last block left.
+ * Non-finite samples stay in the channels that listen to their source.  m17hip_timing_get index 9 is the tuner; m17hip_iq_bytes counts its memory. */
+int m17hip_upload_wide(m17hip_ctx* ctx, const void* host, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_wide_device(m17hip_ctx* ctx, const void* dev, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_wide_async(m17hip_ctx* ctx, const void* host, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_upload_wide_device_async(m17hip_ctx* ctx, const void* dev, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
@@ -672,7 +721,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * which: 0 = fir_rrc150, 1 = dcd, 2 = demod_seq, 3 = viterbi/decode_frames, 4 = correlator, 5 = compaction,
  * 6 = limit_track (the limit filter run ahead of demod_seq; in m17hip_fir_correlator the limit filter's chain, 4 = its correlations),
  * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode),
- * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block). */
+ * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block),
+ * 9 = tune (the tuner of m17hip_upload_wide*: one launch per wideband block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -7,6 +7,7 @@
 #include "m17_decode_device.hpp"
 #include "m17_frontend_kernels.hpp"
 #include "m17_iq_kernels.hpp"
+#include "m17_wide_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -32,7 +33,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -102,6 +103,7 @@ class TurnTable {
 public:
     bool live() const { return t_[cur_].live; }                // the current copy holds a published table
     const uint32_t* dev() const { return t_[cur_].dev; }       // (the current copy, on the device)
+    size_t words() const { return t_[0].dev.size() + t_[1].dev.size(); }   // device words held by both copies
     hipError_t begin_write(size_t cap, uint32_t** staging)
     {
         if (live()) cur_ ^= 1;   // (a write that failed half way is made again into the same copy)
@@ -263,6 +265,21 @@ struct m17hip_ctx {
     DevBuf<char> iq_raw;              // rows of round_up(T, 4) samples of the latest host block's format
     Event ev_iq;
     hipStream_t iq_last = nullptr;    // the stream ev_iq was recorded on (nullptr: never)
+    // WIDEBAND IQ INPUT (m17hip_wide_config, m17hip_upload_wide): S sources at 48 kSPS x decim, every channel tuned to one of them by tune_kernel, which
+    // writes the float slabs as the discriminator does and keeps its last z in iq_carry.  Of its own: the taps, the sources' histories (the last ntaps - 1
+    // converted samples each; two copies that take turns, wide_par names the one to read), the z a launch leaves for wide_carry_kernel, and the channel table
+    // [source[maxC] | fcw[maxC]] — on the host here, on the device in a turn-taking table, so m17hip_wide_channels touches no stream and a queued
+    // block keeps the table it was tuned with.  ev_iq orders these launches across the two streams like the discriminator's.
+    struct Wide {
+        uint32_t S = 0, R = 0, L = 0; int fmt = 0;   // S == 0: not configured
+        DevBuf<float> taps; DevBuf<float2> hist[2], znew;
+        int par = 0;
+        uint64_t count = 0;               // wideband samples per source since the feed began
+        std::vector<uint32_t> table;      // [2 * maxC]
+        bool dirty = true;
+        TurnTable dev;
+        size_t bytes() const { return taps.size() * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size()) * sizeof(float2) + dev.words() * 4; }
+    } wide;
     const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
     {
         return f32_now() ? reinterpret_cast<const int16_t*>(fslab[slot].x + t0) : slab[slot].x + t0;
@@ -1145,7 +1162,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 608; }
+int m17hip_version(void) { return 609; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1546,8 +1563,13 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
 {
     if (!c->iq_carry) return M17HIP_OK;
     const hipStream_t st = c->iq_last;
-    if (!channels) HIPCHK(c, hipMemsetAsync(c->iq_carry, 0, (size_t)c->maxC * sizeof(float2), st));
-    else {
+    if (!channels) {
+        HIPCHK(c, hipMemsetAsync(c->iq_carry, 0, (size_t)c->maxC * sizeof(float2), st));
+        if (c->wide.S) {   // (the wideband sources' feeds as well: histories and sample count; the listed form leaves them alone — they are not a channel's)
+            for (auto& h : c->wide.hist) HIPCHK(c, hipMemsetAsync(h, 0, h.size() * sizeof(float2), st));
+            c->wide.count = 0;
+        }
+    } else {
         std::vector<uint32_t> v(channels, channels + n);
         std::sort(v.begin(), v.end());
         for (size_t i = 0; i < v.size();) {
@@ -1614,6 +1636,97 @@ static int upload_iq(m17hip_ctx* c, const void* p, int iq_format, float gain, ui
     return M17HIP_OK;
 }
 
+// ---- wideband IQ input (ABI 609): the tuner in front of the float slab -----------------------------------------------------------------------
+// Blackman-windowed sinc, cutoff 5500 Hz at 48000 * decim, 32 * decim + 1 taps, in double; unit DC gain, then rounded to float
+static void wide_default(uint32_t R, float* taps)
+{
+    const uint32_t L = 32 * R + 1;
+    const double pi = 3.14159265358979323846, fc = 5500.0 / (48000.0 * R), mid = 0.5 * (L - 1);
+    std::vector<double> h(L);
+    double sum = 0.0;
+    for (uint32_t i = 0; i < L; ++i) {
+        const double t = (double)i - mid, x = 2.0 * pi * fc * t;
+        const double sinc = t == 0.0 ? 2.0 * fc : std::sin(x) / (pi * t);
+        const double w = 0.42 - 0.5 * std::cos(2.0 * pi * i / (L - 1)) + 0.08 * std::cos(4.0 * pi * i / (L - 1));
+        h[i] = sinc * w;
+        sum += h[i];
+    }
+    for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
+}
+static size_t wide_sample_bytes(int fmt) { return fmt == M17HIP_IQ_I16 ? sizeof(short2) : fmt == M17HIP_IQ_F32 ? sizeof(float2) : sizeof(uchar2); }
+template <typename IQT>
+static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
+{
+    auto& w = c->wide;
+    const IQT* src = static_cast<const IQT*>(dev);
+    const uint32_t W = T * w.R, H = w.L - 1;
+    if (w.dirty || !w.dev.live()) {   // the channel table, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, w.dev.begin_write(w.table.size(), &staging));
+        std::memcpy(staging, w.table.data(), w.table.size() * 4);
+        HIPCHK(c, w.dev.publish(w.table.size(), st));
+        w.dirty = false;
+    }
+    HIPCHK(c, w.dev.before_read(st));
+    {
+        TimedK tm(c, KT_WIDE);
+        tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
+                  w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, w.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));   // (two readers: the main stream and the copy stream)
+    hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);   // (behind it: the next block's carries ...)
+    HIPCHK(c, hipGetLastError());
+    if (H) {                                                                                                            // (... and histories)
+        hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
+        HIPCHK(c, hipGetLastError());
+    }
+    w.par ^= 1;
+    w.count += W;
+    return iq_mark(c, st);
+}
+// The four ways in, through the discriminator's frame (upload_iq): the tuner takes the place of the copy.  `p`: [sources][pitch] samples of the configured format.
+static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
+{
+    if (!c || !p || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
+    if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    if (!w.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
+    const size_t W = (size_t)T * w.R;
+    if (pitch < W) return M17HIP_EINVAL;
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    int r;
+    InputTargetT<float> in;
+    float* x = nullptr;
+    hipStream_t st = nullptr;
+    if (how & IQ_STAGED) { if ((r = staging_target(c, x))) return r; st = c->copy; }
+    else { if ((r = input_target(c, in))) return r; x = in.x; st = in.st; }
+    if ((r = iq_order(c, st))) return r;
+    const size_t sb = wide_sample_bytes(w.fmt);
+    const void* dev = p;
+    if (how & IQ_FROM_HOST) {   // the raw block into the context's own buffer first
+        const size_t rp = round_up(W, IQ_LANE);
+        if (c->iq_raw.size() < (size_t)w.S * rp * sb) {
+            HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be read)
+            if ((r = alloc_code(c, c->iq_raw.grow((size_t)w.S * rp * sb, &c->last_hip)))) return r;
+        }
+        HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, p, pitch * sb, W * sb, w.S, hipMemcpyHostToDevice, st));
+        dev = c->iq_raw; pitch = rp;
+    }
+    r = w.fmt == M17HIP_IQ_I16 ? launch_tune<short2>(c, dev, pitch, x, C, T, gain, st)
+      : w.fmt == M17HIP_IQ_F32 ? launch_tune<float2>(c, dev, pitch, x, C, T, gain, st) : launch_tune<uchar2>(c, dev, pitch, x, C, T, gain, st);
+    if (r) return r;
+    if (how & IQ_STAGED) {
+        HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
+        staged_done(c, M17HIP_FORMAT_F32, C, T);
+    } else {
+        HIPCHK(c, hipStreamSynchronize(st));   // the caller's memory belongs to the caller again when this returns
+        input_done(c, in, C, T);
+    }
+    return M17HIP_OK;
+}
+
 }  // extern "C++"
 
 int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
@@ -1646,8 +1759,72 @@ int m17hip_upload_iq_device_async(m17hip_ctx* c, const void* dev, int iq_format,
 int m17hip_iq_bytes(m17hip_ctx* c, uint64_t* bytes)
 {
     if (!c || !bytes) return M17HIP_EINVAL;
-    *bytes = c->iq_carry.size() * sizeof(float2) + c->iq_raw.size();
+    *bytes = c->iq_carry.size() * sizeof(float2) + c->iq_raw.size() + c->wide.bytes();
     return M17HIP_OK;
+}
+
+int m17hip_wide_default_taps(uint32_t decim, float* taps, uint32_t capacity, uint32_t* ntaps)
+{
+    if (decim < 1 || decim > 16 || !ntaps) return M17HIP_EINVAL;
+    *ntaps = 32 * decim + 1;
+    if (!taps || capacity < *ntaps) return M17HIP_EINVAL;
+    wide_default(decim, taps);
+    return M17HIP_OK;
+}
+int m17hip_wide_config(m17hip_ctx* c, uint32_t sources, uint32_t decim, int iq_format, const float* taps, uint32_t ntaps)
+{
+    if (!c || sources < 1 || sources > 256 || decim < 1 || decim > 16) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    std::vector<float> h;
+    if (!taps && ntaps == 0) { h.resize(32 * decim + 1); wide_default(decim, h.data()); }
+    else {
+        if (!taps || ntaps < 1 || ntaps > 1024) return M17HIP_EINVAL;
+        for (uint32_t i = 0; i < ntaps; ++i) if (!std::isfinite(taps[i])) return M17HIP_EINVAL;
+        h.assign(taps, taps + ntaps);
+    }
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;
+    auto& w = c->wide;
+    const hipStream_t st = c->iq_last ? c->iq_last : c->stream;
+    int r;
+    if ((r = ensure_iq(c, st))) return r;
+    HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (a block tuned with the configuration before may still be in flight: its buffers go)
+    const uint32_t L = (uint32_t)h.size();
+    const size_t hn = (size_t)sources * std::max<uint32_t>(L - 1, 1);
+    w.S = 0;   // (not configured until all of it is there)
+    if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
+    for (auto& b : w.hist) if ((r = alloc_code(c, b.alloc(hn)))) return r;
+    if (!w.znew && (r = alloc_code(c, w.znew.alloc(c->maxC)))) return r;
+    HIPCHK(c, hipMemcpy(w.taps, h.data(), L * sizeof(float), hipMemcpyHostToDevice));
+    for (auto& b : w.hist) HIPCHK(c, hipMemsetAsync(b, 0, hn * sizeof(float2), st));
+    if ((r = iq_mark(c, st))) return r;
+    if (w.table.empty()) w.table.assign(2 * (size_t)c->maxC, 0u);
+    for (uint32_t ch = 0; ch < c->maxC; ++ch)   // (a channel on a source that is no longer there goes back to the fresh entry)
+        if (w.table[ch] >= sources) { w.table[ch] = 0; w.table[c->maxC + ch] = 0; }
+    w.dirty = true;
+    w.R = decim; w.L = L; w.fmt = iq_format; w.par = 0; w.count = 0;
+    w.S = sources;
+    return M17HIP_OK;
+}
+int m17hip_wide_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* fcw, uint32_t n)
+{
+    if (!c || n > c->maxC || (n > 0 && (!source || !fcw))) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    if (!w.S) return M17HIP_ESTATE;   // (which sources exist is m17hip_wide_config's to say)
+    for (uint32_t ch = 0; ch < n; ++ch) if (source[ch] >= w.S) return M17HIP_EINVAL;
+    for (uint32_t ch = 0; ch < n; ++ch) { w.table[ch] = source[ch]; w.table[c->maxC + ch] = (uint32_t)fcw[ch]; }
+    w.dirty = true;   // (the next block uploaded brings it to the device: nothing is queued and nothing waited for here)
+    return M17HIP_OK;
+}
+int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }
+int m17hip_upload_wide_device(m17hip_ctx* c, const void* dev, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, dev, gain, C, T, pitch, 0); }
+int m17hip_upload_wide_async(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST | IQ_STAGED);
+}
+int m17hip_upload_wide_device_async(m17hip_ctx* c, const void* dev, float gain, uint32_t C, uint32_t T, size_t pitch)
+{
+    return upload_wide(c, dev, gain, C, T, pitch, IQ_STAGED);
 }
 
 int m17hip_input_format(m17hip_ctx* c, int* stream_format, uint64_t* f32_bytes)

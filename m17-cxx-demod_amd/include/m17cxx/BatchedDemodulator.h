@@ -5,6 +5,7 @@
 
 #include "../../../include/m17hip.h"
 
+#include <cmath>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -76,6 +77,25 @@ public:
         check(m17hip_upload_iq(ctx_, host, M17HIP_IQ_I16, gain, channels, samples, pitch), "m17hip_upload_iq");
         channels_ = channels; samples_ = samples;
     }
+    // Wideband IQ input (m17hip_wide_config, m17hip_wide_channels, m17hip_upload_wide): `sources` wide streams at 48000 * decim, every channel tuned to
+    // one of them on the device — mixed to its offset, low-passed with `taps` (none: the default taps), decimated and discriminated into the float input
+    // slab.  A block is [sources][pitch] interleaved I,Q of the configured format with samples * decim complex samples per row; `samples` counts outputs.
+    void wide_config(uint32_t sources, uint32_t decim, int iq_format = M17HIP_IQ_I16, const float* taps = nullptr, uint32_t ntaps = 0)
+    {
+        check(m17hip_wide_config(ctx_, sources, decim, iq_format, taps, ntaps), "m17hip_wide_config");
+    }
+    void wide_channels(const uint32_t* source, const int32_t* fcw, uint32_t n) { check(m17hip_wide_channels(ctx_, source, fcw, n), "m17hip_wide_channels"); }
+    // the frequency word of an offset in Hz from the source's centre, rounded to the nearest word
+    static int32_t wide_fcw(double offset_hz, uint32_t decim)
+    {
+        const double w = std::nearbyint(offset_hz / (48000.0 * decim) * 4294967296.0);
+        return (int32_t)(uint32_t)(int64_t)w;
+    }
+    void upload_wide(const void* host, uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_wide(ctx_, host, gain, channels, samples, pitch), "m17hip_upload_wide");
+        channels_ = channels; samples_ = samples;
+    }
     // The input generated on the device from the caller's own transmissions, one per channel (m17hip_synth_tx_i16: the framing of
     // apps/m17-mod.cpp:264-504, 509-564 around lsf30[channels][30] and rows[n_rows][32]; impairments and seeding from `base`)
     void synth_tx(const m17_synth_params& base, const m17_tx* tx, const uint8_t* lsf30, const uint8_t* rows, uint32_t n_rows, uint32_t channels,
@@ -133,6 +153,11 @@ public:
     void stage_iq(const int16_t (*pinned_host)[2], uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
     {
         check(m17hip_upload_iq_async(ctx_, pinned_host, M17HIP_IQ_I16, gain, channels, samples, pitch), "m17hip_upload_iq_async");
+        channels_ = channels; samples_ = samples;
+    }
+    void stage_wide(const void* pinned_host, uint32_t channels, uint32_t samples, size_t pitch, float gain = 1.0f)
+    {
+        check(m17hip_upload_wide_async(ctx_, pinned_host, gain, channels, samples, pitch), "m17hip_upload_wide_async");
         channels_ = channels; samples_ = samples;
     }
     void front(uint32_t flags = 0) { check(m17hip_demod_front(ctx_, channels_, samples_, flags), "m17hip_demod_front"); }

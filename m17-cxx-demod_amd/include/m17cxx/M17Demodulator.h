@@ -39,6 +39,7 @@
 #include <cstring>
 #include <functional>
 #include <optional>
+#include <stdexcept>
 #include <tuple>
 #include <vector>
 
@@ -123,6 +124,7 @@ struct M17Demodulator
             return;
         }
         if (!iq_buffer_.empty()) run_iq_block();   // (IQ pushed before this sample comes before it)
+        if (wide_decim_ && wide_buffer_.size() >= wide_decim_) run_wide_block();
         buffer_.push_back((float)input);
         if (buffer_.size() == block_) run_block();
     }
@@ -140,16 +142,73 @@ struct M17Demodulator
             return;
         }
         if (!buffer_.empty()) run_block();
+        if (wide_decim_ && wide_buffer_.size() >= wide_decim_) run_wide_block();
         iq_buffer_.push_back({i, q});
         if (iq_buffer_.size() == block_) run_iq_block();
     }
     void iq_gain(float gain) { iq_gain_ = gain; }   // finite and > 0; 1 = radians per sample (the demodulator normalises by its own deviation estimate)
 
-    // demodulate what is buffered (end of input); safe to call at any time
+    // One channel out of one WIDEBAND feed at 48000 * decim samples per second, offset_hz from its centre: the feed is mixed to the offset, low-passed
+    // with `taps` (empty: the default taps, m17hip_wide_default_taps), every decim-th sample kept and discriminated with iq_gain() — the stage the
+    // reference's users run rtl_fm for.  Starts the feed over.  On the GPU path it is m17hip_wide_config / m17hip_wide_channels; the host form computes the
+    // same words from detail/core.h (nco, ddc_mix, ddc_fir).  An int16 sample converts exactly, a uint8 one is core::ddc_u8.
+    void wide_config(uint32_t decim, double offset_hz, std::vector<float> taps = {})
+    {
+        if (taps.empty()) {
+            uint32_t n = 0;
+            taps.resize(32 * 16 + 1);
+            if (m17hip_wide_default_taps(decim, taps.data(), (uint32_t)taps.size(), &n) != M17HIP_OK) throw std::runtime_error("m17hip_wide_default_taps");
+            taps.resize(n);
+        }
+        wide_decim_ = decim;
+        wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, decim);
+        if (gpu_) {
+            flush();
+            const uint32_t source = 0;
+            const int32_t fcw = (int32_t)wide_fcw_;
+            gpu_->wide_config(1, decim, M17HIP_IQ_F32, taps.data(), (uint32_t)taps.size());
+            gpu_->wide_channels(&source, &fcw, 1);
+            wide_buffer_.clear();
+            return;
+        }
+        wide_taps_ = std::move(taps);
+        wide_m_ = 0;
+        wide_mixed_.clear();   // the mixed feed as (re, im): the zero history of ntaps - 1 samples first, at the phases it would have had
+        for (size_t k = wide_taps_.size() - 1; k > 0; --k) {
+            float re, im;
+            core::ddc_mix(0.0f, 0.0f, wide_fcw_, (uint32_t)(0 - k), re, im);
+            wide_mixed_.push_back(re); wide_mixed_.push_back(im);
+        }
+    }
+    // one wideband sample (wide_config first)
+    void wide(float i, float q)
+    {
+        if (!wide_decim_) throw std::logic_error("M17Demodulator::wide before wide_config");
+        if (cpu_) {
+            float re, im;
+            core::ddc_mix(i, q, wide_fcw_, (uint32_t)wide_m_, re, im);
+            wide_mixed_.push_back(re); wide_mixed_.push_back(im);
+            if (++wide_m_ % wide_decim_ != 0) return;
+            core::ddc_fir(wide_taps_.data(), (uint32_t)wide_taps_.size(), wide_mixed_.data() + wide_mixed_.size() - 2, re, im);
+            const float y = core::fm_discriminate(re, im, iq_prev_[0], iq_prev_[1], iq_gain_);   // (the carry the discriminator's own feed uses: the last z)
+            iq_prev_[0] = re; iq_prev_[1] = im;
+            if (wide_mixed_.size() > 2 * (wide_taps_.size() + 8192)) wide_mixed_.erase(wide_mixed_.begin(), wide_mixed_.end() - 2 * (wide_taps_.size() - 1));
+            cpu_->step((FloatType)y);
+            demodState = (DemodState)cpu_->state();
+            return;
+        }
+        if (!buffer_.empty()) run_block();
+        if (!iq_buffer_.empty()) run_iq_block();
+        wide_buffer_.push_back({i, q});
+        if (wide_buffer_.size() == (size_t)block_ * wide_decim_) run_wide_block();
+    }
+
+    // demodulate what is buffered (end of input); safe to call at any time (wideband samples short of one output stay buffered)
     void flush()
     {
         if (gpu_ && !buffer_.empty()) run_block();
         if (gpu_ && !iq_buffer_.empty()) run_iq_block();
+        if (gpu_ && wide_decim_ && wide_buffer_.size() >= wide_decim_) run_wide_block();
     }
     bool on_gpu() const { return gpu_ != nullptr; }
 
@@ -209,6 +268,13 @@ private:
         iq_buffer_.clear();
         run_uploaded();
     }
+    void run_wide_block()
+    {
+        const size_t n = wide_buffer_.size() / wide_decim_;
+        gpu_->upload_wide(wide_buffer_.data(), 1, (uint32_t)n, n * wide_decim_, iq_gain_);
+        wide_buffer_.erase(wide_buffer_.begin(), wide_buffer_.begin() + n * wide_decim_);
+        run_uploaded();
+    }
     void run_uploaded()
     {
         auto& gpu_ = *this->gpu_;
@@ -232,6 +298,10 @@ private:
     std::vector<float> buffer_;
     std::vector<std::complex<float>> iq_buffer_;   // (one of the two holds samples at a time)
     float iq_gain_ = 1.0f, iq_prev_[2] = {0.0f, 0.0f};
+    std::vector<std::complex<float>> wide_buffer_;   // the GPU path's wideband samples short of a block
+    std::vector<float> wide_taps_, wide_mixed_;      // the host form's filter and mixed feed
+    uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called)
+    uint64_t wide_m_ = 0;
     uint32_t block_;
     bool dcd_ = false;
     bool passall_ = false;

@@ -86,6 +86,59 @@ M17_HD float fm_discriminate(float i, float q, float pi, float pq, float gain)
     return gain * fm_phase(re, im);
 }
 
+// ---- a-1: the tuner in front of a0 (wideband IQ input, m17hip_upload_wide): mix to the channel's offset, low-pass, keep every R-th sample ----
+// No reference file: the reference's users run rtl_fm or a channeliser for it.  Written here, once, so that the kernel and the host form give the same words.
+// The oscillator: cos and sin of 2 pi p / 2^32 — the project's own, NOT sincosf (the device library's and glibc's disagree in the last bits).  The quadrant is
+// p >> 30; inside it t = bits 29..6 of p as a fraction (24 bits: the conversion and the scaling are exact, the low 6 bits of p are not looked at), and
+// sin(pi/2 t) = t S(t^2), cos(pi/2 t) = C(t^2): least-squares fits of degree 4 in t^2 over [0, 1], Horner form, multiply and add rounded apart; C's constant
+// term is 1, so t = 0 gives (1, 0) exactly and the four axis phases p = 0, 2^30, 2^31, 3 2^30 give (1,0), (0,1), (-1,0), (0,-1) with zeroes of either sign:
+// the quadrant's rotation is a swap and sign flips.  Absolute error of either component against float64, measured over all 2^26 distinct inputs: 2.8e-7
+// (bound asserted: 2^-21; tests/test_wide_input.py) — far below 2^-17, half an LSB of a full-scale int16 sample.
+M17_HD void nco(uint32_t p, float& c, float& s)
+{
+    const uint32_t q = p >> 30;
+    const float t = (float)((p >> 6) & 0xFFFFFFu) * 5.9604644775390625e-08f;
+    const float u = t * t;
+    float a = 0.000151263870f;
+    a = a * u; a = a + -0.00467313733f;
+    a = a * u; a = a + 0.0796890929f;
+    a = a * u; a = a + -0.645963490f;
+    a = a * u; a = a + 1.57079625f;
+    const float sn = t * a;
+    float b = 0.000862553774f;
+    b = b * u; b = b + -0.0208188817f;
+    b = b * u; b = b + 0.253655702f;
+    b = b * u; b = b + -1.23369920f;
+    b = b * u; b = b + 1.0f;
+    const float x = (q & 1u) ? sn : b, y = (q & 1u) ? b : sn;   // (cos, sin) of quadrant 0 or, swapped, (-cos, sin) of quadrant 1
+    c = (q == 1u || q == 2u) ? -x : x;
+    s = (q >= 2u) ? -y : y;
+}
+// Mixing is fm_cross(i, q, c, s): x * conj(nco), four products and two sums rounded apart.  The phase of wideband sample m of a feed is fcw * (uint32_t)m in
+// uint32 — exact modulo 2^32, no accumulator, so a block boundary cannot shift it.
+M17_HD void ddc_mix(float i, float q, uint32_t fcw, uint32_t m, float& re, float& im)
+{
+    float c, s;
+    nco(fcw * m, c, s);
+    fm_cross(i, q, c, s, re, im);
+}
+// One step of the low-pass filter's two chains, real and imaginary apart: acc = fma(h, v, acc).  z[n] = sum_{i=0}^{L-1} h[i] mixed[nR + R - 1 - i] is these
+// steps from (+0, +0) in the order i = 0, 1, ..., L - 1 and in no other; the fused form is exact by construction on both sides (as in scale_i16), and on the
+// device one packed fma does both chains.
+M17_HD void ddc_tap(float h, float vre, float vim, float& re, float& im)
+{
+    re = __builtin_fmaf(h, vre, re);
+    im = __builtin_fmaf(h, vim, im);
+}
+// the whole sum over a linear array: newest[0] is mixed[nR + R - 1] as (re, im), newest[-2 i] the sample i taps back
+M17_HD void ddc_fir(const float* h, uint32_t L, const float* newest, float& re, float& im)
+{
+    re = 0.0f; im = 0.0f;
+    for (uint32_t i = 0; i < L; ++i) ddc_tap(h[i], newest[-2 * (int64_t)i], newest[-2 * (int64_t)i + 1], re, im);
+}
+// an 8-bit IQ component in rtl_sdr's convention: unsigned around 127.5 (exact)
+M17_HD float ddc_u8(uint8_t u) { return (float)u - 127.5f; }
+
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).
 constexpr int RRC_TAPS = 150;

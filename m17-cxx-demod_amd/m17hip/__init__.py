@@ -29,7 +29,7 @@ DIAG = np.dtype(
 assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
-KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8}
+KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -69,9 +69,12 @@ EXPORTS = [
     "m17hip_upload_f32", "m17hip_upload_f32_device", "m17hip_upload_f32_async", "m17hip_upload_f32_device_async", "m17hip_download_f32",
     "m17hip_input_format",
     "m17hip_upload_iq", "m17hip_upload_iq_device", "m17hip_upload_iq_async", "m17hip_upload_iq_device_async", "m17hip_iq_bytes",
+    "m17hip_wide_default_taps", "m17hip_wide_config", "m17hip_wide_channels",
+    "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async", "m17hip_upload_wide_device_async",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
+IQ_U8 = 3                       # (wideband input only)
 ETRUNC = -6
 EOVERFLOW = -5
 COMM_ID_BYTES = 128
@@ -143,6 +146,31 @@ def load_library():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def wide_default_taps(decim):
+    """The default low-pass of wide_config for decimation `decim`: float32 [32 * decim + 1] — m17hip_wide_default_taps (no context, no GPU)."""
+    n = C.c_uint32(0)
+    taps = np.zeros(32 * 16 + 1, dtype=np.float32)
+    code = load_library().m17hip_wide_default_taps(C.c_uint32(decim), _ptr(taps), C.c_uint32(taps.size), C.byref(n))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_default_taps: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return taps[: n.value].copy()
+
+
+def wide_fcw(offset_hz, decim):
+    """The signed 32-bit frequency word of an offset in Hz at 48000 * decim samples per second, rounded to the nearest word (wide_channels)."""
+    w = int(round(float(offset_hz) / (48000.0 * decim) * 4294967296.0))
+    return (w + (1 << 31)) % (1 << 32) - (1 << 31)
+
+
+def _wide_array(a):
+    """(format, contiguous [S][W]... array) of a numpy wideband block: complex64 [S][W], int16 or uint8 [S][W][2]; a single source may leave [S] out."""
+    if a.dtype == np.complex64 and a.ndim in (1, 2):
+        return IQ_F32, np.ascontiguousarray(a if a.ndim == 2 else a[None, :])
+    if a.dtype in (np.int16, np.uint8) and a.ndim in (2, 3) and a.shape[-1] == 2:
+        return (IQ_I16 if a.dtype == np.int16 else IQ_U8), np.ascontiguousarray(a if a.ndim == 3 else a[None, :, :])
+    raise TypeError("a wideband block is complex64 [S][W], or int16 / uint8 [S][W][2]")
 
 
 def comm_get_id():
@@ -309,6 +337,68 @@ class Context:
     def upload_iq_device_async(self, dev_ptr, channels, samples, pitch=None, iq_format=IQ_F32, gain=1.0):
         """Stage the NEXT run's input from IQ in device memory (complete when the call is made; kept alive and unmodified until upload_wait)."""
         self._upload_iq_raw("m17hip_upload_iq_device_async", dev_ptr, channels, samples, pitch, iq_format, gain)
+
+    # ---- wideband IQ input: the tuner on the device (m17hip_wide_*, m17hip_upload_wide*) ------------------------
+    def wide_config(self, sources, decim, fmt=None, taps=None):
+        """`sources` wide IQ streams at 48000 * decim samples per second in format `fmt` (IQ_I16 — the default —, IQ_F32, IQ_U8), low-passed with
+        `taps` (None: wide_default_taps(decim)).  Starts every source's feed over; may be called again — m17hip_wide_config."""
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self._chk(self.lib.m17hip_wide_config(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_int(IQ_I16 if fmt is None else fmt), _ptr(t),
+                                              C.c_uint32(0 if t is None else t.size)))
+        self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+
+    def wide_channels(self, source, fcw):
+        """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""
+        src = np.ascontiguousarray(np.asarray(source, dtype=np.uint32).reshape(-1))
+        w = np.ascontiguousarray(np.asarray(fcw, dtype=np.int64).reshape(-1).astype(np.int32))
+        if src.size != w.size:
+            raise ValueError("one source and one frequency word per channel")
+        self._chk(self.lib.m17hip_wide_channels(self.h, _ptr(src) if src.size else None, w.ctypes.data_as(C.c_void_p) if w.size else None, C.c_uint32(src.size)))
+
+    def upload_wide(self, x, gain=1.0, staged=False, channels=None):
+        """The input of the next run from one block of every source: numpy complex64 [S][W], int16 or uint8 [S][W][2] (W = outputs * decim; the dtype must
+        be the configured format), or a torch tensor of those ON THE DEVICE, COMPLETE when this is called (see upload_iq).  `channels` (default: the
+        context's) are tuned, filtered, decimated and discriminated into the float input slab.  staged: for the NEXT run, on the copy stream (host memory
+        then has to be pinned and kept unmodified until upload_wait; so has a device tensor)."""
+        dev = hasattr(x, "data_ptr") and x.is_cuda
+        if hasattr(x, "data_ptr"):
+            kinds = {"torch.complex64": IQ_F32, "torch.int16": IQ_I16, "torch.uint8": IQ_U8}
+            f = kinds.get(str(x.dtype))
+            if f is None or (f != IQ_F32 and (x.dim() < 2 or x.shape[-1] != 2)) or (f == IQ_F32 and x.dim() not in (1, 2)):
+                raise TypeError("a wideband block is complex64 [S][W], or int16 / uint8 [S][W][2]")
+            if not dev:
+                return self.upload_wide(x.numpy(), gain, staged, channels)
+            a = x.contiguous()
+            if (f == IQ_F32 and a.dim() == 1) or (f != IQ_F32 and a.dim() == 2):
+                a = a[None]
+            ptr = a.data_ptr()
+        else:
+            f, a = _wide_array(np.asarray(x))
+            ptr = a.ctypes.data
+        S, R, fmt = getattr(self, "_wide", (0, 0, 0))
+        if not S:
+            raise M17HipError("m17hip error -4: wide_config has not been called")
+        if f != fmt or a.shape[0] != S or a.shape[1] == 0 or a.shape[1] % R:
+            raise TypeError(f"a block of the configured format {fmt} with {S} sources and a multiple of {R} samples per source")
+        self._keep = a   # (a staged block is read until upload_wait)
+        name = "m17hip_upload_wide" + ("_device" if dev else "") + ("_async" if staged else "")
+        self._upload_wide_raw(name, ptr, self.max_channels if channels is None else channels, a.shape[1] // R, a.shape[1], gain)
+
+    def _upload_wide_raw(self, name, ptr, channels, samples, pitch, gain):
+        self.C, self.T = int(channels), int(samples)
+        self._chk(getattr(self.lib, name)(self.h, C.c_void_p(int(ptr)), C.c_float(gain), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(pitch)))
+
+    def upload_wide_async(self, host_ptr, channels, samples, pitch, gain=1.0):
+        """Stage the NEXT run's input from a wideband block in pinned host memory (pitch in complex samples; kept unmodified until upload_wait)."""
+        self._upload_wide_raw("m17hip_upload_wide_async", host_ptr, channels, samples, pitch, gain)
+
+    def upload_wide_device(self, dev_ptr, channels, samples, pitch, gain=1.0):
+        """A wideband block in device memory, complete when the call is made; the tuner has read it when this returns."""
+        self._upload_wide_raw("m17hip_upload_wide_device", dev_ptr, channels, samples, pitch, gain)
+
+    def upload_wide_device_async(self, dev_ptr, channels, samples, pitch, gain=1.0):
+        """Stage the NEXT run's input from a wideband block in device memory (complete when the call is made; kept unmodified until upload_wait)."""
+        self._upload_wide_raw("m17hip_upload_wide_device_async", dev_ptr, channels, samples, pitch, gain)
 
     def iq_bytes(self):
         """Device bytes the context holds for IQ input (the carry and the host forms' raw buffer); 0 if it has never seen IQ — m17hip_iq_bytes."""

@@ -1,0 +1,93 @@
+"""The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
+    python tools/wide_time.py [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+int16 input, device form, default taps (L = 32 R + 1).  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
+launch); the time between two events on the context's main stream around the call and the wall time of the synchronous call are printed beside it.
+The floor counts what the algorithm needs from the shapes, at the f32 vector rate of the chip (64 FLOP per clock and SIMD: a packed fma wave instruction
+— two chains of 64 outputs by one tap — every 4 clocks, a plain one every 2):
+    filter:  C T L packed fma per lane, / 64 lanes
+    mixing:  C T R samples (each channel mixes its own copy: independent of the number of sources), MIX_OPS plain vector operations each — counted from
+             detail/core.h: the oscillator's 2 + 2 x 8 + 2 multiplies and adds and 9 integer / select steps, fm_cross's 6, 2 conversions, 3 address steps
+over 4 SIMDs x CUs x the shader clock seen while the blocks ran (read from sysfs, read only)."""
+import glob, json, os, sys, threading, time
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
+import numpy as np
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'm17-cxx-demod_amd'))
+import m17hip
+
+S = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+PER = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+T = int(sys.argv[3]) if len(sys.argv) > 3 else 48000
+R = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+REP = int(sys.argv[5]) if len(sys.argv) > 5 else 10
+C = S * PER
+L = 32 * R + 1
+MIX_OPS = 40
+DEMOD_STEP_MS = (20.0, 23.0)   # the demodulation step of 4096 channels x 480 000 samples (README): scaled to this shape below
+
+
+class Clocks(threading.Thread):
+    """The highest current sclk (MHz) seen per card while it runs."""
+    def __init__(self):
+        super().__init__(daemon=True)
+        self.files = sorted(glob.glob('/sys/class/drm/card*/device/pp_dpm_sclk'))
+        self.seen, self.stop = {}, False
+
+    def run(self):
+        while not self.stop:
+            for f in self.files:
+                try:
+                    cur = [l for l in open(f).read().splitlines() if l.rstrip().endswith('*')]
+                    mhz = int(''.join(ch for ch in cur[0].split(':')[1] if ch.isdigit())) if cur else 0
+                    self.seen[f.split('/')[4]] = max(self.seen.get(f.split('/')[4], 0), mhz)
+                except Exception:
+                    pass
+            time.sleep(0.002)
+
+
+ctx = m17hip.Context(C, T)
+stream = ctx.torch_stream()
+g = torch.Generator(device='cuda').manual_seed(609)
+x = torch.randint(-20000, 20000, (S, T * R, 2), dtype=torch.int16, device='cuda', generator=g)
+torch.cuda.synchronize()
+ctx.wide_config(S, R, m17hip.IQ_I16)
+rng = np.random.default_rng(609)
+ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, R) for f in rng.uniform(-24000.0 * R, 24000.0 * R, C)])
+
+
+def call():
+    ctx.upload_wide_device(x.data_ptr(), C, T, T * R)
+
+
+clocks = Clocks()
+clocks.start()
+ctx.reset()
+call()   # warm-up (the table's upload, first launch)
+ctx.timing(True); ctx.timing_reset()
+ev, wall = [], []
+for _ in range(REP):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    t0 = time.perf_counter(); call(); wall.append((time.perf_counter() - t0) * 1e3)
+    b.record(stream)
+    b.synchronize()
+    ev.append(a.elapsed_time(b))
+ms, n = ctx.timing_get("tune")
+ctx.timing(False)
+clocks.stop = True
+cus = torch.cuda.get_device_properties(0).multi_processor_count
+mhz = max(clocks.seen.values()) if clocks.seen else 2400
+cycles = C * T * L / 64 * 4 + C * T * R * MIX_OPS / 64 * 2
+floor_ms = cycles / (4 * cus * mhz * 1e6) * 1e3
+kernel_ms = ms / n
+step = [v * T / 480000.0 * C / 4096.0 for v in DEMOD_STEP_MS]
+print(json.dumps({
+    "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, "repeats": REP, "launches": n,
+    "kernel_ms": round(kernel_ms, 3), "stream_ms": [round(v, 3) for v in ev], "stream_ms_median": round(float(np.median(ev)), 3),
+    "wall_ms_median": round(float(np.median(wall)), 3),
+    "floor_ms": round(floor_ms, 3), "floor_filter_share": round(C * T * L / 64 * 4 / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
+    "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
+    "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
+}))
