@@ -236,26 +236,8 @@ def test_host_blocks_continue_one_another(feed_case):
 
 # ---- 3: table changes ------------------------------------------------------------------------------------------------------------------------------
 def _feeds(data, taps, src, fcw):
-    """One host-form tuner per channel, fed block by block; retune(c, source, fcw) moves a channel (its carry goes with it, the history is the source's)."""
-    class Feeds:
-        def __init__(self):
-            self.per_source = [wl.Tuner(taps, FEED_R, 0, FEED_GAIN) for _ in range(FEED_S)]   # (for the histories and the count alone)
-            self.src, self.fcw = list(src), list(fcw)
-            self.carry = [np.zeros(2, dtype=np.float32) for _ in src]
-
-        def block(self, a, b):
-            out = []
-            for c in range(len(self.src)):
-                s = self.src[c]
-                t = wl.Tuner(taps, FEED_R, int(self.fcw[c]), FEED_GAIN, count=self.per_source[s].count)
-                t.hist[:] = self.per_source[s].hist
-                t.carry[:] = self.carry[c]
-                out.append(t.block(data[s][a * FEED_R: b * FEED_R]))
-                self.carry[c] = t.carry
-            for s in range(FEED_S):
-                self.per_source[s].block(data[s][a * FEED_R: b * FEED_R])
-            return np.stack(out)
-    return Feeds()
+    """One host-form tuner per channel, fed block by block (wide_lib.Feeds at this module's decimation and gain)."""
+    return wl.Feeds(data, taps, src, fcw, FEED_R, FEED_GAIN)
 
 
 def test_table_changes_resets_and_what_a_staged_block_keeps(feed_case):
@@ -546,6 +528,116 @@ def test_state_rules_memory_and_timing(feed_case):
             ts[c].block(xi[FEED_SRC[c]])
         e = np.stack([iq.discriminate(nb[c], 1.0, ts[c].carry)[0] for c in range(Cn)])
         _assert_words(ctx.download_f32(), e, "a narrowband block behind a wideband one")
+    finally:
+        ctx.close()
+
+
+# ---- 5b: the limits m17hip_wide_config accepts, launched ----------------------------------------------------------------------------------------------
+# (16, 1024): the largest LDS the kernel is ever asked for (42 880 B); (1, 1024): one plane, the longest chain per plane; (16, 1023): a tap tail of 7
+# behind 127 groups of 8; (3, 1024): the last polyphase row holds one tap
+LIM_SHAPES = ((16, 1024), (1, 1024), (16, 1023), (3, 1024))
+LIM_C, LIM_T = 3, 511   # two tiles and one output
+LIM_SRC = np.array([0, 1, 0], dtype=np.uint32)
+LIM_FCW = np.array([-0x12345679, 1 << 30, INT32_MIN], dtype=np.int64)
+LIM_GAIN = 1.25
+F64_EXCLUDED_CAP = 0.02
+
+
+def _lim_sources(R, fmt, n=LIM_T):
+    """Two sources: the carriers the channels on each listen to (tests/test_wide_input.py's signal), so that the float64 bound on y speaks about nearly
+    every output."""
+    x = np.stack([wl.carriers(R, [LIM_FCW[c] for c in range(LIM_C) if LIM_SRC[c] == s], n, fmt, seed=6095 + s) for s in range(2)])
+    x.setflags(write=False)
+    return x
+
+
+@pytest.mark.parametrize("R,L", LIM_SHAPES)
+def test_tuner_at_the_limits_of_its_configuration(R, L):
+    """Shapes the one-hop test stops short of, all three formats, host and device sources: the host form's words; the int16 floats are also within the
+    derived bound of the float64 statement (tests/test_wide_input.py), which the reference is asked about first."""
+    taps = wl.hamming_taps(L)
+    ctx = m17hip.Context(LIM_C, LIM_T)
+    try:
+        for name, f in FMTS.items():
+            x = _lim_sources(R, f)
+            exp = wl.tune_channels(x, LIM_SRC, LIM_FCW, taps, R, LIM_GAIN)
+            if f == wl.IQ_I16:
+                for c in range(LIM_C):
+                    worst, excluded = wl.f64_check_y(exp[c], x[LIM_SRC[c]], taps, R, int(LIM_FCW[c]), LIM_GAIN)
+                    assert excluded <= F64_EXCLUDED_CAP, (R, L, c, excluded)
+            ctx.wide_config(2, R, f, taps)
+            ctx.wide_channels(LIM_SRC, LIM_FCW)
+            for way in (x, _dev(x)):
+                ctx.reset()
+                ctx.upload_wide(way, gain=LIM_GAIN)
+                got = ctx.download_f32()
+                _assert_words(got, exp, (R, L, name))
+                if f == wl.IQ_I16:
+                    for c in range(LIM_C):
+                        worst, _ = wl.f64_check_y(got[c], x[LIM_SRC[c]], taps, R, int(LIM_FCW[c]), LIM_GAIN)
+                        print(f"tuner on the device vs float64, R = {R}, L = {L}, channel {c}: y error {worst:.3f} of its bound")
+                        assert worst <= 1.0, (R, L, c, worst)
+    finally:
+        ctx.close()
+
+
+def test_blocks_far_shorter_than_the_history():
+    """(16, 1024): a feed of 1, 2 and 508 outputs — 16, 32 and 8128 samples against a history of 1023 — in place and staged by turns; every block finds what
+    the shorter ones before it left of the history, and the concatenation is the one-block result."""
+    R, L = 16, 1024
+    taps = wl.hamming_taps(L)
+    x = _lim_sources(R, wl.IQ_I16)
+    whole = wl.tune_channels(x, LIM_SRC, LIM_FCW, taps, R, LIM_GAIN)
+    ref = wl.Feeds(x, taps, LIM_SRC, LIM_FCW, R, LIM_GAIN)
+    dev = _dev(x)
+    sb, W = SB[wl.IQ_I16], LIM_T * R
+    ctx = m17hip.Context(LIM_C, 508)
+    try:
+        ctx.wide_config(2, R, wl.IQ_I16, taps)
+        ctx.wide_channels(LIM_SRC, LIM_FCW)
+        a = 0
+        for k, n in enumerate((1, 2, 508)):
+            e = ref.block(a, a + n)
+            assert np.array_equal(_u32(e), _u32(whole[:, a:a + n]))
+            if k == 1:
+                ctx.upload_wide_device_async(dev.data_ptr() + a * R * sb, LIM_C, n, W, LIM_GAIN)
+                ctx.run(channels=LIM_C, samples=n)
+            elif k == 0:
+                ctx.upload_wide_device(dev.data_ptr() + a * R * sb, LIM_C, n, W, LIM_GAIN)
+            else:
+                ctx.upload_wide(x[:, a * R: (a + n) * R], gain=LIM_GAIN)
+            _assert_words(ctx.download_f32(), e, ("block", k, n))
+            a += n
+        ctx.upload_wait()
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("fmt", ["f32", "i16"])
+def test_the_last_of_256_sources(fmt):
+    """256 sources of 64 outputs at R = 2, channels on sources 255, 128 and 0; every other source of the float array is NaN (of the int16 one: noise of
+    its own), so that a channel that read a wrong row — or a raw buffer sized by channels, not by sources — shows."""
+    R, S, n = 2, 256, 64
+    f = FMTS[fmt]
+    src = np.array([255, 128, 0], dtype=np.uint32)
+    taps = m17hip.wide_default_taps(R)
+    rng = np.random.default_rng(6096)
+    if f == wl.IQ_F32:
+        x = np.full((S, n * R), np.nan + 1j * np.nan, dtype=np.complex64)
+    else:
+        x = rng.integers(-32768, 32768, size=(S, n * R, 2)).astype(np.int16)
+    for c, s in enumerate(src):
+        x[s] = wl.carriers(R, [LIM_FCW[c]], n, f, seed=6097 + c)
+    exp = wl.tune_channels(x, src, LIM_FCW, taps, R, LIM_GAIN)
+    assert np.isfinite(exp).all() and len(set(_u32(exp[c]).tobytes() for c in range(3))) == 3
+    ctx = m17hip.Context(LIM_C, n)
+    try:
+        ctx.wide_config(S, R, f, taps)
+        ctx.wide_channels(src, LIM_FCW)
+        for way in (x, _dev(x)):
+            ctx.reset()
+            ctx.upload_wide(way, gain=LIM_GAIN)
+            _assert_words(ctx.download_f32(), exp, (fmt, "host" if way is x else "device"))
     finally:
         ctx.close()
 

@@ -174,6 +174,93 @@ def test_three_transmissions_in_one_wideband_carry_their_basebands_frames(baseba
         assert len(expect) >= 7 and got == expect, (R, case, f, len(got), len(expect))
 
 
+# ---- 4b: the whole operation against a plain float64 statement of it -------------------------------------------------------------------------------------
+# wide_lib.tune_f64 on wide_lib.carriers (600 outputs; the default taps at L = 32 R + 1, wide_lib.hamming_taps otherwise): mix at fcw m mod 2^32, filter from a zero history, keep sample n R + R - 1, gain arg(z[n] conj z[n-1]).  The bounds are DERIVED:
+#   |z_host - z_f64| <= scale (2^-20.5 + (L + 2) 2^-24), scale = sum|taps| max|x|: the oscillator's asserted 2^-21 on both components (sqrt 2 of it on
+#       the complex factor), one rounding of 2^-24 per tap of the fma chain, and two for the cross product that mixes a sample;
+#   |y_host - y_f64| (mod 2 pi) <= gain (2 bound / min|z| + 2^-20) wherever z[n] and z[n-1] of the reference both exceed 8 bound: each z is off by at most
+#       `bound`, which turns it by at most bound / |z|, and 2^-20 is fm_phase's asserted bound (tests/test_iq_input.py).
+# Measured here: the z error reaches at most 0.37 of its bound, the y error 0.13; the reference excludes at most 0.84 % of a case's outputs (cap: 2 %).
+F64_RS = (1, 2, 5, 16)
+F64_N = 600
+F64_GAIN = 1.25
+F64_WORDS = {"generic": -0x12345679, "+2^30": 1 << 30, "-2^30": -(1 << 30), "int32_min": -(1 << 31)}
+F64_CARRIER_HZ = 0.0   # the carrier's offset from the TUNED word: it is made where the channel listens, whatever the word
+F64_EXCLUDED_CAP = 0.02
+
+
+def _f64_response(taps, R, hz):
+    """|H| of the taps at `hz` (at 48000 R samples per second) over sum|taps|."""
+    h = np.asarray(taps, dtype=np.float64)
+    return abs(np.sum(h * np.exp(-2j * np.pi * hz / (48000.0 * R) * np.arange(h.size)))) / np.abs(h).sum()
+
+
+def _f64_taps(R, L):
+    return m17hip.wide_default_taps(R) if L == 32 * R + 1 else wl.hamming_taps(L)
+
+
+def _f64_signal(R, fcw, fmt, seed):
+    return wl.carriers(R, [fcw], F64_N, fmt, seed, offset_hz=F64_CARRIER_HZ)
+
+
+_f64_bounds = wl.f64_bound
+
+
+def _f64_compare(x, taps, R, fcw, what):
+    """(z error / its bound, y error / its bound, excluded share) of the host form against the float64 statement; the cap on the excluded share and the
+    passband are asserted on the reference alone, before the host form is looked at."""
+    L = taps.size
+    y64, z64, scale = wl.tune_f64(x, taps, R, fcw, F64_GAIN)
+    bound = _f64_bounds(scale, L)
+    mag = np.abs(z64)
+    ok = np.zeros(F64_N, dtype=bool)
+    ok[1:] = (mag[1:] > 8.0 * bound) & (mag[:-1] > 8.0 * bound)
+    excluded = 1.0 - ok.mean()
+    assert excluded <= F64_EXCLUDED_CAP, (what, excluded)
+    assert _f64_response(taps, R, F64_CARRIER_HZ) > 0.5, (what, "the tuned carrier lies inside the passband of these taps")
+    lo, hi = (np.int64(fcw) - np.int64(F64_WORDS["generic"])) % (1 << 32), 4294967296.0 / (48000.0 * R)   # (words per Hz)
+    if fcw != F64_WORDS["generic"] and 32 * R + 1 == L:
+        off = min(lo, (1 << 32) - lo) / hi
+        assert _f64_response(taps, R, off) < 0.01, (what, "the generic word's carrier, left in place, would lie outside the default taps' passband")
+    y, z = wl.Tuner(taps, R, fcw, F64_GAIN).block(x, want_z=True)
+    ez = float(np.abs(z.astype(np.complex128) - z64).max()) / bound
+    lowest = np.minimum(mag[1:], mag[:-1])[ok[1:]]
+    dy = np.abs(np.angle(np.exp(1j * (y.astype(np.float64) - y64) / F64_GAIN)))[ok] * F64_GAIN
+    ey = float((dy / (F64_GAIN * (2.0 * bound / lowest + 2.0 ** -20))).max())
+    assert y[0] == 0.0 and y64[0] == 0.0
+    return ez, ey, excluded
+
+
+@pytest.mark.parametrize("fmt", [wl.IQ_I16, wl.IQ_F32], ids=["i16", "f32"])
+@pytest.mark.parametrize("R", F64_RS)
+def test_the_whole_tuner_is_within_derived_bounds_of_float64(R, fmt):
+    worst = [0.0, 0.0, 0.0]
+    for L in sorted({1, R, 4 * R + 1, 32 * R + 1, 1024}):
+        taps = _f64_taps(R, L)
+        assert taps.size == L
+        for name, fcw in F64_WORDS.items():
+            x = _f64_signal(R, fcw, fmt, seed=6094 + L)
+            ez, ey, excluded = _f64_compare(x, taps, R, fcw, (R, L, name))
+            assert ez <= 1.0 and ey <= 1.0, (R, L, name, ez, ey)
+            worst = [max(a, b) for a, b in zip(worst, (ez, ey, excluded))]
+    print(f"tuner vs float64, R = {R}: z error {worst[0]:.3f} of its bound, y error {worst[1]:.3f}, excluded {100 * worst[2]:.2f} %")
+
+
+def test_a_reference_that_keeps_the_wrong_sample_misses_the_z_bound():
+    """The float64 statement with sample n R + R - 2 kept in place of n R + R - 1: the host form is orders of magnitude outside the bound it meets
+    against the right one — a tuner with the wrong decimation phase (or a tap shifted by one) could not pass the test above."""
+    R = 2
+    taps = m17hip.wide_default_taps(R)
+    fcw = F64_WORDS["generic"]
+    x = _f64_signal(R, fcw, wl.IQ_I16, seed=6094)
+    _, z = wl.Tuner(taps, R, fcw, F64_GAIN).block(x, want_z=True)
+    _, right, scale = wl.tune_f64(x, taps, R, fcw, F64_GAIN)
+    _, shifted, _ = wl.tune_f64(x, taps, R, fcw, F64_GAIN, keep=R - 2)
+    bound = _f64_bounds(scale, taps.size)
+    assert np.abs(z - right).max() <= bound
+    assert np.abs(z - shifted).max() > 1000.0 * bound
+
+
 # ---- 5: exports and refusals ---------------------------------------------------------------------------------------------------------------------------
 NEW = ["m17hip_wide_default_taps", "m17hip_wide_config", "m17hip_wide_channels", "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async",
        "m17hip_upload_wide_device_async"]
