@@ -220,8 +220,8 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: polyphase / FFT channelisers, non-integer resampling, multi-stage decimation, per-source sample counts,
- * squelch / RSSI. */
+ * Out of scope, for a later pull request: polyphase / FFT channelisers, non-integer resampling, per-source sample counts, squelch / RSSI.  (Sources above
+ * 16 x 48 kSPS: two stages, ABI 610, below.) */
 #define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
 /* The filter m17hip_wide_config takes by default — what a user of rtl_fm leaves to its built-in low-pass: ntaps = 32 * decim + 1, a Blackman-windowed
  * sinc with its cutoff at 5500 Hz of 48000 * decim, computed in double, scaled to unit DC gain and rounded to float.  No context is needed.  *ntaps is set
@@ -256,6 +256,36 @@ int m17hip_upload_wide(m17hip_ctx* ctx, const void* host, float gain, uint32_t c
 int m17hip_upload_wide_device(m17hip_ctx* ctx, const void* dev, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 int m17hip_upload_wide_async(m17hip_ctx* ctx, const void* host, float gain, uint32_t channels, uint32_t samples, size_t pitch);
 int m17hip_upload_wide_device_async(m17hip_ctx* ctx, const void* dev, float gain, uint32_t channels, uint32_t samples, size_t pitch);
+
+/* ---- wideband IQ input above 16 x: two decimation stages (ABI 610) -------------------------------------
+ * m17hip_wide_config stops at 48000 * 16 = 768 kSPS, and the rates a dongle is run at to cover many channels lie above it (rtl_sdr: 0.96, 1.44, 1.92, 2.4,
+ * 2.88 MSPS; at 2.4 MSPS one source holds 192 channels of 12.5 kHz).  Two integer stages, decim1 then decim2, each 1..16: the source's rate is
+ * 48000 * decim1 * decim2.  Per channel, one kernel (csrc/m17_wide2_kernels.hpp):
+ *     mixed[m] = x[m] * conj(nco(fcw * m))                             (as above; mixed[m] = 0 for m < 0)
+ *     u[p]     = sum_{i < ntaps1} taps1[i] * mixed[p decim1 + decim1 - 1 - i]
+ *     z[n]     = sum_{i < ntaps2} taps2[i] * u[n decim2 + decim2 - 1 - i]
+ *     y[n]     = gain * arg(z[n] * conj(z[n-1]))
+ * with the arithmetic of ABI 609 in both stages (ddc_mix per input sample, ddc_tap chains from +0 in tap order, fm_discriminate; core::ddc_fir2 is the host
+ * form of these words).  The frequency word means fcw / 2^32 * 48000 * decim1 * decim2 Hz.  The first filter is short: all it has to do is keep what the first
+ * decimation folds onto the channel out of it; the channel's own filter is the second, at 48000 * decim2.
+ * Out of scope: more than two stages, and folding the oscillator into per-channel complex first-stage taps (other arithmetic, other words). */
+/* The default taps of both stages.  Stage 2: m17hip_wide_default_taps(decim2) word for word (32 * decim2 + 1 taps).  Stage 1: 8 * decim1 + 1 taps, a
+ * Blackman-windowed sinc with its cutoff at 24000 * decim2 Hz of 48000 * decim1 * decim2, in double, unit DC gain, rounded to float (decim1 == 1: one tap
+ * of 1).  For decim1 and decim2 in 2..16 it is within 0.003 dB of unity over +-6 kHz and at least 69 dB down on every band k * 48000 * decim2 +- 12 kHz that
+ * the first decimation folds onto the channel; no claim is made for decim2 == 1.  No context is needed.  *ntaps1 and *ntaps2 are set whenever both
+ * decimations are valid; M17HIP_EINVAL if one is not, if ntaps1 or ntaps2 is NULL, or if a taps pointer is NULL or its capacity too small (nothing written). */
+int m17hip_wide_default_taps2(uint32_t decim1, uint32_t decim2, float* taps1, uint32_t cap1, uint32_t* ntaps1, float* taps2, uint32_t cap2, uint32_t* ntaps2);
+/* m17hip_wide_config in two stages: `sources` (1..256) at 48000 * decim1 * decim2 (each 1..16), taps1[ntaps1] (1..256) and taps2[ntaps2] (1..1024), all
+ * finite; a NULL pointer with a count of 0 selects that stage's default taps.  In every other respect it is m17hip_wide_config: it starts the feeds over, may
+ * be called again, waits for tuner launches in flight and never for a run, clears channels of sources that are gone, and returns M17HIP_ESTATE between
+ * m17hip_demod_front and its run.  The two calls replace one another: whichever was made last decides which kernel the next upload launches.
+ * m17hip_wide_channels and m17hip_upload_wide* serve both: under a two-stage configuration every source row holds samples * decim1 * decim2 complex
+ * samples and pitch is at least that; a row of more than 2^32 - 1 complex samples is M17HIP_EINVAL.
+ * THE FEED is the one described above.  Per source the last (ntaps2 - 1) * decim1 + ntaps1 - 1 converted samples are carried (the u in front of a block
+ * are recomputed from them); per channel nothing but the float2 carry (the last z), so resets, retunes and the staged-block rule read as above.
+ * m17hip_timing_get index 10 is this tuner (index 9 stays the single-stage one); m17hip_iq_bytes counts its memory. */
+int m17hip_wide_config2(m17hip_ctx* ctx, uint32_t sources, uint32_t decim1, const float* taps1, uint32_t ntaps1, uint32_t decim2, const float* taps2,
+                        uint32_t ntaps2, int iq_format);
 
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
@@ -722,7 +752,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 6 = limit_track (the limit filter run ahead of demod_seq; in m17hip_fir_correlator the limit filter's chain, 4 = its correlations),
  * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode),
  * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block),
- * 9 = tune (the tuner of m17hip_upload_wide*: one launch per wideband block). */
+ * 9 = tune (the tuner of m17hip_upload_wide* under m17hip_wide_config: one launch per wideband block),
+ * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

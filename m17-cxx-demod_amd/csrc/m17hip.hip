@@ -8,6 +8,7 @@
 #include "m17_frontend_kernels.hpp"
 #include "m17_iq_kernels.hpp"
 #include "m17_wide_kernels.hpp"
+#include "m17_wide2_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -33,7 +34,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -272,13 +273,16 @@ struct m17hip_ctx {
     // block keeps the table it was tuned with.  ev_iq orders these launches across the two streams like the discriminator's.
     struct Wide {
         uint32_t S = 0, R = 0, L = 0; int fmt = 0;   // S == 0: not configured
-        DevBuf<float> taps; DevBuf<float2> hist[2], znew;
+        uint32_t R2 = 0, L2 = 0;                     // R2 == 0: one stage (m17hip_wide_config); else R and L are stage 1's (m17hip_wide_config2: tune2_kernel)
+        uint32_t rate() const { return R2 ? R * R2 : R; }                       // wideband samples per output
+        uint32_t hlen() const { return R2 ? (L2 - 1) * R + L - 1 : L - 1; }     // converted samples a source carries
+        DevBuf<float> taps, taps2; DevBuf<float2> hist[2], znew;
         int par = 0;
         uint64_t count = 0;               // wideband samples per source since the feed began
         std::vector<uint32_t> table;      // [2 * maxC]
         bool dirty = true;
         TurnTable dev;
-        size_t bytes() const { return taps.size() * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size()) * sizeof(float2) + dev.words() * 4; }
+        size_t bytes() const { return (taps.size() + taps2.size()) * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size()) * sizeof(float2) + dev.words() * 4; }
     } wide;
     const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
     {
@@ -1162,7 +1166,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 609; }
+int m17hip_version(void) { return 610; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1653,13 +1657,31 @@ static void wide_default(uint32_t R, float* taps)
     }
     for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
 }
+// The first of two stages (ABI 610): all it has to do is keep what the first decimation folds onto the channel out of it.  Blackman-windowed sinc, cutoff
+// 24000 * R2 Hz at 48000 * R1 * R2 (half the rate it leaves), 8 * R1 + 1 taps, in double; unit DC gain, then rounded to float.  R1 = 1: one tap of 1.
+static void wide_default1(uint32_t R1, uint32_t R2, float* taps)
+{
+    if (R1 == 1) { taps[0] = 1.0f; return; }
+    const uint32_t L = 8 * R1 + 1;
+    const double pi = 3.14159265358979323846, fc = 24000.0 * R2 / (48000.0 * R1 * R2), mid = 0.5 * (L - 1);
+    std::vector<double> h(L);
+    double sum = 0.0;
+    for (uint32_t i = 0; i < L; ++i) {
+        const double t = (double)i - mid, x = 2.0 * pi * fc * t;
+        const double sinc = t == 0.0 ? 2.0 * fc : std::sin(x) / (pi * t);
+        const double w = 0.42 - 0.5 * std::cos(2.0 * pi * i / (L - 1)) + 0.08 * std::cos(4.0 * pi * i / (L - 1));
+        h[i] = sinc * w;
+        sum += h[i];
+    }
+    for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
+}
 static size_t wide_sample_bytes(int fmt) { return fmt == M17HIP_IQ_I16 ? sizeof(short2) : fmt == M17HIP_IQ_F32 ? sizeof(float2) : sizeof(uchar2); }
 template <typename IQT>
 static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
 {
     auto& w = c->wide;
     const IQT* src = static_cast<const IQT*>(dev);
-    const uint32_t W = T * w.R, H = w.L - 1;
+    const uint32_t W = T * w.rate(), H = w.hlen();   // (W fits: upload_wide has seen to it)
     if (w.dirty || !w.dev.live()) {   // the channel table, into the copy no queued launch reads
         uint32_t* staging = nullptr;
         HIPCHK(c, w.dev.begin_write(w.table.size(), &staging));
@@ -1668,7 +1690,12 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         w.dirty = false;
     }
     HIPCHK(c, w.dev.before_read(st));
-    {
+    if (w.R2) {
+        TimedK tm(c, KT_WIDE2);
+        tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
+                  w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
+                  (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+    } else {
         TimedK tm(c, KT_WIDE);
         tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
                   w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
@@ -1692,8 +1719,8 @@ static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uin
     if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
     auto& w = c->wide;
     if (!w.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
-    const size_t W = (size_t)T * w.R;
-    if (pitch < W) return M17HIP_EINVAL;
+    const uint64_t W = (uint64_t)T * w.rate();
+    if (pitch < W || W > 0xFFFFFFFFull) return M17HIP_EINVAL;   // (the kernels count a row's samples in 32 bits)
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
     int r;
@@ -1771,17 +1798,18 @@ int m17hip_wide_default_taps(uint32_t decim, float* taps, uint32_t capacity, uin
     wide_default(decim, taps);
     return M17HIP_OK;
 }
-int m17hip_wide_config(m17hip_ctx* c, uint32_t sources, uint32_t decim, int iq_format, const float* taps, uint32_t ntaps)
+// the caller's taps of one stage checked and copied, or the default ones where there are none: false is M17HIP_EINVAL
+static bool wide_stage_taps(const float* taps, uint32_t ntaps, uint32_t limit, std::vector<float>& h)
 {
-    if (!c || sources < 1 || sources > 256 || decim < 1 || decim > 16) return M17HIP_EINVAL;
-    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
-    std::vector<float> h;
-    if (!taps && ntaps == 0) { h.resize(32 * decim + 1); wide_default(decim, h.data()); }
-    else {
-        if (!taps || ntaps < 1 || ntaps > 1024) return M17HIP_EINVAL;
-        for (uint32_t i = 0; i < ntaps; ++i) if (!std::isfinite(taps[i])) return M17HIP_EINVAL;
-        h.assign(taps, taps + ntaps);
-    }
+    if (!taps && ntaps == 0) return true;   // (h holds the default taps)
+    if (!taps || ntaps < 1 || ntaps > limit) return false;
+    for (uint32_t i = 0; i < ntaps; ++i) if (!std::isfinite(taps[i])) return false;
+    h.assign(taps, taps + ntaps);
+    return true;
+}
+// What m17hip_wide_config and m17hip_wide_config2 share, the arguments checked: h2 empty and decim2 == 0 is the single stage.
+static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t decim, const std::vector<float>& h, uint32_t decim2, const std::vector<float>& h2)
+{
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
     auto& w = c->wide;
@@ -1789,22 +1817,55 @@ int m17hip_wide_config(m17hip_ctx* c, uint32_t sources, uint32_t decim, int iq_f
     int r;
     if ((r = ensure_iq(c, st))) return r;
     HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (a block tuned with the configuration before may still be in flight: its buffers go)
-    const uint32_t L = (uint32_t)h.size();
-    const size_t hn = (size_t)sources * std::max<uint32_t>(L - 1, 1);
+    const uint32_t L = (uint32_t)h.size(), L2 = (uint32_t)h2.size();
+    const size_t hn = (size_t)sources * std::max<uint32_t>(decim2 ? (L2 - 1) * decim + L - 1 : L - 1, 1);
     w.S = 0;   // (not configured until all of it is there)
     if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
+    if (decim2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
+    else w.taps2.release(&c->last_hip);
     for (auto& b : w.hist) if ((r = alloc_code(c, b.alloc(hn)))) return r;
     if (!w.znew && (r = alloc_code(c, w.znew.alloc(c->maxC)))) return r;
     HIPCHK(c, hipMemcpy(w.taps, h.data(), L * sizeof(float), hipMemcpyHostToDevice));
+    if (decim2) HIPCHK(c, hipMemcpy(w.taps2, h2.data(), L2 * sizeof(float), hipMemcpyHostToDevice));
     for (auto& b : w.hist) HIPCHK(c, hipMemsetAsync(b, 0, hn * sizeof(float2), st));
     if ((r = iq_mark(c, st))) return r;
     if (w.table.empty()) w.table.assign(2 * (size_t)c->maxC, 0u);
     for (uint32_t ch = 0; ch < c->maxC; ++ch)   // (a channel on a source that is no longer there goes back to the fresh entry)
         if (w.table[ch] >= sources) { w.table[ch] = 0; w.table[c->maxC + ch] = 0; }
     w.dirty = true;
-    w.R = decim; w.L = L; w.fmt = iq_format; w.par = 0; w.count = 0;
+    w.R = decim; w.L = L; w.R2 = decim2; w.L2 = L2; w.fmt = iq_format; w.par = 0; w.count = 0;
     w.S = sources;
     return M17HIP_OK;
+}
+int m17hip_wide_config(m17hip_ctx* c, uint32_t sources, uint32_t decim, int iq_format, const float* taps, uint32_t ntaps)
+{
+    if (!c || sources < 1 || sources > 256 || decim < 1 || decim > 16) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    std::vector<float> h(32 * decim + 1);
+    wide_default(decim, h.data());
+    if (!wide_stage_taps(taps, ntaps, 1024, h)) return M17HIP_EINVAL;
+    return wide_setup(c, sources, iq_format, decim, h, 0, std::vector<float>());
+}
+int m17hip_wide_default_taps2(uint32_t decim1, uint32_t decim2, float* taps1, uint32_t cap1, uint32_t* ntaps1, float* taps2, uint32_t cap2, uint32_t* ntaps2)
+{
+    if (decim1 < 1 || decim1 > 16 || decim2 < 1 || decim2 > 16 || !ntaps1 || !ntaps2) return M17HIP_EINVAL;
+    *ntaps1 = decim1 == 1 ? 1 : 8 * decim1 + 1;
+    *ntaps2 = 32 * decim2 + 1;
+    if (!taps1 || cap1 < *ntaps1 || !taps2 || cap2 < *ntaps2) return M17HIP_EINVAL;
+    wide_default1(decim1, decim2, taps1);
+    wide_default(decim2, taps2);
+    return M17HIP_OK;
+}
+int m17hip_wide_config2(m17hip_ctx* c, uint32_t sources, uint32_t decim1, const float* taps1, uint32_t ntaps1, uint32_t decim2, const float* taps2,
+                        uint32_t ntaps2, int iq_format)
+{
+    if (!c || sources < 1 || sources > 256 || decim1 < 1 || decim1 > 16 || decim2 < 1 || decim2 > 16) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    std::vector<float> h1(decim1 == 1 ? 1 : 8 * decim1 + 1), h2(32 * decim2 + 1);
+    wide_default1(decim1, decim2, h1.data());
+    wide_default(decim2, h2.data());
+    if (!wide_stage_taps(taps1, ntaps1, 256, h1) || !wide_stage_taps(taps2, ntaps2, 1024, h2)) return M17HIP_EINVAL;
+    return wide_setup(c, sources, iq_format, decim1, h1, decim2, h2);
 }
 int m17hip_wide_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* fcw, uint32_t n)
 {

@@ -84,6 +84,13 @@ public:
     {
         check(m17hip_wide_config(ctx_, sources, decim, iq_format, taps, ntaps), "m17hip_wide_config");
     }
+    // The same in two stages, for sources above 16 x 48 kSPS (m17hip_wide_config2): 48000 * decim1 * decim2 samples per second, every row
+    // samples * decim1 * decim2 complex samples; frequency words are wide_fcw(offset_hz, decim1 * decim2).  It and wide_config replace one another.
+    void wide_config2(uint32_t sources, uint32_t decim1, uint32_t decim2, int iq_format = M17HIP_IQ_I16, const float* taps1 = nullptr, uint32_t ntaps1 = 0,
+                      const float* taps2 = nullptr, uint32_t ntaps2 = 0)
+    {
+        check(m17hip_wide_config2(ctx_, sources, decim1, taps1, ntaps1, decim2, taps2, ntaps2, iq_format), "m17hip_wide_config2");
+    }
     void wide_channels(const uint32_t* source, const int32_t* fcw, uint32_t n) { check(m17hip_wide_channels(ctx_, source, fcw, n), "m17hip_wide_channels"); }
     // the frequency word of an offset in Hz from the source's centre, rounded to the nearest word
     static int32_t wide_fcw(double offset_hz, uint32_t decim)

@@ -161,6 +161,7 @@ struct M17Demodulator
             taps.resize(n);
         }
         wide_decim_ = decim;
+        wide_r1_ = 0;
         wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, decim);
         if (gpu_) {
             flush();
@@ -180,6 +181,42 @@ struct M17Demodulator
             wide_mixed_.push_back(re); wide_mixed_.push_back(im);
         }
     }
+    // The same out of a feed at 48000 * decim1 * decim2 samples per second, decimated in two stages (m17hip_wide_config2: a 2.4 MSPS dongle is 10 x 5):
+    // low-passed with taps1 and every decim1-th sample kept, then with taps2 and every decim2-th; empty: that stage's default taps
+    // (m17hip_wide_default_taps2).  The host form is core::ddc_fir2.
+    void wide_config(uint32_t decim1, uint32_t decim2, double offset_hz, std::vector<float> taps1 = {}, std::vector<float> taps2 = {})
+    {
+        if (taps1.empty() || taps2.empty()) {
+            uint32_t n1 = 0, n2 = 0;
+            std::vector<float> d1(8 * 16 + 1), d2(32 * 16 + 1);
+            if (m17hip_wide_default_taps2(decim1, decim2, d1.data(), (uint32_t)d1.size(), &n1, d2.data(), (uint32_t)d2.size(), &n2) != M17HIP_OK)
+                throw std::runtime_error("m17hip_wide_default_taps2");
+            if (taps1.empty()) taps1.assign(d1.begin(), d1.begin() + n1);
+            if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
+        }
+        wide_decim_ = decim1 * decim2;
+        wide_r1_ = decim1;
+        wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, wide_decim_);
+        if (gpu_) {
+            flush();
+            const uint32_t source = 0;
+            const int32_t fcw = (int32_t)wide_fcw_;
+            gpu_->wide_config2(1, decim1, decim2, M17HIP_IQ_F32, taps1.data(), (uint32_t)taps1.size(), taps2.data(), (uint32_t)taps2.size());
+            gpu_->wide_channels(&source, &fcw, 1);
+            wide_buffer_.clear();
+            return;
+        }
+        wide_taps_ = std::move(taps1);
+        wide_taps2_ = std::move(taps2);
+        wide_m_ = 0;
+        wide_mixed_.clear();   // the zero history of (ntaps2 - 1) decim1 + ntaps1 - 1 samples first, at the phases it would have had
+        for (size_t k = (wide_taps2_.size() - 1) * decim1 + wide_taps_.size() - 1; k > 0; --k) {
+            float re, im;
+            core::ddc_mix(0.0f, 0.0f, wide_fcw_, (uint32_t)(0 - k), re, im);
+            wide_mixed_.push_back(re); wide_mixed_.push_back(im);
+        }
+        wide_u_.assign(2 * (wide_taps2_.size() - 1), 0.0f);   // (the u in front of the feed: made from that history with the first output)
+    }
     // one wideband sample (wide_config first)
     void wide(float i, float q)
     {
@@ -189,6 +226,24 @@ struct M17Demodulator
             core::ddc_mix(i, q, wide_fcw_, (uint32_t)wide_m_, re, im);
             wide_mixed_.push_back(re); wide_mixed_.push_back(im);
             if (++wide_m_ % wide_decim_ != 0) return;
+            if (wide_r1_) {   // two stages: the decim2 new u and the z over them (the u in front are kept: they are a function of the mixed feed alone)
+                const uint32_t L2 = (uint32_t)wide_taps2_.size(), R2 = wide_decim_ / wide_r1_;
+                const size_t H = (size_t)(L2 - 1) * wide_r1_ + wide_taps_.size() - 1;
+                wide_u_.resize(wide_u_.size() + 2 * R2);
+                float z[2];
+                core::ddc_fir2(wide_taps_.data(), (uint32_t)wide_taps_.size(), wide_r1_, wide_taps2_.data(), L2, R2,
+                               wide_mixed_.data() + wide_mixed_.size() - 2 * (size_t)wide_decim_, 1, wide_m_ == wide_decim_ ? L2 - 1 : 0,
+                               wide_u_.data() + wide_u_.size() - 2 * R2, z);
+                const float y2 = core::fm_discriminate(z[0], z[1], iq_prev_[0], iq_prev_[1], iq_gain_);
+                iq_prev_[0] = z[0]; iq_prev_[1] = z[1];
+                if (wide_mixed_.size() > 2 * (H + 65536)) {
+                    wide_mixed_.erase(wide_mixed_.begin(), wide_mixed_.end() - 2 * H);
+                    wide_u_.erase(wide_u_.begin(), wide_u_.end() - 2 * (size_t)(L2 - 1));
+                }
+                cpu_->step((FloatType)y2);
+                demodState = (DemodState)cpu_->state();
+                return;
+            }
             core::ddc_fir(wide_taps_.data(), (uint32_t)wide_taps_.size(), wide_mixed_.data() + wide_mixed_.size() - 2, re, im);
             const float y = core::fm_discriminate(re, im, iq_prev_[0], iq_prev_[1], iq_gain_);   // (the carry the discriminator's own feed uses: the last z)
             iq_prev_[0] = re; iq_prev_[1] = im;
@@ -300,7 +355,9 @@ private:
     float iq_gain_ = 1.0f, iq_prev_[2] = {0.0f, 0.0f};
     std::vector<std::complex<float>> wide_buffer_;   // the GPU path's wideband samples short of a block
     std::vector<float> wide_taps_, wide_mixed_;      // the host form's filter and mixed feed
-    uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called)
+    std::vector<float> wide_taps2_, wide_u_;         // two stages: the second filter and the feed between the two
+    uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called); wideband samples per output
+    uint32_t wide_r1_ = 0;                           // the first stage's decimation (0: one stage)
     uint64_t wide_m_ = 0;
     uint32_t block_;
     bool dcd_ = false;

@@ -138,6 +138,17 @@ M17_HD void ddc_fir(const float* h, uint32_t L, const float* newest, float& re, 
 }
 // an 8-bit IQ component in rtl_sdr's convention: unsigned around 127.5 (exact)
 M17_HD float ddc_u8(uint8_t u) { return (float)u - 127.5f; }
+// Two stages (m17hip_wide_config2), R1 then R2: u[p] = sum_i h1[i] mixed[p R1 + R1 - 1 - i], z[n] = sum_i h2[i] u[n R2 + R2 - 1 - i] — ddc_fir over the mixed
+// feed, then ddc_fir over the u, nothing else.  One block of n outputs over linear arrays of (re, im): `mixed` points at the block's sample 0 and `u` at its
+// u 0 (n R2 of them follow).  The u from -fresh on are computed here: fresh = L2 - 1 makes all the u the block reads from the (L2 - 1) R1 + L1 - 1 mixed
+// samples in front of it, as the kernel does (a u is a function of the mixed feed alone, so a caller that kept the u of the block before passes 0 and gets the
+// same words).  z: [n][2].
+M17_HD void ddc_fir2(const float* h1, uint32_t L1, uint32_t R1, const float* h2, uint32_t L2, uint32_t R2, const float* mixed, uint32_t n, uint32_t fresh,
+                     float* u, float* z)
+{
+    for (int64_t p = -(int64_t)fresh; p < (int64_t)n * R2; ++p) ddc_fir(h1, L1, mixed + 2 * (p * R1 + R1 - 1), u[2 * p], u[2 * p + 1]);
+    for (uint32_t m = 0; m < n; ++m) ddc_fir(h2, L2, u + 2 * ((int64_t)m * R2 + R2 - 1), z[2 * m], z[2 * m + 1]);
+}
 
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).

@@ -29,7 +29,8 @@ DIAG = np.dtype(
 assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
-KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9}
+KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
+           "tune2": 10}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -71,6 +72,7 @@ EXPORTS = [
     "m17hip_upload_iq", "m17hip_upload_iq_device", "m17hip_upload_iq_async", "m17hip_upload_iq_device_async", "m17hip_iq_bytes",
     "m17hip_wide_default_taps", "m17hip_wide_config", "m17hip_wide_channels",
     "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async", "m17hip_upload_wide_device_async",
+    "m17hip_wide_default_taps2", "m17hip_wide_config2",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
@@ -156,6 +158,18 @@ def wide_default_taps(decim):
     if code != 0:
         raise M17HipError(f"m17hip_wide_default_taps: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
     return taps[: n.value].copy()
+
+
+def wide_default_taps2(decim1, decim2):
+    """The default taps of wide_config2's two stages: (float32 [8 * decim1 + 1] — [1] at decim1 = 1 —, float32 [32 * decim2 + 1]) —
+    m17hip_wide_default_taps2 (no context, no GPU)."""
+    n1, n2 = C.c_uint32(0), C.c_uint32(0)
+    t1, t2 = np.zeros(8 * 16 + 1, dtype=np.float32), np.zeros(32 * 16 + 1, dtype=np.float32)
+    code = load_library().m17hip_wide_default_taps2(C.c_uint32(decim1), C.c_uint32(decim2), _ptr(t1), C.c_uint32(t1.size), C.byref(n1), _ptr(t2),
+                                                    C.c_uint32(t2.size), C.byref(n2))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_default_taps2: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return t1[: n1.value].copy(), t2[: n2.value].copy()
 
 
 def wide_fcw(offset_hz, decim):
@@ -346,6 +360,16 @@ class Context:
         self._chk(self.lib.m17hip_wide_config(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_int(IQ_I16 if fmt is None else fmt), _ptr(t),
                                               C.c_uint32(0 if t is None else t.size)))
         self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+
+    def wide_config2(self, sources, decim1, decim2, fmt=None, taps1=None, taps2=None):
+        """`sources` wide IQ streams at 48000 * decim1 * decim2 samples per second (each 1..16) in format `fmt`, decimated in two stages: low-passed with
+        `taps1` and every decim1-th sample kept, then with `taps2` and every decim2-th (None: that stage of wide_default_taps2(decim1, decim2)).  Replaces
+        wide_config and is replaced by it; the frequency words are wide_fcw(offset_hz, decim1 * decim2) — m17hip_wide_config2."""
+        t1 = None if taps1 is None else np.ascontiguousarray(taps1, dtype=np.float32).reshape(-1)
+        t2 = None if taps2 is None else np.ascontiguousarray(taps2, dtype=np.float32).reshape(-1)
+        self._chk(self.lib.m17hip_wide_config2(self.h, C.c_uint32(sources), C.c_uint32(decim1), _ptr(t1), C.c_uint32(0 if t1 is None else t1.size),
+                                               C.c_uint32(decim2), _ptr(t2), C.c_uint32(0 if t2 is None else t2.size), C.c_int(IQ_I16 if fmt is None else fmt)))
+        self._wide = (int(sources), int(decim1) * int(decim2), IQ_I16 if fmt is None else int(fmt))
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

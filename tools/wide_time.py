@@ -1,6 +1,8 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
-int16 input, device form, default taps (L = 32 R + 1).  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
+    python tools/wide_time.py [--decim2 R2] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
+csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
+C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
 launch); the time between two events on the context's main stream around the call and the wall time of the synchronous call are printed beside it.
 The floor counts what the algorithm needs from the shapes, at the f32 vector rate of the chip (64 FLOP per clock and SIMD: a packed fma wave instruction
 — two chains of 64 outputs by one tap — every 4 clocks, a plain one every 2):
@@ -17,13 +19,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'm17-cxx-demod_amd'))
 import m17hip
 
-S = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-PER = int(sys.argv[2]) if len(sys.argv) > 2 else 64
-T = int(sys.argv[3]) if len(sys.argv) > 3 else 48000
-R = int(sys.argv[4]) if len(sys.argv) > 4 else 5
-REP = int(sys.argv[5]) if len(sys.argv) > 5 else 10
+ARGS = sys.argv[1:]
+R2 = 0   # (0: one stage)
+if "--decim2" in ARGS:
+    k = ARGS.index("--decim2")
+    R2 = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+S = int(ARGS[0]) if len(ARGS) > 0 else 64
+PER = int(ARGS[1]) if len(ARGS) > 1 else 64
+T = int(ARGS[2]) if len(ARGS) > 2 else 48000
+R = int(ARGS[3]) if len(ARGS) > 3 else 5
+REP = int(ARGS[4]) if len(ARGS) > 4 else 10
 C = S * PER
 L = 32 * R + 1
+RATE = R * (R2 if R2 else 1)   # wideband samples per output
+if R2:
+    L, L2 = (t.size for t in m17hip.wide_default_taps2(R, R2))
 MIX_OPS = 40
 DEMOD_STEP_MS = (20.0, 23.0)   # the demodulation step of 4096 channels x 480 000 samples (README): scaled to this shape below
 
@@ -50,15 +61,18 @@ class Clocks(threading.Thread):
 ctx = m17hip.Context(C, T)
 stream = ctx.torch_stream()
 g = torch.Generator(device='cuda').manual_seed(609)
-x = torch.randint(-20000, 20000, (S, T * R, 2), dtype=torch.int16, device='cuda', generator=g)
+x = torch.randint(-20000, 20000, (S, T * RATE, 2), dtype=torch.int16, device='cuda', generator=g)
 torch.cuda.synchronize()
-ctx.wide_config(S, R, m17hip.IQ_I16)
+if R2:
+    ctx.wide_config2(S, R, R2, m17hip.IQ_I16)
+else:
+    ctx.wide_config(S, R, m17hip.IQ_I16)
 rng = np.random.default_rng(609)
-ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, R) for f in rng.uniform(-24000.0 * R, 24000.0 * R, C)])
+ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATE) for f in rng.uniform(-24000.0 * RATE, 24000.0 * RATE, C)])
 
 
 def call():
-    ctx.upload_wide_device(x.data_ptr(), C, T, T * R)
+    ctx.upload_wide_device(x.data_ptr(), C, T, T * RATE)
 
 
 clocks = Clocks()
@@ -74,20 +88,21 @@ for _ in range(REP):
     b.record(stream)
     b.synchronize()
     ev.append(a.elapsed_time(b))
-ms, n = ctx.timing_get("tune")
+ms, n = ctx.timing_get("tune2" if R2 else "tune")
 ctx.timing(False)
 clocks.stop = True
 cus = torch.cuda.get_device_properties(0).multi_processor_count
 mhz = max(clocks.seen.values()) if clocks.seen else 2400
-cycles = C * T * L / 64 * 4 + C * T * R * MIX_OPS / 64 * 2
+FILTER = C * T * (R2 * L + L2 if R2 else L) / 64 * 4
+cycles = FILTER + C * T * RATE * MIX_OPS / 64 * 2
 floor_ms = cycles / (4 * cus * mhz * 1e6) * 1e3
 kernel_ms = ms / n
 step = [v * T / 480000.0 * C / 4096.0 for v in DEMOD_STEP_MS]
 print(json.dumps({
-    "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, "repeats": REP, "launches": n,
+    "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, **({"decim2": R2, "taps2": L2} if R2 else {}), "repeats": REP, "launches": n,
     "kernel_ms": round(kernel_ms, 3), "stream_ms": [round(v, 3) for v in ev], "stream_ms_median": round(float(np.median(ev)), 3),
     "wall_ms_median": round(float(np.median(wall)), 3),
-    "floor_ms": round(floor_ms, 3), "floor_filter_share": round(C * T * L / 64 * 4 / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
+    "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
