@@ -118,6 +118,57 @@ def test_two_stage_tuner_one_hop(case, fmt):
         ctx.close()
 
 
+# ---- 1b: one hop where a chunk's chains hold fewer than 64 u -------------------------------------------------------------------------------------
+# Q < 64 is wide_chains<0> (the chains' distance is not a constant) and chunks of 4 Q u that are no multiple of the wave: (16, 12, 256, 1024) has Q = 56,
+# (16, 16, 256, 700) Q = 45 — an odd chunk of 180 u — and the limit Q = 40.  The limit and Q = 45 also from float32 and uint8 rows: the sixteen-load fill
+# group of those sample types beside chunks that end inside a group.  (case, expected Q, formats)
+LOWQ_CASES = [((16, 12, 256, 1024), 56, ("i16",)), ((16, 16, 256, 700), 45, ("i16", "f32", "u8")), ((16, 16, 256, 1024), 40, ("f32", "u8"))]
+LOWQ_TS = (1, 255, 256, 511)
+LOWQ_CN = (1, 3)
+
+
+def _lowq_params():
+    return [pytest.param(case, q, name, id="{}x{}_{}_{}-q{}-{}".format(*case, q, name)) for case, q, names in LOWQ_CASES for name in names]
+
+
+@pytest.mark.parametrize("case,q,fmt", _lowq_params())
+def test_two_stage_tuner_one_hop_with_short_chains(case, q, fmt):
+    """The configurations whose LDS leaves fewer than 64 u per chain of a stage-1 chunk, from device rows that are not 16-byte aligned, three sources (the
+    float one in the middle holds infinities and NaNs), 1 and 3 channels, a tile's edges and two tiles and one output: the host form's words.  What Q and
+    how much LDS each configuration has is asserted from the restated layout (wide2_lib.q_and_lds)."""
+    R1, R2, L1, L2 = case
+    R, f = R1 * R2, FMTS[fmt]
+    got_q, lds = w2.q_and_lds(L1, R1, L2, R2)
+    assert got_q == q < 64 and lds <= 65536, (case, got_q, lds)
+    rng = np.random.default_rng(6110 + 7 * f + R + L2)
+    Tmax = max(LOWQ_TS)
+    P = Tmax * R + 3
+    host = _hop_data(f, P, rng)
+    dev = _dev(host)
+    Cmax = max(LOWQ_CN)
+    fcw = rng.integers(INT32_MIN, 1 << 31, Cmax).astype(np.int64)
+    fcw[1] = INT32_MIN
+    src = HOP_SRC[:Cmax]
+    taps1 = (rng.standard_normal(L1) / np.sqrt(L1)).astype(np.float32)
+    taps2 = (rng.standard_normal(L2) / np.sqrt(L2)).astype(np.float32)
+    gain = GAINS[1]
+    exp = np.stack([w2.tune2(host[src[c]][: Tmax * R], taps1, R1, taps2, R2, int(fcw[c]), gain) for c in range(Cmax)])
+    if f == wl.IQ_F32:
+        assert np.isnan(exp[BAD_SRC]).any() and np.isfinite(exp[0]).all()
+    ctx = m17hip.Context(Cmax, Tmax)
+    try:
+        assert _config2(ctx, HOP_S, R1, taps1, R2, taps2, f) == 0
+        ctx.wide_channels(src, fcw)
+        for T in LOWQ_TS:
+            for Cn in LOWQ_CN:
+                ctx.reset()   # (a fresh feed: every T is a prefix of the one expectation)
+                assert _raw(ctx, "m17hip_upload_wide_device", dev.data_ptr(), Cn, T, P, gain) == 0
+                ctx.C, ctx.T = Cn, T
+                _assert_words(ctx.download_f32(), exp[:Cn, :T], (case, fmt, Cn, T))
+    finally:
+        ctx.close()
+
+
 # ---- 2: the feed ---------------------------------------------------------------------------------------------------------------------------------
 # (10, 5, 81, 161): a block of one output is 50 samples against a history of 1680; (16, 1, 129, 33): 16 against 640
 FEED_CASES = [(10, 5, 81, 161), (16, 1, 129, 33)]

@@ -106,7 +106,8 @@ def test_a_two_stage_feed_cut_at_block_boundaries_gives_the_words_of_the_uncut_f
 #   |z_host - z_f64| <= scale (2^-20.5 + (L1 + L2 + 2) 2^-24), scale = sum|taps2| sum|taps1| max|x|;
 #   |y_host - y_f64| (mod 2 pi) <= gain (2 bound / min|z| + 2^-20) wherever z[n] and z[n-1] of the reference both exceed 8 bound (wide_lib.f64_check_y's rule).
 # At most 1 % of a case's outputs may fall under that floor: asserted on the float64 reference alone, before the host form is looked at.
-F64_CASES = [(1, 1, 1, 1), (2, 3, 5, 7), (10, 5, 81, 161), (16, 1, 129, 33), (3, 16, 1, 513), (16, 16, 256, 1024)]
+# The last two are the configurations tests/test_gpu_wide2_input.py launches with fewer than 64 u per chain of a chunk (Q = 56 and Q = 45).
+F64_CASES = [(1, 1, 1, 1), (2, 3, 5, 7), (10, 5, 81, 161), (16, 1, 129, 33), (3, 16, 1, 513), (16, 16, 256, 1024), (16, 12, 256, 1024), (16, 16, 256, 700)]
 F64_N = 600
 F64_GAIN = 1.25
 F64_WORDS = {"generic": -0x12345679, "+2^30": 1 << 30, "int32_min": -(1 << 31)}
@@ -131,6 +132,20 @@ def test_the_two_stage_tuner_is_within_derived_bounds_of_float64(case, fmt):
         assert ez <= 1.0 and ey <= 1.0, (case, name, ez, ey)
         worst = [max(a, b) for a, b in zip(worst, (ez, ey, excluded))]
     print(f"two stages vs float64, {case}: z error {worst[0]:.3f} of its bound, y error {worst[1]:.3f}, excluded {100 * worst[2]:.2f} %")
+
+
+def test_the_restated_lds_layout_gives_the_recorded_q_and_bytes():
+    """wide2_lib.q_and_lds against the table NOTES.md recorded for ABI 610 and the two configurations added since: the GPU cases that are there for Q < 64
+    do have Q < 64, and none asks for more than 64 KB."""
+    table = {(10, 5, 81, 161): (64, 34688), (2, 3, 5, 7): (64, 12368), (16, 1, 129, 33): (64, 38144), (3, 16, 1, 513): (64, 45056),
+             (16, 16, 256, 1024): (40, 65280)}
+    for (R1, R2, L1, L2), e in table.items():
+        assert w2.q_and_lds(L1, R1, L2, R2) == e, (R1, R2, L1, L2)
+    assert w2.q_and_lds(256, 16, 1024, 12)[0] == 56 and w2.q_and_lds(256, 16, 700, 16)[0] == 45
+    for R1 in range(1, 17):
+        for R2 in range(1, 17):
+            q, lds = w2.q_and_lds(256, R1, 1024, R2)
+            assert 40 <= q <= 64 and lds <= 65536, (R1, R2, q, lds)
 
 
 def test_a_wrong_decimation_phase_in_either_stage_misses_the_z_bound():

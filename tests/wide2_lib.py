@@ -35,6 +35,20 @@ def hist_len(L1, R1, L2):
     return (L2 - 1) * R1 + L1 - 1
 
 
+TILE_Z, PER_LANE, WAVE, LDS_LIMIT = 256, 4, 64, 65536
+
+
+def q_and_lds(L1, R1, L2, R2):
+    """(Q, LDS bytes of a workgroup) of tune2_kernel, RESTATED from the layout csrc/m17_wide2_kernels.hpp describes (not read from it: a change to
+    wide2_q shows as a difference).  In complex samples of 8 bytes: R2 planes of 255 + J2 u, the tile's 256 z and one chunk of R1 planes of 4 Q + J1 - 1
+    mixed samples, J = ceil(L / R); Q is the most that fits 64 KB, and 64 at the most."""
+    j1, j2 = -(-L1 // R1), -(-L2 // R2)
+    fixed = R2 * (TILE_Z - 1 + j2) + TILE_Z
+    places = (LDS_LIMIT // 8 - fixed) // R1
+    q = min((places + 1 - j1) // PER_LANE, WAVE)
+    return q, 8 * (fixed + R1 * (PER_LANE * q + j1 - 1))
+
+
 class Tuner2:
     """One channel on one source in two stages, as a feed: the source's history, the sample count and the channel's carry go from block to block."""
 
