@@ -3,7 +3,9 @@
 // I,Q of the narrowband FM channel, int16 or float32, discriminated on the device with --iq-gain G, default 1; with --wide-i16 / --wide-f32 / --wide-u8
 // --decim R --offset-hz F: interleaved I,Q of a WIDEBAND feed at 48000 R samples per second, the channel F Hz from its centre tuned, filtered, decimated and
 // discriminated on the device — rtl_sdr -s 240000 ... | m17-demod-gpu --wide-u8 --decim 5 --offset-hz 12500; with --decim2 R2 as well the feed is at
-// 48000 R R2 and decimated in two stages — rtl_sdr -s 2400000 ... | m17-demod-gpu --wide-u8 --decim 10 --decim2 5 --offset-hz 12500), one line per frame callback on
+// 48000 R R2 and decimated in two stages — rtl_sdr -s 2400000 ... | m17-demod-gpu --wide-u8 --decim 10 --decim2 5 --offset-hz 12500; with --raster M --bin B in place of --offset-hz
+// the feed at 48000 R (R up to 64) is split into M channels by the polyphase channeliser and bin B of them demodulated — rtl_sdr -s 2400000 ... |
+// m17-demod-gpu --wide-u8 --decim 50 --raster 192 --bin 1), one line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -43,6 +45,8 @@ int main(int argc, char** argv)
     int wide = 0;   // M17HIP_IQ_I16 / _F32 / _U8: a wideband feed of that format
     uint32_t decim = 1, decim2 = 0;   // (decim2 == 0: one stage)
     double offset_hz = 0.0;
+    uint32_t raster = 0;   // (0: a tuner)
+    long bin = 0;
     float iq_gain = 1.0f;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
@@ -55,14 +59,22 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--decim") && i + 1 < argc) decim = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--decim2") && i + 1 < argc) { decim2 = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!decim2) decim2 = 17; }
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) offset_hz = std::strtod(argv[++i], nullptr);
+        else if (!std::strcmp(argv[i], "--raster") && i + 1 < argc) { raster = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!raster) raster = 257; }
+        else if (!std::strcmp(argv[i], "--bin") && i + 1 < argc) bin = std::strtol(argv[++i], nullptr, 10);
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R] [--decim2 R2] [--offset-hz F] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R] [--decim2 R2] [--offset-hz F | --raster M --bin B] [--iq-gain G] < samples\n");
             return 2;
         }
     }
     if (((iq || wide) && float_input) || (iq && wide) || !(iq_gain > 0.0f) || !std::isfinite(iq_gain)) { std::fprintf(stderr, "m17-demod-gpu: one input format, and a finite gain > 0\n"); return 2; }
     const double half_hz = 24000.0 * decim * (decim2 ? decim2 : 1);
-    if (wide && (decim < 1 || decim > 16 || decim2 > 16 || !(std::fabs(offset_hz) <= half_hz))) {
+    if (wide && raster) {
+        uint32_t m1, m2;
+        if (decim < 1 || decim > 64 || decim2 || !core::chan_factor(raster, m1, m2) || bin < -(long)(raster / 2) || bin > (long)((raster - 1) / 2)) {
+            std::fprintf(stderr, "m17-demod-gpu: a decimation of 1 to 64 in one stage, a raster that factors into two numbers up to 16, and a bin inside it\n");
+            return 2;
+        }
+    } else if (wide && (decim < 1 || decim > 16 || decim2 > 16 || !(std::fabs(offset_hz) <= half_hz))) {
         std::fprintf(stderr, "m17-demod-gpu: decimations of 1 to 16, and an offset inside the +-%g Hz the feed covers\n", half_hz);
         return 2;
     }
@@ -83,7 +95,8 @@ int main(int argc, char** argv)
     }
     if (iq) return 0;
     if (wide) {   // a wideband feed: the tuner runs on the device
-        if (decim2) demod.wide_config(decim, decim2, offset_hz);
+        if (raster) demod.wide_raster(decim, raster, (int32_t)bin);
+        else if (decim2) demod.wide_config(decim, decim2, offset_hz);
         else demod.wide_config(decim, offset_hz);
         while (std::cin) {
             if (wide == M17HIP_IQ_I16) { int16_t s[2]; std::cin.read(reinterpret_cast<char*>(s), 4); if (std::cin) demod.wide((float)s[0], (float)s[1]); }

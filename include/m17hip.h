@@ -220,8 +220,8 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: polyphase / FFT channelisers, non-integer resampling, per-source sample counts, squelch / RSSI.  (Sources above
- * 16 x 48 kSPS: two stages, ABI 610, below.) */
+ * Out of scope, for a later pull request: non-integer resampling, per-source sample counts, squelch / RSSI.  (Sources above 16 x 48 kSPS: two stages,
+ * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.) */
 #define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
 /* The filter m17hip_wide_config takes by default — what a user of rtl_fm leaves to its built-in low-pass: ntaps = 32 * decim + 1, a Blackman-windowed
  * sinc with its cutoff at 5500 Hz of 48000 * decim, computed in double, scaled to unit DC gain and rounded to float.  No context is needed.  *ntaps is set
@@ -286,6 +286,52 @@ int m17hip_wide_default_taps2(uint32_t decim1, uint32_t decim2, float* taps1, ui
  * m17hip_timing_get index 10 is this tuner (index 9 stays the single-stage one); m17hip_iq_bytes counts its memory. */
 int m17hip_wide_config2(m17hip_ctx* ctx, uint32_t sources, uint32_t decim1, const float* taps1, uint32_t ntaps1, uint32_t decim2, const float* taps2,
                         uint32_t ntaps2, int iq_format);
+
+/* ---- wideband IQ input on a channel raster: the polyphase channeliser (ABI 611) ---------------------------
+ * The tuners pay for every channel separately: each mixes all its source's samples with its own oscillator and filters them once more.  Where the channels
+ * of a source sit on a RASTER — `bins` = M channels spaced 48000 * decim / M Hz, as the 192 channels of 12.5 kHz in a 2.4 MSPS source do — mixing and
+ * filtering are shared.  Bin b, -M/2 <= b < M/2, is centred b spacings from the source's centre; k = b mod M; m is the absolute index of a source sample
+ * since the feed began (x[m] = 0 for m < 0), and output n of a block that began at sample count c0 has its newest sample at m_n = c0 + n decim + decim - 1,
+ * the tuner's convention:
+ *     z_b[n] = sum_{i < ntaps} taps[i] * x[m_n - i] * exp(-2 pi j k (m_n - i) / M)
+ *     y_b[n] = gain * arg(z_b[n] * conj(z_b[n-1]))
+ * — the single-stage tuner's z with the oscillator exactly on the raster — computed, per source and output, as a fold and one M-point DFT:
+ *     w_n[r] = sum over i = i0, i0 + M, i0 + 2M, ... < ntaps of taps[i] * x[m_n - i],   i0 = (m_n - r) mod M,   r = 0 .. M-1
+ *     z_b[n] = sum_{r < M} w_n[r] * exp(-2 pi j k r / M)
+ * The phase of tap i depends on (m_n - i) mod M = r alone, so no correction factor remains and only c0 mod M enters (taken from all 64 bits of the count).
+ * One kernel (csrc/m17_chan_kernels.hpp), a workgroup per source and tile of outputs.  The arithmetic is defined once for host and device
+ * (m17cxx/detail/core.h): chan_fold — the two fma chains of ddc_tap from +0 in ascending i, zero history like any sample —; the DFT as two passes of small
+ * direct DFTs over M = M1 x M2 (chan_factor: M2 the largest divisor of M whose square is at most M; accepted when M1 <= 16 — which covers 48, 64, 96, 120,
+ * 128, 144, 192, 240 and 256, the 10, 12.5, 20 and 25 kHz rasters of the rates a dongle runs at; every other M is M17HIP_EINVAL), chan_pass1 and chan_pass2:
+ * chains of chan_mac, four fma per step in a fixed order, from +0; the second pass is evaluated for the bins some channel listens to only.  fm_discriminate
+ * is unchanged.  The twiddles exp(-2 pi j j / M) are DATA: made in one place, on the host, in double, rounded to float, exactly 0 / +-1 on the axes, and
+ * tw[M - j] the conjugate of tw[j] to the bit; m17hip_wide_raster_twiddles returns the table the device is given, so a host computes the device's words
+ * whatever its libm.
+ * Out of scope, for a later pull request: a raster shifted by a fraction of a spacing, non-integer resampling, per-source sample counts, squelch / RSSI. */
+/* The default taps of m17hip_wide_raster: the formula of m17hip_wide_default_taps (32 * decim + 1 taps, Blackman-windowed sinc, cutoff 5500 Hz) for
+ * decim 1..64, word for word that function's for decim <= 16.  No context is needed.  *ntaps is set whenever decim is valid; M17HIP_EINVAL if it is not, if
+ * ntaps is NULL, or if taps is NULL or capacity < *ntaps (nothing written to taps). */
+int m17hip_wide_raster_default_taps(uint32_t decim, float* taps, uint32_t capacity, uint32_t* ntaps);
+/* The twiddle table of a raster of `bins`: out[2 j], out[2 j + 1] = re, im of exp(-2 pi j j / bins), j < bins; capacity counts floats (>= 2 * bins).  No
+ * context is needed.  M17HIP_EINVAL for a `bins` m17hip_wide_raster refuses, a NULL pointer or too small a capacity (nothing written). */
+int m17hip_wide_raster_twiddles(uint32_t bins, float* out, uint32_t capacity);
+/* m17hip_wide_config for a raster: `sources` (1..256) at 48000 * decim (decim 1..64) in iq_format, split into `bins` channels (see above for the values
+ * accepted), low-passed with taps[ntaps] (1..4096, finite; NULL with 0: the default taps).  In every other respect it is m17hip_wide_config: it starts the
+ * feeds over, may be called again, waits for tuner launches in flight and never for a run, leaves the carries, and returns M17HIP_ESTATE between
+ * m17hip_demod_front and its run.  The three configurations replace one another: whichever call was made last decides which kernel the next upload
+ * launches.  The channel table is kept across a call that leaves `bins` as it was (a channel whose source is gone goes back to source 0, bin 0); a call that
+ * changes the kind of configuration or `bins` starts the table over — a frequency word is no bin, nor is a bin of one raster a bin of another.
+ * m17hip_upload_wide* serve it as they serve the tuners: rows hold samples * decim complex samples.  THE FEED is the one described above: per source the
+ * last ntaps - 1 converted samples, per channel the float2 carry (the last z); m17hip_demod_reset and m17hip_demod_reset_channels as for the tuners.
+ * m17hip_timing_get index 11 is the channeliser; m17hip_iq_bytes counts its memory. */
+int m17hip_wide_raster(m17hip_ctx* ctx, uint32_t sources, uint32_t decim, uint32_t bins, int iq_format, const float* taps, uint32_t ntaps);
+/* m17hip_wide_channels for a raster: local channel c < n listens to bin[c] of source[c]; several channels may name the same (source, bin).  Entries at n
+ * and above keep their value; a fresh table is all (0, 0).  It applies to the blocks uploaded AFTER the call — a block already staged keeps the table it was
+ * tuned with — and never waits for anything in flight (two device tables take turns).  The retune and carry rules are m17hip_wide_channels'.
+ * M17HIP_EINVAL, with nothing changed: n > max_channels, a source at or above `sources`, a bin outside [-bins/2, bins/2), NULL with n > 0.
+ * TABLE OWNERSHIP: each table call returns M17HIP_ESTATE under a configuration that is not its own — this one before m17hip_wide_raster or under a tuner,
+ * m17hip_wide_channels under a raster. */
+int m17hip_wide_raster_channels(m17hip_ctx* ctx, const uint32_t* source, const int32_t* bin, uint32_t n);
 
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
@@ -753,7 +799,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 7 = voice (the voice consumer, m17hip_tune key 34: one launch per run, on the payload stream behind the deferred decode),
  * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block),
  * 9 = tune (the tuner of m17hip_upload_wide* under m17hip_wide_config: one launch per wideband block),
- * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise). */
+ * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
+ * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

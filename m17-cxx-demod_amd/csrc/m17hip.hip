@@ -9,6 +9,7 @@
 #include "m17_iq_kernels.hpp"
 #include "m17_wide_kernels.hpp"
 #include "m17_wide2_kernels.hpp"
+#include "m17_chan_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -34,7 +35,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -276,13 +277,22 @@ struct m17hip_ctx {
         uint32_t R2 = 0, L2 = 0;                     // R2 == 0: one stage (m17hip_wide_config); else R and L are stage 1's (m17hip_wide_config2: tune2_kernel)
         uint32_t rate() const { return R2 ? R * R2 : R; }                       // wideband samples per output
         uint32_t hlen() const { return R2 ? (L2 - 1) * R + L - 1 : L - 1; }     // converted samples a source carries
-        DevBuf<float> taps, taps2; DevBuf<float2> hist[2], znew;
+        uint32_t M = 0, M1 = 0, M2 = 0;              // M != 0: a raster of M bins (m17hip_wide_raster: chan_kernel); R and L are its decimation and taps, R2 == 0
+        DevBuf<float> taps, taps2; DevBuf<float2> hist[2], znew, tw;
         int par = 0;
         uint64_t count = 0;               // wideband samples per source since the feed began
         std::vector<uint32_t> table;      // [2 * maxC]
         bool dirty = true;
         TurnTable dev;
-        size_t bytes() const { return (taps.size() + taps2.size()) * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size()) * sizeof(float2) + dev.words() * 4; }
+        // Under a raster the table's second half holds bin mod M, and the device reads it sorted by source (chan_table_words; csrc/m17_chan_kernels.hpp), made
+        // for the channels of the launch: a copy of its own, written when the table or the launch's channel count has changed.
+        TurnTable rdev;
+        uint32_t rdev_C = 0;
+        size_t bytes() const
+        {
+            return (taps.size() + taps2.size()) * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) +
+                   (dev.words() + rdev.words()) * 4;
+        }
     } wide;
     const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
     {
@@ -1166,7 +1176,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 610; }
+int m17hip_version(void) { return 611; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1712,6 +1722,57 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     w.count += W;
     return iq_mark(c, st);
 }
+// The channeliser's launch (m17hip_wide_raster): the same frame, one workgroup per source and tile of output times.
+template <typename IQT>
+static int launch_chan(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
+{
+    auto& w = c->wide;
+    const IQT* src = static_cast<const IQT*>(dev);
+    const uint32_t W = T * w.R, H = w.L - 1;   // (W fits: upload_wide has seen to it)
+    if (w.dirty || !w.rdev.live() || w.rdev_C != C) {   // the channel table by source, into the copy no queued launch reads
+        uint32_t* t = nullptr;
+        HIPCHK(c, w.rdev.begin_write(chan_table_words(256, c->maxC), &t));
+        const uint32_t S = w.S, maxC = c->maxC;
+        uint32_t* first = t;                 // [S + 1]
+        uint32_t* ufirst = t + S + 1;        // [S + 1]
+        uint32_t* pairs = t + 2 * (S + 1);   // [C][2]
+        uint32_t* ubins = pairs + 2 * (size_t)C;
+        std::fill(t, t + 2 * (S + 1), 0u);
+        for (uint32_t ch = 0; ch < C; ++ch) ++first[w.table[ch] + 1];
+        for (uint32_t s = 0; s < S; ++s) first[s + 1] += first[s];
+        std::vector<uint32_t> at(first, first + S);
+        for (uint32_t ch = 0; ch < C; ++ch) { uint32_t& a = at[w.table[ch]]; pairs[2 * a] = w.table[maxC + ch]; pairs[2 * a + 1] = ch; ++a; }
+        std::vector<uint8_t> seen(w.M);
+        uint32_t U = 0;
+        for (uint32_t s = 0; s < S; ++s) {
+            std::fill(seen.begin(), seen.end(), 0);
+            ufirst[s] = U;
+            for (uint32_t a = first[s]; a < first[s + 1]; ++a) if (!seen[pairs[2 * a]]) { seen[pairs[2 * a]] = 1; ubins[U++] = pairs[2 * a]; }
+        }
+        ufirst[S] = U;
+        HIPCHK(c, w.rdev.publish(chan_table_words(S, C), st));
+        w.dirty = false; w.rdev_C = C;
+    }
+    HIPCHK(c, w.rdev.before_read(st));
+    {
+        const uint32_t TT = chan_tile(w.L, w.R, w.M);
+        TimedK tm(c, KT_CHAN);
+        tm.launch(chan_kernel<IQT>, dim3((T + TT - 1) / TT, w.S), dim3(CHAN_THREADS), chan_lds_bytes(w.L, w.R, w.M, TT), st, src, pitch, W, w.hist[w.par].get(),
+                  w.taps.get(), w.L, w.R, w.M1, w.M2, w.tw.get(), w.rdev.dev(), w.S, (uint32_t)(w.count % w.M), TT, C, x, c->xpitch, T, c->iq_carry.get(),
+                  w.znew.get(), gain);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, w.rdev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
+    HIPCHK(c, hipGetLastError());
+    if (H) {
+        hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
+        HIPCHK(c, hipGetLastError());
+    }
+    w.par ^= 1;
+    w.count += W;
+    return iq_mark(c, st);
+}
 // The four ways in, through the discriminator's frame (upload_iq): the tuner takes the place of the copy.  `p`: [sources][pitch] samples of the configured format.
 static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
 {
@@ -1741,8 +1802,12 @@ static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uin
         HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, p, pitch * sb, W * sb, w.S, hipMemcpyHostToDevice, st));
         dev = c->iq_raw; pitch = rp;
     }
-    r = w.fmt == M17HIP_IQ_I16 ? launch_tune<short2>(c, dev, pitch, x, C, T, gain, st)
-      : w.fmt == M17HIP_IQ_F32 ? launch_tune<float2>(c, dev, pitch, x, C, T, gain, st) : launch_tune<uchar2>(c, dev, pitch, x, C, T, gain, st);
+    if (w.M)
+        r = w.fmt == M17HIP_IQ_I16 ? launch_chan<short2>(c, dev, pitch, x, C, T, gain, st)
+          : w.fmt == M17HIP_IQ_F32 ? launch_chan<float2>(c, dev, pitch, x, C, T, gain, st) : launch_chan<uchar2>(c, dev, pitch, x, C, T, gain, st);
+    else
+        r = w.fmt == M17HIP_IQ_I16 ? launch_tune<short2>(c, dev, pitch, x, C, T, gain, st)
+          : w.fmt == M17HIP_IQ_F32 ? launch_tune<float2>(c, dev, pitch, x, C, T, gain, st) : launch_tune<uchar2>(c, dev, pitch, x, C, T, gain, st);
     if (r) return r;
     if (how & IQ_STAGED) {
         HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
@@ -1807,8 +1872,23 @@ static bool wide_stage_taps(const float* taps, uint32_t ntaps, uint32_t limit, s
     h.assign(taps, taps + ntaps);
     return true;
 }
-// What m17hip_wide_config and m17hip_wide_config2 share, the arguments checked: h2 empty and decim2 == 0 is the single stage.
-static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t decim, const std::vector<float>& h, uint32_t decim2, const std::vector<float>& h2)
+// the channeliser's twiddles, tw[j] = exp(-2 pi j j / M) as (re, im): cos and sin in double for j <= M / 2, rounded to float, exactly 0 / +-1 where 4 j is a
+// multiple of M; the upper half is the lower one's conjugate to the bit
+static void chan_twiddles(uint32_t M, float* tw)
+{
+    const double pi = 3.14159265358979323846;
+    for (uint32_t j = 0; j <= M / 2; ++j) {
+        float re, im;
+        if (4 * j % M == 0) { const uint32_t q = 4 * j / M; re = q == 0 ? 1.0f : q == 2 ? -1.0f : 0.0f; im = q == 1 ? 1.0f : 0.0f; }
+        else { re = (float)std::cos(2.0 * pi * j / M); im = (float)std::sin(2.0 * pi * j / M); }
+        tw[2 * j] = re; tw[2 * j + 1] = -im;
+        if (j) { tw[2 * (M - j)] = re; tw[2 * (M - j) + 1] = im; }
+    }
+    if (M % 2 == 0) tw[M + 1] = 0.0f;   // (j = M / 2: -1, and its own conjugate)
+}
+// What the three configurations share, the arguments checked: h2 empty and decim2 == 0 is a single stage; bins != 0 the raster (a single stage, no oscillator).
+static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t decim, const std::vector<float>& h, uint32_t decim2, const std::vector<float>& h2,
+                      uint32_t bins = 0)
 {
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
@@ -1827,13 +1907,21 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     if (!w.znew && (r = alloc_code(c, w.znew.alloc(c->maxC)))) return r;
     HIPCHK(c, hipMemcpy(w.taps, h.data(), L * sizeof(float), hipMemcpyHostToDevice));
     if (decim2) HIPCHK(c, hipMemcpy(w.taps2, h2.data(), L2 * sizeof(float), hipMemcpyHostToDevice));
+    if (bins) {
+        std::vector<float> tw(2 * (size_t)bins);
+        chan_twiddles(bins, tw.data());
+        if ((r = alloc_code(c, w.tw.alloc(bins)))) return r;
+        HIPCHK(c, hipMemcpy(w.tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    } else w.tw.release(&c->last_hip);
     for (auto& b : w.hist) HIPCHK(c, hipMemsetAsync(b, 0, hn * sizeof(float2), st));
     if ((r = iq_mark(c, st))) return r;
-    if (w.table.empty()) w.table.assign(2 * (size_t)c->maxC, 0u);
+    if (w.table.empty() || w.M != bins) w.table.assign(2 * (size_t)c->maxC, 0u);   // (a frequency word is no bin, nor a bin of M one of another M: all fresh)
     for (uint32_t ch = 0; ch < c->maxC; ++ch)   // (a channel on a source that is no longer there goes back to the fresh entry)
         if (w.table[ch] >= sources) { w.table[ch] = 0; w.table[c->maxC + ch] = 0; }
     w.dirty = true;
     w.R = decim; w.L = L; w.R2 = decim2; w.L2 = L2; w.fmt = iq_format; w.par = 0; w.count = 0;
+    w.M = bins; w.M1 = w.M2 = 0;
+    if (bins) core::chan_factor(bins, w.M1, w.M2);
     w.S = sources;
     return M17HIP_OK;
 }
@@ -1871,9 +1959,45 @@ int m17hip_wide_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* f
 {
     if (!c || n > c->maxC || (n > 0 && (!source || !fcw))) return M17HIP_EINVAL;
     auto& w = c->wide;
-    if (!w.S) return M17HIP_ESTATE;   // (which sources exist is m17hip_wide_config's to say)
+    if (!w.S || w.M) return M17HIP_ESTATE;   // (which sources exist is m17hip_wide_config's to say; under a raster the table is m17hip_wide_raster_channels')
     for (uint32_t ch = 0; ch < n; ++ch) if (source[ch] >= w.S) return M17HIP_EINVAL;
     for (uint32_t ch = 0; ch < n; ++ch) { w.table[ch] = source[ch]; w.table[c->maxC + ch] = (uint32_t)fcw[ch]; }
+    w.dirty = true;   // (the next block uploaded brings it to the device: nothing is queued and nothing waited for here)
+    return M17HIP_OK;
+}
+int m17hip_wide_raster_default_taps(uint32_t decim, float* taps, uint32_t capacity, uint32_t* ntaps)
+{
+    if (decim < 1 || decim > 64 || !ntaps) return M17HIP_EINVAL;
+    *ntaps = 32 * decim + 1;
+    if (!taps || capacity < *ntaps) return M17HIP_EINVAL;
+    wide_default(decim, taps);
+    return M17HIP_OK;
+}
+int m17hip_wide_raster_twiddles(uint32_t bins, float* out, uint32_t capacity)
+{
+    uint32_t m1, m2;
+    if (!core::chan_factor(bins, m1, m2) || !out || capacity < 2 * bins) return M17HIP_EINVAL;
+    chan_twiddles(bins, out);
+    return M17HIP_OK;
+}
+int m17hip_wide_raster(m17hip_ctx* c, uint32_t sources, uint32_t decim, uint32_t bins, int iq_format, const float* taps, uint32_t ntaps)
+{
+    uint32_t m1, m2;
+    if (!c || sources < 1 || sources > 256 || decim < 1 || decim > 64 || !core::chan_factor(bins, m1, m2)) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    std::vector<float> h(32 * decim + 1);
+    wide_default(decim, h.data());
+    if (!wide_stage_taps(taps, ntaps, 4096, h)) return M17HIP_EINVAL;
+    return wide_setup(c, sources, iq_format, decim, h, 0, std::vector<float>(), bins);
+}
+int m17hip_wide_raster_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* bin, uint32_t n)
+{
+    if (!c || n > c->maxC || (n > 0 && (!source || !bin))) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    if (!w.S || !w.M) return M17HIP_ESTATE;   // (which sources and bins exist is m17hip_wide_raster's to say)
+    const int32_t lo = -(int32_t)(w.M / 2), hi = (int32_t)((w.M - 1) / 2);
+    for (uint32_t ch = 0; ch < n; ++ch) if (source[ch] >= w.S || bin[ch] < lo || bin[ch] > hi) return M17HIP_EINVAL;
+    for (uint32_t ch = 0; ch < n; ++ch) { w.table[ch] = source[ch]; w.table[c->maxC + ch] = (uint32_t)(bin[ch] < 0 ? bin[ch] + (int32_t)w.M : bin[ch]); }
     w.dirty = true;   // (the next block uploaded brings it to the device: nothing is queued and nothing waited for here)
     return M17HIP_OK;
 }

@@ -5,6 +5,7 @@
 
 #include "../../../include/m17hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -90,6 +91,26 @@ public:
                       const float* taps2 = nullptr, uint32_t ntaps2 = 0)
     {
         check(m17hip_wide_config2(ctx_, sources, decim1, taps1, ntaps1, decim2, taps2, ntaps2, iq_format), "m17hip_wide_config2");
+    }
+    // S sources split into `bins` channels each on a raster of 48000 * decim / bins Hz by the polyphase channeliser (m17hip_wide_raster; decim 1..64, every
+    // row samples * decim complex samples); channels are named by wide_raster_channels(source, bin), wide_bin gives the bin of an offset.  It replaces
+    // wide_config and wide_config2 and is replaced by them.
+    void wide_raster(uint32_t sources, uint32_t decim, uint32_t bins, int iq_format = M17HIP_IQ_I16, const float* taps = nullptr, uint32_t ntaps = 0)
+    {
+        check(m17hip_wide_raster(ctx_, sources, decim, bins, iq_format, taps, ntaps), "m17hip_wide_raster");
+    }
+    void wide_raster_channels(const uint32_t* source, const int32_t* bin, uint32_t n)
+    {
+        check(m17hip_wide_raster_channels(ctx_, source, bin, n), "m17hip_wide_raster_channels");
+    }
+    // the bin of an offset in Hz from the source's centre; throws where the offset is not on the raster or outside it
+    static int32_t wide_bin(double offset_hz, uint32_t decim, uint32_t bins)
+    {
+        const double b = offset_hz * bins / (48000.0 * decim);
+        const double k = std::nearbyint(b);
+        if (std::fabs(b - k) > 1e-9 * std::max(1.0, std::fabs(b)) || k < -(double)(bins / 2) || k > (double)((bins - 1) / 2))
+            throw std::invalid_argument("wide_bin: the offset is not a channel of the raster");
+        return (int32_t)k;
     }
     void wide_channels(const uint32_t* source, const int32_t* fcw, uint32_t n) { check(m17hip_wide_channels(ctx_, source, fcw, n), "m17hip_wide_channels"); }
     // the frequency word of an offset in Hz from the source's centre, rounded to the nearest word

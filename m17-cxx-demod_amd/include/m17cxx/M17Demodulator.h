@@ -162,6 +162,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim;
         wide_r1_ = 0;
+        raster_m_ = 0;
         wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, decim);
         if (gpu_) {
             flush();
@@ -196,6 +197,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim1 * decim2;
         wide_r1_ = decim1;
+        raster_m_ = 0;
         wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, wide_decim_);
         if (gpu_) {
             flush();
@@ -217,10 +219,62 @@ struct M17Demodulator
         }
         wide_u_.assign(2 * (wide_taps2_.size() - 1), 0.0f);   // (the u in front of the feed: made from that history with the first output)
     }
-    // one wideband sample (wide_config first)
+    // The same for a channel ON A RASTER of `bins` channels spaced 48000 * decim / bins Hz (decim 1..64; m17hip_wide_raster: the polyphase channeliser):
+    // bin `bin`, -bins/2 <= bin < bins/2, of the feed; taps empty: the default taps (m17hip_wide_raster_default_taps).  The host form computes the same
+    // words from detail/core.h (chan_fold, chan_pass1, chan_pass2) over the library's twiddle table.
+    void wide_raster(uint32_t decim, uint32_t bins, int32_t bin, std::vector<float> taps = {})
+    {
+        uint32_t m1 = 0, m2 = 0;
+        if (!core::chan_factor(bins, m1, m2) || bin < -(int32_t)(bins / 2) || bin > (int32_t)((bins - 1) / 2)) throw std::invalid_argument("M17Demodulator::wide_raster");
+        if (taps.empty()) {
+            uint32_t n = 0;
+            taps.resize(32 * 64 + 1);
+            if (m17hip_wide_raster_default_taps(decim, taps.data(), (uint32_t)taps.size(), &n) != M17HIP_OK) throw std::runtime_error("m17hip_wide_raster_default_taps");
+            taps.resize(n);
+        }
+        wide_decim_ = decim;
+        wide_r1_ = 0;
+        if (gpu_) {
+            flush();
+            const uint32_t source = 0;
+            gpu_->wide_raster(1, decim, bins, M17HIP_IQ_F32, taps.data(), (uint32_t)taps.size());
+            gpu_->wide_raster_channels(&source, &bin, 1);
+            wide_buffer_.clear();
+            raster_m_ = bins;
+            return;
+        }
+        raster_tw_.resize(2 * (size_t)bins);
+        if (m17hip_wide_raster_twiddles(bins, raster_tw_.data(), (uint32_t)raster_tw_.size()) != M17HIP_OK) throw std::runtime_error("m17hip_wide_raster_twiddles");
+        raster_m_ = bins; raster_m1_ = m1; raster_m2_ = m2;
+        raster_k_ = (uint32_t)(bin < 0 ? bin + (int32_t)bins : bin);
+        raster_w_.resize(4 * (size_t)bins);
+        wide_taps_ = std::move(taps);
+        wide_m_ = 0;
+        wide_mixed_.assign(2 * (wide_taps_.size() - 1), 0.0f);   // the feed itself as (re, im) — nothing is mixed — behind its zero history of ntaps - 1 samples
+    }
+    // one wideband sample (wide_config or wide_raster first)
     void wide(float i, float q)
     {
         if (!wide_decim_) throw std::logic_error("M17Demodulator::wide before wide_config");
+        if (cpu_ && raster_m_) {
+            wide_mixed_.push_back(i); wide_mixed_.push_back(q);
+            if (++wide_m_ % wide_decim_ != 0) return;
+            const uint32_t M = raster_m_, L = (uint32_t)wide_taps_.size(), mm = (uint32_t)((wide_m_ - 1) % M);   // (the newest sample is number wide_m_ - 1)
+            float* w = raster_w_.data();
+            float* a = w + 2 * (size_t)M;
+            for (uint32_t r = 0; r < M; ++r) core::chan_fold(wide_taps_.data(), L, M, (mm + M - r) % M, wide_mixed_.data() + wide_mixed_.size() - 2, w[2 * r], w[2 * r + 1]);
+            for (uint32_t r1 = 0; r1 < raster_m1_; ++r1)
+                for (uint32_t k2 = 0; k2 < raster_m2_; ++k2)
+                    core::chan_pass1(w, raster_m1_, raster_m2_, raster_tw_.data(), r1, k2, a[2 * (r1 * raster_m2_ + k2)], a[2 * (r1 * raster_m2_ + k2) + 1]);
+            float re, im;
+            core::chan_pass2(a, raster_m1_, raster_m2_, raster_tw_.data(), raster_k_, re, im);
+            const float y = core::fm_discriminate(re, im, iq_prev_[0], iq_prev_[1], iq_gain_);
+            iq_prev_[0] = re; iq_prev_[1] = im;
+            if (wide_mixed_.size() > 2 * ((size_t)L + 65536)) wide_mixed_.erase(wide_mixed_.begin(), wide_mixed_.end() - 2 * ((size_t)L - 1));
+            cpu_->step((FloatType)y);
+            demodState = (DemodState)cpu_->state();
+            return;
+        }
         if (cpu_) {
             float re, im;
             core::ddc_mix(i, q, wide_fcw_, (uint32_t)wide_m_, re, im);
@@ -358,6 +412,8 @@ private:
     std::vector<float> wide_taps2_, wide_u_;         // two stages: the second filter and the feed between the two
     uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called); wideband samples per output
     uint32_t wide_r1_ = 0;                           // the first stage's decimation (0: one stage)
+    uint32_t raster_m_ = 0, raster_m1_ = 0, raster_m2_ = 0, raster_k_ = 0;   // wide_raster: the bins (0: a tuner), their factors and the bin mod M
+    std::vector<float> raster_tw_, raster_w_;        // the twiddle table; the partial sums and the first pass's sums of one output
     uint64_t wide_m_ = 0;
     uint32_t block_;
     bool dcd_ = false;

@@ -150,6 +150,73 @@ M17_HD void ddc_fir2(const float* h1, uint32_t L1, uint32_t R1, const float* h2,
     for (uint32_t m = 0; m < n; ++m) ddc_fir(h2, L2, u + 2 * ((int64_t)m * R2 + R2 - 1), z[2 * m], z[2 * m + 1]);
 }
 
+// ---- a-1c: the channeliser (m17hip_wide_raster): M channels on a raster, spaced rate / M.  The single-stage tuner's z with the oscillator exactly on the
+// raster, z_k[n] = sum_i h[i] x[m_n - i] exp(-2 pi j k (m_n - i) / M), computed as a FOLD of the taps into M partial sums — the phase of tap i depends on
+// (m_n - i) mod M alone — and one M-point DFT over a table of M twiddles, tw[j] = exp(-2 pi j j / M) as (re, im) floats.  The table is data: made once, on the
+// host, in double (m17hip_wide_raster_twiddles), so no libm enters the words.
+// The fold of residue r at an output whose newest sample is m_n: the two chains of ddc_tap from +0 over the taps i = i0, i0 + M, i0 + 2M, ... < L in that
+// order, i0 = (m_n - r) mod M.  `newest` as in ddc_fir; a residue no tap falls on (i0 >= L) is (+0, +0).
+M17_HD void chan_fold(const float* h, uint32_t L, uint32_t M, uint32_t i0, const float* newest, float& re, float& im)
+{
+    re = 0.0f; im = 0.0f;
+    uint32_t i = i0;
+    // (eight taps and samples fetched together, then their eight steps in order: the same chain — on the device the loads' latencies are paid once, not
+    // once per step)
+    for (; L > 7 * M && i < L - 7 * M; i += 8 * M) {
+        float t[8], vre[8], vim[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int64_t j = (int64_t)i + (int64_t)k * M;
+            t[k] = h[j]; vre[k] = newest[-2 * j]; vim[k] = newest[-2 * j + 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ddc_tap(t[k], vre[k], vim[k], re, im);
+    }
+    for (; i < L; i += M) ddc_tap(h[i], newest[-2 * (int64_t)i], newest[-2 * (int64_t)i + 1], re, im);
+}
+// One step of a DFT sum: acc += a * t, complex, as four fma in this order (the real chain takes a.re t.re then -a.im t.im, the imaginary one a.re t.im then
+// a.im t.re).  A twiddle on an axis (0 / +-1) adds its term exactly.
+M17_HD void chan_mac(float are, float aim, float tre, float tim, float& re, float& im)
+{
+    re = __builtin_fmaf(are, tre, re);
+    re = __builtin_fmaf(-aim, tim, re);
+    im = __builtin_fmaf(are, tim, im);
+    im = __builtin_fmaf(aim, tre, im);
+}
+// M = M1 x M2 with M2 the largest divisor of M whose square is at most M (so M2 <= M1, and M1 is the smallest cofactor any factorisation offers): accepted
+// when M1 <= 16.  6 = 3 x 2, 12 = 4 x 3, 192 = 16 x 12, 256 = 16 x 16; a prime p <= 16 is p x 1; 34 = 17 x 2 is refused.
+M17_HD bool chan_factor(uint32_t M, uint32_t& M1, uint32_t& M2)
+{
+    M1 = 0; M2 = 1;
+    if (M < 1 || M > 256) return false;
+    for (uint32_t d = 1; d * d <= M; ++d) if (M % d == 0) M2 = d;
+    M1 = M / M2;
+    return M1 <= 16;
+}
+// With r = r1 + M1 r2 and k = M2 k1 + k2 (r1, k1 < M1; r2, k2 < M2):  z_k = sum_{r1} tw[(k r1) mod M] * a[r1][k2],  a[r1][k2] = sum_{r2} tw[M1 ((k2 r2) mod M2)]
+// * w[r1 + M1 r2].  Pass 1, one element: r2 ascending from (+0, +0).  w: [M][2].
+M17_HD void chan_pass1(const float* w, uint32_t M1, uint32_t M2, const float* tw, uint32_t r1, uint32_t k2, float& re, float& im)
+{
+    const uint32_t M = M1 * M2, dt = M1 * k2;
+    re = 0.0f; im = 0.0f;
+    for (uint32_t r2 = 0, t = 0; r2 < M2; ++r2) {
+        const uint32_t r = r1 + M1 * r2;
+        chan_mac(w[2 * r], w[2 * r + 1], tw[2 * t], tw[2 * t + 1], re, im);
+        t += dt; if (t >= M) t -= M;
+    }
+}
+// Pass 2, one bin k < M: r1 ascending from (+0, +0).  a: [M1][M2][2].
+M17_HD void chan_pass2(const float* a, uint32_t M1, uint32_t M2, const float* tw, uint32_t k, float& re, float& im)
+{
+    const uint32_t M = M1 * M2, k2 = k % M2;
+    re = 0.0f; im = 0.0f;
+    for (uint32_t r1 = 0, t = 0; r1 < M1; ++r1) {
+        const uint32_t e = r1 * M2 + k2;
+        chan_mac(a[2 * e], a[2 * e + 1], tw[2 * t], tw[2 * t + 1], re, im);
+        t += k; if (t >= M) t -= M;
+    }
+}
+
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).
 constexpr int RRC_TAPS = 150;

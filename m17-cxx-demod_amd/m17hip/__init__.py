@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10}
+           "tune2": 10, "channelise": 11}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -73,6 +73,7 @@ EXPORTS = [
     "m17hip_wide_default_taps", "m17hip_wide_config", "m17hip_wide_channels",
     "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async", "m17hip_upload_wide_device_async",
     "m17hip_wide_default_taps2", "m17hip_wide_config2",
+    "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
@@ -170,6 +171,37 @@ def wide_default_taps2(decim1, decim2):
     if code != 0:
         raise M17HipError(f"m17hip_wide_default_taps2: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
     return t1[: n1.value].copy(), t2[: n2.value].copy()
+
+
+def wide_raster_default_taps(decim):
+    """The default low-pass of wide_raster for decimation `decim` (1..64): float32 [32 * decim + 1], wide_default_taps(decim) word for word where that
+    exists — m17hip_wide_raster_default_taps (no context, no GPU)."""
+    n = C.c_uint32(0)
+    taps = np.zeros(32 * 64 + 1, dtype=np.float32)
+    code = load_library().m17hip_wide_raster_default_taps(C.c_uint32(decim), _ptr(taps), C.c_uint32(taps.size), C.byref(n))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_raster_default_taps: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return taps[: n.value].copy()
+
+
+def wide_raster_twiddles(bins):
+    """The channeliser's twiddle table for a raster of `bins`: complex64 [bins], exp(-2 pi j k / bins) made in double and rounded — the very words the
+    device computes with; m17hip_wide_raster_twiddles (no context, no GPU)."""
+    tw = np.zeros(max(int(bins), 1), dtype=np.complex64)
+    code = load_library().m17hip_wide_raster_twiddles(C.c_uint32(bins), tw.ctypes.data_as(C.c_void_p), C.c_uint32(2 * tw.size))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_raster_twiddles: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return tw
+
+
+def wide_bin(hz, decim, bins):
+    """The bin of an offset in Hz from the source's centre on a raster of `bins` channels at 48000 * decim samples per second (wide_raster_channels).
+    Raises ValueError when `hz` is not on the raster or outside it."""
+    b = float(hz) * int(bins) / (48000.0 * int(decim))
+    k = int(round(b))
+    if abs(b - k) > 1e-9 * max(1.0, abs(b)) or k < -(int(bins) // 2) or k > (int(bins) - 1) // 2:
+        raise ValueError(f"{hz} Hz is not a channel of a raster of {bins} at {48000 * int(decim)} samples per second")
+    return k
 
 
 def wide_fcw(offset_hz, decim):
@@ -370,6 +402,25 @@ class Context:
         self._chk(self.lib.m17hip_wide_config2(self.h, C.c_uint32(sources), C.c_uint32(decim1), _ptr(t1), C.c_uint32(0 if t1 is None else t1.size),
                                                C.c_uint32(decim2), _ptr(t2), C.c_uint32(0 if t2 is None else t2.size), C.c_int(IQ_I16 if fmt is None else fmt)))
         self._wide = (int(sources), int(decim1) * int(decim2), IQ_I16 if fmt is None else int(fmt))
+
+    def wide_raster(self, sources, decim, bins, fmt=None, taps=None):
+        """`sources` wide IQ streams at 48000 * decim samples per second (decim 1..64) in format `fmt`, every one split into `bins` channels spaced
+        48000 * decim / bins Hz by the polyphase channeliser, low-passed with `taps` (None: wide_raster_default_taps(decim)).  Replaces wide_config and
+        wide_config2 and is replaced by them; channels are named by wide_raster_channels — m17hip_wide_raster."""
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self._chk(self.lib.m17hip_wide_raster(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_uint32(bins), C.c_int(IQ_I16 if fmt is None else fmt),
+                                              _ptr(t), C.c_uint32(0 if t is None else t.size)))
+        self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+
+    def wide_raster_channels(self, source, bin):
+        """Local channel c listens to bin[c] (wide_bin; -bins / 2 <= bin < bins / 2) of source[c] from the blocks uploaded after this call; several
+        channels may name the same one — m17hip_wide_raster_channels."""
+        src = np.ascontiguousarray(np.asarray(source, dtype=np.uint32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(bin, dtype=np.int64).reshape(-1).astype(np.int32))
+        if src.size != b.size:
+            raise ValueError("one source and one bin per channel")
+        self._chk(self.lib.m17hip_wide_raster_channels(self.h, _ptr(src) if src.size else None, b.ctypes.data_as(C.c_void_p) if b.size else None,
+                                                       C.c_uint32(src.size)))
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

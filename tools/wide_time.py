@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --raster M] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -9,7 +9,13 @@ The floor counts what the algorithm needs from the shapes, at the f32 vector rat
     filter:  C T L packed fma per lane, / 64 lanes
     mixing:  C T R samples (each channel mixes its own copy: independent of the number of sources), MIX_OPS plain vector operations each — counted from
              detail/core.h: the oscillator's 2 + 2 x 8 + 2 multiplies and adds and 9 integer / select steps, fm_cross's 6, 2 conversions, 3 address steps
-over 4 SIMDs x CUs x the shader clock seen while the blocks ran (read from sysfs, read only)."""
+over 4 SIMDs x CUs x the shader clock seen while the blocks ran (read from sysfs, read only).
+With --raster M it is the channeliser of m17hip_wide_raster (chan_kernel, csrc/m17_chan_kernels.hpp; library timer "channelise") at `decim` (1..64) with the
+default taps, every source heard on channels_per_source distinct bins.  Its floor is counted per SOURCE and output, not per channel:
+    fold:    S T L packed fma (every tap meets one sample)
+    pass 1:  S T M M2 complex steps of 4 plain fma, M = M1 x M2 as the library factors it
+    pass 2:  C T M1 complex steps of 4 plain fma
+and no mixing term: there is no oscillator."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -24,6 +30,11 @@ R2 = 0   # (0: one stage)
 if "--decim2" in ARGS:
     k = ARGS.index("--decim2")
     R2 = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+RASTER = 0   # (0: a tuner)
+if "--raster" in ARGS:
+    k = ARGS.index("--raster")
+    RASTER = int(ARGS[k + 1])
     del ARGS[k:k + 2]
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
@@ -63,12 +74,16 @@ stream = ctx.torch_stream()
 g = torch.Generator(device='cuda').manual_seed(609)
 x = torch.randint(-20000, 20000, (S, T * RATE, 2), dtype=torch.int16, device='cuda', generator=g)
 torch.cuda.synchronize()
-if R2:
+rng = np.random.default_rng(609)
+if RASTER:
+    ctx.wide_raster(S, R, RASTER, m17hip.IQ_I16)
+    ctx.wide_raster_channels(np.repeat(np.arange(S), PER), np.concatenate([rng.permutation(RASTER)[:PER] - RASTER // 2 for _ in range(S)]))
+elif R2:
     ctx.wide_config2(S, R, R2, m17hip.IQ_I16)
 else:
     ctx.wide_config(S, R, m17hip.IQ_I16)
-rng = np.random.default_rng(609)
-ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATE) for f in rng.uniform(-24000.0 * RATE, 24000.0 * RATE, C)])
+if not RASTER:
+    ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATE) for f in rng.uniform(-24000.0 * RATE, 24000.0 * RATE, C)])
 
 
 def call():
@@ -88,18 +103,24 @@ for _ in range(REP):
     b.record(stream)
     b.synchronize()
     ev.append(a.elapsed_time(b))
-ms, n = ctx.timing_get("tune2" if R2 else "tune")
+ms, n = ctx.timing_get("channelise" if RASTER else "tune2" if R2 else "tune")
 ctx.timing(False)
 clocks.stop = True
 cus = torch.cuda.get_device_properties(0).multi_processor_count
 mhz = max(clocks.seen.values()) if clocks.seen else 2400
 FILTER = C * T * (R2 * L + L2 if R2 else L) / 64 * 4
 cycles = FILTER + C * T * RATE * MIX_OPS / 64 * 2
+if RASTER:
+    M2 = max(d for d in range(1, RASTER + 1) if RASTER % d == 0 and d * d <= RASTER)
+    M1 = RASTER // M2
+    FILTER = S * T * L / 64 * 4
+    cycles = FILTER + (S * T * RASTER * M2 + C * T * M1) * 4 / 64 * 2
 floor_ms = cycles / (4 * cus * mhz * 1e6) * 1e3
 kernel_ms = ms / n
 step = [v * T / 480000.0 * C / 4096.0 for v in DEMOD_STEP_MS]
 print(json.dumps({
-    "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, **({"decim2": R2, "taps2": L2} if R2 else {}), "repeats": REP, "launches": n,
+    "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, **({"decim2": R2, "taps2": L2} if R2 else {}),
+    **({"raster": RASTER} if RASTER else {}), "repeats": REP, "launches": n,
     "kernel_ms": round(kernel_ms, 3), "stream_ms": [round(v, 3) for v in ev], "stream_ms_median": round(float(np.median(ev)), 3),
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
