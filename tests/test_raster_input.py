@@ -364,3 +364,47 @@ def test_example_takes_a_bin_of_a_2400k_raster(basebands):
                 ["--raster", "192", "--bin", "0", "--decim2", "5"]):
         assert subprocess.run([exe, "--wide-u8", "--decim", "50"] + bad, input=b"", capture_output=True, env=env).returncode == 2, bad
     assert subprocess.run([exe, "--wide-u8", "--decim", "65", "--raster", "192", "--bin", "0"], input=b"", capture_output=True, env=env).returncode == 2
+
+
+# ---- 8: the inputs of tests/test_gpu_call_orders_raster.py ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["i16", "u8"])
+def test_reference_data_of_the_call_order_module_meets_its_premises(fmt):
+    """tests/test_gpu_call_orders_raster.py's reference data built without a device — its sources (the same seed and length), the distinct channel set, the
+    alternative tables — and the conditions on them its cases lean on, at a block 1 of 385 outputs and a block of 384 behind it (a prefix of the module's
+    block 1: rows that differ here differ there): exactly one pair of channels has identical words and every other pair differs, in both blocks; under
+    every alternative table each moved channel differs from the base table's, in block 1 and in the block behind; the count at the boundary is nonzero
+    mod 192 and a feed that lost it has other words on every channel whose bin notices; and — over the module's whole block 1, on the nine channels that
+    listen to a transmission — every transmission bin yields records."""
+    import test_gpu_call_orders_raster as cr
+    import test_gpu_call_orders_formats as par
+    import copy
+    n1, nb = cr.TB + 1, cr.TB
+    assert sorted(set(cr.BINS.tolist())) == sorted(set(cr.TX_BINS) | set(cr._OTHERS)) and {-96, 0, 95} <= set(cr.BINS.tolist())
+    assert [int(np.sum(cr.SRC == s)) for s in range(cr.S)] == [32, 32] and cr.ALL == 64 * cr.REP and cr.NS <= 256
+    x = cr.sources(cr.FMTS[fmt])
+    assert x.shape[1] == cr.TOTAL * cr.R and cr.REP * x[0].nbytes * cr.S <= 512 * 10 ** 6
+    base = cr.feeds(x)
+    y1 = base.block(0, n1)
+    cr.one_pair_alike(y1)
+    assert base.per_source[0].count == n1 * cr.R and (n1 * cr.R) % cr.M != 0 and ((cr.T1 + 1) * cr.R) % cr.M == (n1 * cr.R) % cr.M
+    behind = copy.deepcopy(base)
+    y2 = base.block(n1, n1 + nb)
+    cr.one_pair_alike(y2)
+    lost = copy.deepcopy(behind)
+    for t in lost.per_source:
+        t.count = 0
+    notices = [c for c in range(64) if (cr.BINS[c] * n1 * cr.R) % cr.M != 0]
+    assert len(notices) >= 60 and (_u32(lost.block(n1, n1 + nb)) != _u32(y2)).any(axis=1)[notices].all()
+    for k in (1, 2, 3):
+        who, src, bins = cr.table(k)
+        assert who.size == 16 and (src[who] != cr.SRC[who]).all() and sorted(np.bincount(src).tolist()) == [16, 48]
+        assert len({(int(s), int(b)) for s, b in zip(src, bins)}) < 63 and not {(int(s), int(b)) for s, b in zip(src, bins)} <= {(int(s), int(b)) for s, b in zip(cr.SRC, cr.BINS)}
+        cr.moved_differ(y1, cr.feeds(x, src, bins).block(0, n1), who)
+        other = copy.deepcopy(behind)
+        other.src, other.bins = list(src), list(bins)
+        cr.moved_differ(y2, other.block(n1, n1 + nb), who)
+    tx = cr.TX_CHANNELS
+    y = cr.feeds(x, cr.SRC[tx], cr.BINS[tx]).block(0, cr.T1)
+    assert np.array_equal(_u32(y[:, :n1]), _u32(y1[tx]))
+    rows = par.Expect(y).run(0, cr.T1)
+    assert all(r.size > 0 for r in rows), [r.size for r in rows]
