@@ -367,6 +367,25 @@ int m17hip_slice_llr(m17hip_ctx* ctx, const float* sym_host, uint32_t rows, uint
 int m17hip_decode_frames(m17hip_ctx* ctx, const int8_t* llr368_host, uint32_t n_frames, const uint8_t* sync_type,
                          uint8_t* state_io, uint8_t* lich_io, uint8_t* lsf_io, int8_t* dep401_io, int64_t* cost_io,
                          m17_frame_rec* recs, uint8_t* nrec);
+/* TEST HOOK (ABI 612; no product path calls it): M17FrameDecoder::operator() over `channels` independent sequences of `frames` 368-LLR frames
+ * each, in the form of the decoder the caller names — the forms the full chain runs are otherwise reached through m17hip_demod_run alone, on
+ * whatever LLRs a signal produces.
+ *   form 0  one lane per channel, the lane-per-frame decoder with 32-bit metrics (the arithmetic of m17hip_decode_frames, frame after frame);
+ *   form 1  one wave per channel, the wave decoder (sixteen lanes = sixteen states), every frame decoded where it completes: what the
+ *           sequential kernel runs under m17hip_tune key 15 = 0, and for every LSF, LICH and packet frame under any setting;
+ *   form 2  one wave per channel with a deferred-frame store: stream and BERT payload frames are left in the store, then the kernel that
+ *           settles the end of a run and the deferred decode (one lane per frame, packed 16-bit metrics) run as m17hip_demod_run queues them.
+ * llr368[channels][frames][368], sync_type[channels][frames] (0 LSF, 1 stream, 2 packet, 3 BERT); per channel in and out, as
+ * m17hip_decode_frames: state_io (State enum, 0..4), lich_io, lsf_io[30], dep401_io, cost_io (-1 = size_t(-1)).  Out: recs[channels][rec_cap]
+ * (slots beyond a channel's callbacks stay zero; `channel` = the sequence, `seq` = the callback's index, `sample_pos` = the frame's index),
+ * nrec[channels] (callbacks, those that found the store full included), *overflow_out (1 if any did), cost_trace[channels][frames]: the
+ * viterbi_cost as it stands after each frame, -1 for size_t(-1).  The three forms give the same results.
+ * M17HIP_EINVAL — before anything is launched — for a NULL pointer, another form, channels, frames or rec_cap of 0, an LLR or a dep401
+ * outside [-7, 7] (the slicer produces nothing else and the store's nibbles hold nothing else), a state above 4, a sync type above 3, a
+ * cost below -1 or above INT32_MAX.  The context's runs, records and demodulator state are not touched. */
+int m17hip_decode_sequences(m17hip_ctx* ctx, int form, const int8_t* llr368_host, const uint8_t* sync_type, uint32_t channels, uint32_t frames,
+                            uint32_t rec_cap, uint8_t* state_io, uint8_t* lich_io, uint8_t* lsf_io, int8_t* dep401_io, int64_t* cost_io,
+                            m17_frame_rec* recs, uint32_t* nrec, uint32_t* overflow_out, int32_t* cost_trace);
 
 /* ---- the full chain ------------------------------------------------------------------------------- */
 /* Fresh demodulators for every channel (M17Demodulator ctor + zero-initialised storage). */

@@ -307,4 +307,126 @@ __global__ __launch_bounds__(64) void settle_tail_kernel(SettleParams P)
     }
 }
 
+// TEST HOOK (parity API, m17hip_decode_sequences): C channels x F frames of caller-chosen LLRs through the frame decoder in each form the device has
+// it in.  The two drivers below only CALL decode_frame: the lane form (decode_frame<false>, today's decode_frames_kernel over F frames in order) and the
+// wave form (decode_frame<true>, what K5 runs: with no deferred-frame store every frame is decoded where it completes — m17hip_tune key 15 = 0 —, with
+// one the stream and BERT payload frames are left to settle_tail_kernel and decode_deferred_kernel, which the host then launches as they stand).
+struct DecodeSeqParams {
+    const int8_t* llr;        // [C][F][368]
+    const uint8_t* sync_type; // [C][F]
+    uint8_t* state_io;        // [C]
+    uint8_t* lich_io;         // [C]
+    uint8_t* lsf_io;          // [C][30]
+    int8_t* dep401_io;        // [C]
+    int64_t* cost_io;         // [C] (-1: size_t(-1); the wave form with a store leaves it to the host, which reads it from `state` behind settle_tail_kernel)
+    FrameRec* recs;           // [C][rec_cap]
+    uint32_t rec_cap;
+    uint32_t* nrec;           // [C] callbacks of the channel, those beyond rec_cap included
+    int32_t* cost_trace;      // [C][F] viterbi_cost after each frame (without a store)
+    uint32_t* defer;          // wave form only: [C][rec_cap][46] deferred-frame store, or nullptr
+    SeqState* state;          // with a store: [C], of which the two cost fields are written
+    Diag* diag;               // with a store: [C][F], entry f carries the cost (or the tag that stands for it) after frame f
+    uint32_t C, F;
+    const DecodeTables* tables;
+    uint32_t* overflow;
+};
+
+__global__ __launch_bounds__(64) void decode_seq_lane_kernel(DecodeSeqParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    DecodeLds L;
+    L.llr = lds;                // [92][64], as decode_frames_kernel
+    L.hist = lds + 92 * 64;     // [122][64]
+    L.outb = L.hist + 122 * 64; // [8][64]
+    L.lsf = L.outb + 8 * 64;    // [8][64]
+    L.stride = 64;
+    L.prof = nullptr;
+    L.soft = nullptr;
+    L.src = &P.tables->src[0][0];
+    L.lich_src = P.tables->lich_src;
+    const int lane = threadIdx.x;
+    const uint32_t c = blockIdx.x * 64 + lane;
+    if (c >= P.C) return;
+    for (int k = 0; k < 8; ++k) {
+        uint32_t w = 0;
+        for (int q = 0; q < 4; ++q)
+            if (4 * k + q < 30) w |= (uint32_t)P.lsf_io[(size_t)c * 30 + 4 * k + q] << (8 * q);
+        L.lsf[k * 64 + lane] = w;
+    }
+    DecoderRegs D{P.state_io[c], P.lich_io[c], (int)P.dep401_io[c]};
+    const int64_t cin = P.cost_io[c];
+    uint32_t cost = cin < 0 ? 0xFFFFFFFFu : (uint32_t)cin;
+    uint32_t n_run = 0, seq = 0;
+    for (uint32_t f = 0; f < P.F; ++f) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(P.llr + ((size_t)c * P.F + f) * 368);
+        for (int k = 0; k < 92; ++k) L.llr[k * 64 + lane] = src[k];
+        const uint32_t st = P.sync_type[(size_t)c * P.F + f];
+        RecSink S{P.recs + (size_t)c * P.rec_cap, P.rec_cap, nullptr, nullptr, c, f, st, P.overflow, nullptr};   // (the record's sample position: the frame's index)
+        cost = decode_frame(P.tables, L, lane, st, D, cost, S, n_run, seq);
+        P.cost_trace[(size_t)c * P.F + f] = (int32_t)cost;
+    }
+    P.state_io[c] = (uint8_t)D.state;
+    P.lich_io[c] = (uint8_t)D.lich_segments;
+    P.dep401_io[c] = (int8_t)D.stale401;
+    P.cost_io[c] = cost == 0xFFFFFFFFu ? (int64_t)-1 : (int64_t)cost;
+    P.nrec[c] = n_run;
+    for (int k = 0; k < 30; ++k) P.lsf_io[(size_t)c * 30 + k] = (uint8_t)byte_at(L.lsf, 64, lane, k);
+}
+
+// one wave per channel; LDS as K5 lays a wave's decoder out (m17_wave_body.inc): stride 1, the cost words, the frame, the decisions, the output bytes, the LSF
+__global__ __launch_bounds__(64) void decode_seq_wave_kernel(DecodeSeqParams P)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[488 + 92 + 122 + 8 + 8];
+    DecodeLds L;
+    L.soft = reinterpret_cast<int32_t*>(lds);   // [488]
+    L.llr = lds + 488;                          // [92]
+    L.hist = L.llr + 92;                        // [122]
+    L.outb = L.hist + 122;                      // [8]
+    L.lsf = L.outb + 8;                         // [8]
+    L.stride = 1;
+    L.prof = nullptr;
+    L.src = &P.tables->src[0][0];
+    L.lich_src = P.tables->lich_src;
+    const int wl = threadIdx.x;
+    const uint32_t c = blockIdx.x;   // (wave-uniform: the frame decoder's branches are taken by the whole wave, as in K5)
+    if (c >= P.C) return;
+    if (wl < 8) {
+        uint32_t w = 0;
+        for (int q = 0; q < 4; ++q)
+            if (4 * wl + q < 30) w |= (uint32_t)P.lsf_io[(size_t)c * 30 + 4 * wl + q] << (8 * q);
+        L.lsf[wl] = w;
+    }
+    DecoderRegs D{P.state_io[c], P.lich_io[c], (int)P.dep401_io[c]};
+    const int64_t cin = P.cost_io[c];
+    uint32_t cost = cin < 0 ? 0xFFFFFFFFu : (uint32_t)cin;
+    uint32_t n_run = 0, seq = 0;
+    uint32_t* defer = P.defer ? P.defer + (size_t)c * P.rec_cap * 46 : nullptr;
+    for (uint32_t f = 0; f < P.F; ++f) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(P.llr + ((size_t)c * P.F + f) * 368);
+        wave_lds_sync();
+        for (int k = wl; k < 92; k += 64) L.llr[k] = src[k];
+        wave_lds_sync();
+        const uint32_t st = P.sync_type[(size_t)c * P.F + f];
+        RecSink S{P.recs + (size_t)c * P.rec_cap, P.rec_cap, nullptr, nullptr, c, f, st, P.overflow, defer};
+        cost = decode_frame<true>(P.tables, L, 0, st, D, cost, S, n_run, seq, wl);
+        wave_lds_sync();
+        if (wl == 0) {
+            if (P.diag) P.diag[(size_t)c * P.F + f].viterbi_cost = (int32_t)cost;
+            else P.cost_trace[(size_t)c * P.F + f] = (int32_t)cost;
+        }
+    }
+    wave_lds_sync();
+    if (wl == 0) {
+        P.state_io[c] = (uint8_t)D.state;
+        P.lich_io[c] = (uint8_t)D.lich_segments;
+        P.dep401_io[c] = (int8_t)D.stale401;
+        if (P.state) {   // the two places of a channel's state that can hold a tag at the end of a run (settle_tail_kernel)
+            P.state[c].hot.viterbi_cost = cost;
+            P.state[c].cold.diag.viterbi_cost = (int32_t)cost;
+        } else P.cost_io[c] = cost == 0xFFFFFFFFu ? (int64_t)-1 : (int64_t)cost;
+        P.nrec[c] = n_run;
+        for (int k = 0; k < 30; ++k) P.lsf_io[(size_t)c * 30 + k] = (uint8_t)byte_at(L.lsf, 1, 0, k);
+    }
+}
+
 }  // namespace m17

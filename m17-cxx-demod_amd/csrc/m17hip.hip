@@ -1176,7 +1176,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 611; }
+int m17hip_version(void) { return 612; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1303,6 +1303,8 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     if (hipFuncSetAttribute((const void*)decode_deferred_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DEFER_LDS_BYTES) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipFuncSetAttribute((const void*)decode_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (92 + 122 + 16) * 64 * 4) != hipSuccess)
+        return fail(M17HIP_EHIP);
+    if (hipFuncSetAttribute((const void*)decode_seq_lane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (92 + 122 + 16) * 64 * 4) != hipSuccess)
         return fail(M17HIP_EHIP);
     if (hipMemset(c->overflow, 0, 32) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);   // (default-stream work of the creation is through before the context's own streams start)
     for (Event* e : {&c->sets[0].done, &c->sets[1].done, &c->sets[0].chain, &c->sets[1].chain, &c->ev_dst, &c->ev_switch, &c->ev_fetch})
@@ -2289,6 +2291,107 @@ int m17hip_decode_frames(m17hip_ctx* c, const int8_t* llr368_host, uint32_t n, c
     HIPCHK(c, hipMemcpyAsync(recs, b + o_rec, (size_t)n * 2 * sizeof(FrameRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(nrec, b + o_nrec, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return M17HIP_OK;
+}
+
+// TEST HOOK (include/m17hip.h): the frame decoder in each of its device forms on caller-chosen LLRs.  Everything lives in the operator scratch — the
+// context's record sets, demodulator state, diagnostic log and overflow words are not touched.
+int m17hip_decode_sequences(m17hip_ctx* c, int form, const int8_t* llr368_host, const uint8_t* sync_type, uint32_t C, uint32_t F, uint32_t rec_cap,
+                            uint8_t* state_io, uint8_t* lich_io, uint8_t* lsf_io, int8_t* dep401_io, int64_t* cost_io, m17_frame_rec* recs,
+                            uint32_t* nrec, uint32_t* overflow_out, int32_t* cost_trace)
+{
+    if (!llr368_host || !sync_type || !state_io || !lich_io || !lsf_io || !dep401_io || !cost_io || !recs || !nrec || !overflow_out || !cost_trace)
+        return M17HIP_EINVAL;
+    if (form < 0 || form > 2 || C == 0 || F == 0 || rec_cap == 0) return M17HIP_EINVAL;
+    if (rec_cap > 0x7FFFFFFFu || (uint64_t)C * F > 0x7FFFFFFFull / 368u || (uint64_t)C * rec_cap > 0x7FFFFFFFull / 184u) return M17HIP_EINVAL;   // (a slot is a tag's low 31 bits; sizes within 2 GB)
+    // the domain: what the slicer produces and the nibble forms can hold
+    const size_t nf = (size_t)C * F;
+    for (size_t i = 0; i < nf * 368; ++i)
+        if (llr368_host[i] < -7 || llr368_host[i] > 7) return M17HIP_EINVAL;
+    for (size_t i = 0; i < nf; ++i)
+        if (sync_type[i] > 3) return M17HIP_EINVAL;
+    for (uint32_t i = 0; i < C; ++i)
+        if (dep401_io[i] < -7 || dep401_io[i] > 7 || state_io[i] > 4 || cost_io[i] < -1 || cost_io[i] > 0x7FFFFFFF) return M17HIP_EINVAL;   // (no tag comes in as a cost)
+    if (!c) return M17HIP_EINVAL;
+    GUARD(c);
+    const bool store = form == 2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += round_up(bytes, 256); return o; };
+    const size_t rec_b = (size_t)C * rec_cap * sizeof(FrameRec);
+    const size_t o_llr = take(nf * 368), o_st = take(nf), o_state = take(C), o_lich = take(C), o_lsf = take((size_t)C * 30), o_dep = take(C),
+                 o_cost = take((size_t)C * 8), o_rec = take(rec_b), o_nrec = take((size_t)C * 4), o_trace = take(nf * 4), o_ovf = take(4),
+                 o_defer = take(store ? (size_t)C * rec_cap * 46 * 4 : 0), o_seq = take(store ? (size_t)C * sizeof(SeqState) : 0),
+                 o_diag = take(store ? nf * sizeof(Diag) : 0), o_dcnt = take(store ? (size_t)C * 4 : 0),
+                 o_hist = take(store ? (size_t)C * DEFER_HIST_WORDS * 64 * 4 : 0);
+    HIPCHK(c, c->scratch.grow(off, &c->last_hip));
+    char* b = c->scratch;
+    HIPCHK(c, hipMemcpyAsync(b + o_llr, llr368_host, nf * 368, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_st, sync_type, nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_state, state_io, C, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_lich, lich_io, C, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_lsf, lsf_io, (size_t)C * 30, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_dep, dep401_io, C, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b + o_cost, cost_io, (size_t)C * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(b + o_rec, 0, rec_b, c->stream));
+    HIPCHK(c, hipMemsetAsync(b + o_ovf, 0, 4, c->stream));
+    DecodeSeqParams P{};
+    P.llr = (const int8_t*)(b + o_llr); P.sync_type = (const uint8_t*)(b + o_st); P.state_io = (uint8_t*)(b + o_state); P.lich_io = (uint8_t*)(b + o_lich);
+    P.lsf_io = (uint8_t*)(b + o_lsf); P.dep401_io = (int8_t*)(b + o_dep); P.cost_io = (int64_t*)(b + o_cost); P.recs = (FrameRec*)(b + o_rec);
+    P.rec_cap = rec_cap; P.nrec = (uint32_t*)(b + o_nrec); P.cost_trace = (int32_t*)(b + o_trace); P.C = C; P.F = F; P.tables = c->tables;
+    P.overflow = (uint32_t*)(b + o_ovf);
+    std::vector<Diag> diag;
+    std::vector<SeqState> seq;
+    const EvParams no_fold{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u};   // (no EVM operations: neither kernel gets fold blocks)
+    if (form == 0) {
+        hipLaunchKernelGGL(decode_seq_lane_kernel, dim3((C + 63) / 64), dim3(64), (92 + 122 + 16) * 64 * 4, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+    } else if (!store) {
+        hipLaunchKernelGGL(decode_seq_wave_kernel, dim3(C), dim3(64), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+    } else {
+        // K5's part, then the production kernels as they stand and in production order: settle_tail_kernel (the one or two costs the state still names), then
+        // decode_deferred_kernel (every other deferred frame; its tag replacement over the diagnostic rows is what fills cost_trace)
+        P.defer = (uint32_t*)(b + o_defer); P.state = (SeqState*)(b + o_seq); P.diag = (Diag*)(b + o_diag);
+        HIPCHK(c, hipMemsetAsync(b + o_seq, 0, (size_t)C * sizeof(SeqState), c->stream));
+        HIPCHK(c, hipMemsetAsync(b + o_diag, 0, nf * sizeof(Diag), c->stream));
+        std::vector<uint32_t> dcnt(C, F);
+        HIPCHK(c, hipMemcpyAsync(b + o_dcnt, dcnt.data(), (size_t)C * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (dcnt is a local)
+        hipLaunchKernelGGL(decode_seq_wave_kernel, dim3(C), dim3(64), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+        SettleParams S{P.recs, rec_cap, P.defer, c->tables, P.state, C, no_fold};
+        hipLaunchKernelGGL(settle_tail_kernel, dim3(C), dim3(64), SETTLE_LDS_BYTES, c->stream, S);
+        HIPCHK(c, hipGetLastError());
+        DeferParams D{};
+        D.recs = P.recs; D.rec_cap = rec_cap; D.rec_count = P.nrec; D.defer = P.defer; D.hist = (uint32_t*)(b + o_hist); D.tables = c->tables;
+        D.state = P.state; D.diag_log = P.diag; D.diag_cap = F; D.diag_count = (const uint32_t*)(b + o_dcnt); D.C = C;
+        D.ev = no_fold;
+        hipLaunchKernelGGL(decode_deferred_kernel, dim3(defer_blocks(C)), dim3(64 * DEFER_CPB), DEFER_LDS_BYTES, c->stream, D);
+        HIPCHK(c, hipGetLastError());
+        diag.resize(nf);
+        seq.resize(C);
+        HIPCHK(c, hipMemcpyAsync(diag.data(), b + o_diag, nf * sizeof(Diag), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(seq.data(), b + o_seq, (size_t)C * sizeof(SeqState), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(state_io, b + o_state, C, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(lich_io, b + o_lich, C, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(lsf_io, b + o_lsf, (size_t)C * 30, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dep401_io, b + o_dep, C, hipMemcpyDeviceToHost, c->stream));
+    if (!store) {
+        HIPCHK(c, hipMemcpyAsync(cost_io, b + o_cost, (size_t)C * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cost_trace, b + o_trace, nf * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(recs, b + o_rec, rec_b, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nrec, b + o_nrec, (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(overflow_out, b + o_ovf, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (store) {
+        for (size_t i = 0; i < nf; ++i) cost_trace[i] = diag[i].viterbi_cost;
+        for (uint32_t i = 0; i < C; ++i) {
+            const uint32_t v = seq[i].hot.viterbi_cost;
+            cost_io[i] = v == 0xFFFFFFFFu ? (int64_t)-1 : (int64_t)v;
+        }
+    }
     return M17HIP_OK;
 }
 

@@ -74,6 +74,7 @@ EXPORTS = [
     "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async", "m17hip_upload_wide_device_async",
     "m17hip_wide_default_taps2", "m17hip_wide_config2",
     "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
+    "m17hip_decode_sequences",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
@@ -626,6 +627,32 @@ class Context:
         self._chk(self.lib.m17hip_decode_frames(self.h, _ptr(l), C.c_uint32(n), _ptr(st), _ptr(state), _ptr(lich), _ptr(lsf), _ptr(dep401),
                                                 _ptr(cost), _ptr(recs), _ptr(nrec)))
         return recs, nrec, state, lich, lsf, dep401, cost
+
+    def decode_sequences(self, form, llr368, sync_type, rec_cap, state=None, lich=None, lsf=None, dep401=None, cost=None):
+        """TEST HOOK (m17hip_decode_sequences): C sequences of F frames through the frame decoder in device form `form` (0 lane per channel, 1 wave
+        per channel, 2 wave with a deferred-frame store + the kernels that settle and decode it).  llr368 [C][F][368] within [-7, 7], sync_type
+        [C][F].  Returns (recs [C][rec_cap], nrec [C], overflow, state, lich, lsf, dep401, cost, cost_trace [C][F])."""
+        l = np.ascontiguousarray(llr368, dtype=np.int8)
+        if l.ndim != 3 or l.shape[2] != 368:
+            raise TypeError("llr368 is [channels][frames][368]")
+        n, F = l.shape[0], l.shape[1]
+        st = np.ascontiguousarray(sync_type, dtype=np.uint8)
+        if st.shape != (n, F):
+            raise TypeError("sync_type is [channels][frames]")
+        state = np.zeros(n, np.uint8) if state is None else np.ascontiguousarray(state, dtype=np.uint8).copy()
+        lich = np.zeros(n, np.uint8) if lich is None else np.ascontiguousarray(lich, dtype=np.uint8).copy()
+        lsf = np.zeros((n, 30), np.uint8) if lsf is None else np.ascontiguousarray(lsf, dtype=np.uint8).copy()
+        dep401 = np.zeros(n, np.int8) if dep401 is None else np.ascontiguousarray(dep401, dtype=np.int8).copy()
+        cost = np.zeros(n, np.int64) if cost is None else np.ascontiguousarray(cost, dtype=np.int64).copy()
+        if state.shape != (n,) or lich.shape != (n,) or lsf.shape != (n, 30) or dep401.shape != (n,) or cost.shape != (n,):
+            raise TypeError("the decoder state is one entry per channel")
+        recs = np.zeros((n, max(int(rec_cap), 1)), dtype=FRAME_REC)
+        nrec = np.zeros(n, dtype=np.uint32)
+        ovf = C.c_uint32(0)
+        trace = np.zeros((n, F), dtype=np.int32)
+        self._chk(self.lib.m17hip_decode_sequences(self.h, C.c_int(form), _ptr(l), _ptr(st), C.c_uint32(n), C.c_uint32(F), C.c_uint32(rec_cap), _ptr(state),
+                                                   _ptr(lich), _ptr(lsf), _ptr(dep401), _ptr(cost), _ptr(recs), _ptr(nrec), C.byref(ovf), _ptr(trace)))
+        return recs, nrec, int(ovf.value), state, lich, lsf, dep401, cost, trace
 
     def kalman_trace(self, z, dt, wrap, z0=0.0, order=3):
         """rows x n updates of the 2-state Kalman filter (kal_update, as the full-chain kernel runs it): state after each update."""
