@@ -5,12 +5,15 @@
 // discriminated on the device — rtl_sdr -s 240000 ... | m17-demod-gpu --wide-u8 --decim 5 --offset-hz 12500; with --decim2 R2 as well the feed is at
 // 48000 R R2 and decimated in two stages — rtl_sdr -s 2400000 ... | m17-demod-gpu --wide-u8 --decim 10 --decim2 5 --offset-hz 12500; with --raster M --bin B in place of --offset-hz
 // the feed at 48000 R (R up to 64) is split into M channels by the polyphase channeliser and bin B of them demodulated — rtl_sdr -s 2400000 ... |
-// m17-demod-gpu --wide-u8 --decim 50 --raster 192 --bin 1), one line per frame callback on
+// m17-demod-gpu --wide-u8 --decim 50 --raster 192 --bin 1; with --scan STRIDE beside --raster every STRIDE-th output of the feed is surveyed on the device
+// and after each block the occupied bins — more than --scan-margin dB, default 20, over the median of the 192 — are printed to stderr: bin, Hz from the
+// centre, dB over the floor), one line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
 #include "m17cxx/M17Demodulator.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +51,8 @@ int main(int argc, char** argv)
     uint32_t raster = 0;   // (0: a tuner)
     long bin = 0;
     float iq_gain = 1.0f;
+    uint32_t scan = 0;   // (0: no survey)
+    double scan_margin = 20.0;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -61,8 +66,10 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) offset_hz = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(argv[i], "--raster") && i + 1 < argc) { raster = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!raster) raster = 257; }
         else if (!std::strcmp(argv[i], "--bin") && i + 1 < argc) bin = std::strtol(argv[++i], nullptr, 10);
+        else if (!std::strcmp(argv[i], "--scan") && i + 1 < argc) { scan = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!scan) scan = 4097; }
+        else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) scan_margin = std::strtod(argv[++i], nullptr);
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R] [--decim2 R2] [--offset-hz F | --raster M --bin B] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R] [--decim2 R2] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -78,6 +85,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "m17-demod-gpu: decimations of 1 to 16, and an offset inside the +-%g Hz the feed covers\n", half_hz);
         return 2;
     }
+    if (scan && (!(wide && raster) || scan > 4096)) { std::fprintf(stderr, "m17-demod-gpu: --scan STRIDE (1 to 4096) goes with --raster\n"); return 2; }
     M17Demodulator<float> demod(handle_frame);
     demod.diagnostics([](bool, float, float, float, bool, float, int, int, int, int) {});
     demod.iq_gain(iq_gain);
@@ -98,6 +106,23 @@ int main(int argc, char** argv)
         if (raster) demod.wide_raster(decim, raster, (int32_t)bin);
         else if (decim2) demod.wide_config(decim, decim2, offset_hz);
         else demod.wide_config(decim, offset_hz);
+        if (scan) {   // the occupied bins of the one source after each block: the floor is the median of the plane
+            const double spacing = 48000.0 * decim / raster;
+            const bool on = demod.wide_survey(scan, [=](const std::vector<float>& power, uint32_t times, uint64_t first_output) {
+                std::vector<float> sorted(power);
+                std::sort(sorted.begin(), sorted.end());
+                const size_t M = sorted.size();
+                const double floor = M % 2 ? sorted[M / 2] : 0.5 * ((double)sorted[M / 2 - 1] + (double)sorted[M / 2]);
+                std::fprintf(stderr, "scan: outputs from %llu, %u survey times\n", (unsigned long long)first_output, times);
+                if (!(floor > 0.0) || !std::isfinite(floor)) return;
+                for (size_t k = 0; k < M; ++k) {
+                    const double db = 10.0 * std::log10((double)power[k] / floor);
+                    const long b = k <= (M - 1) / 2 ? (long)k : (long)k - (long)M;
+                    if (db > scan_margin) std::fprintf(stderr, "scan: bin %ld %+.1f Hz %.2f dB\n", b, b * spacing, db);
+                }
+            });
+            if (!on) std::fprintf(stderr, "m17-demod-gpu: --scan needs the GPU path (the survey runs on the device); not surveying\n");
+        }
         while (std::cin) {
             if (wide == M17HIP_IQ_I16) { int16_t s[2]; std::cin.read(reinterpret_cast<char*>(s), 4); if (std::cin) demod.wide((float)s[0], (float)s[1]); }
             else if (wide == M17HIP_IQ_F32) { float s[2]; std::cin.read(reinterpret_cast<char*>(s), 8); if (std::cin) demod.wide(s[0], s[1]); }

@@ -220,7 +220,8 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: non-integer resampling, per-source sample counts, squelch / RSSI.  (Sources above 16 x 48 kSPS: two stages,
+ * Out of scope, for a later pull request: non-integer resampling, per-source sample counts, squelch / RSSI under a tuner (per bin of a raster: the survey,
+ * ABI 613, below).  (Sources above 16 x 48 kSPS: two stages,
  * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.) */
 #define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
 /* The filter m17hip_wide_config takes by default — what a user of rtl_fm leaves to its built-in low-pass: ntaps = 32 * decim + 1, a Blackman-windowed
@@ -307,7 +308,8 @@ int m17hip_wide_config2(m17hip_ctx* ctx, uint32_t sources, uint32_t decim1, cons
  * is unchanged.  The twiddles exp(-2 pi j j / M) are DATA: made in one place, on the host, in double, rounded to float, exactly 0 / +-1 on the axes, and
  * tw[M - j] the conjugate of tw[j] to the bit; m17hip_wide_raster_twiddles returns the table the device is given, so a host computes the device's words
  * whatever its libm.
- * Out of scope, for a later pull request: a raster shifted by a fraction of a spacing, non-integer resampling, per-source sample counts, squelch / RSSI. */
+ * Out of scope, for a later pull request: a raster shifted by a fraction of a spacing, non-integer resampling, per-source sample counts.  (Which bins carry
+ * anything — RSSI per bin: the raster survey, ABI 613, below.) */
 /* The default taps of m17hip_wide_raster: the formula of m17hip_wide_default_taps (32 * decim + 1 taps, Blackman-windowed sinc, cutoff 5500 Hz) for
  * decim 1..64, word for word that function's for decim <= 16.  No context is needed.  *ntaps is set whenever decim is valid; M17HIP_EINVAL if it is not, if
  * ntaps is NULL, or if taps is NULL or capacity < *ntaps (nothing written to taps). */
@@ -332,6 +334,36 @@ int m17hip_wide_raster(m17hip_ctx* ctx, uint32_t sources, uint32_t decim, uint32
  * TABLE OWNERSHIP: each table call returns M17HIP_ESTATE under a configuration that is not its own — this one before m17hip_wide_raster or under a tuner,
  * m17hip_wide_channels under a raster. */
 int m17hip_wide_raster_channels(m17hip_ctx* ctx, const uint32_t* source, const int32_t* bin, uint32_t n);
+
+/* ---- the raster survey: per-bin power of every source beside the channeliser (ABI 613) -----------------------
+ * m17hip_wide_raster_channels takes (source, bin) pairs; this says which bins carry anything, without a demodulator channel on them: survey, pick, assign,
+ * demodulate.  With the survey on at `stride`, every wideband block uploaded under a raster is surveyed beside its channeliser:
+ *     c0 = the feed's 64-bit sample count at the block's start (a multiple of decim), N0 = c0 / decim;
+ *     output n of the block is a SURVEY TIME iff (N0 + n + 1) % stride == 0 — a property of the feed, not of how it is cut into blocks; the block's
+ *     survey times are t_0 < ... < t_{J-1}, and J may be 0;
+ *     for every source s and every k < bins, z_k[t_j] is the word the channeliser computes for bin k at output t_j (chan_fold, chan_pass1, chan_pass2 over
+ *     the same history, the same count mod bins and the same twiddle table), whether or not any channel listens to s or k;
+ *     p_j = chan_power(z.re, z.im) = fmaf(re, re, im * im);
+ *     q_g = the chain from +0 of plain float adds of p_j, j = 16 g .. min(16 g + 15, J - 1), ascending (CHAN_SURVEY_GROUP = 16);
+ *     P[s][k] = the chain from +0 of plain float adds of q_g, g ascending.  With J = 0 every P is +0.
+ * The two-level order is part of the definition (m17cxx/detail/core.h has chan_power and the group size, so a host computes the device's words): a grid of
+ * (group, source) workgroups does the first level and a fixed-order kernel the second — no atomics, no serial chain over a long block.  Two kernels
+ * (csrc/m17_chan_survey_kernels.hpp) on the block's own stream behind the channeliser: m17hip_upload_wait and the in-place forms' synchronisation cover
+ * them, the floats the channels get are untouched, and with the survey off a block queues exactly what it queued under ABI 611.  m17hip_timing_get index 12
+ * is the survey (both kernels, one entry per block); m17hip_iq_bytes counts its scratch and planes.
+ * Out of scope, for a later pull request: a survey under the two tuners (they share no z), a waterfall of per-time spectra, channel assignment on the device,
+ * squelching the demodulator itself. */
+/* stride 0 turns the survey off (the default); 1..4096 turns it on for the blocks uploaded AFTER the call — a block already staged is not surveyed
+ * retroactively.  It never waits for anything in flight.  Planes of blocks surveyed before the call are no longer fetched.  M17HIP_ESTATE unless the last
+ * wideband configuration is a raster, and between m17hip_demod_front and its run; M17HIP_EINVAL for a stride above 4096 or a NULL context.  Every
+ * m17hip_wide_config, m17hip_wide_config2 or m17hip_wide_raster call turns the survey off: the plane's shape belongs to the configuration. */
+int m17hip_wide_survey(m17hip_ctx* ctx, uint32_t stride);
+/* The plane of the latest block uploaded with the survey on (back = 0) or of the block before it (back = 1; two planes and two events take turns):
+ * power_host[sources][bins] floats, indexed by k = bin mod bins; *times = J and *first_output = N0 of that block (either may be NULL).  It waits for that
+ * block's survey kernels only, on an event recorded behind the second of them — never for a demodulation run or a later block.  M17HIP_ESTATE if no such
+ * plane exists: the survey is off, no block (or, for back = 1, one block) since it was turned on, or none since m17hip_demod_reset, which starts the feeds
+ * over.  M17HIP_EINVAL for back > 1, a NULL power_host or capacity (in floats) < sources * bins; nothing is written then. */
+int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* times, uint64_t* first_output);
 
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
@@ -819,7 +851,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 8 = discriminate (the FM discriminator of m17hip_upload_iq*: one launch per IQ block),
  * 9 = tune (the tuner of m17hip_upload_wide* under m17hip_wide_config: one launch per wideband block),
  * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
- * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise). */
+ * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
+ * entry per surveyed block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -10,6 +10,7 @@
 #include "m17_wide_kernels.hpp"
 #include "m17_wide2_kernels.hpp"
 #include "m17_chan_kernels.hpp"
+#include "m17_chan_survey_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -35,7 +36,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -288,10 +289,25 @@ struct m17hip_ctx {
         // for the channels of the launch: a copy of its own, written when the table or the launch's channel count has changed.
         TurnTable rdev;
         uint32_t rdev_C = 0;
+        // The raster survey (m17hip_wide_survey; csrc/m17_chan_survey_kernels.hpp): stride != 0 is on.  Two power planes [S][M] take turns like hist, each
+        // with the event recorded behind the block's chan_survey_sum_kernel and the block's J and N0; `latest` names the one of the latest surveyed block.
+        // The scratch [S][groups][M] is every block's: the blocks' launches are ordered by ev_iq.
+        struct Survey {
+            uint32_t stride = 0;
+            DevBuf<float> scratch, plane[2];
+            Event ev[2];
+            bool valid[2] = {false, false};
+            uint32_t times[2] = {0, 0};
+            uint64_t first_output[2] = {0, 0};
+            int latest = 0;
+            hipStream_t fetch = nullptr;   // m17hip_wide_survey_fetch's copies: a stream of its own, behind nothing but the plane's event
+            void forget() { valid[0] = valid[1] = false; }
+            ~Survey() { if (fetch) (void)hipStreamDestroy(fetch); }
+        } sv;
         size_t bytes() const
         {
-            return (taps.size() + taps2.size()) * sizeof(float) + (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) +
-                   (dev.words() + rdev.words()) * 4;
+            return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size()) * sizeof(float) +
+                   (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words()) * 4;
         }
     } wide;
     const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
@@ -1176,7 +1192,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 612; }
+int m17hip_version(void) { return 613; }
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1584,6 +1600,7 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
         if (c->wide.S) {   // (the wideband sources' feeds as well: histories and sample count; the listed form leaves them alone — they are not a channel's)
             for (auto& h : c->wide.hist) HIPCHK(c, hipMemsetAsync(h, 0, h.size() * sizeof(float2), st));
             c->wide.count = 0;
+            c->wide.sv.forget();   // (the planes were blocks of the feed that ends here)
         }
     } else {
         std::vector<uint32_t> v(channels, channels + n);
@@ -1724,6 +1741,43 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     w.count += W;
     return iq_mark(c, st);
 }
+// The survey of one block (m17hip_wide_survey is on), queued behind chan_kernel on the block's stream: it reads what chan_kernel read — src, w.hist[w.par],
+// w.count — and writes the plane whose turn it is.  A block without a survey time (J = 0) queues the second kernel alone: its plane is all +0.
+template <typename IQT>
+static int launch_survey(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, hipStream_t st)
+{
+    auto& w = c->wide;
+    auto& sv = w.sv;
+    const uint64_t N0 = w.count / w.R;
+    const uint32_t first = (uint32_t)((sv.stride - (N0 + 1) % sv.stride) % sv.stride);
+    const uint32_t J = first < T ? (T - 1 - first) / sv.stride + 1 : 0;
+    const uint32_t G = (J + core::CHAN_SURVEY_GROUP - 1) / core::CHAN_SURVEY_GROUP;
+    const int p = sv.latest ^ 1;
+    int r;
+    if (!sv.fetch) HIPCHK(c, hipStreamCreateWithFlags(&sv.fetch, hipStreamNonBlocking));
+    for (auto& e : sv.ev) if (!e) HIPCHK(c, e.create());
+    for (auto& b : sv.plane) if ((r = alloc_code(c, b.grow((size_t)w.S * w.M, &c->last_hip)))) return r;   // (released with every configuration: nothing reads them)
+    if (sv.scratch.size() < (size_t)w.S * G * w.M) {
+        HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be surveyed)
+        if ((r = alloc_code(c, sv.scratch.grow((size_t)w.S * G * w.M, &c->last_hip)))) return r;
+    }
+    sv.valid[p] = false;
+    {
+        Timed tm(c, KT_SURVEY, st);
+        if (G) {
+            const uint32_t WP = survey_wpitch(w.L, w.R, sv.stride), TS = survey_tile(w.L, WP, w.M);
+            hipLaunchKernelGGL(chan_survey_kernel<IQT>, dim3(G, w.S), dim3(SURVEY_THREADS), survey_lds_bytes(w.L, WP, w.M, TS), st, src, pitch, W,
+                               w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.M1, w.M2, w.tw.get(), (uint32_t)(w.count % w.M), first, sv.stride, J, WP, TS,
+                               sv.scratch.get());
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(chan_survey_sum_kernel, dim3((w.S * w.M + 255) / 256), dim3(256), 0, st, sv.scratch.get(), G, w.M, w.S, sv.plane[p].get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(sv.ev[p], st));
+    sv.times[p] = J; sv.first_output[p] = N0; sv.valid[p] = true; sv.latest = p;
+    return M17HIP_OK;
+}
 // The channeliser's launch (m17hip_wide_raster): the same frame, one workgroup per source and tile of output times.
 template <typename IQT>
 static int launch_chan(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
@@ -1767,6 +1821,7 @@ static int launch_chan(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     HIPCHK(c, w.rdev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
     hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
     HIPCHK(c, hipGetLastError());
+    if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;
     if (H) {
         hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
         HIPCHK(c, hipGetLastError());
@@ -1902,6 +1957,9 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     const uint32_t L = (uint32_t)h.size(), L2 = (uint32_t)h2.size();
     const size_t hn = (size_t)sources * std::max<uint32_t>(decim2 ? (L2 - 1) * decim + L - 1 : L - 1, 1);
     w.S = 0;   // (not configured until all of it is there)
+    w.sv.stride = 0; w.sv.forget();   // (the survey's plane has the configuration's shape: off, and its memory back)
+    w.sv.scratch.release(&c->last_hip);
+    for (auto& b : w.sv.plane) b.release(&c->last_hip);
     if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
     if (decim2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
     else w.taps2.release(&c->last_hip);
@@ -2001,6 +2059,33 @@ int m17hip_wide_raster_channels(m17hip_ctx* c, const uint32_t* source, const int
     for (uint32_t ch = 0; ch < n; ++ch) if (source[ch] >= w.S || bin[ch] < lo || bin[ch] > hi) return M17HIP_EINVAL;
     for (uint32_t ch = 0; ch < n; ++ch) { w.table[ch] = source[ch]; w.table[c->maxC + ch] = (uint32_t)(bin[ch] < 0 ? bin[ch] + (int32_t)w.M : bin[ch]); }
     w.dirty = true;   // (the next block uploaded brings it to the device: nothing is queued and nothing waited for here)
+    return M17HIP_OK;
+}
+int m17hip_wide_survey(m17hip_ctx* c, uint32_t stride)
+{
+    if (!c || stride > 4096) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    if (!w.S || !w.M || c->front_queued) return M17HIP_ESTATE;   // (a raster's bins are what is surveyed; the staged block belongs to the run being made)
+    w.sv.stride = stride;   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
+    w.sv.forget();
+    return M17HIP_OK;
+}
+int m17hip_wide_survey_fetch(m17hip_ctx* c, uint32_t back, float* power_host, uint64_t capacity, uint32_t* times, uint64_t* first_output)
+{
+    if (!c || back > 1 || !power_host) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sv = w.sv;
+    if (!w.S || !w.M || !sv.stride) return M17HIP_ESTATE;
+    const size_t n = (size_t)w.S * w.M;
+    if (capacity < n) return M17HIP_EINVAL;
+    const int p = sv.latest ^ (int)back;
+    if (!sv.valid[p]) return M17HIP_ESTATE;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sv.ev[p]));   // (that block's survey and what its stream held in front of it: no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(power_host, sv.plane[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, sv.fetch));
+    HIPCHK(c, hipStreamSynchronize(sv.fetch));
+    if (times) *times = sv.times[p];
+    if (first_output) *first_output = sv.first_output[p];
     return M17HIP_OK;
 }
 int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }

@@ -103,6 +103,14 @@ public:
     {
         check(m17hip_wide_raster_channels(ctx_, source, bin, n), "m17hip_wide_raster_channels");
     }
+    // The raster survey (m17hip_wide_survey): from the blocks uploaded after the call every stride-th output of the feed (1..4096; 0: off) adds the power of
+    // every bin of every source to the block's plane.  wide_survey_fetch: the plane [sources][bins] (indexed by bin mod bins) of the latest surveyed block
+    // (back = 0) or the one before (back = 1), its survey times and the feed's output index at its start; it waits for that block's survey kernels only.
+    void wide_survey(uint32_t stride) { check(m17hip_wide_survey(ctx_, stride), "m17hip_wide_survey"); }
+    void wide_survey_fetch(uint32_t back, float* power, uint64_t capacity, uint32_t* times = nullptr, uint64_t* first_output = nullptr)
+    {
+        check(m17hip_wide_survey_fetch(ctx_, back, power, capacity, times, first_output), "m17hip_wide_survey_fetch");
+    }
     // the bin of an offset in Hz from the source's centre; throws where the offset is not on the raster or outside it
     static int32_t wide_bin(double offset_hz, uint32_t decim, uint32_t bins)
     {

@@ -252,6 +252,20 @@ struct M17Demodulator
         wide_m_ = 0;
         wide_mixed_.assign(2 * (wide_taps_.size() - 1), 0.0f);   // the feed itself as (re, im) — nothing is mixed — behind its zero history of ntaps - 1 samples
     }
+    // The raster survey beside wide_raster on the GPU path (m17hip_wide_survey): every stride-th output of the feed adds the power of EVERY bin to the
+    // block's plane, and after each block `report` gets the plane (indexed by bin mod bins), the block's survey times and the feed's output index at its
+    // start.  stride 0 turns it off.  Returns false, with nothing changed, on the host form: the survey is a device feature.
+    using survey_callback_t = std::function<void(const std::vector<float>& power, uint32_t times, uint64_t first_output)>;
+    bool wide_survey(uint32_t stride, survey_callback_t report)
+    {
+        if (!gpu_) return false;
+        if (!raster_m_) throw std::logic_error("M17Demodulator::wide_survey before wide_raster");
+        flush();
+        gpu_->wide_survey(stride);
+        survey_stride_ = stride;
+        survey_report_ = std::move(report);
+        return true;
+    }
     // one wideband sample (wide_config or wide_raster first)
     void wide(float i, float q)
     {
@@ -382,6 +396,13 @@ private:
         const size_t n = wide_buffer_.size() / wide_decim_;
         gpu_->upload_wide(wide_buffer_.data(), 1, (uint32_t)n, n * wide_decim_, iq_gain_);
         wide_buffer_.erase(wide_buffer_.begin(), wide_buffer_.begin() + n * wide_decim_);
+        if (survey_stride_ && survey_report_) {   // (the plane of the block just uploaded: the fetch waits for its survey kernels, not for the run)
+            survey_power_.resize(raster_m_);
+            uint32_t times = 0;
+            uint64_t first = 0;
+            gpu_->wide_survey_fetch(0, survey_power_.data(), survey_power_.size(), &times, &first);
+            survey_report_(survey_power_, times, first);
+        }
         run_uploaded();
     }
     void run_uploaded()
@@ -413,6 +434,9 @@ private:
     uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called); wideband samples per output
     uint32_t wide_r1_ = 0;                           // the first stage's decimation (0: one stage)
     uint32_t raster_m_ = 0, raster_m1_ = 0, raster_m2_ = 0, raster_k_ = 0;   // wide_raster: the bins (0: a tuner), their factors and the bin mod M
+    uint32_t survey_stride_ = 0;                     // wide_survey: 0 = off
+    survey_callback_t survey_report_;
+    std::vector<float> survey_power_;
     std::vector<float> raster_tw_, raster_w_;        // the twiddle table; the partial sums and the first pass's sums of one output
     uint64_t wide_m_ = 0;
     uint32_t block_;

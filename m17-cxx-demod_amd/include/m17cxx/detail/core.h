@@ -216,6 +216,11 @@ M17_HD void chan_pass2(const float* a, uint32_t M1, uint32_t M2, const float* tw
         t += k; if (t >= M) t -= M;
     }
 }
+// The raster survey (m17hip_wide_survey): the power of one z, and how many powers a first-level sum holds.  A bin's power over a block's survey times
+// p_0 .. p_{J-1} is a sum on two levels, both chains of plain float adds from +0 in ascending order: q_g over p_j, j = 16 g .. min(16 g + 15, J - 1), then
+// the q_g.  The order is part of the definition (a workgroup per group on the device, a fixed-order second step, no atomics).
+constexpr uint32_t CHAN_SURVEY_GROUP = 16;
+M17_HD float chan_power(float re, float im) { return __builtin_fmaf(re, re, im * im); }
 
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).

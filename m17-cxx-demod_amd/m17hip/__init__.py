@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11}
+           "tune2": 10, "channelise": 11, "survey": 12}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -74,6 +74,7 @@ EXPORTS = [
     "m17hip_upload_wide", "m17hip_upload_wide_device", "m17hip_upload_wide_async", "m17hip_upload_wide_device_async",
     "m17hip_wide_default_taps2", "m17hip_wide_config2",
     "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
+    "m17hip_wide_survey", "m17hip_wide_survey_fetch",
     "m17hip_decode_sequences",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
@@ -203,6 +204,27 @@ def wide_bin(hz, decim, bins):
     if abs(b - k) > 1e-9 * max(1.0, abs(b)) or k < -(int(bins) // 2) or k > (int(bins) - 1) // 2:
         raise ValueError(f"{hz} Hz is not a channel of a raster of {bins} at {48000 * int(decim)} samples per second")
     return k
+
+
+def wide_raster_occupied(power, margin_db):
+    """The occupied bins of a survey plane (Context.wide_survey_fetch): per source the floor is the MEDIAN of its row, and every bin more than `margin_db`
+    dB above it is reported as (source, signed bin in [-M / 2, M / 2), dB over the floor), strongest first.  A row whose median is 0 or not finite reports
+    nothing.  Pure numpy."""
+    p = np.asarray(power, dtype=np.float32)
+    if p.ndim == 1:
+        p = p[None, :]
+    M = p.shape[1]
+    out = []
+    for s in range(p.shape[0]):
+        floor = float(np.median(p[s].astype(np.float64)))
+        if not np.isfinite(floor) or floor <= 0.0:
+            continue
+        with np.errstate(divide="ignore", invalid="ignore"):
+            db = 10.0 * np.log10(p[s].astype(np.float64) / floor)
+        for k in np.nonzero(db > float(margin_db))[0]:
+            out.append((s, int(k) if k <= (M - 1) // 2 else int(k) - M, float(db[k])))
+    out.sort(key=lambda e: -e[2])
+    return out
 
 
 def wide_fcw(offset_hz, decim):
@@ -412,6 +434,7 @@ class Context:
         self._chk(self.lib.m17hip_wide_raster(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_uint32(bins), C.c_int(IQ_I16 if fmt is None else fmt),
                                               _ptr(t), C.c_uint32(0 if t is None else t.size)))
         self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+        self._wide_bins = int(bins)
 
     def wide_raster_channels(self, source, bin):
         """Local channel c listens to bin[c] (wide_bin; -bins / 2 <= bin < bins / 2) of source[c] from the blocks uploaded after this call; several
@@ -422,6 +445,25 @@ class Context:
             raise ValueError("one source and one bin per channel")
         self._chk(self.lib.m17hip_wide_raster_channels(self.h, _ptr(src) if src.size else None, b.ctypes.data_as(C.c_void_p) if b.size else None,
                                                        C.c_uint32(src.size)))
+
+    def wide_survey(self, stride):
+        """The raster survey: from the blocks uploaded after this call, every `stride`-th output of the feed (1..4096; 0: off, the default) adds the power
+        of EVERY bin of every source to the block's plane, listened to or not — m17hip_wide_survey.  Any wide_config / wide_config2 / wide_raster call
+        turns it off."""
+        self._chk(self.lib.m17hip_wide_survey(self.h, C.c_uint32(stride)))
+
+    def wide_survey_fetch(self, back=0):
+        """(power float32 [sources][bins] indexed by bin mod bins, survey times in the block, the feed's output index at the block's start) of the latest
+        block uploaded with the survey on (back = 0) or the one before it (back = 1); waits for that block's survey kernels only —
+        m17hip_wide_survey_fetch.  wide_raster_occupied reads the plane."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_survey_fetch: back is 0 or 1")
+        cap = 256 * 256
+        buf = np.zeros(cap, dtype=np.float32)
+        times, first = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self.lib.m17hip_wide_survey_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(cap), C.byref(times), C.byref(first)))
+        S, M = self._wide[0], self._wide_bins   # (the call succeeded: wide_raster has set both)
+        return buf[: S * M].reshape(S, M).copy(), int(times.value), int(first.value)
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --raster M] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --raster M [--survey STRIDE]] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -15,7 +15,11 @@ default taps, every source heard on channels_per_source distinct bins.  Its floo
     fold:    S T L packed fma (every tap meets one sample)
     pass 1:  S T M M2 complex steps of 4 plain fma, M = M1 x M2 as the library factors it
     pass 2:  C T M1 complex steps of 4 plain fma
-and no mixing term: there is no oscillator."""
+and no mixing term: there is no oscillator.
+With --survey STRIDE beside --raster the same blocks are then timed once more with the raster survey on (m17hip_wide_survey; chan_survey_kernel and
+chan_survey_sum_kernel, csrc/m17_chan_survey_kernels.hpp; library timer "survey"): the channeliser's time with the survey on and the survey's own, against
+the survey's floor, counted per source and SURVEY TIME (outputs / STRIDE of them): L packed fma for the fold, M M2 steps of 4 plain fma for pass 1 and
+M M1 for pass 2 — all M bins."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -36,6 +40,12 @@ if "--raster" in ARGS:
     k = ARGS.index("--raster")
     RASTER = int(ARGS[k + 1])
     del ARGS[k:k + 2]
+SURVEY = 0   # (0: not timed)
+if "--survey" in ARGS:
+    k = ARGS.index("--survey")
+    SURVEY = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+    assert RASTER and SURVEY >= 1, "--survey STRIDE goes with --raster M"
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
 T = int(ARGS[2]) if len(ARGS) > 2 else 48000
@@ -104,6 +114,17 @@ for _ in range(REP):
     b.synchronize()
     ev.append(a.elapsed_time(b))
 ms, n = ctx.timing_get("channelise" if RASTER else "tune2" if R2 else "tune")
+survey = {}
+if SURVEY:   # the same blocks once more with the survey on: a warm-up block (the scratch and the planes are allocated), then REP timed ones
+    ctx.wide_survey(SURVEY)
+    call()
+    ctx.timing_reset()
+    times = 0
+    for _ in range(REP):
+        call()
+        times += ctx.wide_survey_fetch()[1]
+    (ms_c, n_c), (ms_s, n_s) = ctx.timing_get("channelise"), ctx.timing_get("survey")
+    survey = {"stride": SURVEY, "launches": n_s, "times_per_block": times / REP, "channelise_ms_survey_on": round(ms_c / n_c, 3), "survey_ms": round(ms_s / n_s, 3)}
 ctx.timing(False)
 clocks.stop = True
 cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -116,6 +137,10 @@ if RASTER:
     FILTER = S * T * L / 64 * 4
     cycles = FILTER + (S * T * RASTER * M2 + C * T * M1) * 4 / 64 * 2
 floor_ms = cycles / (4 * cus * mhz * 1e6) * 1e3
+if SURVEY:
+    sc = S * survey["times_per_block"] * (L / 64 * 4 + (RASTER * M2 + RASTER * M1) * 4 / 64 * 2)
+    survey["floor_ms"] = round(sc / (4 * cus * mhz * 1e6) * 1e3, 4)
+    survey["survey_over_floor"] = round(survey["survey_ms"] / (sc / (4 * cus * mhz * 1e6) * 1e3), 2)
 kernel_ms = ms / n
 step = [v * T / 480000.0 * C / 4096.0 for v in DEMOD_STEP_MS]
 print(json.dumps({
@@ -125,5 +150,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
+    **({"survey": survey} if SURVEY else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
