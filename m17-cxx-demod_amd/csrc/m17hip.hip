@@ -3980,10 +3980,10 @@ int m17hip_replay_drops(m17hip_ctx* c, uint64_t* count)
 {
     if (!c || !count) return M17HIP_EINVAL;
     GUARD(c);
-    uint32_t w[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, c->overflow, 16, hipMemcpyDeviceToHost, c->stream));
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(w, c->overflow, 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *count = w[1];
+    *count = (uint64_t)w[1] + w[5];   // (each record set has its own four words, and the runs of a stream alternate between the sets)
     return M17HIP_OK;
 }
 

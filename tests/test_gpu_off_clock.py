@@ -132,7 +132,8 @@ def test_run_in_segments(ctx, seg):
 
 
 def test_chunks_of_a_frame_and_seven_samples(ctx):
-    """Runs of 1920 + 7 samples: the run boundary walks through every phase of a frame while the clock drifts; every run's diagnostic log."""
+    """Runs of 1920 + 7 samples: the run boundary moves seven samples through the frame with every run while the clock drifts, so the 49 runs over
+    96 000 samples meet 49 of a frame's 1920 phases (every phase: tests/test_gpu_boundary_phases.py); every run's diagnostic log."""
     x, rows, diags, logs = _main()
     lengths = [1927] * (T // 1927) + ([T % 1927] if T % 1927 else [])
     ctx.tune(9, 8)
