@@ -419,6 +419,19 @@ int m17hip_decode_sequences(m17hip_ctx* ctx, int form, const int8_t* llr368_host
                             uint32_t rec_cap, uint8_t* state_io, uint8_t* lich_io, uint8_t* lsf_io, int8_t* dep401_io, int64_t* cost_io,
                             m17_frame_rec* recs, uint32_t* nrec, uint32_t* overflow_out, int32_t* cost_trace);
 
+/* TEST HOOK (ABI 614; no product path calls it): other taps for the matched filter.  The 149 non-zero taps of BaseFirFilter<float,150> are not
+ * compiled into any kernel: every form of the matched filter — K1 rolled and skewed, int16 and float32 input, uniform and per-channel polarity,
+ * K2's patch window and the sequential kernel's own filter at a gate reopening — reads them from two host-built tables of the context.  The
+ * call waits for everything the context has queued, then rewrites both from taps149[0..148] (taps149[i] multiplies the sample i steps back,
+ * FirFilter.h:36-40); tap 150 stays the zero it is.  taps149 == NULL restores the RRC taps (M17Demodulator.h:79-118).  The taps stay in force
+ * until the next call or m17hip_ctx_destroy — across m17hip_demod_reset and m17hip_demod_reset_channels — for the operator entry points above
+ * and the full chain alike.  What it is for: the RRC taps are symmetric, so a mirrored tap index computes the same words; asymmetric taps make
+ * it a value error.  And with the identity (taps149[0] = 1, the rest 0) on a float32 stream the matched filter's output IS the input, so a test
+ * writes what the correlator, the sync search, the level estimator and the slicer see, sample by sample.
+ * M17HIP_EINVAL for a NULL context or a tap that is not finite; M17HIP_ESTATE between m17hip_demod_front and its m17hip_demod_run (the run's
+ * matched filter is queued with the tables as they are); nothing is changed then. */
+int m17hip_set_fir_taps(m17hip_ctx* ctx, const float* taps149);
+
 /* ---- the full chain ------------------------------------------------------------------------------- */
 /* Fresh demodulators for every channel (M17Demodulator ctor + zero-initialised storage). */
 int m17hip_demod_reset(m17hip_ctx* ctx);

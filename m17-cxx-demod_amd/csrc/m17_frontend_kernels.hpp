@@ -223,9 +223,10 @@ constexpr int fs_off(int e) { return e + 2 * ((e - (e < 0 ? 15 : 0)) / 16); }
 // Host side: the tap table of the kernel.  Body bi, position p serves step s = 32 (bi - 1) + 22 + p with the pair (T2(s), T2(s + 1)),
 // T2(s) = tap_{s-1} (zero outside taps 0..148); even positions read the pair at [p, p + 1] of the first half, odd ones at
 // [p - 1, p] of the second half (the same sequence shifted by one), so that every pair is an aligned scalar register pair.
-inline void fs_build_tap_table(float* tab /* FS_NBODY * FS_TAB */)
+// taps149 = nullptr: the RRC taps (m17hip_set_fir_taps, a test hook, passes others).
+inline void fs_build_tap_table(float* tab /* FS_NBODY * FS_TAB */, const float* taps149 = nullptr)
 {
-    auto T2 = [](int s) { return (s >= 1 && s <= 149) ? rrc_tap(s - 1) : 0.0f; };
+    auto T2 = [taps149](int s) { return (s >= 1 && s <= 149) ? (taps149 ? taps149[s - 1] : rrc_tap(s - 1)) : 0.0f; };
     for (int bi = 0; bi < FS_NBODY; ++bi)
         for (int k = 0; k < 32; ++k) {
             const int s = 32 * (bi - 1) + (FS_BODY - FS_ENTRY) + k;

@@ -1192,7 +1192,20 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 613; }
+int m17hip_version(void) { return 614; }
+
+// The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
+// nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
+static hipError_t write_fir_taps(m17hip_ctx* c, const float* taps149)
+{
+    float taps[160] = {0};
+    for (int i = 0; i < NTAPS; ++i) taps[i] = taps149 ? taps149[i] : rrc_tap(i);
+    hipError_t e = hipMemcpy(c->taps, taps, sizeof(taps), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    float skew[FS_NBODY * FS_TAB];
+    fs_build_tap_table(skew, taps149);
+    return hipMemcpy(c->taps_skew, skew, sizeof(skew), hipMemcpyHostToDevice);
+}
 
 int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m17hip_ctx** out)
 {
@@ -1258,14 +1271,9 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
         hipError_t e = hipMemcpy(c->tables, t, sizeof(DecodeTables), hipMemcpyHostToDevice);
         delete t;
         if (e != hipSuccess) { c->last_hip = (int)e; return fail(M17HIP_EHIP); }
-        float taps[160] = {0};
-        for (int i = 0; i < NTAPS; ++i) taps[i] = rrc_tap(i);
         float edges[64] = {0};
         build_llr_edges(edges);
-        if (hipMemcpy(c->taps, taps, sizeof(taps), hipMemcpyHostToDevice) != hipSuccess) return fail(M17HIP_EHIP);
-        float skew[FS_NBODY * FS_TAB];
-        fs_build_tap_table(skew);
-        if (hipMemcpy(c->taps_skew, skew, sizeof(skew), hipMemcpyHostToDevice) != hipSuccess) return fail(M17HIP_EHIP);
+        if (write_fir_taps(c, nullptr) != hipSuccess) return fail(M17HIP_EHIP);
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) return fail(M17HIP_EHIP);
         c->n_cu = (uint32_t)ncu;
@@ -2376,6 +2384,20 @@ int m17hip_decode_frames(m17hip_ctx* c, const int8_t* llr368_host, uint32_t n, c
     HIPCHK(c, hipMemcpyAsync(recs, b + o_rec, (size_t)n * 2 * sizeof(FrameRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(nrec, b + o_nrec, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return M17HIP_OK;
+}
+
+// TEST HOOK (include/m17hip.h): other matched-filter taps for every form that reads the context's two tap tables.  No kernel knows of it.
+int m17hip_set_fir_taps(m17hip_ctx* c, const float* taps149)
+{
+    if (!c) return M17HIP_EINVAL;
+    if (taps149)
+        for (int i = 0; i < NTAPS; ++i)
+            if (!std::isfinite(taps149[i])) return M17HIP_EINVAL;
+    if (c->front_queued) return M17HIP_ESTATE;   // the run m17hip_demod_front began would get its K1 from one table and its K2 / K5 from another
+    GUARD(c);
+    HIPCHK(c, hipDeviceSynchronize());   // (everything queued has read the tables it was queued with)
+    HIPCHK(c, write_fir_taps(c, taps149));
     return M17HIP_OK;
 }
 

@@ -75,7 +75,7 @@ EXPORTS = [
     "m17hip_wide_default_taps2", "m17hip_wide_config2",
     "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
     "m17hip_wide_survey", "m17hip_wide_survey_fetch",
-    "m17hip_decode_sequences",
+    "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
 IQ_I16, IQ_F32 = 1, 2           # M17HIP_IQ_*
@@ -695,6 +695,16 @@ class Context:
         self._chk(self.lib.m17hip_decode_sequences(self.h, C.c_int(form), _ptr(l), _ptr(st), C.c_uint32(n), C.c_uint32(F), C.c_uint32(rec_cap), _ptr(state),
                                                    _ptr(lich), _ptr(lsf), _ptr(dep401), _ptr(cost), _ptr(recs), _ptr(nrec), C.byref(ovf), _ptr(trace)))
         return recs, nrec, int(ovf.value), state, lich, lsf, dep401, cost, trace
+
+    def set_fir_taps(self, taps149=None):
+        """TEST HOOK (m17hip_set_fir_taps): the 149 taps every matched-filter form of this context reads from now on; None restores the RRC taps."""
+        if taps149 is None:
+            self._chk(self.lib.m17hip_set_fir_taps(self.h, None))
+            return
+        t = np.ascontiguousarray(taps149, dtype=np.float32)
+        if t.shape != (149,):
+            raise TypeError("taps149 is 149 floats")
+        self._chk(self.lib.m17hip_set_fir_taps(self.h, _ptr(t)))
 
     def kalman_trace(self, z, dt, wrap, z0=0.0, order=3):
         """rows x n updates of the 2-state Kalman filter (kal_update, as the full-chain kernel runs it): state after each update."""

@@ -117,6 +117,7 @@ struct DemodulatorT {
     // optional taps for tests: called with (pos, filtered sample) / per symbol
     std::function<void(uint64_t, float, float)> on_symbol;  // pos, normalised symbol, raw filtered
     std::function<void(uint64_t, const Diag&)> on_diag;     // every diagnostic callback: sample position, arguments
+    std::function<void(uint64_t, float, float)> on_levels;  // every update_values: pos, outer levels min and max as the estimator gets them
 
     DemodulatorT() {}
     DemodulatorT(const DemodulatorT&) = delete;
@@ -127,6 +128,7 @@ struct DemodulatorT {
     {
         float mn, mx;
         corr.outer_symbol_levels(sample_index, mn, mx);
+        if (on_levels) on_levels(pos, mn, mx);
         dev.update(mn, mx);
         sync_sample_index = index;
     }

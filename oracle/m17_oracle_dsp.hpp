@@ -417,6 +417,8 @@ struct ClockRecovery {  // reference ClockRecovery.h:16-111
     size_t count = 0;
     int8_t sample_index_ = 0;
     float clock_estimate_ = 0.f, sample_estimate_ = 0.f;
+    double round_arg = 0.;   // tap for tests: what std::round last saw, and how often it was asked
+    size_t n_round = 0;
     static int8_t wrap10(int8_t v)
     {
         v = v < 0 ? v + 10 : v;
@@ -435,6 +437,7 @@ struct ClockRecovery {  // reference ClockRecovery.h:16-111
     {
         kf.update((float)index, count, 10);
         sample_estimate_ = kf.x[0];
+        round_arg = (double)sample_estimate_; ++n_round;
         sample_index_ = wrap10((int8_t)std::round((double)sample_estimate_));
         clock_estimate_ = kf.x[1];
         count = 0;
@@ -445,6 +448,7 @@ struct ClockRecovery {  // reference ClockRecovery.h:16-111
         double csw = std::fmod((double)v, 10.0);
         if (csw < 0.) csw += 10;
         else if (csw >= 10) csw -= 10;
+        round_arg = csw; ++n_round;
         sample_index_ = wrap10((int8_t)std::round(csw));
     }
     float clock_estimate() const { return clock_estimate_; }
