@@ -259,7 +259,6 @@ struct m17hip_ctx {
     // other format is refused until the next reset.  Each slab pair remembers the format of the input it holds; a run takes its slab's.
     int stream_fmt = 0;               // M17HIP_FORMAT_*; 0: free
     int slab_fmt[2] = {0, 0};
-    bool f32_now() const { return slab_fmt[slot] == M17HIP_FORMAT_F32; }
     // COMPLEX IQ INPUT (m17hip_upload_iq): the discriminator writes the float pair's slabs, so behind it the stream is a float stream.  What it holds of its
     // own, allocated with the first IQ input: the carry — one float2 per channel, the last IQ sample of the previous IQ block, zero for a fresh feed — and,
     // for the host forms, a buffer for the raw IQ of one block (grown when a later block is larger).  In-place blocks run on the main stream and staged ones
@@ -310,10 +309,6 @@ struct m17hip_ctx {
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words()) * 4;
         }
     } wide;
-    const int16_t* x_now(uint32_t t0)   // the current input rows from sample t0 on, as the parameter blocks of K2 / K5 name them (float rows under the same member)
-    {
-        return f32_now() ? reinterpret_cast<const int16_t*>(fslab[slot].x + t0) : slab[slot].x + t0;
-    }
     Slab& now() { return slab[slot]; }         // the current / latest run's
     Slab& other() { return slab[slot ^ 1]; }   // the staging pair (the run before the latest one's)
     bool foreign_streams[4] = {false, false, false, false};   // tools build, keys 40-43: side / side2 / side3 / copy belong to the experiment, not to the context
@@ -698,11 +693,12 @@ __global__ void seq_reset_kernel(SeqState* st, DcdState* ds, EvState* es, uint32
 
 // ---- m17hip_demod_reset_channels: the same over a LIST of n channels (each listed once, every entry < max_channels) -------------------------
 // front end: the channel's 152-sample input prefix (FIR history, DFT delay) and / or its sliding-DFT state; a workgroup per listed channel
-__global__ void front_reset_list_kernel(const uint32_t* list, uint32_t n, int16_t* x, size_t xpitch, DcdState* ds)
+template <typename XT>
+__global__ void front_reset_list_kernel(const uint32_t* list, uint32_t n, XT* x, size_t xpitch, DcdState* ds)
 {
     if (blockIdx.x >= n) return;
     const uint32_t c = list[blockIdx.x];
-    if (x) for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = 0;
+    if (x) for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = XT(0);
     if (ds && threadIdx.x == 0) fresh_dcd_state(ds, c);
 }
 // the 96-sample prefixes of the matched-filter output and of the limit-filter history; a workgroup per listed channel
@@ -720,70 +716,69 @@ __global__ void seq_reset_list_kernel(const uint32_t* list, uint32_t n, SeqState
     fresh_demod_state(st, es, list[i], pos);
 }
 
-// the same for the rows of a float stream
-__global__ void front_reset_list_xf32_kernel(const uint32_t* list, uint32_t n, float* x, size_t xpitch, DcdState* ds)
+// ---- the prefixes of the rows: ONE family for every element type and prefix length ------------------------------------------------------------
+// XT, PRE = int16_t or float with XPRE for input rows (pitch and prefix in samples whatever the type), float with YPRE for the y and h rows.
+// A workgroup per channel.  The forms over x AND y do in one launch what a run's end and the reset need of both.
+template <typename XT, int PRE>
+__global__ void zero_prefix_kernel(XT* x, size_t pitch)
 {
-    if (blockIdx.x >= n) return;
-    const uint32_t c = list[blockIdx.x];
-    if (x) for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = 0.f;
-    if (ds && threadIdx.x == 0) fresh_dcd_state(ds, c);
+    for (int k = threadIdx.x; k < PRE; k += blockDim.x) x[(size_t)blockIdx.x * pitch + k] = XT(0);
 }
-
-__global__ void zero_prefix_kernel(int16_t* x, size_t xpitch, float* y, size_t ypitch, uint32_t C)
+template <typename XT>
+__global__ void zero_prefix_xy_kernel(XT* x, size_t xpitch, float* y, size_t ypitch)
 {
-    const uint32_t c = blockIdx.x;
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)c * xpitch + k] = 0;
-    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) y[(size_t)c * ypitch + k] = 0.f;
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)blockIdx.x * xpitch + k] = XT(0);
+    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) y[(size_t)blockIdx.x * ypitch + k] = 0.f;
 }
-
-// carry the last XPRE / YPRE samples of a run into the prefix of the next one
-__global__ void carry_tail_kernel(int16_t* x, size_t xpitch, float* y, size_t ypitch, uint32_t C, uint32_t T)
+// carry the last PRE samples of a run into the prefix of the next one
+template <typename XT, int PRE>
+__global__ void carry_tail_kernel(XT* x, size_t pitch, uint32_t T)
 {
-    const uint32_t c = blockIdx.x;
-    __shared__ int16_t xs[XPRE];
+    __shared__ XT xs[PRE];
+    XT* xr = x + (size_t)blockIdx.x * pitch;
+    for (int k = threadIdx.x; k < PRE; k += blockDim.x) xs[k] = xr[(size_t)T + k];   // = row[PRE + T - PRE + k]
+    __syncthreads();
+    for (int k = threadIdx.x; k < PRE; k += blockDim.x) xr[k] = xs[k];
+}
+template <typename XT>
+__global__ void carry_tail_xy_kernel(XT* x, size_t xpitch, float* y, size_t ypitch, uint32_t T)
+{
+    __shared__ XT xs[XPRE];
     __shared__ float ys[YPRE];
-    int16_t* xr = x + (size_t)c * xpitch;
-    float* yr = y + (size_t)c * ypitch;
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xs[k] = xr[(size_t)T + k];   // = row[XPRE + T - XPRE + k]
+    XT* xr = x + (size_t)blockIdx.x * xpitch;
+    float* yr = y + (size_t)blockIdx.x * ypitch;
+    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xs[k] = xr[(size_t)T + k];
     for (int k = threadIdx.x; k < YPRE; k += blockDim.x) ys[k] = yr[(size_t)T + k];
     __syncthreads();
     for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xr[k] = xs[k];
     for (int k = threadIdx.x; k < YPRE; k += blockDim.x) yr[k] = ys[k];
 }
-
-// The input rows of a float stream: the same helpers over float samples (pitch and prefix in samples, as for int16).
-__global__ void zero_prefix_xf32_kernel(float* x, size_t xpitch)
+// staged runs: the other slab's prefix = the prefix of the previous run's rows (which that run's last kernel carried its tail into) ...
+template <typename XT, int PRE>
+__global__ void copy_prefix_kernel(const XT* src, XT* dst, size_t pitch)
 {
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) x[(size_t)blockIdx.x * xpitch + k] = 0.f;
+    for (int k = threadIdx.x; k < PRE; k += blockDim.x) dst[(size_t)blockIdx.x * pitch + k] = src[(size_t)blockIdx.x * pitch + k];
 }
-__global__ void carry_tail_xf32_kernel(float* x, size_t xpitch, uint32_t T)
+// ... or the last PRE samples of the previous run's input, read where they lie: row[T .. T + PRE)
+template <typename XT, int PRE>
+__global__ void copy_tail_kernel(const XT* src, XT* dst, size_t pitch, uint32_t T)
 {
-    __shared__ float xs[XPRE];
-    float* xr = x + (size_t)blockIdx.x * xpitch;
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xs[k] = xr[(size_t)T + k];
-    __syncthreads();
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) xr[k] = xs[k];
+    for (int k = threadIdx.x; k < PRE; k += blockDim.x) dst[(size_t)blockIdx.x * pitch + k] = src[(size_t)blockIdx.x * pitch + T + k];
 }
-__global__ void copy_prefix_xf32_kernel(const float* src, float* dst, size_t xpitch)
+// rows of T samples (pitch spitch) into the data region of the slab's rows: 16 bytes per lane where the source allows it
+template <typename XT>
+__global__ void copy_rows_kernel(const XT* src, size_t spitch, XT* dst, size_t dpitch, uint32_t T)
 {
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + k];
-}
-__global__ void copy_tail_xf32_kernel(const float* src, float* dst, size_t xpitch, uint32_t T)
-{
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + T + k];
-}
-// rows of T floats (pitch spitch) into the data region of the slab's rows: four samples per lane
-__global__ void copy_rows_xf32_kernel(const float* src, size_t spitch, float* dst, size_t dpitch, uint32_t T)
-{
+    constexpr uint32_t N = 16 / sizeof(XT);
     const uint32_t c = blockIdx.y;
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) * N;
     if (t >= T) return;
-    const float* s = src + (size_t)c * spitch + t;
-    float* d = dst + (size_t)c * dpitch + XPRE + t;
-    if (t + 4 <= T && (((uintptr_t)s) & 15) == 0) {
-        *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
+    const XT* s = src + (size_t)c * spitch + t;
+    XT* d = dst + (size_t)c * dpitch + XPRE + t;
+    if (t + N <= T && (((uintptr_t)s) & 15) == 0) {
+        *reinterpret_cast<int4*>(d) = *reinterpret_cast<const int4*>(s);
     } else {
-        for (uint32_t q = 0; q < 4 && t + q < T; ++q) d[q] = s[q];
+        for (uint32_t q = 0; q < N && t + q < T; ++q) d[q] = s[q];
     }
 }
 
@@ -967,44 +962,6 @@ __global__ void consumer_reset_list_kernel(const uint32_t* list, uint32_t n, Ber
     if (voice) fresh_voice_state(voice, list[i]);   // (an open call is abandoned, as a half-assembled packet is; its seq restarts)
 }
 
-__global__ void copy_prefix_i16_kernel(const int16_t* src, int16_t* dst, size_t xpitch)
-{
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + k];
-}
-
-// staged runs: the other slab's prefix = the last XPRE samples of the previous run's input (read where they lie: row[T .. T + XPRE))
-__global__ void copy_tail_i16_kernel(const int16_t* src, int16_t* dst, size_t xpitch, uint32_t T)
-{
-    for (int k = threadIdx.x; k < XPRE; k += blockDim.x) dst[(size_t)blockIdx.x * xpitch + k] = src[(size_t)blockIdx.x * xpitch + T + k];
-}
-__global__ void copy_prefix_f32_kernel(const float* src, float* dst, size_t ypitch)
-{
-    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) dst[(size_t)blockIdx.x * ypitch + k] = src[(size_t)blockIdx.x * ypitch + k];
-}
-
-__global__ void carry_tail_f32_kernel(float* y, size_t ypitch, uint32_t T)
-{
-    __shared__ float ys[YPRE];
-    float* yr = y + (size_t)blockIdx.x * ypitch;
-    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) ys[k] = yr[(size_t)T + k];
-    __syncthreads();
-    for (int k = threadIdx.x; k < YPRE; k += blockDim.x) yr[k] = ys[k];
-}
-
-__global__ void copy_rows_i16_kernel(const int16_t* src, size_t spitch, int16_t* dst, size_t dpitch, uint32_t T)
-{
-    const uint32_t c = blockIdx.y;
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
-    if (t >= T) return;
-    const int16_t* s = src + (size_t)c * spitch + t;
-    int16_t* d = dst + (size_t)c * dpitch + XPRE + t;
-    if (t + 8 <= T && (((uintptr_t)s) & 15) == 0) {
-        *reinterpret_cast<int4*>(d) = *reinterpret_cast<const int4*>(s);
-    } else {
-        for (uint32_t q = 0; q < 8 && t + q < T; ++q) d[q] = s[q];
-    }
-}
-
 // exclusive prefix sum of the per-channel record counts (single block; C <= a few 100k)
 __global__ void rec_offsets_kernel(const uint32_t* counts, uint32_t rec_cap, uint64_t* offsets, uint32_t C)
 {
@@ -1037,6 +994,35 @@ __global__ void compact_kernel(const FrameRec* recs, uint32_t rec_cap, const uin
         if (offsets[c] + k / 4 < out_cap) dst[k] = src[k];
 }
 
+// ---- the sample format of a slab pair's input rows (int16, or float32 in the reference's units): known HERE -----------------------------------
+template <typename XT> constexpr int fmt_of() { return std::is_same<XT, float>::value ? M17HIP_FORMAT_F32 : M17HIP_FORMAT_I16; }
+// the input rows of slab pair `slot` in that format (nullptr: not allocated)
+template <typename XT> XT* slab_x(m17hip_ctx* c, int slot)
+{
+    if constexpr (std::is_same<XT, float>::value) return c->fslab[slot].x;
+    else return c->slab[slot].x;
+}
+// f(the input rows of slab pair `slot` as what they hold — int16_t* or float*, slab_fmt[slot]); what f returns.  Whatever depends on the element type
+// (a helper kernel's instantiation, the kernels below, the float histories) is written once, inside f.
+template <typename F> auto with_x(m17hip_ctx* c, int slot, F&& f)
+{
+    return c->slab_fmt[slot] == M17HIP_FORMAT_F32 ? f(slab_x<float>(c, slot)) : f(slab_x<int16_t>(c, slot));
+}
+// The kernels that read input rows, chosen by the rows' pointer: K1 and K3 for channels of one polarity (INV) or of mixed ones, K2, K5 (KORDER as
+// demod_wave_kernel has it).  The two forms of K3 take the same arguments.
+template <bool INV> auto fir_kernel(const int16_t*) { return fir_rrc150_skew_kernel<INV>; }
+template <bool INV> auto fir_kernel(const float*) { return fir_rrc150_skew_f32_kernel<INV>; }
+auto fir_mixed_kernel(const int16_t*) { return fir_rrc150_skew_mixed_kernel; }
+auto fir_mixed_kernel(const float*) { return fir_rrc150_skew_mixed_f32_kernel; }
+template <bool INV> auto dcd_kernel_of(const int16_t*, bool one_wave) { return one_wave ? dcd_kernel<INV> : dcd_pipe_kernel<INV>; }
+template <bool INV> auto dcd_kernel_of(const float*, bool one_wave) { return one_wave ? dcd_f32_kernel<INV> : dcd_pipe_f32_kernel<INV>; }
+auto dcd_mixed_kernel_of(const int16_t*, bool one_wave) { return one_wave ? dcd_mixed_kernel : dcd_pipe_mixed_kernel; }
+auto dcd_mixed_kernel_of(const float*, bool one_wave) { return one_wave ? dcd_mixed_f32_kernel : dcd_pipe_mixed_f32_kernel; }
+auto gate_kernel(const int16_t*) { return limit_track_kernel; }
+auto gate_kernel(const float*) { return limit_track_f32_kernel; }
+template <int KORDER> auto wave_kernel(const int16_t*) { return demod_wave_kernel<4, false, false, KORDER>; }
+template <int KORDER> auto wave_kernel(const float*) { return demod_wave_f32_kernel<4, KORDER>; }
+
 // t0: first sample of the slab to process (segment of a run); the kernels see the slab from there on
 constexpr size_t SEQ_LDS_BYTES_4 = 34816;   // see the K5 launch
 // K1's grid.  A workgroup loops over (channel, tile) items; how many it takes decides how long it holds its place on a CU, i.e. how long a K5
@@ -1050,15 +1036,19 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
                const uint32_t* pol = nullptr)
 {
     TimedK tm(c, KT_FIR);
+    return with_x(c, c->slot, [&](auto* x) -> int {
 #ifdef M17_TOOLS
-    if (c->fir_form == 0 && c->f32_now()) return M17HIP_ESTATE;   // (round 4's kernel reads int16 rows only: a float stream is refused, m17hip_tune key 11)
-    if (c->fir_form == 0 && pol) return M17HIP_EINVAL;   // (round 4's kernel has no per-channel form: refused, not computed under the flag alone)
-    if (c->fir_form == 0) {   // round 4's kernel: the measurement build keeps it for same-box comparisons (tools/k1_forms.py, the clk_k1 pass of tools/profile_round.sh)
-        dim3 grid((T + FIR_TILE - 1) / FIR_TILE, C);
-        tm.launch((fir_rrc150_rolled_kernel<FIR_R, 4>), grid, dim3(FIR_THREADS), 0, st, c->now().x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, flags, c->taps);
-    } else
+        if (c->fir_form == 0) {   // round 4's kernel: the measurement build keeps it for same-box comparisons (tools/k1_forms.py, the clk_k1 pass of tools/profile_round.sh)
+            if constexpr (!std::is_same<decltype(x), int16_t*>::value) return M17HIP_ESTATE;   // (it reads int16 rows only: a float stream is refused, m17hip_tune key 11)
+            else {
+                if (pol) return M17HIP_EINVAL;   // (it has no per-channel form: refused, not computed under the flag alone)
+                dim3 grid((T + FIR_TILE - 1) / FIR_TILE, C);
+                tm.launch((fir_rrc150_rolled_kernel<FIR_R, 4>), grid, dim3(FIR_THREADS), 0, st, x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, flags, c->taps);
+                HIPCHK(c, hipGetLastError());
+                return M17HIP_OK;
+            }
+        }
 #endif
-    {
         const uint32_t tiles = (T + FS_TILE - 1) / FS_TILE;
         const uint64_t items64 = (uint64_t)tiles * C;
         if (items64 > 0xFFFFFFFFull) return M17HIP_EINVAL;
@@ -1066,23 +1056,15 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
         const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
-        const auto go = [&](auto kernel, const auto* xin, auto... mixed) {
-            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, xin + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
+        const auto go = [&](auto kernel, auto... mixed) {
+            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
         };
-        if (c->f32_now()) {   // a float stream: the float forms over the float pair
-            const float* xf = c->fslab[c->slot].x;
-            if (pol) go(fir_rrc150_skew_mixed_f32_kernel, xf, pol, flags & 1u);
-            else if (flags & 1u) go(fir_rrc150_skew_f32_kernel<true>, xf);
-            else go(fir_rrc150_skew_f32_kernel<false>, xf);
-        } else {
-            const int16_t* xi = c->now().x;
-            if (pol) go(fir_rrc150_skew_mixed_kernel, xi, pol, flags & 1u);
-            else if (flags & 1u) go(fir_rrc150_skew_kernel<true>, xi);
-            else go(fir_rrc150_skew_kernel<false>, xi);
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    return M17HIP_OK;
+        if (pol) go(fir_mixed_kernel(x), pol, flags & 1u);
+        else if (flags & 1u) go(fir_kernel<true>(x));
+        else go(fir_kernel<false>(x));
+        HIPCHK(c, hipGetLastError());
+        return M17HIP_OK;
+    });
 }
 // `pos`: the stream position of the slab's first sample (of the run, where t0 names a segment); `latency`: the four-wave pipeline where the piece allows it
 int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t pos, bool latency, hipStream_t st, uint32_t t0 = 0, const uint32_t* pol = nullptr)
@@ -1093,28 +1075,14 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     // (the pipeline needs whole 32-sample blocks that start on a block boundary of the stream: ragged pieces take the one-wave form)
     const bool one_wave = !latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK;
     const dim3 grid(one_wave ? (C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB) : (C + DP_CPB - 1) / DP_CPB), block(one_wave ? 64 * DCD_WPB : 256);
-    const auto go = [&](auto kernel, const auto* xin, auto... mixed) {   // (both forms take the same arguments)
-        tm.launch(kernel, grid, block, 0, st, xin + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
-    };
-    if (c->f32_now()) {   // a float stream: the float forms over the float pair
-        const float* xf = c->fslab[c->slot].x;
-        if (one_wave) {
-            if (pol) go(dcd_mixed_f32_kernel, xf, pol);
-            else if (flags & 1u) go(dcd_f32_kernel<true>, xf);
-            else go(dcd_f32_kernel<false>, xf);
-        } else if (pol) go(dcd_pipe_mixed_f32_kernel, xf, pol);
-        else if (flags & 1u) go(dcd_pipe_f32_kernel<true>, xf);
-        else go(dcd_pipe_f32_kernel<false>, xf);
-    } else {
-        const int16_t* xi = c->now().x;
-        if (one_wave) {
-            if (pol) go(dcd_mixed_kernel, xi, pol);
-            else if (flags & 1u) go(dcd_kernel<true>, xi);
-            else go(dcd_kernel<false>, xi);
-        } else if (pol) go(dcd_pipe_mixed_kernel, xi, pol);
-        else if (flags & 1u) go(dcd_pipe_kernel<true>, xi);
-        else go(dcd_pipe_kernel<false>, xi);
-    }
+    with_x(c, c->slot, [&](auto* x) {
+        const auto go = [&](auto kernel, auto... mixed) {
+            tm.launch(kernel, grid, block, 0, st, x + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
+        };
+        if (pol) go(dcd_mixed_kernel_of(x, one_wave), pol);
+        else if (flags & 1u) go(dcd_kernel_of<true>(x, one_wave));
+        else go(dcd_kernel_of<false>(x, one_wave));
+    });
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -1416,14 +1384,6 @@ static int stage_prepare(m17hip_ctx* c)
 }
 
 extern "C++" {   // (templates)
-// ---- the sample format of the input (int16, or float32 in the reference's units) ---------------------------------------------------------
-template <typename XT> constexpr int fmt_of() { return std::is_same<XT, float>::value ? M17HIP_FORMAT_F32 : M17HIP_FORMAT_I16; }
-// the input rows of slab pair `slot` in that format (nullptr: not allocated)
-template <typename XT> static XT* slab_x(m17hip_ctx* c, int slot)
-{
-    if constexpr (std::is_same<XT, float>::value) return c->fslab[slot].x;
-    else return c->slab[slot].x;
-}
 // The float pair's slab of `slot` and the float history arrays, the first time they are needed.  A fresh slab's prefix is zeroed on `st` (the stream
 // its input is written on): what a stream that begins in it finds where an int16 stream finds the prefix m17hip_demod_reset cleared.
 static int ensure_f32(m17hip_ctx* c, int slot, hipStream_t st)
@@ -1445,18 +1405,19 @@ static int ensure_f32(m17hip_ctx* c, int slot, hipStream_t st)
 // input of format `fmt` is about to be written: refused on a stream of the other format
 static int claim_format(const m17hip_ctx* c, int fmt) { return (c->stream_fmt && c->stream_fmt != fmt) ? M17HIP_ESTATE : M17HIP_OK; }
 
-// Where an in-place producer (m17hip_upload_i16 / _f32, m17hip_upload_i16_device / _f32_device, m17hip_synth_i16) writes: the current input slab on the
-// main stream, or — tuning knob 16 — the STAGING slab on the copy stream, as soon as the run before the latest one has released it.
-template <typename XT> struct InputTargetT { XT* x = nullptr; hipStream_t st = nullptr; bool stage = false; int slot = 0; };
-using InputTarget = InputTargetT<int16_t>;
+// Where a way in writes its rows: the current input slab on the main stream, or the STAGING slab on the copy stream, as soon as the run before the
+// latest one has released it — `staged`: an _async entry point; or any in-place producer (m17hip_upload_i16 / _f32, their _device forms, the IQ and
+// wideband ones, m17hip_synth_i16) under tuning knob 16.
+template <typename XT> struct InputTarget { XT* x = nullptr; hipStream_t st = nullptr; bool stage = false; int slot = 0; };
 template <typename XT>
-static int input_target(m17hip_ctx* c, InputTargetT<XT>& t)
+static int input_target(m17hip_ctx* c, InputTarget<XT>& t, bool staged = false)
 {
     int r;
     if ((r = claim_format(c, fmt_of<XT>()))) return r;
-    if (!c->stage_inputs) { t.slot = c->slot; t.st = c->stream; t.stage = false; }
+    if (!staged && !c->stage_inputs) { t.slot = c->slot; t.st = c->stream; t.stage = false; }
     else {
         if ((r = stage_prepare(c))) return r;
+        // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
         HIPCHK(c, c->other().wait_free(c->copy));
         t.slot = c->slot ^ 1; t.st = c->copy; t.stage = true;
     }
@@ -1465,7 +1426,7 @@ static int input_target(m17hip_ctx* c, InputTargetT<XT>& t)
     return M17HIP_OK;
 }
 template <typename XT>
-static void input_done(m17hip_ctx* c, const InputTargetT<XT>& t, uint32_t C, uint32_t T)
+static void input_done(m17hip_ctx* c, const InputTarget<XT>& t, uint32_t C, uint32_t T)
 {
     c->stream_fmt = c->slab_fmt[t.slot] = fmt_of<XT>();
     if (t.stage) {
@@ -1477,91 +1438,45 @@ static void input_done(m17hip_ctx* c, const InputTargetT<XT>& t, uint32_t C, uin
     c->lastC = C;
     if (c->have_run) c->inplace_after_run = true;
 }
-// the staging slab of that format, free for the next input (the copy stream has waited for the run that read it)
-template <typename XT>
-static int staging_target(m17hip_ctx* c, XT*& x)
+
+// The frame of every way in (host or device rows of either format, IQ through the discriminator, a wideband block through the tuner or the channeliser),
+// in place or staged for the next run.  `p`: the caller's rows or raw block.  `own()`: the checks particular to the way in, made once the common
+// arguments are good; what it refuses is the call's result.  `produce(x, st)`: queues on `st` whatever writes C rows of T samples behind the prefix of x.
+template <typename XT, typename Own, typename Produce>
+static int upload_frame(m17hip_ctx* c, const void* p, uint32_t C, uint32_t T, bool staged, Own&& own, Produce&& produce)
 {
-    int r;
-    if ((r = claim_format(c, fmt_of<XT>()))) return r;
-    if ((r = stage_prepare(c))) return r;
-    // the staging slab was the input of the run BEFORE the one now queued / running: free once that run is done with it
-    HIPCHK(c, c->other().wait_free(c->copy));
-    if constexpr (std::is_same<XT, float>::value) if ((r = ensure_f32(c, c->slot ^ 1, c->copy))) return r;
-    x = slab_x<XT>(c, c->slot ^ 1);
+    if (!c || !p || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
+    if (int r = own()) return r;
+    GUARD(c);
+    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
+    InputTarget<XT> in;
+    int r = input_target(c, in, staged);
+    if (r) return r;
+    if ((r = produce(in.x, in.st))) return r;
+    if (staged) HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
+    else HIPCHK(c, hipStreamSynchronize(in.st));   // the caller's memory belongs to the caller again when this returns
+    input_done(c, in, C, T);
     return M17HIP_OK;
-}
-static void staged_done(m17hip_ctx* c, int fmt, uint32_t C, uint32_t T)
-{
-    c->stream_fmt = c->slab_fmt[c->slot ^ 1] = fmt;
-    c->staged = true; c->stagedC = C; c->stagedT = T; c->other().C = C; c->other().T = T;
-}
-static void launch_copy_rows(const int16_t* dev, size_t pitch, int16_t* x, size_t xpitch, uint32_t C, uint32_t T, hipStream_t st)
-{
-    hipLaunchKernelGGL(copy_rows_i16_kernel, dim3(((T + 7) / 8 + 255) / 256, C), dim3(256), 0, st, dev, pitch, x, xpitch, T);
-}
-static void launch_copy_rows(const float* dev, size_t pitch, float* x, size_t xpitch, uint32_t C, uint32_t T, hipStream_t st)
-{
-    hipLaunchKernelGGL(copy_rows_xf32_kernel, dim3(((T + 3) / 4 + 255) / 256, C), dim3(256), 0, st, dev, pitch, x, xpitch, T);
 }
 
-// The four ways in, for either format (the C entry points below name the instantiations).
+// Rows from host or device memory, for either format (the C entry points below name the instantiations).
 template <typename XT>
-static int upload_host(m17hip_ctx* c, const XT* host, uint32_t C, uint32_t T, size_t pitch)
+static int upload_host(m17hip_ctx* c, const XT* host, uint32_t C, uint32_t T, size_t pitch, bool staged)
 {
-    if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    InputTargetT<XT> in;
-    int r = input_target(c, in);
-    if (r) return r;
-    HIPCHK(c, hipMemcpy2DAsync(in.x + XPRE, c->xpitch * sizeof(XT), host, pitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyHostToDevice, in.st));
-    HIPCHK(c, hipStreamSynchronize(in.st));
-    input_done(c, in, C, T);
-    return M17HIP_OK;
+    return upload_frame<XT>(c, host, C, T, staged, [&] { return pitch < T ? M17HIP_EINVAL : M17HIP_OK; }, [&](XT* x, hipStream_t st) -> int {
+        HIPCHK(c, hipMemcpy2DAsync(x + XPRE, c->xpitch * sizeof(XT), host, pitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyHostToDevice, st));
+        return M17HIP_OK;
+    });
 }
 template <typename XT>
-static int upload_host_async(m17hip_ctx* c, const XT* host, uint32_t C, uint32_t T, size_t pitch)
+static int upload_dev(m17hip_ctx* c, const XT* dev, uint32_t C, uint32_t T, size_t pitch, bool staged)
 {
-    if (!c || !host || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;
-    XT* x;
-    int r = staging_target(c, x);
-    if (r) return r;
-    HIPCHK(c, hipMemcpy2DAsync(x + XPRE, c->xpitch * sizeof(XT), host, pitch * sizeof(XT), (size_t)T * sizeof(XT), C, hipMemcpyHostToDevice, c->copy));
-    HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    staged_done(c, fmt_of<XT>(), C, T);
-    return M17HIP_OK;
-}
-template <typename XT>
-static int upload_dev_async(m17hip_ctx* c, const XT* dev, uint32_t C, uint32_t T, size_t pitch)
-{
-    if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;
-    XT* x;
-    int r = staging_target(c, x);
-    if (r) return r;
-    launch_copy_rows(dev, pitch, x, c->xpitch, C, T, c->copy);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-    staged_done(c, fmt_of<XT>(), C, T);
-    return M17HIP_OK;
-}
-template <typename XT>
-static int upload_dev(m17hip_ctx* c, const XT* dev, uint32_t C, uint32_t T, size_t pitch)
-{
-    if (!c || !dev || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    InputTargetT<XT> in;
-    int r = input_target(c, in);
-    if (r) return r;
-    launch_copy_rows(dev, pitch, in.x, c->xpitch, C, T, in.st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(in.st));   // `dev` belongs to the caller again when this returns
-    input_done(c, in, C, T);
-    return M17HIP_OK;
+    return upload_frame<XT>(c, dev, C, T, staged, [&] { return pitch < T ? M17HIP_EINVAL : M17HIP_OK; }, [&](XT* x, hipStream_t st) -> int {
+        constexpr uint32_t N = 16 / sizeof(XT);   // (samples per lane: copy_rows_kernel)
+        hipLaunchKernelGGL(copy_rows_kernel<XT>, dim3(((T + N - 1) / N + 255) / 256, C), dim3(256), 0, st, dev, pitch, x, c->xpitch, T);
+        HIPCHK(c, hipGetLastError());
+        return M17HIP_OK;
+    });
 }
 template <typename XT>
 static int download_host(m17hip_ctx* c, XT* host, uint32_t C, uint32_t T, size_t pitch)
@@ -1636,53 +1551,51 @@ static int launch_discriminate(m17hip_ctx* c, const void* dev, size_t pitch, flo
     HIPCHK(c, hipGetLastError());
     return iq_mark(c, st);
 }
-// The four ways in (`how`: from host memory / staged for the next run), as upload_host, upload_dev and their _async forms have them for floats: the
-// discriminator takes the place of the copy.
+// f(a value of the type the IQ samples of format `fmt` have — short2, float2 or uchar2); what f returns
+template <typename F> static auto with_iq_type(int fmt, F&& f)
+{
+    return fmt == M17HIP_IQ_I16 ? f(short2{}) : fmt == M17HIP_IQ_F32 ? f(float2{}) : f(uchar2{});
+}
+static size_t iq_sample_bytes(int fmt) { return with_iq_type(fmt, [](auto s) { return sizeof(s); }); }
+// The raw block of a host form (IQ, wideband) into the context's own buffer first, on `st`: `rows` rows of `samples` samples of `sb` bytes from the caller's
+// `dev` (pitch in samples), into rows of a multiple of four samples (16-byte loads).  Afterwards `dev` and `pitch` name the buffer.
+static int stage_raw(m17hip_ctx* c, uint32_t rows, size_t samples, size_t sb, hipStream_t st, const void*& dev, size_t& pitch)
+{
+    const size_t rp = round_up(samples, IQ_LANE);
+    if (c->iq_raw.size() < (size_t)rows * rp * sb) {
+        HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be read)
+        if (int r = alloc_code(c, c->iq_raw.grow((size_t)rows * rp * sb, &c->last_hip))) return r;
+    }
+    HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, dev, pitch * sb, samples * sb, rows, hipMemcpyHostToDevice, st));
+    dev = c->iq_raw; pitch = rp;
+    return M17HIP_OK;
+}
+// The four ways in (`how`: from host memory / staged for the next run) through the frame of all of them: the discriminator takes the place of the copy.
 enum { IQ_FROM_HOST = 1, IQ_STAGED = 2 };
 static int upload_iq(m17hip_ctx* c, const void* p, int iq_format, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
 {
-    if (!c || !p || C == 0 || T == 0 || C > c->maxC || T > c->maxT || pitch < T) return M17HIP_EINVAL;
-    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32) return M17HIP_EINVAL;
-    if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    int r;
-    InputTargetT<float> in;
-    float* x = nullptr;
-    hipStream_t st = nullptr;
-    if (how & IQ_STAGED) { if ((r = staging_target(c, x))) return r; st = c->copy; }
-    else { if ((r = input_target(c, in))) return r; x = in.x; st = in.st; }
-    if ((r = ensure_iq(c, st))) return r;
-    if ((r = iq_order(c, st))) return r;
-    const size_t sb = iq_format == M17HIP_IQ_I16 ? sizeof(short2) : sizeof(float2);
-    const void* dev = p;
-    if (how & IQ_FROM_HOST) {   // the raw IQ into the context's own buffer first, rows of a multiple of four samples (16-byte loads)
-        const size_t rp = round_up(T, IQ_LANE);
-        if (c->iq_raw.size() < (size_t)C * rp * sb) {
-            HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be read)
-            if ((r = alloc_code(c, c->iq_raw.grow((size_t)C * rp * sb, &c->last_hip)))) return r;
-        }
-        HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, p, pitch * sb, (size_t)T * sb, C, hipMemcpyHostToDevice, st));
-        dev = c->iq_raw; pitch = rp;
-    }
-    r = iq_format == M17HIP_IQ_I16 ? launch_discriminate<short2>(c, dev, pitch, x, C, T, gain, st) : launch_discriminate<float2>(c, dev, pitch, x, C, T, gain, st);
-    if (r) return r;
-    if (how & IQ_STAGED) {
-        HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-        staged_done(c, M17HIP_FORMAT_F32, C, T);
-    } else {
-        HIPCHK(c, hipStreamSynchronize(st));   // the caller's memory belongs to the caller again when this returns
-        input_done(c, in, C, T);
-    }
-    return M17HIP_OK;
+    const auto own = [&] {
+        if (pitch < T || (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32)) return M17HIP_EINVAL;   // (no discriminator reads 8-bit samples)
+        return std::isfinite(gain) && gain > 0.0f ? M17HIP_OK : M17HIP_EINVAL;
+    };
+    return upload_frame<float>(c, p, C, T, (how & IQ_STAGED) != 0, own, [&](float* x, hipStream_t st) -> int {
+        int r;
+        if ((r = ensure_iq(c, st))) return r;
+        if ((r = iq_order(c, st))) return r;
+        const void* dev = p;
+        if ((how & IQ_FROM_HOST) && (r = stage_raw(c, C, T, iq_sample_bytes(iq_format), st, dev, pitch))) return r;
+        return with_iq_type(iq_format, [&](auto s) -> int {
+            if constexpr (std::is_same<decltype(s), uchar2>::value) return M17HIP_EINVAL;   // (refused above)
+            else return launch_discriminate<decltype(s)>(c, dev, pitch, x, C, T, gain, st);
+        });
+    });
 }
 
 // ---- wideband IQ input (ABI 609): the tuner in front of the float slab -----------------------------------------------------------------------
-// Blackman-windowed sinc, cutoff 5500 Hz at 48000 * decim, 32 * decim + 1 taps, in double; unit DC gain, then rounded to float
-static void wide_default(uint32_t R, float* taps)
+// Blackman-windowed sinc of L taps, cutoff fc (cycles per sample), in double; unit DC gain, then rounded to float
+static void windowed_sinc(uint32_t L, double fc, float* taps)
 {
-    const uint32_t L = 32 * R + 1;
-    const double pi = 3.14159265358979323846, fc = 5500.0 / (48000.0 * R), mid = 0.5 * (L - 1);
+    const double pi = 3.14159265358979323846, mid = 0.5 * (L - 1);
     std::vector<double> h(L);
     double sum = 0.0;
     for (uint32_t i = 0; i < L; ++i) {
@@ -1694,60 +1607,14 @@ static void wide_default(uint32_t R, float* taps)
     }
     for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
 }
-// The first of two stages (ABI 610): all it has to do is keep what the first decimation folds onto the channel out of it.  Blackman-windowed sinc, cutoff
-// 24000 * R2 Hz at 48000 * R1 * R2 (half the rate it leaves), 8 * R1 + 1 taps, in double; unit DC gain, then rounded to float.  R1 = 1: one tap of 1.
+// The channel filter: cutoff 5500 Hz at 48000 * decim, 32 * decim + 1 taps
+static void wide_default(uint32_t R, float* taps) { windowed_sinc(32 * R + 1, 5500.0 / (48000.0 * R), taps); }
+// The first of two stages (ABI 610): all it has to do is keep what the first decimation folds onto the channel out of it.  Cutoff 24000 * R2 Hz at
+// 48000 * R1 * R2 (half the rate it leaves), 8 * R1 + 1 taps.  R1 = 1: one tap of 1.
 static void wide_default1(uint32_t R1, uint32_t R2, float* taps)
 {
     if (R1 == 1) { taps[0] = 1.0f; return; }
-    const uint32_t L = 8 * R1 + 1;
-    const double pi = 3.14159265358979323846, fc = 24000.0 * R2 / (48000.0 * R1 * R2), mid = 0.5 * (L - 1);
-    std::vector<double> h(L);
-    double sum = 0.0;
-    for (uint32_t i = 0; i < L; ++i) {
-        const double t = (double)i - mid, x = 2.0 * pi * fc * t;
-        const double sinc = t == 0.0 ? 2.0 * fc : std::sin(x) / (pi * t);
-        const double w = 0.42 - 0.5 * std::cos(2.0 * pi * i / (L - 1)) + 0.08 * std::cos(4.0 * pi * i / (L - 1));
-        h[i] = sinc * w;
-        sum += h[i];
-    }
-    for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
-}
-static size_t wide_sample_bytes(int fmt) { return fmt == M17HIP_IQ_I16 ? sizeof(short2) : fmt == M17HIP_IQ_F32 ? sizeof(float2) : sizeof(uchar2); }
-template <typename IQT>
-static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
-{
-    auto& w = c->wide;
-    const IQT* src = static_cast<const IQT*>(dev);
-    const uint32_t W = T * w.rate(), H = w.hlen();   // (W fits: upload_wide has seen to it)
-    if (w.dirty || !w.dev.live()) {   // the channel table, into the copy no queued launch reads
-        uint32_t* staging = nullptr;
-        HIPCHK(c, w.dev.begin_write(w.table.size(), &staging));
-        std::memcpy(staging, w.table.data(), w.table.size() * 4);
-        HIPCHK(c, w.dev.publish(w.table.size(), st));
-        w.dirty = false;
-    }
-    HIPCHK(c, w.dev.before_read(st));
-    if (w.R2) {
-        TimedK tm(c, KT_WIDE2);
-        tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
-                  w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
-                  (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
-    } else {
-        TimedK tm(c, KT_WIDE);
-        tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
-                  w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, w.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));   // (two readers: the main stream and the copy stream)
-    hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);   // (behind it: the next block's carries ...)
-    HIPCHK(c, hipGetLastError());
-    if (H) {                                                                                                            // (... and histories)
-        hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
-        HIPCHK(c, hipGetLastError());
-    }
-    w.par ^= 1;
-    w.count += W;
-    return iq_mark(c, st);
+    windowed_sinc(8 * R1 + 1, 24000.0 * R2 / (48000.0 * R1 * R2), taps);
 }
 // The survey of one block (m17hip_wide_survey is on), queued behind chan_kernel on the block's stream: it reads what chan_kernel read — src, w.hist[w.par],
 // w.count — and writes the plane whose turn it is.  A block without a survey time (J = 0) queues the second kernel alone: its plane is all +0.
@@ -1785,6 +1652,51 @@ static int launch_survey(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W
     HIPCHK(c, hipEventRecord(sv.ev[p], st));
     sv.times[p] = J; sv.first_output[p] = N0; sv.valid[p] = true; sv.latest = p;
     return M17HIP_OK;
+}
+// What follows the tuner's or the channeliser's kernel on its stream `st`, for the next block: the channels' carries, the sources' histories (H converted
+// samples each, into the copy whose turn it is), the feed's sample count.  In between the survey of a raster's block, which reads what that kernel read.
+template <typename IQT>
+static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, uint32_t H, uint32_t C, hipStream_t st)
+{
+    auto& w = c->wide;
+    hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
+    HIPCHK(c, hipGetLastError());
+    if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;   // (m17hip_wide_survey: on under a raster only)
+    if (H) {
+        hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
+        HIPCHK(c, hipGetLastError());
+    }
+    w.par ^= 1;
+    w.count += W;
+    return iq_mark(c, st);
+}
+template <typename IQT>
+static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, uint32_t C, uint32_t T, float gain, hipStream_t st)
+{
+    auto& w = c->wide;
+    const IQT* src = static_cast<const IQT*>(dev);
+    const uint32_t W = T * w.rate(), H = w.hlen();   // (W fits: upload_wide has seen to it)
+    if (w.dirty || !w.dev.live()) {   // the channel table, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, w.dev.begin_write(w.table.size(), &staging));
+        std::memcpy(staging, w.table.data(), w.table.size() * 4);
+        HIPCHK(c, w.dev.publish(w.table.size(), st));
+        w.dirty = false;
+    }
+    HIPCHK(c, w.dev.before_read(st));
+    if (w.R2) {
+        TimedK tm(c, KT_WIDE2);
+        tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
+                  w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
+                  (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+    } else {
+        TimedK tm(c, KT_WIDE);
+        tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
+                  w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, w.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));   // (two readers: the main stream and the copy stream)
+    return wide_after_block(c, src, pitch, W, T, H, C, st);
 }
 // The channeliser's launch (m17hip_wide_raster): the same frame, one workgroup per source and tile of output times.
 template <typename IQT>
@@ -1827,73 +1739,40 @@ static int launch_chan(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, w.rdev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
-    hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
-    HIPCHK(c, hipGetLastError());
-    if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;
-    if (H) {
-        hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
-        HIPCHK(c, hipGetLastError());
-    }
-    w.par ^= 1;
-    w.count += W;
-    return iq_mark(c, st);
+    return wide_after_block(c, src, pitch, W, T, H, C, st);
 }
-// The four ways in, through the discriminator's frame (upload_iq): the tuner takes the place of the copy.  `p`: [sources][pitch] samples of the configured format.
+// The four ways in, as upload_iq has them: the tuner or the channeliser takes the place of the copy.  `p`: [sources][pitch] samples of the configured format.
 static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
 {
-    if (!c || !p || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
-    if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
-    auto& w = c->wide;
-    if (!w.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
-    const uint64_t W = (uint64_t)T * w.rate();
-    if (pitch < W || W > 0xFFFFFFFFull) return M17HIP_EINVAL;   // (the kernels count a row's samples in 32 bits)
-    GUARD(c);
-    if (c->front_queued) return M17HIP_ESTATE;   // the slabs belong to the run m17hip_demod_front has started
-    int r;
-    InputTargetT<float> in;
-    float* x = nullptr;
-    hipStream_t st = nullptr;
-    if (how & IQ_STAGED) { if ((r = staging_target(c, x))) return r; st = c->copy; }
-    else { if ((r = input_target(c, in))) return r; x = in.x; st = in.st; }
-    if ((r = iq_order(c, st))) return r;
-    const size_t sb = wide_sample_bytes(w.fmt);
-    const void* dev = p;
-    if (how & IQ_FROM_HOST) {   // the raw block into the context's own buffer first
-        const size_t rp = round_up(W, IQ_LANE);
-        if (c->iq_raw.size() < (size_t)w.S * rp * sb) {
-            HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be read)
-            if ((r = alloc_code(c, c->iq_raw.grow((size_t)w.S * rp * sb, &c->last_hip)))) return r;
-        }
-        HIPCHK(c, hipMemcpy2DAsync(c->iq_raw, rp * sb, p, pitch * sb, W * sb, w.S, hipMemcpyHostToDevice, st));
-        dev = c->iq_raw; pitch = rp;
-    }
-    if (w.M)
-        r = w.fmt == M17HIP_IQ_I16 ? launch_chan<short2>(c, dev, pitch, x, C, T, gain, st)
-          : w.fmt == M17HIP_IQ_F32 ? launch_chan<float2>(c, dev, pitch, x, C, T, gain, st) : launch_chan<uchar2>(c, dev, pitch, x, C, T, gain, st);
-    else
-        r = w.fmt == M17HIP_IQ_I16 ? launch_tune<short2>(c, dev, pitch, x, C, T, gain, st)
-          : w.fmt == M17HIP_IQ_F32 ? launch_tune<float2>(c, dev, pitch, x, C, T, gain, st) : launch_tune<uchar2>(c, dev, pitch, x, C, T, gain, st);
-    if (r) return r;
-    if (how & IQ_STAGED) {
-        HIPCHK(c, hipEventRecord(c->ev_copy, c->copy));
-        staged_done(c, M17HIP_FORMAT_F32, C, T);
-    } else {
-        HIPCHK(c, hipStreamSynchronize(st));   // the caller's memory belongs to the caller again when this returns
-        input_done(c, in, C, T);
-    }
-    return M17HIP_OK;
+    uint64_t W = 0;
+    const auto own = [&] {
+        if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
+        if (!c->wide.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
+        W = (uint64_t)T * c->wide.rate();
+        return pitch < W || W > 0xFFFFFFFFull ? M17HIP_EINVAL : M17HIP_OK;   // (the kernels count a row's samples in 32 bits)
+    };
+    return upload_frame<float>(c, p, C, T, (how & IQ_STAGED) != 0, own, [&](float* x, hipStream_t st) -> int {
+        auto& w = c->wide;
+        int r;
+        if ((r = iq_order(c, st))) return r;
+        const void* dev = p;
+        if ((how & IQ_FROM_HOST) && (r = stage_raw(c, w.S, W, iq_sample_bytes(w.fmt), st, dev, pitch))) return r;
+        return with_iq_type(w.fmt, [&](auto s) {
+            return w.M ? launch_chan<decltype(s)>(c, dev, pitch, x, C, T, gain, st) : launch_tune<decltype(s)>(c, dev, pitch, x, C, T, gain, st);
+        });
+    });
 }
 
 }  // extern "C++"
 
-int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
-int m17hip_upload_f32(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch); }
-int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host_async(c, host, C, T, pitch); }
-int m17hip_upload_f32_async(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host_async(c, host, C, T, pitch); }
-int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev_async(c, dev, C, T, pitch); }
-int m17hip_upload_f32_device_async(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev_async(c, dev, C, T, pitch); }
-int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch); }
-int m17hip_upload_f32_device(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch); }
+int m17hip_upload_i16(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch, false); }
+int m17hip_upload_f32(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch, false); }
+int m17hip_upload_i16_async(m17hip_ctx* c, const int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch, true); }
+int m17hip_upload_f32_async(m17hip_ctx* c, const float* host, uint32_t C, uint32_t T, size_t pitch) { return upload_host(c, host, C, T, pitch, true); }
+int m17hip_upload_i16_device_async(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch, true); }
+int m17hip_upload_f32_device_async(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch, true); }
+int m17hip_upload_i16_device(m17hip_ctx* c, const int16_t* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch, false); }
+int m17hip_upload_f32_device(m17hip_ctx* c, const float* dev, uint32_t C, uint32_t T, size_t pitch) { return upload_dev(c, dev, C, T, pitch, false); }
 int m17hip_download_i16(m17hip_ctx* c, int16_t* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
 int m17hip_download_f32(m17hip_ctx* c, float* host, uint32_t C, uint32_t T, size_t pitch) { return download_host(c, host, C, T, pitch); }
 
@@ -2142,7 +2021,7 @@ static int synth_impl(m17hip_ctx* c, const m17_synth_params* params, const m17_i
     const size_t sym_bytes = round_up((size_t)C * sym_pitch, 256);
     const size_t pts_at = sym_bytes + round_up((size_t)C * 4, 256);
     const size_t need = points ? pts_at + (size_t)n_points * sizeof(ModImpair) : sym_bytes + (size_t)C * 4;
-    InputTarget in;
+    InputTarget<int16_t> in;
     int r = input_target(c, in);
     if (r) return r;
     // the symbol staging lives in its own allocation: the per-operator scratch may be in use by work queued on the main stream
@@ -2212,7 +2091,7 @@ int m17hip_synth_tx_i16(m17hip_ctx* c, const m17_synth_params* base, const m17_t
     const size_t lsf_at = tx_at + round_up((size_t)C * sizeof(ModTx), 256);
     const size_t rows_at = lsf_at + round_up((size_t)C * 30, 256);
     const size_t need = rows_at + std::max<size_t>((size_t)n_rows * 32, 32);
-    InputTarget in;
+    InputTarget<int16_t> in;
     int r = input_target(c, in);
     if (r) return r;
     if (need > c->synth_scratch.size() && c->synth_scratch) HIPCHK(c, hipDeviceSynchronize());   // (nothing still reads the one it outgrew)
@@ -2523,10 +2402,12 @@ int m17hip_demod_reset(m17hip_ctx* c)
     c->marks.clear();
     hipLaunchKernelGGL(seq_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->seq_state, c->dcd_state, c->evm.state, c->maxC);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(zero_prefix_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, c->maxC);
+    hipLaunchKernelGGL(zero_prefix_xy_kernel<int16_t>, dim3(c->maxC), dim3(64), 0, c->stream, c->now().x.get(), c->xpitch, c->now().y.get(), c->ypitch);
     HIPCHK(c, hipGetLastError());
-    if (c->fslab[c->slot].x) {   // (a context that has seen a float stream: the float pair's prefix and the float histories as well)
-        hipLaunchKernelGGL(zero_prefix_xf32_kernel, dim3(c->maxC), dim3(64), 0, c->stream, c->fslab[c->slot].x.get(), c->xpitch);
+    // (a context that has seen a float stream: the float pair's prefix and the float histories as well — whatever format the slab pair holds NOW: the
+    //  next stream may be of either)
+    if (c->fslab[c->slot].x) {
+        hipLaunchKernelGGL((zero_prefix_kernel<float, XPRE>), dim3(c->maxC), dim3(64), 0, c->stream, c->fslab[c->slot].x.get(), c->xpitch);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(c->hist_f, 0, c->hist_f.size() * sizeof(float), c->stream));
     }
@@ -2735,6 +2616,13 @@ static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 static EvParams ev_fold(const m17hip_ctx* c, const EvmFold::Pass& f, EvLast last) { return EvParams{f.ops, c->evm.pitch(), c->evm.state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, f.C, f.upto, last}; }
 static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}; }
 
+// The parameter blocks of K2 and K5 (GateParams::x, SeqParams::x: filled in launch_gate_seg and seq_params, below) name the input rows as int16_t*
+// whatever they hold.  Float rows go in under that member here, and the float instantiations take them out again: reinterpret_cast<const XT*>(P.x) in
+// limit_track_body<XT> (m17_gate_kernel.hpp) and in the wave body (m17_wave_body.inc).  The kernel a block is launched with comes from the same typed
+// pointer (gate_kernel, wave_kernel), so the two cannot disagree.
+static const int16_t* param_rows(const int16_t* x) { return x; }
+static const int16_t* param_rows(const float* x) { return reinterpret_cast<const int16_t*>(x); }
+
 // One launch of K2 over segment k of the run whose slabs the context names: the whole segment from K5's state (first segment), ahead of
 // K5 from K2's own state, or the redo of the channels K5 flagged in the previous segment.
 static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStream_t st, bool ahead, bool redo, bool redo_stores = false)
@@ -2746,14 +2634,12 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
     const uint32_t C = p.C, t0 = p.t0(k), len = p.t0(k + 1) - t0;
     TimedK tm(c, KT_GATE);
     GateParams G{};
-    G.x = c->x_now(t0); G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
+    G.xpitch = c->xpitch; G.y = c->now().y + t0; G.ypitch = c->ypitch; G.h = c->now().h + t0;
     G.dcd_table = c->now().dcd; G.ticks_cap = c->ticks_cap; G.state = c->seq_state;
     G.final_h = by_parity(c->final_h, k, c->maxC, 4);
     G.chain_in = ahead ? c->gate_exp : nullptr; G.chain_out = c->gate_exp;
     G.only = redo ? by_parity(c->dropped, k - 1u, c->maxC) : nullptr;   // (flags by segment parity)
     G.bnd = redo ? by_parity(c->bnd, k, c->maxC) : nullptr;   // (written by K5 of segment k - 1)
-    const bool f32 = c->f32_now();
-    if (f32) { G.hist_f = c->hist_f; G.bnd_hist_f = redo ? by_parity(c->bnd_hist_f, k, c->maxC, HISTF_PITCH) : nullptr; }
     G.taps = c->taps; G.C = C; G.T = len; G.pos0 = c->pos + t0; G.tick_row0 = c->pos / TICK; G.flags = p.kflags | ((redo && !redo_stores) ? 2u : 0u); G.pol = p.pol;
     G.nblk = (C + GT_CPW - 1) / GT_CPW;
     uint32_t fold_blocks = 0;
@@ -2768,8 +2654,11 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
         G.ev = ev_fold(c, f, k == 0 ? EV_SETTLES : EV_BESIDE_K5);   // (in front of segment 0, which K5 waits for: settled; beside the replay ahead: not)
         fold_blocks = f.blocks();
     }
-    if (f32) tm.launch(limit_track_f32_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
-    else tm.launch(limit_track_kernel, dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
+    with_x(c, c->slot, [&](auto* x) {
+        G.x = param_rows(x + t0);
+        if constexpr (std::is_same<decltype(x), float*>::value) { G.hist_f = c->hist_f; G.bnd_hist_f = redo ? by_parity(c->bnd_hist_f, k, c->maxC, HISTF_PITCH) : nullptr; }
+        tm.launch(gate_kernel(x), dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
+    });
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
 }
@@ -2798,12 +2687,10 @@ static void commit_marks(m17hip_ctx* c)
 static int reset_marked_front(m17hip_ctx* c, uint32_t n, hipStream_t st, Reader which, bool x, bool dcd)
 {
     HIPCHK(c, c->reset_list.before_read(st));
-    if (c->f32_now())
-        hipLaunchKernelGGL(front_reset_list_xf32_kernel, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? c->fslab[c->slot].x.get() : (float*)nullptr, c->xpitch,
+    with_x(c, c->slot, [&](auto* rows) {
+        hipLaunchKernelGGL(front_reset_list_kernel<std::remove_pointer_t<decltype(rows)>>, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? rows : nullptr, c->xpitch,
                            dcd ? c->dcd_state.get() : (DcdState*)nullptr);
-    else
-    hipLaunchKernelGGL(front_reset_list_kernel, dim3(n), dim3(64), 0, st, c->reset_list.dev(), n, x ? c->now().x.get() : (int16_t*)nullptr, c->xpitch,
-                       dcd ? c->dcd_state.get() : (DcdState*)nullptr);
+    });
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->reset_list.after_read(which, st));
     return M17HIP_OK;
@@ -2829,31 +2716,28 @@ static int begin_staged(m17hip_ctx* c, RunPlan& p, uint32_t C, uint32_t T, uint3
     if (C != c->stagedC || T != c->stagedT) return M17HIP_EINVAL;
     if (c->have_run && C != c->lastC) return M17HIP_EINVAL;  // a continued stream keeps its channel count
     if (int r = run_format_check(c, c->slot ^ 1)) return r;
-    const int16_t* xprev = c->now().x;
-    const float* xprev_f = c->fslab[c->slot].x;
     c->slot ^= 1;   // (the staged input's pair becomes now(), the previous run's other())
     c->staged = false; c->uploaded = true;
     c->carryT = c->have_run ? c->runT : 0;
     // the new slab's prefix, behind the staged copy on the copy stream; the slab pair itself is free since now().end (the copy
     // stream waited for it when the input was staged — m17hip_input_alternate stages without a copy, so wait here as well)
     HIPCHK(c, c->now().wait_free(c->copy));
-    if (c->f32_now()) {   // a float stream: the same three cases over the float pair
-        float* xf = c->fslab[c->slot].x;
-        if (c->carryT && !xprev_f) return M17HIP_ESTATE;   // (cannot be: a continued float stream has run on a float slab)
-        if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)
-            hipLaunchKernelGGL(copy_tail_xf32_kernel, dim3(C), dim3(64), 0, c->copy, xprev_f, xf, c->xpitch, c->carryT);
+    const int carried = with_x(c, c->slot, [&](auto* x) -> int {
+        using XT = std::remove_pointer_t<decltype(x)>;
+        const XT* xprev = slab_x<XT>(c, c->slot ^ 1);   // the previous run's rows: of the stream's format, as these are
+        if (c->carryT && !xprev) return M17HIP_ESTATE;   // (cannot be: a continued stream has run on a slab of its format)
+        if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)   // the tail of the previous input, where it lies (that slab is only read while its run is in flight)
+            hipLaunchKernelGGL((copy_tail_kernel<XT, XPRE>), dim3(C), dim3(64), 0, c->copy, xprev, x, c->xpitch, c->carryT);
         else if (c->carryT) {
+            // a run shorter than the prefix: its tail reaches into its own prefix, which its last kernel rewrites — wait for that, and copy the prefix
+            // (or its data region was overwritten in place since: the tail its last kernel carried into its prefix)
             HIPCHK(c, hipStreamWaitEvent(c->copy, c->other().end, 0));
-            hipLaunchKernelGGL(copy_prefix_xf32_kernel, dim3(C), dim3(64), 0, c->copy, xprev_f, xf, c->xpitch);
-        } else HIPCHK(c, hipMemset2DAsync(xf, c->xpitch * sizeof(float), 0, XPRE * sizeof(float), C, c->copy));
-    } else
-    if (c->carryT >= (uint32_t)XPRE && !c->inplace_after_run)   // the tail of the previous input, where it lies (that slab is only read while its run is in flight)
-        hipLaunchKernelGGL(copy_tail_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch, c->carryT);
-    else if (c->carryT) {              // (or its data region was overwritten in place since: the tail its last kernel carried into its prefix)              // a run shorter than the prefix: its tail reaches into its own prefix, which its last kernel rewrites — wait for that
-        HIPCHK(c, hipStreamWaitEvent(c->copy, c->other().end, 0));
-        hipLaunchKernelGGL(copy_prefix_i16_kernel, dim3(C), dim3(64), 0, c->copy, xprev, c->now().x, c->xpitch);
-    } else HIPCHK(c, hipMemset2DAsync(c->now().x, c->xpitch * sizeof(int16_t), 0, XPRE * sizeof(int16_t), C, c->copy));
-    HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL((copy_prefix_kernel<XT, XPRE>), dim3(C), dim3(64), 0, c->copy, xprev, x, c->xpitch);
+        } else HIPCHK(c, hipMemset2DAsync(x, c->xpitch * sizeof(XT), 0, XPRE * sizeof(XT), C, c->copy));   // a fresh stream
+        HIPCHK(c, hipGetLastError());
+        return M17HIP_OK;
+    });
+    if (carried) return carried;
     uint32_t n_reset = 0;   // (m17hip_demod_reset_channels: the marked channels' input prefixes, behind the tail copy)
     if (!c->marks.empty()) {
         if (int r = take_marks(c, n_reset, c->copy)) return r;
@@ -3040,8 +2924,8 @@ static int carry_staged_prefixes(m17hip_ctx* c, const RunPlan& p)
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in_ready, 0));
     if (p.gate0_queued) return M17HIP_OK;   // (m17hip_demod_front has queued these copies on the replay stream, in front of the first segment's replay)
     if (c->carryT) {   // (the previous run ended by carrying its tails into its own prefixes: copy those)
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(p.C), dim3(64), 0, c->stream, c->other().y, c->now().y, c->ypitch);
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(p.C), dim3(64), 0, c->stream, c->other().h, c->now().h, c->ypitch);
+        hipLaunchKernelGGL((copy_prefix_kernel<float, YPRE>), dim3(p.C), dim3(64), 0, c->stream, c->other().y, c->now().y, c->ypitch);
+        hipLaunchKernelGGL((copy_prefix_kernel<float, YPRE>), dim3(p.C), dim3(64), 0, c->stream, c->other().h, c->now().h, c->ypitch);
         HIPCHK(c, hipGetLastError());
     } else {
         HIPCHK(c, hipMemset2DAsync(c->now().y, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), p.C, c->stream));
@@ -3081,15 +2965,17 @@ static int prepare_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     return M17HIP_OK;
 }
 
-// K5's parameters for segment k
-static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet& rs, uint32_t k)
+// K5's parameters for segment k; `x`: the run's input rows (with_x)
+extern "C++" {   // (a template inside the C ABI's extern "C" block)
+template <typename XT>
+static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet& rs, uint32_t k, const XT* x)
 {
     const uint32_t t0 = p.t0(k), len = p.t0(k + 1) - t0;
     SeqParams P{};
     P.h = c->now().h + t0; P.final_h = by_parity(c->final_h, k, c->maxC, 4);
     P.dropped = by_parity(c->dropped, k, c->maxC);
-    P.x = c->x_now(t0); P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
-    if (c->f32_now()) { P.hist_f = c->hist_f; P.bnd_hist_f = by_parity(c->bnd_hist_f, k + 1u, c->maxC, HISTF_PITCH); }
+    P.x = param_rows(x + t0); P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+    if constexpr (std::is_same<XT, float>::value) { P.hist_f = c->hist_f; P.bnd_hist_f = by_parity(c->bnd_hist_f, k + 1u, c->maxC, HISTF_PITCH); }
     P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
     P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
     P.tables = c->tables; P.taps = c->taps; P.llr_edges = c->llr_edges;
@@ -3105,6 +2991,7 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     P.dropped_in = (k > 0 && c->redo_form != 1) ? by_parity(c->dropped, k - 1u, c->maxC) : nullptr;   // (redo in front: nobody starts a segment off the replay)
     return P;
 }
+}  // extern "C++"
 
 // The chain of the run: K2 -> K5 per segment on the main stream, the replay on its stream, and what of the front end follows K5 (tuning knob 5; a gate-aware run's K1).
 // K2 launches: the whole first segment from K5's state; every later segment AHEAD of K5 from the replay's own end state (replay
@@ -3157,18 +3044,16 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
             HIPCHK(c, hipEventRecord(seg[k + 1].gate, c->side3));
         }
         TimedK tm(c, KT_SEQ);
-        const SeqParams P = seq_params(c, p, rs, k);
-#ifdef M17_TOOLS
-        if (c->profile) tm.launch((demod_wave_kernel<4, true>), grid, block, lds, c->stream, P);
-        else if (c->wave_times) tm.launch((demod_wave_kernel<4, false, true>), grid, block, lds, c->stream, P);
-        else
+        with_x(c, c->slot, [&](auto* x) {
+            const SeqParams P = seq_params(c, p, rs, k, x);
+#ifdef M17_TOOLS   // (int16 rows only: run_format_check has refused these instantiations on a float stream)
+            if (c->profile) tm.launch((demod_wave_kernel<4, true>), grid, block, lds, c->stream, P);
+            else if (c->wave_times) tm.launch((demod_wave_kernel<4, false, true>), grid, block, lds, c->stream, P);
+            else
 #endif
-        if (c->f32_now()) {   // a float stream (run_format_check has refused the tools-only instantiations above)
-            if (c->kalman_order == 3u) tm.launch((demod_wave_f32_kernel<4, 3>), grid, block, lds, c->stream, P);
-            else tm.launch(demod_wave_f32_kernel<4>, grid, block, lds, c->stream, P);
-        } else
-        if (c->kalman_order == 3u) tm.launch((demod_wave_kernel<4, false, false, 3>), grid, block, lds, c->stream, P);   // (the default order: no call in the kernel)
-        else tm.launch(demod_wave_kernel<4>, grid, block, lds, c->stream, P);
+            if (c->kalman_order == 3u) tm.launch(wave_kernel<3>(x), grid, block, lds, c->stream, P);   // (the default order: no call in the kernel)
+            else tm.launch(wave_kernel<-1>(x), grid, block, lds, c->stream, P);
+        });
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(seg[k].seq, c->stream));
         if (k + ahead < nseg && (r = launch_front_seg(c, p, k + ahead))) return r;
@@ -3185,12 +3070,10 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     const uint32_t C = p.C, T = p.T;
     // the tails a run that continues in THESE slabs (input uploaded in place) will find as its prefixes; a staged run takes them from
     // here into the other slab pair itself.  (Before the deferred decode: the next staged run's first replay waits for these, not for that.)
-    if (c->f32_now()) {
-        hipLaunchKernelGGL(carry_tail_xf32_kernel, dim3(C), dim3(64), 0, c->stream, c->fslab[c->slot].x.get(), c->xpitch, T);
-        hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().y.get(), c->ypitch, T);
-    } else
-    hipLaunchKernelGGL(carry_tail_kernel, dim3(C), dim3(64), 0, c->stream, c->now().x, c->xpitch, c->now().y, c->ypitch, C, T);
-    hipLaunchKernelGGL(carry_tail_f32_kernel, dim3(C), dim3(64), 0, c->stream, c->now().h, c->ypitch, T);
+    with_x(c, c->slot, [&](auto* x) {
+        hipLaunchKernelGGL(carry_tail_xy_kernel<std::remove_pointer_t<decltype(x)>>, dim3(C), dim3(64), 0, c->stream, x, c->xpitch, c->now().y.get(), c->ypitch, T);
+    });
+    hipLaunchKernelGGL((carry_tail_kernel<float, YPRE>), dim3(C), dim3(64), 0, c->stream, c->now().h.get(), c->ypitch, T);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_tail, c->stream));
     // ---- the end of the run on the MAIN stream: what the next run's chain needs of this one — the one or two deferred costs the state still
@@ -3268,8 +3151,8 @@ int m17hip_demod_front(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags)
     if (c->gate0_early && c->have_run && c->carryT && !c->profile && !p.n_reset) {
         m17hip_ctx::SegEvents& seg0 = c->now().seg[0];
         for (const Event* e : {&c->ev_tail, &c->ev_in_ready, &seg0.fir, &seg0.dcd}) HIPCHK(c, hipStreamWaitEvent(c->side3, *e, 0));
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
-        hipLaunchKernelGGL(copy_prefix_f32_kernel, dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
+        hipLaunchKernelGGL((copy_prefix_kernel<float, YPRE>), dim3(C), dim3(64), 0, c->side3, c->other().y, c->now().y, c->ypitch);
+        hipLaunchKernelGGL((copy_prefix_kernel<float, YPRE>), dim3(C), dim3(64), 0, c->side3, c->other().h, c->now().h, c->ypitch);
         HIPCHK(c, hipGetLastError());
         if (int r = launch_gate_seg(c, p, 0, c->side3, false, false)) return r;
         HIPCHK(c, hipEventRecord(seg0.gate, c->side3));

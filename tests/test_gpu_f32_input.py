@@ -313,6 +313,73 @@ def test_full_chain_staged_live_feed(x4_case, order):
         ctx.close()
 
 
+def test_staged_float_runs_shorter_than_the_prefixes_mixed_with_in_place_runs(off_case):
+    """The float form of test_gpu_streaming's ragged mixed staging: runs shorter than the carried prefixes (152 input samples, 96 filter outputs), no
+    multiples of 8 / 192 / 1920, in place / staged with m17hip_demod_front / staged without it in turn, up to one frame cycle past the last cut.  A staged
+    float run finds its prefix in the previous run's prefix (a run shorter than 152 samples) or in that run's tail where it lies."""
+    import torch
+    x, exp = off_case
+    Cn = 16
+    cuts = [1, 7, 95, 149, 153, 1919, 3841, 1920]   # (the last: one frame cycle)
+    end = sum(cuts)
+    diags = Expect(np.ascontiguousarray(x[:Cn, :end])).diags
+    ctx = _ctx(Cn, CH_T, log=False)
+    try:
+        ctx.reset()
+        pos, keep, total = 0, [], 0
+        for i, n in enumerate(cuts):
+            chunk = np.ascontiguousarray(x[:Cn, pos:pos + n])
+            if i % 3 == 0:                             # in place
+                ctx.upload(chunk)
+                ctx.run()
+            else:
+                pin = torch.from_numpy(chunk).pin_memory()
+                keep.append(pin)
+                ctx.upload_async(pin.data_ptr(), Cn, n, dtype=np.float32)
+                if i % 3 == 1:
+                    ctx.front(channels=Cn, samples=n)
+                ctx.run(channels=Cn, samples=n)
+            rows, _ = exp.run(pos, pos + n)
+            last = i + 1 == len(cuts)
+            _check(ctx, rows[:Cn], None, f"run {i} of {n} samples", diags=diags if last else None)
+            total += sum(r.size for r in rows[:Cn])
+            pos += n
+        ctx.upload_wait()
+        assert pos == end and total > 0
+        assert ctx.input_format()[0] == m17hip.FORMAT_F32
+    finally:
+        ctx.close()
+
+
+def test_staged_float_run_after_an_in_place_overwrite_of_the_previous_slab(off_case):
+    """The float form of test_gpu_streaming's test of that name: a run in place, then the same slab overwritten in place (an input that is never run),
+    then the NEXT chunk staged and run: the staged run's 152-sample prefix must be the tail the last RUN carried, not what the data region holds now."""
+    import torch
+    x, exp = off_case
+    Cn, T = 16, 9600
+    diags = Expect(np.ascontiguousarray(x[:Cn, :2 * T])).diags
+    junk = np.full((Cn, T), 0.3, dtype=np.float32)
+    pinned = torch.from_numpy(np.ascontiguousarray(x[:Cn, T:2 * T])).pin_memory()
+    ctx = _ctx(Cn, CH_T, log=False)
+    try:
+        ctx.reset()
+        ctx.upload(x[:Cn, :T])
+        ctx.run(channels=Cn, samples=T)
+        rows, _ = exp.run(0, T)
+        _check(ctx, rows[:Cn], None, "the run in place")
+        total = sum(r.size for r in rows[:Cn])
+        ctx.upload(junk)                                                   # overwrites the slab the run used (never run)
+        ctx.upload_async(pinned.data_ptr(), Cn, T, dtype=np.float32)       # the real continuation, staged
+        ctx.run(channels=Cn, samples=T)
+        rows, _ = exp.run(T, 2 * T)
+        _check(ctx, rows[:Cn], None, "the staged continuation", diags=diags)
+        total += sum(r.size for r in rows[:Cn])
+        ctx.upload_wait()
+        assert total > Cn
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("order", range(8))
 def test_every_kalman_order(off_case, order):
     x, _ = off_case
