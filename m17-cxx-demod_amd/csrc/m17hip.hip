@@ -191,6 +191,80 @@ struct TimedLaunch { Event a, b; int which; };
 
 struct BertState; struct ChanStat; struct PacketState; struct PacketRec;   // (with the host layer's kernels, below)
 
+// THE PAYLOAD CONSUMERS and the diagnostic log: what works on a run's records behind K5, on the payload stream (flush_payload).  Each owns its buffers and
+// its books.  A consumer's STATE goes from run to run (and through the feeds); what a run completes goes to the STORE of the run's record set (0 / 1), so a
+// fetch of run k reads beside the consumer of run k + 1.  `room` == 0: off.  configure = the m17hip_tune key (quiesce_payload comes first: nothing queued
+// uses the buffers); reset = the consumer's part of m17hip_demod_reset; consume = the consumer over C rows of records, into the store of `set`.  Whether a
+// RUN feeds a consumer is the run's (RecSet::bert / pkt / voice: what was on when it was made).  The methods are defined beside flush_payload.
+struct BertStats {   // PRBS9 statistics (m17hip_tune key 6; m17hip_bert_stats, m17hip_sweep_stats)
+    DevBuf<BertState> state;          // [maxC], from the creation on
+    bool on = false;                  // (the runs made so far keep the setting they were made with)
+    int reset(m17hip_ctx* c, hipStream_t st);
+};
+struct Packets {     // packet reassembly (key 7; m17hip_packets_fetch, m17hip_packets_feed)
+    uint32_t room = 0;                // completed packets a store holds
+    bool fed = false;                 // m17hip_packets_feed has filled a store since the room was set.  m17hip_demod_reset does NOT clear it (the voice
+                                      // consumer's is cleared): a fetch after feed + reset finds the store empty, not M17HIP_ESTATE.  Kept as it is.
+    bool on() const { return room != 0; }
+    PacketState* state_or_null() const { return on() ? state_.get() : nullptr; }
+    const PacketRec* store(int set) const { return recs_[set]; }
+    const uint32_t* count(int set) const { return count_.get() + set; }   // packets completed into the store (not cut at room)
+    int configure(m17hip_ctx* c, uint32_t value);
+    int reset(m17hip_ctx* c, hipStream_t st);
+    int consume(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set);
+private:
+    int fresh(m17hip_ctx* c, hipStream_t st);   // no half-assembled packet, nothing completed (configure, reset)
+    DevBuf<PacketState> state_;       // [maxC]
+    DevBuf<PacketRec> recs_[2];       // [room]
+    DevBuf<uint32_t> count_;          // [2]
+};
+struct Voice {       // codec2 payload planes and the call log (key 34; m17_voice_kernel.hpp; m17hip_voice_fetch, m17hip_calls_fetch, m17hip_voice_feed)
+    uint32_t room = 0, call_room = 0; // voice slots / call slots per channel of a store (nothing but (channel, seq) orders the calls)
+    uint32_t rows[2] = {0, 0};        // channels whose rows of a store the consumer has written (a run's, or m17hip_voice_feed's)
+    bool fed = false;                 // m17hip_voice_feed has filled a store since the room was set or the reset
+    bool on() const { return room != 0; }
+    VoiceState* state_or_null() const { return on() ? state_.get() : nullptr; }
+    const uint8_t* audio(int set) const { return audio_[set]; }                                  // [maxC][room][16]
+    const uint8_t* marks(int set) const { return marks_[set]; }                                  // [maxC][room]
+    const uint32_t* counts(int set) const { return counts_.get() + (size_t)set * maxC_; }        // [maxC] voice records of the run (not cut at room)
+    const CallRec* calls(int set) const { return calls_[set]; }                                  // [maxC][call_room]
+    const uint32_t* call_counts(int set) const { return call_counts_.get() + (size_t)set * maxC_; }   // [maxC] calls closed in the run (not cut at call_room)
+    VoiceParams params(int set, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, uint32_t channel_base) const
+    {
+        return VoiceParams{recs, rec_cap, rec_count, state_, C, audio_[set], marks_[set], counts_.get() + (size_t)set * maxC_, room,
+                           calls_[set], call_counts_.get() + (size_t)set * maxC_, call_room, channel_base};
+    }
+    int configure(m17hip_ctx* c, uint32_t value);
+    int reset(m17hip_ctx* c, hipStream_t st);
+    int consume(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set);
+private:
+    int fresh(m17hip_ctx* c, hipStream_t st);   // no open call, seq back to 0, nothing of the runs before left to fetch (configure, reset)
+    DevBuf<VoiceState> state_;        // [maxC]
+    DevBuf<uint8_t> audio_[2], marks_[2];
+    DevBuf<CallRec> calls_[2];
+    DevBuf<uint32_t> counts_, call_counts_;   // [2][maxC]
+    uint32_t maxC_ = 0;
+};
+struct DiagLog {     // one entry per diagnostic callback of the LATEST run (key 9; m17hip_diag_log_fetch): one store, not one per record set
+    uint32_t room = 0;                // entries per channel
+    bool on() const { return room != 0; }
+    Diag* entries() const { return on() ? log_.get() : nullptr; }   // [maxC][room]: with `room`, the pair the kernels' parameter blocks take
+    uint32_t* count() const { return count_; }                      // [maxC] entries written this run
+    int configure(m17hip_ctx* c, uint32_t value);
+private:
+    DevBuf<Diag> log_;
+    DevBuf<uint32_t> count_;
+};
+
+// The context's eight overflow words on the host (m17hip_ctx::RecSet::ovf is the layout: four words per record set), for what is asked of BOTH sets — the
+// runs of a stream alternate between them.  `read` queues the copy; the words are there once `st` has been synchronised.
+struct OvfWords {
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    hipError_t read(const uint32_t* overflow, hipStream_t st) { return hipMemcpyAsync(w, overflow, 32, hipMemcpyDeviceToHost, st); }
+    bool evm_ops_dropped() const { return (w[2] | w[6]) != 0; }        // a channel outran its row of deferred EVM operations (since the reset): m17_diag::evm is not right
+    uint64_t replay_drops() const { return (uint64_t)w[1] + w[5]; }    // channels that left the limit-filter replay (since the reset)
+};
+
 // What a run looks like: decided once (plan_run) and handed to every launch of the run.  Between m17hip_demod_front and m17hip_demod_run the
 // context keeps it (front_plan), and the run call uses it as it is.
 struct RunPlan {
@@ -335,28 +409,11 @@ struct m17hip_ctx {
     DevBuf<float> final_h;            // [2][maxC][4], by segment parity
     DevBuf<GateExport> gate_exp;      // [maxC] K2's own state at the end of a segment
     DevBuf<uint32_t> dropped;         // [2][maxC] K5: the segment dropped the speculation
-    DevBuf<BertState> bert_state;     // [maxC] (tuning knob 6)
-    bool bert = false;
+    BertStats bert;                   // the payload consumers and the diagnostic log (tuning knobs 6, 7, 34, 9)
+    Packets packets;
+    Voice voice;
+    DiagLog diag;
     DevBuf<ChanStat> chan_words;      // m17hip_sweep_stats' words on their way out / a rank's words on their way into m17hip_gather_sweep_stats (payload stream)
-    DevBuf<PacketState> pkt_state;    // [maxC] (tuning knob 7)
-    DevBuf<PacketRec> pkt_recs2[2];   // [pkt_cap]: packets completed by a run, one store per record set
-    DevBuf<uint32_t> pkt_count2;      // [2]
-    uint32_t pkt_cap = 0;
-    bool pkt_fed = false;
-    // The voice consumer (tuning knob 34; m17_voice_kernel.hpp): per-channel call state, and per record set the planes of a run — payloads,
-    // marks, counts — and the calls it closed, a row of call_room slots per channel (nothing but (channel, seq) orders them).
-    DevBuf<VoiceState> voice_state;   // [maxC]
-    DevBuf<uint8_t> voice_audio2[2];  // [maxC][voice_room][16]
-    DevBuf<uint8_t> voice_marks2[2];  // [maxC][voice_room]
-    DevBuf<uint32_t> voice_counts2;   // [2][maxC] voice records of the run (not cut at voice_room)
-    DevBuf<CallRec> call_recs2[2];    // [maxC][call_room]
-    DevBuf<uint32_t> call_counts2;    // [2][maxC] calls closed in the run (not cut at call_room)
-    uint32_t voice_room = 0, call_room = 0;
-    uint32_t voice_C[2] = {0, 0};     // channels whose rows of a store the consumer has written (a run's, or m17hip_voice_feed's)
-    bool voice_fed = false;
-    DevBuf<Diag> diag_log;            // [maxC][diag_cap] one entry per diagnostic callback of the last run (tuning knob 9)
-    DevBuf<uint32_t> diag_count;      // [maxC]
-    uint32_t diag_cap = 0;
     uint32_t kalman_order = 3;        // evaluation order of the Kalman updates (m17hip_set_kalman_order)
     int gather_fault = 0;             // tuning knob 30 (tests): 1 = this rank's compaction (m17hip_gather_sweep_stats: its upload) fails inside the gather, 2 = the root's staging allocation fails, 3 = its word of exchange 2 is not written,
                                       // 4 = it cannot read exchange 1, 5 = it cannot read exchange 2
@@ -1210,7 +1267,7 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     alloc(c->final_h, 2 * C * 4);
     alloc(c->gate_exp, C);
     alloc(c->dropped, 2 * C);
-    alloc(c->bert_state, C);
+    alloc(c->bert.state, C);
     alloc(s.dcd, C * c->ticks_cap * 12);
     alloc(c->dcd_state, C);
     alloc(c->seq_state, C);
@@ -1231,8 +1288,7 @@ int m17hip_ctx_create(int device, uint32_t max_channels, uint32_t max_samples, m
     // (a gate-aware K1 leaves tiles unwritten: what K2's replay may read there must be finite.  A memset is queued, not done, when it returns: wait —
     //  the first run's K1 is on a stream of its own that would not)
     if (hipMemset(s.y, 0, C * c->ypitch * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(M17HIP_EHIP);
-    hipLaunchKernelGGL(bert_reset_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, 0, c->bert_state, (uint32_t)C);
-    if (hipGetLastError() != hipSuccess) return fail(M17HIP_EHIP);
+    if (c->bert.reset(c, 0)) return fail(M17HIP_EHIP);
     {
         DecodeTables* t = new DecodeTables;
         build_tables(*t);
@@ -2413,20 +2469,9 @@ int m17hip_demod_reset(m17hip_ctx* c)
     }
     if (int r = iq_fresh_feed(c, nullptr, 0)) return r;   // (a context that has seen IQ input: every channel's feed starts over)
     HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
-    hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->bert_state, c->maxC);
-    HIPCHK(c, hipGetLastError());
-    if (c->pkt_cap) {
-        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->pkt_state, c->maxC);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
-    }
-    if (c->voice_room) {   // no open call, seq back to 0; nothing of the runs before is left to fetch
-        hipLaunchKernelGGL(voice_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->voice_state, c->maxC);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemsetAsync(c->voice_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->call_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
-        c->voice_fed = false;
-    }
+    if (int r = c->bert.reset(c, c->stream)) return r;
+    if (int r = c->packets.reset(c, c->stream)) return r;
+    if (int r = c->voice.reset(c, c->stream)) return r;
     for (auto& rs : c->sets) {
         if (rs.rec_count) HIPCHK(c, hipMemsetAsync(rs.rec_count, 0, (size_t)c->maxC * 4, c->stream));
         rs.valid = false;
@@ -2613,7 +2658,7 @@ static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 }
 
 // A fold pass of the deferred EVM (EvmFold) as a kernel gets it; and none — what a kernel that can take a pass along is given when there is nothing to fold.
-static EvParams ev_fold(const m17hip_ctx* c, const EvmFold::Pass& f, EvLast last) { return EvParams{f.ops, c->evm.pitch(), c->evm.state, c->diag_cap ? c->diag_log : nullptr, c->diag_cap, c->seq_state, f.C, f.upto, last}; }
+static EvParams ev_fold(const m17hip_ctx* c, const EvmFold::Pass& f, EvLast last) { return EvParams{f.ops, c->evm.pitch(), c->evm.state, c->diag.entries(), c->diag.room, c->seq_state, f.C, f.upto, last}; }
 static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}; }
 
 // The parameter blocks of K2 and K5 (GateParams::x, SeqParams::x: filled in launch_gate_seg and seq_params, below) name the input rows as int16_t*
@@ -2776,17 +2821,102 @@ static int flush_fold(m17hip_ctx* c)
     return M17HIP_OK;
 }
 
-// The voice consumer over `C` rows of records, into the planes and the call store of record set `set` (payload stream: the state goes from run to run)
-static void launch_voice(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set)
+// ---- the payload consumers and the diagnostic log (BertStats, Packets, Voice, DiagLog, above) ----
+int BertStats::reset(m17hip_ctx* c, hipStream_t st)
 {
-    VoiceParams V{};
-    V.recs = recs; V.rec_cap = rec_cap; V.rec_count = rec_count; V.state = c->voice_state; V.C = C;
-    V.audio = c->voice_audio2[set]; V.marks = c->voice_marks2[set]; V.counts = c->voice_counts2 + (size_t)set * c->maxC; V.room = c->voice_room;
-    V.calls = c->call_recs2[set]; V.call_counts = c->call_counts2 + (size_t)set * c->maxC; V.call_room = c->call_room;
-    V.channel_base = c->channel_base;
+    hipLaunchKernelGGL(bert_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, st, state, c->maxC);
+    HIPCHK(c, hipGetLastError());
+    return M17HIP_OK;
+}
+
+int Packets::fresh(m17hip_ctx* c, hipStream_t st)
+{
+    hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, st, state_, c->maxC);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemsetAsync(count_, 0, 8, st));
+    return M17HIP_OK;
+}
+int Packets::reset(m17hip_ctx* c, hipStream_t st) { return on() ? fresh(c, st) : M17HIP_OK; }   // (`fed` stays: see its comment)
+int Packets::configure(m17hip_ctx* c, uint32_t value)
+{
+    recs_[0].release(&c->last_hip); recs_[1].release(&c->last_hip); room = 0; fed = false;
+    if (value == 0) return M17HIP_OK;
+    if (!state_) {   // (the state and the counts survive a change of the room)
+        HIPCHK(c, state_.alloc(c->maxC));
+        HIPCHK(c, count_.alloc(2));
+    }
+    HIPCHK(c, recs_[0].alloc(value));
+    HIPCHK(c, recs_[1].alloc(value));
+    room = value;   // (a failed allocation has left the consumer off)
+    return fresh(c, c->stream);
+}
+int Packets::consume(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set)
+{
+    HIPCHK(c, hipMemsetAsync(count_.get() + set, 0, 4, ps));
+    hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, recs, rec_cap, rec_count, state_, C, recs_[set], room, count_.get() + set, c->channel_base);
+    HIPCHK(c, hipGetLastError());
+    return M17HIP_OK;
+}
+
+int Voice::fresh(m17hip_ctx* c, hipStream_t st)
+{
+    hipLaunchKernelGGL(voice_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, st, state_, c->maxC);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemsetAsync(counts_, 0, (size_t)2 * c->maxC * 4, st));
+    HIPCHK(c, hipMemsetAsync(call_counts_, 0, (size_t)2 * c->maxC * 4, st));
+    return M17HIP_OK;
+}
+int Voice::reset(m17hip_ctx* c, hipStream_t st)
+{
+    if (!on()) return M17HIP_OK;
+    if (int r = fresh(c, st)) return r;
+    fed = false;
+    return M17HIP_OK;
+}
+int Voice::configure(m17hip_ctx* c, uint32_t value)
+{
+    for (int i = 0; i < 2; ++i) {
+        audio_[i].release(&c->last_hip); marks_[i].release(&c->last_hip); calls_[i].release(&c->last_hip);
+        rows[i] = 0;
+    }
+    room = 0; call_room = 0; fed = false;
+    if (value == 0) return M17HIP_OK;
+    const uint32_t calls = M17HIP_CALLS_PER_CHANNEL(value);
+    maxC_ = c->maxC;
+    if (!state_) {   // (the state and the counts survive a change of the room)
+        HIPCHK(c, state_.alloc(maxC_));
+        HIPCHK(c, counts_.alloc((size_t)2 * maxC_));
+        HIPCHK(c, call_counts_.alloc((size_t)2 * maxC_));
+    }
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(c, audio_[i].alloc((size_t)maxC_ * value * 16));
+        HIPCHK(c, marks_[i].alloc((size_t)maxC_ * value));
+        HIPCHK(c, calls_[i].alloc((size_t)maxC_ * calls));
+    }
+    if (int r = fresh(c, c->stream)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the payload stream, where the consumer works, may be another one)
+    room = value; call_room = calls;   // (a step that failed has left the consumer off)
+    return M17HIP_OK;
+}
+// (the payload stream: the state goes from run to run)
+int Voice::consume(m17hip_ctx* c, hipStream_t ps, const FrameRec* recs, uint32_t rec_cap, const uint32_t* rec_count, uint32_t C, int set)
+{
     TimedK tm(c, KT_VOICE);
-    tm.launch(voice_log_kernel, dim3((C + VOICE_CPB - 1) / VOICE_CPB), dim3(64 * VOICE_CPB), 0, ps, V);
-    c->voice_C[set] = C;
+    tm.launch(voice_log_kernel, dim3((C + VOICE_CPB - 1) / VOICE_CPB), dim3(64 * VOICE_CPB), 0, ps, params(set, recs, rec_cap, rec_count, C, c->channel_base));
+    rows[set] = C;
+    HIPCHK(c, hipGetLastError());
+    return M17HIP_OK;
+}
+
+int DiagLog::configure(m17hip_ctx* c, uint32_t value)
+{
+    log_.release(&c->last_hip); room = 0;
+    if (value == 0) return M17HIP_OK;
+    if (!count_) HIPCHK(c, count_.alloc(c->maxC));
+    HIPCHK(c, hipMemsetAsync(count_, 0, (size_t)c->maxC * 4, c->stream));   // (on the stream the kernels that count into it run on)
+    HIPCHK(c, log_.alloc((size_t)c->maxC * (size_t)value));
+    room = value;
+    return M17HIP_OK;
 }
 
 // Queue the payload work of the runs whose results nobody has asked for yet, in run order, on the payload stream: the frames K5 left to
@@ -2809,7 +2939,7 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
         if (rs.defer_llr && c->defer_hist) {   // (frames are deferred only while both stores exist: m17hip_tune key 15)
             DeferParams D{};
             D.recs = rs.recs; D.rec_cap = rs.rec_cap; D.rec_count = rs.rec_count; D.defer = rs.defer_llr; D.hist = c->defer_hist; D.tables = c->tables;
-            D.state = c->seq_state; D.diag_log = c->diag_cap ? c->diag_log : nullptr; D.diag_cap = c->diag_cap; D.diag_count = c->diag_count; D.C = C;
+            D.state = c->seq_state; D.diag_log = c->diag.entries(); D.diag_cap = c->diag.room; D.diag_count = c->diag.count(); D.C = C;
             D.ev = ev_no_fold(C);
             uint32_t fold_blocks = 0;
             if (fold_beside_decode && c->evm.owed() && i == c->cur) {   // (the latest run's last fold pass, beside its decode on the main stream)
@@ -2821,16 +2951,16 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
             tm.launch(decode_deferred_kernel, dim3(defer_blocks(C) + fold_blocks), dim3(64 * DEFER_CPB), DEFER_LDS_BYTES, ps, D);
             HIPCHK(c, hipGetLastError());
         }
-        if (rs.bert && c->bert_state)   // payload consumer: PRBS9 statistics over this run's BERT records
-            hipLaunchKernelGGL(bert_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->bert_state, C);
-        if (rs.pkt && c->pkt_cap) {   // payload consumer: packet reassembly over this run's packet records
-            HIPCHK(c, hipMemsetAsync(c->pkt_count2 + i, 0, 4, ps));
-            hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->pkt_state, C,
-                               c->pkt_recs2[i], c->pkt_cap, c->pkt_count2 + i, c->channel_base);
+        // the consumers that were on when the run was made (and still are): PRBS9 statistics over its BERT records, packet reassembly over its packet
+        // records, codec2 payload planes and the call log over its stream records (behind their deferred decode)
+        if (rs.bert && c->bert.state) {
+            hipLaunchKernelGGL(bert_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, ps, rs.recs, rs.rec_cap, rs.rec_count, c->bert.state, C);
+            HIPCHK(c, hipGetLastError());
         }
-        if (rs.voice && c->voice_room)   // payload consumer: codec2 payload planes and the call log over this run's stream records (behind their deferred decode)
-            launch_voice(c, ps, rs.recs, rs.rec_cap, rs.rec_count, C, i);
-        HIPCHK(c, hipGetLastError());
+        if (rs.pkt && c->packets.on())
+            if (int r = c->packets.consume(c, ps, rs.recs, rs.rec_cap, rs.rec_count, C, i)) return r;
+        if (rs.voice && c->voice.on())
+            if (int r = c->voice.consume(c, ps, rs.recs, rs.rec_cap, rs.rec_count, C, i)) return r;
         HIPCHK(c, hipEventRecord(rs.done, ps));
         rs.pending = false;
     }
@@ -2841,9 +2971,39 @@ static int flush_payload(m17hip_ctx* c, bool selected_only = false, bool older_o
 // context that ran in place made it on the main stream, its first staged input moves the payload stream to the copy stream, and
 // m17hip_set_stream moves the main one.  So the fetch orders the payload stream behind the run itself: its `done`, or its `chain` while
 // its payload work is still to be queued (flush_payload queues it behind `chain`).  (An event that was never recorded: no wait.)
+// The two forms below are the whole rule; whatever reads a consumer's state or a run's store on the payload stream calls one of them first.
 static int pay_after(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
 {
     HIPCHK(c, hipStreamWaitEvent(c->pay(), rs.pending ? rs.chain : rs.done, 0));
+    return M17HIP_OK;
+}
+// Behind EVERY run: for what reads or changes a consumer's state, which every run's consumer adds to.  The payload work of both runs is queued first.
+static int behind_all_runs(m17hip_ctx* c)
+{
+    if (int r = flush_payload(c)) return r;
+    for (const auto& rs : c->sets)
+        if (rs.valid)
+            if (int r = pay_after(c, rs)) return r;
+    return M17HIP_OK;
+}
+// Behind the SELECTED run (m17hip_frames_select; `set`: its record set and its stores), for what reads that run's results: its payload work is queued
+// first, the later run's is not.  M17HIP_ESTATE when the run before the latest is named and its records are not there; an invalid LATEST set passes and
+// is waited for nothing (a store that a feed has filled).
+static int behind_selected(m17hip_ctx* c, int& set)
+{
+    set = c->cur ^ (int)(c->sel_back & 1u);
+    if (c->sel_back && !c->sets[set].valid) return M17HIP_ESTATE;
+    if (int r = flush_payload(c, true)) return r;
+    return c->sets[set].valid ? pay_after(c, c->sets[set]) : M17HIP_OK;
+}
+// The payload stream and the main stream idle, the payload work that was owed made (m17hip_tune: in front of a change of what that work uses);
+// `fold_first`: the latest run's last EVM fold pass as well (it writes the diagnostic log)
+static int quiesce_payload(m17hip_ctx* c, bool fold_first)
+{
+    if (fold_first) if (int r = flush_fold(c)) return r;
+    if (int r = flush_payload(c)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->pay()));
     return M17HIP_OK;
 }
 
@@ -2982,7 +3142,7 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     P.C = p.C; P.T = len; P.pos0 = c->pos + t0; P.tick_row0 = c->pos / TICK; P.flags = (p.kflags & 1u) | (t0 ? 2u : 0u) | (std::min(k, 23u) << 8); P.pol = p.pol;
     P.kalman_order = c->kalman_order; P.channel_base = c->channel_base;
     P.level_gain = c->level_gain + (size_t)(c->kalman_order & 7u) * core::LEVEL_SCHED_N;
-    P.diag_log = c->diag_cap ? c->diag_log : nullptr; P.diag_cap = c->diag_cap; P.diag_count = c->diag_count;
+    P.diag_log = c->diag.entries(); P.diag_cap = c->diag.room; P.diag_count = c->diag.count();
     P.defer = c->defer_decode ? rs.defer_llr : nullptr;
     if (c->defer_evm) { P.ev_ops = c->evm.ops(); P.ev_pitch = c->evm.pitch(); P.ev_cursor_out = c->evm.cursor_out(k, p.nseg); }
     P.bnd_out = by_parity(c->bnd, k + 1u, c->maxC);
@@ -3092,7 +3252,7 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
     c->now().used = true; c->pos += T; c->inplace_after_run = false; c->have_run = true;
     c->lastC = C; c->runT = T; c->last_nseg = p.nseg;
     rs.valid = true; rs.C = C; rs.rec_cap = c->rec_cap; rs.nseg = p.nseg;
-    rs.pending = true; rs.bert = c->bert; rs.pkt = c->pkt_cap != 0; rs.voice = c->voice_room != 0;
+    rs.pending = true; rs.bert = c->bert.on; rs.pkt = c->packets.on(); rs.voice = c->voice.on();
     c->cur = (int)(&rs - c->sets); c->sel_back = 0;
     return M17HIP_OK;
 }
@@ -3102,9 +3262,9 @@ static int end_run(m17hip_ctx* c, const RunPlan& p, m17hip_ctx::RecSet& rs)
 // and with the diagnostic log on (ONE store, which the deferred decode patches: the next run waits for it).
 static int flush_after_run(m17hip_ctx* c, const m17hip_ctx::RecSet& rs)
 {
-    if (c->streams() && !c->diag_cap) return M17HIP_OK;
+    if (c->streams() && !c->diag.on()) return M17HIP_OK;
     const int r = flush_payload(c, false, false, c->evm.owed() && c->defer_decode && c->pay() == c->stream);   // (the fold beside the decode, as up to round 5)
-    if (r || !c->diag_cap) return r;
+    if (r || !c->diag.on()) return r;
     HIPCHK(c, hipStreamWaitEvent(c->stream, rs.done, 0));
     return flush_fold(c);
 }
@@ -3119,13 +3279,9 @@ static int reset_marked_state(m17hip_ctx* c, const RunPlan& p)
     const uint32_t n = p.n_reset;
     const uint32_t* list = c->reset_list.dev();
     if (int r = flush_fold(c)) return r;
-    if (int r = flush_payload(c)) return r;
-    for (const auto& rs : c->sets)
-        if (rs.valid)
-            if (int r = pay_after(c, rs)) return r;
+    if (int r = behind_all_runs(c)) return r;
     HIPCHK(c, c->reset_list.before_read(c->pay()));
-    hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert_state.get(), c->pkt_cap ? c->pkt_state.get() : (PacketState*)nullptr,
-                       c->voice_room ? c->voice_state.get() : (VoiceState*)nullptr);
+    hipLaunchKernelGGL(consumer_reset_list_kernel, dim3((n + 63) / 64), dim3(64), 0, c->pay(), list, n, c->bert.state.get(), c->packets.state_or_null(), c->voice.state_or_null());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->reset_list.after_read(RD_PAY, c->pay()));
     HIPCHK(c, c->reset_list.before_read(c->stream));
@@ -3217,8 +3373,8 @@ static int compact_into(m17hip_ctx* c, FrameRec* dev_out, uint64_t cap, uint64_t
 {
     m17hip_ctx::RecSet* rs = selected_set(c);
     if (!rs) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c, true)) return fr;
-    if (int fr = pay_after(c, *rs)) return fr;   // (behind the selected run wherever its payload work was queued)
+    int set = 0;
+    if (int fr = behind_selected(c, set)) return fr;   // (`set` is rs's; behind that run wherever its payload work was queued)
     const uint32_t C = rs->C;
     if (dev_out && dev_out != c->compact && c->sel_back == 0 && c->pay() != c->stream) {
         // a device destination of the caller's: whatever the caller queued on the main stream for it (a fill, its previous consumer) comes first —
@@ -3299,28 +3455,31 @@ int m17hip_diag_fetch(m17hip_ctx* c, m17_diag* diag_host, uint32_t C)
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->now().seg[0].gate, 0));
     HIPCHK(c, hipMemcpy2DAsync(diag_host, sizeof(Diag), &c->seq_state[0].cold.diag, sizeof(SeqState), sizeof(Diag), C, hipMemcpyDeviceToHost,
                                c->stream));
-    uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(ovf, c->overflow, 32, hipMemcpyDeviceToHost, c->stream));
+    OvfWords ovf;
+    HIPCHK(c, ovf.read(c->overflow, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return (ovf[2] | ovf[6]) ? M17HIP_EOVERFLOW : M17HIP_OK;   // (a channel outran its row of deferred EVM operations: every field but `evm` is right)
+    return ovf.evm_ops_dropped() ? M17HIP_EOVERFLOW : M17HIP_OK;   // (every field but `evm` is right)
 }
 
 int m17hip_diag_log_fetch(m17hip_ctx* c, m17_diag* log_host, uint32_t* counts_host, uint32_t C, uint32_t capacity)
 {
     if (!c || !log_host || !counts_host || C == 0 || C > c->maxC || capacity == 0) return M17HIP_EINVAL;
     GUARD(c);
-    if (!c->diag_cap || !c->sets[c->cur].valid) return M17HIP_ESTATE;
+    if (!c->diag.on() || !c->sets[c->cur].valid) return M17HIP_ESTATE;
     if (int fr = flush_fold(c)) return fr;
+    // Neither behind_all_runs nor behind_selected: there is ONE log, the latest run's whatever m17hip_frames_select names, and it is read on the main
+    // stream, where K5 and the fold wrote it.  So all payload work is queued and the HOST waits for the payload stream; payload work that went to the
+    // main stream (before the payload stream moved) is in front of the copies below in stream order.
     if (int fr = flush_payload(c)) return fr;
     HIPCHK(c, hipStreamSynchronize(c->pay()));   // (the deferred decode has put the costs into the log's entries)
-    HIPCHK(c, hipMemcpyAsync(counts_host, c->diag_count, (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
-    const uint32_t n = std::min(capacity, c->diag_cap);
-    HIPCHK(c, hipMemcpy2DAsync(log_host, (size_t)capacity * sizeof(Diag), c->diag_log, (size_t)c->diag_cap * sizeof(Diag), (size_t)n * sizeof(Diag), C,
+    HIPCHK(c, hipMemcpyAsync(counts_host, c->diag.count(), (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
+    const uint32_t n = std::min(capacity, c->diag.room);
+    HIPCHK(c, hipMemcpy2DAsync(log_host, (size_t)capacity * sizeof(Diag), c->diag.entries(), (size_t)c->diag.room * sizeof(Diag), (size_t)n * sizeof(Diag), C,
                                hipMemcpyDeviceToHost, c->stream));
+    OvfWords ovf;
+    HIPCHK(c, ovf.read(c->overflow, c->stream));   // (on the stream of the two copies above: one synchronisation for the three)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpy(ovf, c->overflow, 32, hipMemcpyDeviceToHost));
-    if (ovf[2] | ovf[6]) return M17HIP_EOVERFLOW;   // (deferred EVM operations were dropped: see m17hip_diag_fetch)
+    if (ovf.evm_ops_dropped()) return M17HIP_EOVERFLOW;   // (see m17hip_diag_fetch)
     bool trunc = false;
     for (uint32_t i = 0; i < C; ++i) trunc = trunc || counts_host[i] > n;
     return trunc ? M17HIP_ETRUNC : M17HIP_OK;
@@ -3347,13 +3506,10 @@ int m17hip_bert_stats(m17hip_ctx* c, m17_bert_stat* stats_host, uint32_t C)
 {
     if (!c || !stats_host || C == 0 || C > c->maxC) return M17HIP_EINVAL;
     GUARD(c);
-    if (!c->bert) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c)) return fr;
-    for (const auto& rs : c->sets)   // (every run's consumer adds to the state: behind both runs, wherever their payload work was queued)
-        if (rs.valid)
-            if (int fr = pay_after(c, rs)) return fr;
+    if (!c->bert.on) return M17HIP_ESTATE;
+    if (int fr = behind_all_runs(c)) return fr;
     std::vector<BertState> tmp(C);
-    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->bert_state, (size_t)C * sizeof(BertState), hipMemcpyDeviceToHost, c->pay()));   // (behind the consumers of the runs queued so far)
+    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->bert.state, (size_t)C * sizeof(BertState), hipMemcpyDeviceToHost, c->pay()));   // (behind the consumers of the runs queued so far)
     HIPCHK(c, hipStreamSynchronize(c->pay()));
     for (uint32_t i = 0; i < C; ++i) {
         stats_host[i].bits = tmp[i].bit_count; stats_host[i].errors = tmp[i].err_count;
@@ -3375,51 +3531,53 @@ int m17hip_sweep_stats(m17hip_ctx* c, uint32_t n_points, m17_chan_stat* host, ui
     if (!c || !host || n_points == 0 || C == 0 || C > c->maxC) return M17HIP_EINVAL;
     GUARD(c);
     static_assert(sizeof(ChanStat) == sizeof(m17_chan_stat) && sizeof(ChanStat) == 32, "m17_chan_stat layout");
-    if (!c->bert || !c->have_run) return M17HIP_ESTATE;
+    if (!c->bert.on || !c->have_run) return M17HIP_ESTATE;
     // m17hip_diag_fetch's order for `evm`: the latest run's last fold pass on the main stream (or the replay m17hip_demod_front queued is making it)
     if (int fr = flush_fold(c)) return fr;
     if (c->front_queued && c->front_plan.gate0_queued) HIPCHK(c, hipStreamWaitEvent(c->stream, c->now().seg[0].gate, 0));
     // ... m17hip_bert_stats' order for the PRBS9 state: the payload work of both runs, wherever it was queued
-    if (int fr = flush_payload(c)) return fr;
-    for (const auto& rs : c->sets)
-        if (rs.valid)
-            if (int fr = pay_after(c, rs)) return fr;
+    if (int fr = behind_all_runs(c)) return fr;
     // ... and the words are made and copied on the payload stream, behind the main stream's work so far
     if (c->pay() != c->stream) {
         HIPCHK(c, hipEventRecord(c->ev_fetch, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->pay(), c->ev_fetch, 0));
     }
     if (int r = ensure_chan_words(c, c->maxC)) return r;
-    hipLaunchKernelGGL(sweep_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), c->bert_state, c->seq_state, c->overflow, C,
+    hipLaunchKernelGGL(sweep_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), c->bert.state, c->seq_state, c->overflow, C,
                        c->channel_base, n_points, c->chan_words);
     HIPCHK(c, hipGetLastError());
-    uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    OvfWords ovf;
     HIPCHK(c, hipMemcpyAsync(host, c->chan_words, (size_t)C * sizeof(ChanStat), hipMemcpyDeviceToHost, c->pay()));
-    HIPCHK(c, hipMemcpyAsync(ovf, c->overflow, 32, hipMemcpyDeviceToHost, c->pay()));
+    HIPCHK(c, ovf.read(c->overflow, c->pay()));
     HIPCHK(c, hipStreamSynchronize(c->pay()));
-    return (ovf[2] | ovf[6]) ? M17HIP_EOVERFLOW : M17HIP_OK;
+    return ovf.evm_ops_dropped() ? M17HIP_EOVERFLOW : M17HIP_OK;
+}
+
+// m17hip_packets_feed, m17hip_voice_feed: the caller's records [C][pitch] and counts [C] copied to the scratch buffer on the payload stream, where the
+// runs' own consumer works on the same state — behind the payload work of every run (the state goes from run to run)
+static int stage_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t C, uint32_t pitch, FrameRec*& drec, uint32_t*& dcnt)
+{
+    if (int fr = behind_all_runs(c)) return fr;
+    const size_t rec_b = round_up((size_t)C * pitch * sizeof(FrameRec), 256);
+    HIPCHK(c, c->scratch.grow(rec_b + (size_t)C * 4, &c->last_hip));
+    drec = reinterpret_cast<FrameRec*>(c->scratch.get());
+    dcnt = reinterpret_cast<uint32_t*>(c->scratch + rec_b);
+    HIPCHK(c, hipMemcpyAsync(drec, recs_host, (size_t)C * pitch * sizeof(FrameRec), hipMemcpyHostToDevice, c->pay()));
+    HIPCHK(c, hipMemcpyAsync(dcnt, counts_host, (size_t)C * 4, hipMemcpyHostToDevice, c->pay()));
+    return M17HIP_OK;
 }
 
 int m17hip_packets_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uint32_t* counts_host, uint32_t C, uint32_t pitch)
 {
     if (!c || !recs_host || !counts_host || C == 0 || C > c->maxC || pitch == 0) return M17HIP_EINVAL;
     GUARD(c);
-    if (!c->pkt_cap) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c)) return fr;
-    const size_t rec_b = round_up((size_t)C * pitch * sizeof(FrameRec), 256);
-    HIPCHK(c, c->scratch.grow(rec_b + (size_t)C * 4, &c->last_hip));
-    FrameRec* drec = reinterpret_cast<FrameRec*>(c->scratch.get());
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(c->scratch + rec_b);
-    // (the payload stream: where the runs' own packet consumer works on the same reassembly state)
-    HIPCHK(c, hipMemcpyAsync(drec, recs_host, (size_t)C * pitch * sizeof(FrameRec), hipMemcpyHostToDevice, c->pay()));
-    HIPCHK(c, hipMemcpyAsync(dcnt, counts_host, (size_t)C * 4, hipMemcpyHostToDevice, c->pay()));
-    const int ps = c->cur;   // (the store of the latest run's set: what m17hip_packets_fetch names unless m17hip_frames_select says otherwise)
-    HIPCHK(c, hipMemsetAsync(c->pkt_count2 + ps, 0, 4, c->pay()));
-    hipLaunchKernelGGL(packet_asm_kernel, dim3((C + 63) / 64), dim3(64), 0, c->pay(), drec, pitch, dcnt, c->pkt_state, C,
-                       c->pkt_recs2[ps], c->pkt_cap, c->pkt_count2 + ps, c->channel_base);
-    HIPCHK(c, hipGetLastError());
+    if (!c->packets.on()) return M17HIP_ESTATE;   // (not refused between m17hip_demod_front and m17hip_demod_run, as m17hip_voice_feed is: kept)
+    FrameRec* drec; uint32_t* dcnt;
+    if (int r = stage_feed(c, recs_host, counts_host, C, pitch, drec, dcnt)) return r;
+    // (the store of the latest run's set: what m17hip_packets_fetch names unless m17hip_frames_select says otherwise)
+    if (int r = c->packets.consume(c, c->pay(), drec, pitch, dcnt, C, c->cur)) return r;
     HIPCHK(c, hipStreamSynchronize(c->pay()));   // the host buffers may go away
-    c->pkt_fed = true;
+    c->packets.fed = true;
     return M17HIP_OK;
 }
 
@@ -3428,35 +3586,28 @@ int m17hip_packets_fetch(m17hip_ctx* c, m17_packet_rec* recs_host, uint32_t capa
     if (!c || !count || (capacity && !recs_host)) return M17HIP_EINVAL;
     GUARD(c);
     static_assert(sizeof(PacketRec) == sizeof(m17_packet_rec) && sizeof(PacketRec) == 864, "m17_packet_rec layout");
-    if (!c->pkt_cap || !(c->have_run || c->pkt_fed)) return M17HIP_ESTATE;
-    const int ps = c->cur ^ (int)(c->sel_back & 1u);   // the packets completed by the SELECTED run (m17hip_frames_select)
-    if (c->sel_back && !c->sets[ps].valid) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c, true)) return fr;
-    if (c->sets[ps].valid)   // (the selected run's store, wherever its consumer was queued)
-        if (int fr = pay_after(c, c->sets[ps])) return fr;
+    const Packets& pk = c->packets;
+    if (!pk.on() || !(c->have_run || pk.fed)) return M17HIP_ESTATE;
+    int ps = 0;   // the packets completed by the SELECTED run (m17hip_frames_select)
+    if (int r = behind_selected(c, ps)) return r;
     uint32_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, c->pkt_count2 + ps, 4, hipMemcpyDeviceToHost, c->pay()));
+    HIPCHK(c, hipMemcpyAsync(&total, pk.count(ps), 4, hipMemcpyDeviceToHost, c->pay()));
     HIPCHK(c, hipStreamSynchronize(c->pay()));
     *count = total;
-    const uint32_t stored = std::min(total, c->pkt_cap);
+    const uint32_t stored = std::min(total, pk.room);
     std::vector<PacketRec> tmp(stored);
-    if (stored) HIPCHK(c, hipMemcpy(tmp.data(), c->pkt_recs2[ps], (size_t)stored * sizeof(PacketRec), hipMemcpyDeviceToHost));
+    if (stored) HIPCHK(c, hipMemcpy(tmp.data(), pk.store(ps), (size_t)stored * sizeof(PacketRec), hipMemcpyDeviceToHost));
     std::sort(tmp.begin(), tmp.end(), [](const PacketRec& a, const PacketRec& b) { return a.channel != b.channel ? a.channel < b.channel : a.seq < b.seq; });
     const uint32_t n = std::min(stored, capacity);
     if (n) std::memcpy(recs_host, tmp.data(), (size_t)n * sizeof(PacketRec));
-    return total > c->pkt_cap ? M17HIP_EOVERFLOW : M17HIP_OK;
+    return total > pk.room ? M17HIP_EOVERFLOW : M17HIP_OK;
 }
 
 // The store of the run the fetch family names (m17hip_frames_select), ordered behind that run's payload work wherever it was queued
 static int voice_select(m17hip_ctx* c, int& ps)
 {
-    if (!c->voice_room || !(c->have_run || c->voice_fed)) return M17HIP_ESTATE;
-    ps = c->cur ^ (int)(c->sel_back & 1u);
-    if (c->sel_back && !c->sets[ps].valid) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c, true)) return fr;
-    if (c->sets[ps].valid)
-        if (int fr = pay_after(c, c->sets[ps])) return fr;
-    return M17HIP_OK;
+    if (!c->voice.on() || !(c->have_run || c->voice.fed)) return M17HIP_ESTATE;
+    return behind_selected(c, ps);
 }
 
 int m17hip_voice_fetch(m17hip_ctx* c, uint8_t* audio_host, uint8_t* marks_host, uint32_t* counts_host, uint32_t C, uint32_t slots)
@@ -3465,12 +3616,13 @@ int m17hip_voice_fetch(m17hip_ctx* c, uint8_t* audio_host, uint8_t* marks_host, 
     GUARD(c);
     int ps = 0;
     if (int r = voice_select(c, ps)) return r;
-    if (C > c->voice_C[ps]) return M17HIP_EINVAL;   // (rows the consumer has not written)
-    const uint32_t room = c->voice_room, w = std::min(slots, room);
-    HIPCHK(c, hipMemcpyAsync(counts_host, c->voice_counts2 + (size_t)ps * c->maxC, (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
+    const Voice& v = c->voice;
+    if (C > v.rows[ps]) return M17HIP_EINVAL;   // (rows the consumer has not written)
+    const uint32_t room = v.room, w = std::min(slots, room);
+    HIPCHK(c, hipMemcpyAsync(counts_host, v.counts(ps), (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
     if (w) {   // rows cut at `slots` (slots beyond the room are not written)
-        HIPCHK(c, hipMemcpy2DAsync(audio_host, (size_t)slots * 16, c->voice_audio2[ps], (size_t)room * 16, (size_t)w * 16, C, hipMemcpyDeviceToHost, c->pay()));
-        HIPCHK(c, hipMemcpy2DAsync(marks_host, slots, c->voice_marks2[ps], room, w, C, hipMemcpyDeviceToHost, c->pay()));
+        HIPCHK(c, hipMemcpy2DAsync(audio_host, (size_t)slots * 16, v.audio(ps), (size_t)room * 16, (size_t)w * 16, C, hipMemcpyDeviceToHost, c->pay()));
+        HIPCHK(c, hipMemcpy2DAsync(marks_host, slots, v.marks(ps), room, w, C, hipMemcpyDeviceToHost, c->pay()));
     }
     HIPCHK(c, hipStreamSynchronize(c->pay()));
     bool over = false, trunc = false;
@@ -3485,8 +3637,8 @@ int m17hip_voice_device(m17hip_ctx* c, const uint8_t** audio_dev, const uint8_t*
     int ps = 0;
     if (int r = voice_select(c, ps)) return r;
     HIPCHK(c, hipStreamSynchronize(c->pay()));
-    *audio_dev = c->voice_audio2[ps]; *marks_dev = c->voice_marks2[ps]; *counts_dev = c->voice_counts2 + (size_t)ps * c->maxC;
-    *pitch_slots = c->voice_room;
+    *audio_dev = c->voice.audio(ps); *marks_dev = c->voice.marks(ps); *counts_dev = c->voice.counts(ps);
+    *pitch_slots = c->voice.room;
     return M17HIP_OK;
 }
 
@@ -3497,16 +3649,16 @@ int m17hip_calls_fetch(m17hip_ctx* c, m17_call_rec* host, uint32_t capacity, uin
     static_assert(sizeof(CallRec) == sizeof(m17_call_rec) && sizeof(CallRec) == 72, "m17_call_rec layout");
     int ps = 0;
     if (int r = voice_select(c, ps)) return r;
-    const uint32_t C = c->voice_C[ps], room = c->call_room;
+    const uint32_t C = c->voice.rows[ps], room = c->voice.call_room;
     std::vector<uint32_t> cnt(C);
-    if (C) HIPCHK(c, hipMemcpyAsync(cnt.data(), c->call_counts2 + (size_t)ps * c->maxC, (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
+    if (C) HIPCHK(c, hipMemcpyAsync(cnt.data(), c->voice.call_counts(ps), (size_t)C * 4, hipMemcpyDeviceToHost, c->pay()));
     HIPCHK(c, hipStreamSynchronize(c->pay()));
     uint64_t total = 0; uint32_t most = 0; bool over = false;
     for (uint32_t n : cnt) { total += n; most = std::max(most, std::min(n, room)); over = over || n > room; }
     *count = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFu);
     if (most && capacity) {   // the columns in use of every channel's row, then row after row: (channel, seq) order
         std::vector<CallRec> tmp((size_t)C * most);
-        HIPCHK(c, hipMemcpy2D(tmp.data(), (size_t)most * sizeof(CallRec), c->call_recs2[ps], (size_t)room * sizeof(CallRec), (size_t)most * sizeof(CallRec), C,
+        HIPCHK(c, hipMemcpy2D(tmp.data(), (size_t)most * sizeof(CallRec), c->voice.calls(ps), (size_t)room * sizeof(CallRec), (size_t)most * sizeof(CallRec), C,
                               hipMemcpyDeviceToHost));
         uint32_t written = 0;
         for (uint32_t ch = 0; ch < C && written < capacity; ++ch) {
@@ -3522,21 +3674,12 @@ int m17hip_voice_feed(m17hip_ctx* c, const m17_frame_rec* recs_host, const uint3
 {
     if (!c || !recs_host || !counts_host || C == 0 || C > c->maxC || pitch == 0) return M17HIP_EINVAL;
     GUARD(c);
-    if (c->front_queued || !c->voice_room) return M17HIP_ESTATE;
-    if (int fr = flush_payload(c)) return fr;
-    for (const auto& rs : c->sets)   // (the consumer's state goes from run to run: behind both runs, wherever their payload work was queued)
-        if (rs.valid)
-            if (int fr = pay_after(c, rs)) return fr;
-    const size_t rec_b = round_up((size_t)C * pitch * sizeof(FrameRec), 256);
-    HIPCHK(c, c->scratch.grow(rec_b + (size_t)C * 4, &c->last_hip));
-    FrameRec* drec = reinterpret_cast<FrameRec*>(c->scratch.get());
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(c->scratch + rec_b);
-    HIPCHK(c, hipMemcpyAsync(drec, recs_host, (size_t)C * pitch * sizeof(FrameRec), hipMemcpyHostToDevice, c->pay()));
-    HIPCHK(c, hipMemcpyAsync(dcnt, counts_host, (size_t)C * 4, hipMemcpyHostToDevice, c->pay()));
-    launch_voice(c, c->pay(), drec, pitch, dcnt, C, c->cur);   // (the store of the latest run's set, as m17hip_packets_feed)
-    HIPCHK(c, hipGetLastError());
+    if (c->front_queued || !c->voice.on()) return M17HIP_ESTATE;
+    FrameRec* drec; uint32_t* dcnt;
+    if (int r = stage_feed(c, recs_host, counts_host, C, pitch, drec, dcnt)) return r;
+    if (int r = c->voice.consume(c, c->pay(), drec, pitch, dcnt, C, c->cur)) return r;   // (the store of the latest run's set, as m17hip_packets_feed)
     HIPCHK(c, hipStreamSynchronize(c->pay()));   // the host buffers may go away
-    c->voice_fed = true;
+    c->voice.fed = true;
     return M17HIP_OK;
 }
 
@@ -3885,10 +4028,10 @@ int m17hip_replay_drops(m17hip_ctx* c, uint64_t* count)
 {
     if (!c || !count) return M17HIP_EINVAL;
     GUARD(c);
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(w, c->overflow, 32, hipMemcpyDeviceToHost, c->stream));
+    OvfWords ovf;
+    HIPCHK(c, ovf.read(c->overflow, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *count = (uint64_t)w[1] + w[5];   // (each record set has its own four words, and the runs of a stream alternate between the sets)
+    *count = ovf.replay_drops();
     return M17HIP_OK;
 }
 
@@ -3904,75 +4047,24 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
         c->seg_len = (uint32_t)value;
         return M17HIP_OK;
     case 6:  // BERT statistics (m17hip_bert_stats) on/off (the runs made so far keep the setting they were made with)
-        c->bert = value != 0;
+        c->bert.on = value != 0;
         return M17HIP_OK;
-    case 7: {  // packet reassembly (m17hip_packets_fetch): room for `value` completed packets per run, 0 = off
+    case 7:  // packet reassembly (m17hip_packets_fetch): room for `value` completed packets per run, 0 = off
         if (value < 0 || value > (1 << 24)) return M17HIP_EINVAL;
-        if (int fr = flush_payload(c)) return fr;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->pay()));
-        c->pkt_recs2[0].release(&c->last_hip); c->pkt_recs2[1].release(&c->last_hip); c->pkt_cap = 0; c->pkt_fed = false;
-        if (value == 0) return M17HIP_OK;
-        if (!c->pkt_state) {
-            HIPCHK(c, c->pkt_state.alloc(c->maxC));
-            HIPCHK(c, c->pkt_count2.alloc(2));
-        }
-        HIPCHK(c, c->pkt_recs2[0].alloc((size_t)value));
-        HIPCHK(c, c->pkt_recs2[1].alloc((size_t)value));
-        c->pkt_cap = (uint32_t)value;
-        hipLaunchKernelGGL(packet_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->pkt_state, c->maxC);
-        HIPCHK(c, hipMemsetAsync(c->pkt_count2, 0, 8, c->stream));
-        HIPCHK(c, hipGetLastError());
-        return M17HIP_OK;
-    }
-    case 34: {  // voice consumer (m17hip_voice_fetch, m17hip_calls_fetch): `value` voice slots per channel and run, 0 = off
+        if (int r = quiesce_payload(c, false)) return r;
+        return c->packets.configure(c, (uint32_t)value);
+    case 34:  // voice consumer (m17hip_voice_fetch, m17hip_calls_fetch): `value` voice slots per channel and run, 0 = off
         if (value < 0 || value > 65536) return M17HIP_EINVAL;
-        if (int fr = flush_payload(c)) return fr;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->pay()));
-        for (int i = 0; i < 2; ++i) {
-            c->voice_audio2[i].release(&c->last_hip); c->voice_marks2[i].release(&c->last_hip); c->call_recs2[i].release(&c->last_hip);
-            c->voice_C[i] = 0;
-        }
-        c->voice_room = 0; c->call_room = 0; c->voice_fed = false;
-        if (value == 0) return M17HIP_OK;
-        const uint32_t room = (uint32_t)value, call_room = M17HIP_CALLS_PER_CHANNEL(room);
-        if (!c->voice_state) {
-            HIPCHK(c, c->voice_state.alloc(c->maxC));
-            HIPCHK(c, c->voice_counts2.alloc((size_t)2 * c->maxC));
-            HIPCHK(c, c->call_counts2.alloc((size_t)2 * c->maxC));
-        }
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(c, c->voice_audio2[i].alloc((size_t)c->maxC * room * 16));
-            HIPCHK(c, c->voice_marks2[i].alloc((size_t)c->maxC * room));
-            HIPCHK(c, c->call_recs2[i].alloc((size_t)c->maxC * call_room));
-        }
-        hipLaunchKernelGGL(voice_reset_kernel, dim3((c->maxC + 63) / 64), dim3(64), 0, c->stream, c->voice_state, c->maxC);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemsetAsync(c->voice_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->call_counts2, 0, (size_t)2 * c->maxC * 4, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // (the payload stream, where the consumer works, may be another one)
-        c->voice_room = room; c->call_room = call_room;
-        return M17HIP_OK;
-    }
+        if (int r = quiesce_payload(c, false)) return r;
+        return c->voice.configure(c, (uint32_t)value);
     case 8:  // record slots per channel and run actually used (0 = all that were allocated): exercises M17HIP_EOVERFLOW
         if (value < 0 || value > (int64_t)c->rec_cap_alloc) return M17HIP_EINVAL;
         c->rec_cap = value ? (uint32_t)value : c->rec_cap_alloc;   // (the sets keep the layout they were written with: a finished run's records stay fetchable)
         return M17HIP_OK;
-    case 9: {  // diagnostic log: room for `value` diagnostic callbacks per channel and run, 0 = off (m17hip_diag_log_fetch)
+    case 9:  // diagnostic log: room for `value` diagnostic callbacks per channel and run, 0 = off (m17hip_diag_log_fetch)
         if (value < 0 || value > (1 << 20)) return M17HIP_EINVAL;
-        if (int fr = flush_fold(c)) return fr;
-        if (int fr = flush_payload(c)) return fr;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->pay()));
-        c->diag_log.release(&c->last_hip); c->diag_cap = 0;
-        if (value == 0) return M17HIP_OK;
-        if (!c->diag_count) HIPCHK(c, c->diag_count.alloc(c->maxC));
-        HIPCHK(c, hipMemsetAsync(c->diag_count, 0, (size_t)c->maxC * 4, c->stream));   // (on the stream the kernels that count into it run on)
-        HIPCHK(c, c->diag_log.alloc((size_t)c->maxC * (size_t)value));
-        c->diag_cap = (uint32_t)value;
-        return M17HIP_OK;
-    }
+        if (int r = quiesce_payload(c, true)) return r;
+        return c->diag.configure(c, (uint32_t)value);
     case 10:  // K3 form: 0 = one wave per 32 channels (throughput), 1 = four-wave pipeline (latency), -1 (default) = the pipeline for the runs m17hip_demod_front queues
         if (value < -1 || value > 1) return M17HIP_EINVAL;
         c->dcd_form = (int)value;
@@ -4000,9 +4092,7 @@ int m17hip_tune(m17hip_ctx* c, int key, int64_t value)
     case 15:  // payload frames of running stream / BERT transmissions decoded after the run, one lane per frame (1, default), or in K5 (0)
         c->defer_decode = value != 0;
         if (!c->defer_decode && c->defer_hist) {   // give the stores back (a run in flight may still use them: wait for it)
-            if (int fr = flush_payload(c)) return fr;
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->pay()));
+            if (int r = quiesce_payload(c, false)) return r;
             for (auto& rs_ : c->sets) rs_.defer_llr.release(&c->last_hip);
             c->defer_hist.release(&c->last_hip);
         }

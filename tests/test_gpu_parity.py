@@ -594,6 +594,49 @@ def test_packet_reassembly_rules_on_crafted_records(ctx):
     assert got.size > 5 * C and 0 < int((got["seq_errors"] > 0).sum()) < got.size
 
 
+def test_packets_feed_after_the_payload_stream_has_moved():
+    """m17hip_packets_feed works on the reassembly state the runs' own consumer leaves, so it goes behind every run's payload work wherever
+    that was queued.  Here it was queued on the main stream (an in-place run) and the payload stream has moved to the copy stream since (the first
+    staged input): one packet transmission per channel, every packet still open at the end of the run, closed by hand-made records through the
+    feed.  The packets are those of the oracle's decode_packet restatement fed the run's records and then the closing ones."""
+    import torch
+    C, T = 16, 19200
+    x = np.stack([ol.generate(ol.gen_params(seed=9100 + c, kind=(4, 4, 2)[c % 3], n_frames=(12, 20, 33, 16)[c % 4], lead_in=3072, lead_sigma=40000.0,
+                                            noise_sigma=(300.0, 900.0)[c % 2], tail_sigma=400.0, total=2 * T))[:T] for c in range(C)])
+    recs, counts, _ = ol.demod_batch(x, cap=2 * (T // 1920 + 2) + 4, threads=8)
+    rng = np.random.default_rng(77)
+    closing = np.zeros((C, 2), dtype=m17hip.FRAME_REC)   # odd channels: a numbered frame (in sequence or not) in front of the closing frame
+    n_closing = np.array([1 + (c & 1) for c in range(C)], dtype=np.uint32)
+    for c in range(C):
+        for k in range(n_closing[c]):
+            r = closing[c, k]
+            r["channel"], r["seq"], r["sample_pos"], r["frame_type"] = c, int(counts[c]) + k, T + 1920 * k, 3 + (c >> 1 & 1)
+            r["payload"][:26] = rng.integers(0, 256, 26, dtype=np.uint8)
+            last = k + 1 == n_closing[c]
+            in_seq = int(np.isin(recs[c, :counts[c]]["frame_type"], (3, 4)).sum())   # the number the run's frames lead up to (none was lost here)
+            num = in_seq if c % 4 == 1 and not last else int(rng.integers(0, 32))
+            r["payload"][25] = (0x80 if last else 0) | (num << 2) | int(rng.integers(0, 4))
+    exp = []
+    for c in range(C):
+        asm = ol.PacketAssembler()
+        assert asm.feed(recs[c, :counts[c]]["frame_type"], recs[c, :counts[c]]["payload"]) == []   # nothing closes within the run
+        exp.append(asm.feed(closing[c, :n_closing[c]]["frame_type"], closing[c, :n_closing[c]]["payload"]))
+    assert all(len(e) == 1 for e in exp) and sum(e[0]["frames"] > 4 for e in exp) >= C // 2   # ... and the run's frames are in the packets
+    pinned = torch.from_numpy(np.ascontiguousarray(x)).pin_memory()
+    c2 = m17hip.Context(C, T)   # (a context that has never staged input: its payload stream is still the main stream)
+    try:
+        c2.tune(7, 64)
+        c2.upload(x)
+        c2.run()
+        c2.upload_async(pinned.data_ptr(), C, T)   # the payload stream is the copy stream from here on
+        c2.upload_wait()
+        c2.packets_feed(closing, n_closing)
+        got = c2.packets()
+    finally:
+        c2.close()
+    _check_packets(got, exp)
+
+
 def test_full_size_properties():
     """BASELINE config 3 at full size (4096 channels x 480 000 samples, synthesized on the device), checked through properties
     that need no oracle run: BERT channels -> the PRBS9 receiver locks and counts (almost) no errors over ~240 frames; voice
