@@ -306,9 +306,12 @@ struct LlrTable {
 inline const LlrTable& llr_table() { static const LlrTable t; return t; }
 
 // ---------------------------------------------------------------------------
-// a9/a10: Kalman filters — PARITY UNPINNED (blaze, the reference's linear-algebra dependency, is absent from
-// /root/reference: `.gitmodules:1-3`, empty submodule, pinned version unknown).  Reference call sites:
-// KalmanFilter.h:18-108, ClockRecovery.h:16-111, FreqDevEstimator.h:14-54.
+// a9/a10: Kalman filters.  blaze, the reference's linear-algebra dependency, is absent (`.gitmodules:1-3`, empty submodule, pinned
+// version unknown).  Reference call sites: KalmanFilter.h:18-108, ClockRecovery.h:16-111, FreqDevEstimator.h:14-54.
+//
+// PINNED: this file's ClockRecovery, FreqDevEstimator and Kalman2 against the reference's own classes compiled over the blaze STAND-IN of
+// oracle/blaze_min (not blaze; -DBLAZE_MIN_ORDER = the switch below), value for value under all eight orders, and through them the whole
+// demodulator (tests/test_ref_demod.py).  STILL READING: that blaze itself associates and rounds the products as order 3 says.
 //
 // KalmanFilter.h:49-64 keeps `S` and `K` as `auto`, i.e. as lazy blaze expression templates, so how the products are
 // associated and where they are rounded is decided by blaze's restructuring operators, not by the source text.  The

@@ -1,10 +1,14 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.
 // Thin extern "C" shim over the REFERENCE's own headers, compiled where they lie
-// (-I$(REF)/include/m17cxx) into oracle/_ref/libm17ref.so by oracle/Makefile.  No
-// reference source is copied into this repository.  Only the operators whose
-// headers compile stand-alone are covered; KalmanFilter.h / ClockRecovery.h /
-// FreqDevEstimator.h / M17Demodulator.h need the absent third-party `blaze`
-// library and are therefore NOT buildable here (no stand-ins are written).
+// (-I$(REF)/include/m17cxx) into oracle/_ref/ by oracle/Makefile.  No reference
+// source is copied into this repository.  Two translation units come out of this file:
+//   _ref/libm17ref.so            the operators whose headers compile stand-alone (everything below the
+//                                #else), and the oracle's orchestrator over them (ref_hybrid_demod);
+//   _ref/libm17ref_kalman_o<k>.so  (-DM17REF_KALMAN -DBLAZE_MIN_ORDER=k -Ioracle/blaze_min) the reference's
+//                                ClockRecovery.h and FreqDevEstimator.h, hence KalmanFilter.h, over this
+//                                project's STAND-IN for the absent third-party `blaze` (oracle/blaze_min:
+//                                not blaze; what each order bit stands for is said there).
+// M17Demodulator.h itself is compiled over the same stand-in by oracle/ref_demod_main.cpp.
 //
 // Harness rules from SURVEY §8c/§9: <stdlib.h> before the reference headers so
 // that the unqualified abs() in SyncWord::find_peak resolves to the float
@@ -12,6 +16,63 @@
 // placement-new into zero-filled storage (Q4).
 #include <stdlib.h>
 #include <math.h>
+
+#ifdef M17REF_KALMAN
+#include "ClockRecovery.h"
+#include "FreqDevEstimator.h"
+
+#include <cstdint>
+#include <cstring>
+#include <new>
+
+using namespace mobilinkd;
+
+namespace {
+template <typename T>
+struct Zeroed {  // placement-new into zero-filled storage
+    alignas(64) unsigned char raw[sizeof(T)];
+    T* p = nullptr;
+    T& make() { std::memset(raw, 0, sizeof(raw)); p = new (raw) T(); return *p; }
+    ~Zeroed() { if (p) p->~T(); }
+};
+}  // namespace
+
+extern "C" {
+
+int ref_kalman_order(void) { return BLAZE_MIN_ORDER; }
+
+// ClockRecovery<float,10>.  Step i: `count[i]` calls of operator() (one per sample), then op[i]: 0 = reset(index[i]),
+// 1 = update(index[i]), 2 = update().  out[i][9] = sample_index(), clock_estimate(), sample_estimate_, then the filter's
+// x0, x1, P00, P01, P10, P11 (layout of m17o_kalman_trace after the first three).
+void ref_clock_trace(const uint8_t* op, const uint8_t* index, const uint32_t* count, size_t n, float* out)
+{
+    Zeroed<ClockRecovery<float, 10>> z;
+    auto& c = z.make();
+    for (size_t i = 0; i < n; ++i) {
+        for (uint32_t k = 0; k < count[i]; ++k) c(0.f);
+        if (op[i] == 0) c.reset((float)index[i]);
+        else if (op[i] == 1) c.update(index[i]);
+        else c.update();
+        float* o = out + 9 * i;
+        o[0] = (float)c.sample_index(); o[1] = c.clock_estimate(); o[2] = c.sample_estimate_;
+        o[3] = c.kf_.x[0]; o[4] = c.kf_.x[1]; o[5] = c.kf_.P(0, 0); o[6] = c.kf_.P(0, 1); o[7] = c.kf_.P(1, 0); o[8] = c.kf_.P(1, 1);
+    }
+}
+
+// FreqDevEstimator<float>: reset() where reset_before[i], then update(mn[i], mx[i]).  out[i][3] = idev(), offset(), deviation().
+void ref_dev_trace(const float* mn, const float* mx, size_t n, const uint8_t* reset_before, float* out)
+{
+    Zeroed<FreqDevEstimator<float>> z;
+    auto& d = z.make();
+    for (size_t i = 0; i < n; ++i) {
+        if (reset_before && reset_before[i]) d.reset();
+        d.update(mn[i], mx[i]);
+        out[3 * i] = d.idev(); out[3 * i + 1] = d.offset(); out[3 * i + 2] = d.deviation();
+    }
+}
+
+}  // extern "C"
+#else
 
 #include "FirFilter.h"
 #include "IirFilter.h"
@@ -440,3 +501,5 @@ size_t ref_hybrid_diag_log(const float* taps150, const int16_t* s, size_t n, int
 }
 
 }  // extern "C"
+
+#endif  // M17REF_KALMAN

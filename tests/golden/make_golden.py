@@ -9,6 +9,11 @@ code produced for them, plus the known-answer vectors held by the reference's un
   hybrid_vectors.npz  what the reference's OWN operator objects deliver under the oracle's orchestrator (oracle/ref_shim.cpp,
                     ref_hybrid_demod) for 48 scenarios of oracle_lib.random_scenario: frame records, last diagnostic callback, and a
                     checksum of each input (`make_golden.py hybrid` writes this file alone)
+  ref_demod_vectors.npz  what the reference's OWN DEMODULATOR (M17Demodulator.h compiled as it lies over the blaze stand-in of
+                    oracle/blaze_min: oracle/ref_demod_main.cpp, oracle/_ref/m17ref_demod_o<k>) delivers on the rows of
+                    ref_demod_lib.FIXTURE_CHANNELS under orders 0 and 3: every frame callback, every diagnostic callback and the last one,
+                    the generator arguments and a SHA-256 of each row (rows are regenerated, never stored), and the clock-recovery and
+                    deviation-estimator traces of oracle/_ref/libm17ref_kalman_o<k>.so (`make_golden.py ref_demod` writes this file alone)
 
 The input signals come from the repository's own synthetic generator (oracle/m17_oracle_gen.hpp).
 """
@@ -184,9 +189,39 @@ def hybrid():
     print("wrote hybrid_vectors.npz:", int(out["counts"].sum()), "records of", len(counts), "scenarios,", os.path.getsize(os.path.join(HERE, "hybrid_vectors.npz")), "bytes")
 
 
+def ref_demod():
+    """The reference's own demodulator, frozen: tests/test_ref_demod.py compares the oracle with it everywhere, tests/test_gpu_ref_demod.py the device."""
+    import ref_demod_lib as rl
+    assert rl.have_ref(), "oracle/_ref not built"
+    x, pol = rl.fixture_rows()
+    out = {"family": np.array([f for f, _ in rl.FIXTURE_CHANNELS]), "index": np.array([i for _, i in rl.FIXTURE_CHANNELS], dtype=np.int64),
+           "polarity": pol, "total": np.int64(rl.FIX_T), "sha256": rl.sha256_rows(x)}
+    for order in rl.FIXTURE_ORDERS:
+        got = rl.ref_demod_many(list(x), pol.tolist(), order)
+        assert all(lg.size for _, lg in got)
+        out[f"rec_count_o{order}"] = np.array([r.size for r, _ in got], dtype=np.int64)
+        out[f"recs_o{order}"] = np.concatenate([r for r, _ in got]).view(np.uint8).reshape(-1, 64)
+        out[f"log_count_o{order}"] = np.array([lg.size for _, lg in got], dtype=np.int64)
+        out[f"log_o{order}"] = np.concatenate([lg for _, lg in got]).view(np.uint8).reshape(-1, 64)
+        out[f"last_diag_o{order}"] = np.concatenate([lg[-1:] for _, lg in got]).view(np.uint8).reshape(-1, 64)
+        for j, s in enumerate(rl.clock_sequences()):
+            out[f"clock_o{order}_{j}"] = rl.ref_clock_trace(order, s)
+        for j, r in enumerate(rl.dev_sequences()):
+            out[f"dev_o{order}_{j}"] = rl.ref_dev_trace(order, r)
+    path = os.path.join(HERE, "ref_demod_vectors.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    print("wrote ref_demod_vectors.npz:", len(rl.FIXTURE_CHANNELS), "channels,", int(out["rec_count_o3"].sum()), "records,", int(out["log_count_o3"].sum()),
+          "diagnostic callbacks per order,", size, "bytes")
+    assert size <= os.path.getsize(os.path.join(HERE, "ref_vectors.npz")), "larger than the largest fixture there is: drop channels, not fields"
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "hybrid":
         hybrid()
+    elif len(sys.argv) > 1 and sys.argv[1] == "ref_demod":
+        ref_demod()
     else:
         main()
         hybrid()
+        ref_demod()
