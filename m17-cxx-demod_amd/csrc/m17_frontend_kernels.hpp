@@ -26,8 +26,9 @@ __device__ __forceinline__ v2f dcd_scale2(int a, int b)   // core::scale_i16 on 
 // the context's polarity table (m17hip_set_channel_polarity: pol[c] = 0 / 1, XOR the call's M17HIP_FLAG_INVERT).  The mixed forms negate in int16, where
 // the reference does (-(-32768) wraps to -32768), under a mask m = 0 (plain) / -1 (inverted): (s ^ m) - m, two samples per instruction on the packed
 // word the loads deliver; the scaling behind it is the plain form's, so every value is core::scale_i16's (tests/test_scale_newton_exhaustive.py).
-// A uniform and a mixed kernel are ONE text (the *_body.inc files, included into both), so that the uniform instantiations compile to what they were
-// before the mixed ones existed.
+// A uniform and a mixed kernel are ONE text, a kernel template over <XT, INVERT, MIXED> with `pol` always in its argument list (the uniform forms are
+// handed nullptr and never read it): what MIXED adds stands under `if constexpr (MIXED)`, so the uniform instantiations compile to what they were before
+// the mixed ones existed.
 __device__ __forceinline__ int pol_mask(const uint32_t* __restrict__ pol, uint32_t c, uint32_t flip) { return -(int)((pol[c] ^ flip) & 1u); }
 __device__ __forceinline__ int pol_word(int w, int m)   // a word of two int16 samples
 {
@@ -248,44 +249,184 @@ __device__ __forceinline__ v2f fs_tap_pair_times(v2f taps, v2f wpair)
     return r;
 }
 
-template <bool INVERT>
-__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_kernel(const int16_t* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
+// XT: the sample type of the input slab — int16_t, or float (a float stream, m17hip_upload_f32: samples in the reference's units, 32 bytes per eight-sample
+// chunk, staged as they are, negated by a sign-bit XOR — under the item's mask in the mixed form; no dcd_scale2.  The input of an item in flight is 24
+// registers instead of 12; still four workgroups per CU without scratch, NOTES 2026-10-18).
+// INVERT / MIXED: the polarity of the launch (above).  pol, flip: the polarity table and bit 0 of the call's flags; read by the MIXED forms only, the
+// uniform ones are handed nullptr, 0.
+template <typename XT, bool INVERT, bool MIXED>
+__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_kernel(const XT* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
                                                                        uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
-                                                                       const uint32_t* __restrict__ first_needed)
+                                                                       const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
 {
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr; const uint32_t flip = 0u;
-    typedef int16_t XT;
-#include "m17_fir_skew_body.inc"
-}
-// the same with the polarity per channel: pol[c] XOR flip (bit 0)
-__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
-                                                                             uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
-                                                                             const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef int16_t XT;
-#include "m17_fir_skew_body.inc"
-}
-// The float forms (a float stream, m17hip_upload_f32: samples in the reference's units): the same text over float rows.  The input of an item in flight is
-// 24 registers instead of 12; still four workgroups per CU without scratch (NOTES 2026-10-18).
-template <bool INVERT>
-__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_f32_kernel(const float* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
-                                                                           uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
-                                                                           const uint32_t* __restrict__ first_needed)
-{
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr; const uint32_t flip = 0u;
-    typedef float XT;
-#include "m17_fir_skew_body.inc"
-}
-__global__ __launch_bounds__(FS_THREADS, 4) void fir_rrc150_skew_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, float* __restrict__ y, size_t ypitch,
-                                                                                 uint32_t T, const float* __restrict__ tab, uint32_t tiles, uint32_t items,
-                                                                                 const uint32_t* __restrict__ first_needed, const uint32_t* __restrict__ pol, uint32_t flip)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef float XT;
-#include "m17_fir_skew_body.inc"
+    // first_needed (may be null): per channel, the first sample of this slab the carrier can be on for (gate_forecast_kernel): tiles that end
+    // before it are skipped
+    __shared__ __attribute__((aligned(16))) float win[FS_LDS_FLOATS];
+    const int tid = threadIdx.x;
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    constexpr int NCH = (FS_WIN + 7) / 8;             // 531 chunks of eight samples
+    constexpr int CPT = (NCH + FS_THREADS - 1) / FS_THREADS;   // 3 per thread (the third for 19 threads only)
+    constexpr bool F32 = std::is_same<XT, float>::value;
+    // float rows: the two whole chunks of a lane are 32 bytes each; the last 152 samples of the window (chunks 512 .. 530, which the int16 form gives
+    // to nineteen lanes as a third chunk) go one sample per lane — 17 registers in flight instead of 24, which the 128 of four workgroups per CU do not hold
+    constexpr int FS_LAST = FS_WIN - 16 * FS_THREADS; // 152
+    static_assert(FS_LAST > 0 && FS_LAST <= FS_THREADS && CPT == 3, "the float form's split of the window");
+    v4i pre[F32 ? 4 : CPT];
+    int pre_last = 0;
+    int m = 0;                                        // MIXED: the polarity mask of the item being staged
+    // the int16 input of an item: chunk k <-> window samples 8k .. 8k + 7 <-> times t0 - 152 + 8k ...; beyond the slab's end: zero
+    auto fetch = [&](uint32_t item) {
+        const uint32_t c = item / tiles, tile = item - c * tiles;
+        const XT* xr = x + (size_t)c * xpitch + XPRE;
+        const int64_t w0 = (int64_t)tile * FS_TILE - FS_WOFF;
+#pragma unroll
+        for (int q = 0; q < CPT; ++q) {
+            const int k = tid + q * FS_THREADS;
+            const int64_t t = w0 + 8 * k;
+            v4i v = {0, 0, 0, 0};
+            if constexpr (F32) {
+                if (q < 2) {                          // (k < NCH for both)
+                    v4i v2 = {0, 0, 0, 0};
+                    if (t + 8 <= (int64_t)T) {
+                        v = *reinterpret_cast<const v4i*>(xr + t);
+                        v2 = *reinterpret_cast<const v4i*>(xr + t + 4);
+                    } else {                          // the slab ends inside this chunk (once per channel at most): sample by sample
+                        uint32_t w[8];
+#pragma unroll
+                        for (int h = 0; h < 8; ++h) w[h] = t + h < (int64_t)T ? __float_as_uint(xr[t + h]) : 0u;
+                        v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+                        v2 = v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+                    }
+                    pre[2 * q] = v; pre[2 * q + 1] = v2;
+                } else {
+                    const int64_t tl = w0 + 16 * FS_THREADS + tid;
+                    pre_last = (tid < FS_LAST && tl < (int64_t)T) ? (int)__float_as_uint(xr[tl]) : 0;
+                }
+            } else {
+            if (k < NCH) {
+                if (t + 8 <= (int64_t)T) v = *reinterpret_cast<const v4i*>(xr + t);
+                else {                                // the slab ends inside this chunk (once per channel at most): sample by sample
+                    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+                    for (int h = 0; h < 8; ++h)
+                        if (t + h < (int64_t)T) w[h >> 1] |= (uint32_t)(uint16_t)xr[t + h] << (16 * (h & 1));
+                    v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+                }
+            }
+            pre[q] = v;
+            }
+        }
+    };
+    auto stage = [&] {
+#pragma unroll
+        for (int q = 0; q < CPT; ++q) {
+            const int k = tid + q * FS_THREADS;
+            int sm = INVERT ? (int)0x80000000u : 0;   // (float rows) the sign bit where the sample is negated
+            if constexpr (F32 && MIXED) sm = m & (int)0x80000000u;
+            if constexpr (F32) if (q == 2) {          // the window's last 152 samples, one per lane
+                const int j = 16 * FS_THREADS + tid;
+                if (tid < FS_LAST) win[FS_PADF + j + 2 * (j >> 4)] = __int_as_float(pre_last ^ sm);
+                continue;
+            }
+            if (k < NCH) {
+                float* dst = win + FS_PADF + 8 * k + 2 * (k >> 1);   // sample j = 8k at word j + 2 (j >> 4)
+                if constexpr (F32) {
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) {
+                        const v4i r = pre[2 * q + (h >> 1)];
+                        const int a = ((h & 1) ? r[2] : r[0]) ^ sm, b = ((h & 1) ? r[3] : r[1]) ^ sm;
+                        *reinterpret_cast<v2f*>(dst + 2 * h) = v2f{__int_as_float(a), __int_as_float(b)};
+                    }
+                } else
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    int w = pre[q][h];
+                    if constexpr (MIXED) w = pol_word(w, m);
+                    const v2f f = dcd_scale2<INVERT>((int)(int16_t)(w & 0xFFFF), w >> 16);
+                    *reinterpret_cast<v2f*>(dst + 2 * h) = f;
+                }
+            }
+        }
+    };
+    auto next_item = [&](uint32_t it) {               // the first item from `it` on (stride = the grid) that is not skipped
+        if (first_needed) {
+            while (it < items) {
+                const uint32_t c = it / tiles, tile = it - c * tiles;
+                if ((uint64_t)(tile + 1u) * FS_TILE > (uint64_t)first_needed[c]) break;
+                it += gridDim.x;
+            }
+        }
+        return it;
+    };
+    uint32_t item = next_item(blockIdx.x);
+    if (item < items) fetch(item);
+    const float* lbase = win + FS_PADF + 18 * tid;    // lane-relative element e at lbase[fs_off(e)]
+    while (item < items) {
+        const uint32_t c = item / tiles, tile = item - c * tiles;
+        const uint32_t following = next_item(item + gridDim.x);
+        // MIXED: consecutive items of a workgroup may differ in polarity.  The window is staged under the polarity of the item it is staged FOR — this
+        // one, about to be computed; what goes in flight in `pre` during its tap loop is raw int16 and belongs to the item after.
+        if constexpr (MIXED) m = pol_mask(pol, c, flip);
+        stage();
+        dp_handover();                                // (LDS only: no wait for the stores of the item before)
+        if (following < items) fetch(following);      // in flight during the tap loop
+        v2f acc[8], ring[16];
+        v2f late = {0.0f, 0.0f};                      // pair 7's product of the step before (added one step late: +0 first, harmless)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] = v2f{0.0f, 0.0f};
+        // the ring before step 0: the pairs that positions in front of the entry point would have loaded (elements 142 .. 167)
+        static_for<0, 13>([&](auto kc) {
+            constexpr int e = 142 + 2 * decltype(kc)::value;
+            ring[(e & 31) >> 1] = *reinterpret_cast<const v2f*>(lbase + fs_off(e));
+        });
+        const float* lb = lbase + 36;                 // body b reads from lbase - 36 b: b = -1 first
+#pragma unroll 1
+        for (int bi = 0; bi < FS_NBODY; ++bi) {
+            const float* tb = tab + bi * FS_TAB;      // wave-uniform: scalar loads
+            auto half = [&](auto lo_c, auto hi_c) {
+                static_for<decltype(lo_c)::value, decltype(hi_c)::value>([&](auto pc) {
+                    constexpr int p = decltype(pc)::value;
+                    // step s = 32 b + 22 + p; pair q reads element e = 153 + 2q - s = 131 - 32 b + 2q - p: slot (131 + 2q - p) mod 32
+                    if constexpr ((p & 1) == 0) {     // the pair of elements first needed twelve steps from now
+                        constexpr int e = 118 - p;    // (minus 32 b: folded into lb)
+                        ring[(e & 31) >> 1] = *reinterpret_cast<const v2f*>(lb + fs_off(e));
+                    }
+                    const v2f tp = (p & 1) ? *reinterpret_cast<const v2f*>(tb + 32 + p - 1) : *reinterpret_cast<const v2f*>(tb + p);
+                    v2f pr[8];                        // the eight products first, then the eight additions: no dependent neighbours
+                    static_for<0, 8>([&](auto qc) {
+                        constexpr int q = decltype(qc)::value;
+                        constexpr int slot = (131 + 2 * q - p) & 31;
+                        pr[q] = fs_tap_pair_times<slot & 1>(tp, ring[slot >> 1]);
+                    });
+                    // (the compiler counts an asm statement as no wait state at all and pads a reader of ANY asm result that follows a run of
+                    //  them with an s_nop: pair 7's addition of the step before goes first — its product is eight real instructions old)
+                    acc[7] = acc[7] + late;
+#pragma unroll
+                    for (int q = 0; q < 7; ++q) acc[q] = acc[q] + pr[q];
+                    late = pr[7];
+                });
+            };
+            if (bi > 0) half(std::integral_constant<int, 0>{}, std::integral_constant<int, FS_ENTRY>{});
+            half(std::integral_constant<int, FS_ENTRY>{}, std::integral_constant<int, FS_BODY>{});
+            lb -= 36;
+        }
+        acc[7] = acc[7] + late;
+        // outputs 16 tid .. 16 tid + 15 of the tile, from the registers
+        const uint32_t t = tile * FS_TILE + 16u * (uint32_t)tid;
+        float* yo = y + (size_t)c * ypitch + YPRE + t;
+        if (t + 16 <= T) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(yo + 4 * g) = make_float4(acc[2 * g].x, acc[2 * g].y, acc[2 * g + 1].x, acc[2 * g + 1].y);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (t + 2 * q < T) yo[2 * q] = acc[q].x;
+                if (t + 2 * q + 1 < T) yo[2 * q + 1] = acc[q].y;
+            }
+        }
+        dp_handover();                                // every wave is through with the window before the next item is staged
+        item = following;
+    }
 }
 
 // =====================================================================================================
@@ -505,43 +646,148 @@ __device__ __forceinline__ void dcd_step(DcdLane& s, float delta)
 // 4096-channel launch take a wave slot on every SIMD of 32 CUs instead of one SIMD on each of 128 CUs — K5 (whose workgroups
 // need a slot on all four SIMDs of a CU) then loses 32 workgroup slots to K3 instead of 128, K1 likewise.
 constexpr int DCD_WPB = 4;
-template <bool INVERT>
-__global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+// XT: the sample type of the input slab — int16_t, or float (a float stream: nothing is scaled, negation is a sign-bit XOR, under the lane's mask in the
+// mixed form; the recurrence is the same).  INVERT / MIXED: the polarity of the launch; MIXED: per channel (one channel per lane pair: a per-lane mask),
+// pol[c] XOR bit 0 of flags.  The uniform forms are handed pol = nullptr and never read it.
+template <typename XT, bool INVERT, bool MIXED>
+__global__ __launch_bounds__(64 * DCD_WPB) void dcd_kernel(const XT* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
                                                  float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                 uint64_t pos0, DcdCoef k, uint32_t flags)
+                                                 uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
 {
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr;
-    typedef int16_t XT;
-#include "m17_dcd_body.inc"
-}
-// the same with the polarity per channel (one channel per lane pair: a per-lane mask): pol[c] XOR bit 0 of flags
-__global__ __launch_bounds__(64 * DCD_WPB) void dcd_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                       float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                       uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef int16_t XT;
-#include "m17_dcd_body.inc"
-}
-// the float forms (a float stream): the same text over float rows — nothing is scaled, the recurrence is the same
-template <bool INVERT>
-__global__ __launch_bounds__(64 * DCD_WPB) void dcd_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                     float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                     uint64_t pos0, DcdCoef k, uint32_t flags)
-{
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr;
-    typedef float XT;
-#include "m17_dcd_body.inc"
-}
-__global__ __launch_bounds__(64 * DCD_WPB) void dcd_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                           float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                           uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef float XT;
-#include "m17_dcd_body.inc"
+    constexpr bool F32 = std::is_same<XT, float>::value;
+    __shared__ __attribute__((aligned(16))) float dl_all[DCD_WPB][DCD_CPW][DCD_PITCH];
+    float (*dl)[DCD_PITCH] = dl_all[threadIdx.x >> 6];
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 1, bin = lane & 1;
+    uint32_t c = (blockIdx.x * DCD_WPB + (threadIdx.x >> 6)) * DCD_CPW + g;
+    const bool live = c < C;   // lanes beyond the last channel shadow it and never store
+    if (!live) c = C - 1;
+    const XT* xr = x + (size_t)c * xpitch + XPRE;
+    DcdState* st = state + c;
+    // MIXED: the channels' polarities as a LANE MASK in a scalar pair; the per-lane mask (0 / -1) is formed from it where samples are converted — a
+    // register kept across the recurrence cost the kernel its seventh wave per SIMD (74 VGPRs against 72)
+    uint64_t inv_lanes = 0;
+    if constexpr (MIXED) inv_lanes = __ballot(pol_mask(pol, c, flags) != 0);
+    auto lane_mask = [&]() -> int {
+        uint64_t il = inv_lanes;
+        asm volatile("" : "+s"(il));   // (formed anew at every use: not hoisted out of the block loop)
+        return __builtin_amdgcn_inverse_ballot_w64(il) ? -1 : 0;
+    };
+    DcdLane s;
+    s.X = v2f{st->xr[bin], st->xi[bin]};
+    s.cc = bin ? v2f{k.c1r, k.c1i} : v2f{k.c0r, k.c0i};
+    s.cs = v2f{-s.cc.y, s.cc.x};
+    s.a01 = v2f{st->acc[0][bin], st->acc[1][bin]};
+    s.a23 = v2f{st->acc[2][bin], st->acc[3][bin]};
+    s.a45 = v2f{st->acc[4][bin], st->acc[5][bin]};
+    float* tab = table + (size_t)c * ticks_cap * 12 + bin * 6;
+    const float* mydl = dl[g];
+    uint32_t phase = (uint32_t)(pos0 % TICK);  // position inside the current tick (wave-uniform)
+    uint64_t tick = pos0 / TICK;
+    uint32_t row = 0;
+    auto lds_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+    };
+    auto tick_begin = [&] {  // the sum that restarts with this tick
+        const uint32_t j = (uint32_t)(tick % 5);
+        if (j == 0) s.a01.x = 0.f;
+        if (j == 1) s.a01.y = 0.f;
+        if (j == 2) s.a23.x = 0.f;
+        if (j == 3) s.a23.y = 0.f;
+        if (j == 4) s.a45.x = 0.f;
+    };
+    auto tick_end = [&] {
+        if (live) {
+            float* o = tab + (size_t)row * 12;
+            *reinterpret_cast<float2*>(o) = make_float2(s.a01.x, s.a01.y);
+            *reinterpret_cast<float2*>(o + 2) = make_float2(s.a23.x, s.a23.y);
+            *reinterpret_cast<float2*>(o + 4) = make_float2(s.a45.x, s.a45.y);
+        }
+        phase = 0; ++tick; ++row;
+    };
+    auto one_sample = [&](uint32_t t) {  // generic path: head / tail of a run; x[n] and x[n-120] are one packed pair
+        if (phase == 0) tick_begin();
+        if constexpr (F32) {
+            int sm = INVERT ? (int)0x80000000u : 0;
+            if constexpr (MIXED) sm = lane_mask() & (int)0x80000000u;
+            const float fn = __int_as_float(__float_as_int(xr[t]) ^ sm), fd = __int_as_float(__float_as_int(xr[(int64_t)t - 120]) ^ sm);
+            dcd_step(s, fn - fd);
+        } else {
+        int xn = (int)xr[t], xd = (int)xr[(int64_t)t - 120];
+        if constexpr (MIXED) { const int m = lane_mask(); xn = pol_i16(xn, m); xd = pol_i16(xd, m); }
+        const v2f f = dcd_scale2<INVERT>(xn, xd);
+        dcd_step(s, f.x - f.y);
+        }
+        if (++phase == TICK) tick_end();
+    };
+
+    uint32_t t = 0;
+    while (t < T && (phase % DCD_BLK) != 0) { one_sample(t); ++t; }   // head: up to a block boundary of the tick
+    // whole blocks: lane (g, bin) converts samples [HALF bin, HALF bin + HALF) of its channel's block
+    if (t + DCD_BLK <= T) {
+        constexpr int HALF = DCD_BLK / 2, NQ = HALF / 8;
+        constexpr int NV = F32 ? 2 * NQ : NQ;   // 16-byte registers per half block
+        int4 pa[NV], pb[NV];
+        auto issue = [&](uint32_t t0) {
+            constexpr int SPV = F32 ? 4 : 8;    // samples per 16-byte register
+#pragma unroll
+            for (int q = 0; q < NV; ++q) {
+                const XT* p = xr + (size_t)t0 + HALF * bin + SPV * q;
+                pa[q] = *reinterpret_cast<const int4*>(p);
+                pb[q] = *reinterpret_cast<const int4*>(p - 120);
+            }
+        };
+        auto lo = [](int w) { return (int)(int16_t)(w & 0xFFFF); };
+        auto hi = [](int w) { return w >> 16; };
+        issue(t);
+        for (; t + DCD_BLK <= T; t += DCD_BLK) {
+            float* wrow = dl[g] + HALF * bin;
+            int m = 0;
+            if constexpr (MIXED) m = lane_mask();
+            if constexpr (F32) {
+                const int sm = MIXED ? (m & (int)0x80000000u) : (INVERT ? (int)0x80000000u : 0);
+                auto neg = [&](int w) { return __int_as_float(w ^ sm); };
+#pragma unroll
+                for (int q = 0; q < NV; ++q) {
+                    const int4 a = pa[q], d = pb[q];
+                    *reinterpret_cast<float4*>(wrow + 4 * q) = make_float4(neg(a.x) - neg(d.x), neg(a.y) - neg(d.y), neg(a.z) - neg(d.z), neg(a.w) - neg(d.w));
+                }
+            } else
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                int4 a = pa[q], d = pb[q];
+                if constexpr (MIXED) { a = pol_word4(a, m); d = pol_word4(d, m); }
+                const v2f u0 = dcd_scale2<INVERT>(lo(a.x), hi(a.x)) - dcd_scale2<INVERT>(lo(d.x), hi(d.x));
+                const v2f u1 = dcd_scale2<INVERT>(lo(a.y), hi(a.y)) - dcd_scale2<INVERT>(lo(d.y), hi(d.y));
+                const v2f u2 = dcd_scale2<INVERT>(lo(a.z), hi(a.z)) - dcd_scale2<INVERT>(lo(d.z), hi(d.z));
+                const v2f u3 = dcd_scale2<INVERT>(lo(a.w), hi(a.w)) - dcd_scale2<INVERT>(lo(d.w), hi(d.w));
+                *reinterpret_cast<float4*>(wrow + 8 * q) = make_float4(u0.x, u0.y, u1.x, u1.y);
+                *reinterpret_cast<float4*>(wrow + 8 * q + 4) = make_float4(u2.x, u2.y, u3.x, u3.y);
+            }
+            lds_sync();
+            if (t + 2 * DCD_BLK <= T) issue(t + DCD_BLK);   // in flight while the recurrence below runs
+            if (phase == 0) tick_begin();
+            float d[DCD_BLK];
+#pragma unroll
+            for (int u = 0; u < DCD_BLK / 4; ++u) {
+                const float4 v = *reinterpret_cast<const float4*>(mydl + 4 * u);
+                d[4 * u] = v.x; d[4 * u + 1] = v.y; d[4 * u + 2] = v.z; d[4 * u + 3] = v.w;
+            }
+#pragma unroll
+            for (int u = 0; u < DCD_BLK; ++u) dcd_step(s, d[u]);
+            phase += DCD_BLK;
+            if (phase == TICK) tick_end();
+            lds_sync();
+        }
+    }
+    for (; t < T; ++t) one_sample(t);  // tail
+    if (live) {
+        st->xr[bin] = s.X.x; st->xi[bin] = s.X.y;
+        st->acc[0][bin] = s.a01.x; st->acc[1][bin] = s.a01.y; st->acc[2][bin] = s.a23.x;
+        st->acc[3][bin] = s.a23.y; st->acc[4][bin] = s.a45.x; st->acc[5][bin] = s.a45.y;
+    }
 }
 
 
@@ -571,42 +817,171 @@ constexpr int DP_PF = 3;                 // blocks of input the producer keeps i
 
 // preconditions (the host launches dcd_kernel otherwise): T and pos0 are multiples of DP_BLK, T >= 4 blocks, so every block
 // is whole and tick boundaries (192 = 6 x 32 samples) are block boundaries
-template <bool INVERT>
-__global__ __launch_bounds__(256) void dcd_pipe_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
+// XT, INVERT, MIXED, pol: as dcd_kernel has them (MIXED: the producer's per-lane mask is its channel's entry of pol XOR bit 0 of flags)
+template <typename XT, bool INVERT, bool MIXED>
+__global__ __launch_bounds__(256) void dcd_pipe_kernel(const XT* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
                                                        float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                       uint64_t pos0, DcdCoef k, uint32_t flags)
+                                                       uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
 {
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr;
-    typedef int16_t XT;
-#include "m17_dcd_pipe_body.inc"
-}
-__global__ __launch_bounds__(256) void dcd_pipe_mixed_kernel(const int16_t* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                             float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                             uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef int16_t XT;
-#include "m17_dcd_pipe_body.inc"
-}
-// the float forms (a float stream)
-template <bool INVERT>
-__global__ __launch_bounds__(256) void dcd_pipe_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                           float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                           uint64_t pos0, DcdCoef k, uint32_t flags)
-{
-    constexpr bool MIXED = false;
-    const uint32_t* pol = nullptr;
-    typedef float XT;
-#include "m17_dcd_pipe_body.inc"
-}
-__global__ __launch_bounds__(256) void dcd_pipe_mixed_f32_kernel(const float* __restrict__ x, size_t xpitch, DcdState* __restrict__ state,
-                                                                 float* __restrict__ table, uint32_t ticks_cap, uint32_t C, uint32_t T,
-                                                                 uint64_t pos0, DcdCoef k, uint32_t flags, const uint32_t* __restrict__ pol)
-{
-    constexpr bool INVERT = false, MIXED = true;
-    typedef float XT;
-#include "m17_dcd_pipe_body.inc"
+    constexpr bool F32 = std::is_same<XT, float>::value;
+    __shared__ __attribute__((aligned(16))) float dbuf[2][DP_CPB][DP_DPITCH];
+    __shared__ __attribute__((aligned(16))) float4 xb[2][DP_BLK / 2][64];
+    const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 1, bin = lane & 1;
+    uint32_t c = blockIdx.x * DP_CPB + g;
+    const bool live = c < C;   // lanes beyond the last channel shadow it and never store
+    if (!live) c = C - 1;
+    const XT* xr = x + (size_t)c * xpitch + XPRE;
+    DcdState* st = state + c;
+    const uint32_t NB = T / DP_BLK;       // blocks
+    // every role runs NI hand-overs: NB + 2 for pipeline fill and drain, rounded up to a multiple of DP_PF so that the
+    // producer's unrolled loop has no early exit (its registers stay in fixed slots and its waits stay partial)
+    const uint32_t NI = (NB + 2u + DP_PF - 1u) / DP_PF * DP_PF;
+
+    if (role == 0) {
+        // ---- P: scaling and delta.  A block lasts ~0.5 us, an HBM round trip twice that: the loads of block b are issued DP_PF
+        // blocks ahead (slot = b % DP_PF is a compile-time constant: the loop is unrolled DP_PF times and every body issues the
+        // same loads — past the end the last block again — so the wait for a slot leaves the other slots in flight).
+        int m = 0;             // MIXED: this lane's channel's polarity mask
+        if constexpr (MIXED) m = pol_mask(pol, c, flags);
+        constexpr int NV = F32 ? 4 : 2, SPV = F32 ? 4 : 8;   // 16-byte registers per sixteen samples; samples per register
+        int4 pa[DP_PF][NV], pb[DP_PF][NV];
+        auto issue = [&](uint32_t b, int slot) {   // lane (g, bin) converts samples [16 bin, 16 bin + 16) of its channel's block
+            const XT* p = xr + (size_t)min(b, NB - 1u) * DP_BLK + 16 * bin;
+#pragma unroll
+            for (int q = 0; q < NV; ++q) {
+                pa[slot][q] = *reinterpret_cast<const int4*>(p + SPV * q);
+                pb[slot][q] = *reinterpret_cast<const int4*>(p + SPV * q - 120);
+            }
+        };
+#pragma unroll
+        for (int j = 0; j < DP_PF; ++j) issue((uint32_t)j, j);
+        auto lo = [](int w) { return (int)(int16_t)(w & 0xFFFF); };
+        auto hi = [](int w) { return w >> 16; };
+        for (uint32_t i0 = 0; i0 < NI; i0 += DP_PF) {
+#pragma unroll
+            for (int slot = 0; slot < DP_PF; ++slot) {
+                const uint32_t i = i0 + (uint32_t)slot;
+                {
+                    float4 o[4];
+                    if constexpr (F32) {
+                        const int sm = MIXED ? (m & (int)0x80000000u) : (INVERT ? (int)0x80000000u : 0);
+                        auto neg = [&](int w) { return __int_as_float(w ^ sm); };
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int4 a = pa[slot][q], d = pb[slot][q];
+                            o[q] = make_float4(neg(a.x) - neg(d.x), neg(a.y) - neg(d.y), neg(a.z) - neg(d.z), neg(a.w) - neg(d.w));
+                        }
+                    } else
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        int4 a = pa[slot][q], d = pb[slot][q];
+                        if constexpr (MIXED) { a = pol_word4(a, m); d = pol_word4(d, m); }
+                        const v2f u0 = dcd_scale2<INVERT>(lo(a.x), hi(a.x)) - dcd_scale2<INVERT>(lo(d.x), hi(d.x));
+                        const v2f u1 = dcd_scale2<INVERT>(lo(a.y), hi(a.y)) - dcd_scale2<INVERT>(lo(d.y), hi(d.y));
+                        const v2f u2 = dcd_scale2<INVERT>(lo(a.z), hi(a.z)) - dcd_scale2<INVERT>(lo(d.z), hi(d.z));
+                        const v2f u3 = dcd_scale2<INVERT>(lo(a.w), hi(a.w)) - dcd_scale2<INVERT>(lo(d.w), hi(d.w));
+                        o[2 * q] = make_float4(u0.x, u0.y, u1.x, u1.y);
+                        o[2 * q + 1] = make_float4(u2.x, u2.y, u3.x, u3.y);
+                    }
+                    issue(i + DP_PF, slot);   // this slot's registers are free again: block i + DP_PF goes in flight
+                    if (i < NB && !(flags & 16u)) {
+                        float* wrow = &dbuf[i & 1u][g][16 * bin];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(wrow + 4 * q) = o[q];
+                    }
+                    dp_handover();
+                }
+            }
+        }
+    } else if (role == 1) {
+        // ---- R: the recurrence and nothing else
+        v2f X = v2f{st->xr[bin], st->xi[bin]};
+        const v2f cc = bin ? v2f{k.c1r, k.c1i} : v2f{k.c0r, k.c0i};
+        const v2f cs = v2f{-cc.y, cc.x};
+        auto step = [&](float delta) {
+            const float a = X.x + delta;
+            const v2f m1 = v2f{a, a} * cc;          // (ac, ad)
+            const v2f m2 = v2f{X.y, X.y} * cs;      // (-bd, bc)
+            X = m1 + m2;                            // (ac - bd, ad + bc)
+        };
+        for (uint32_t i = 0; i < NI; ++i) {
+            if (i >= 1u && i <= NB && !(flags & 32u)) {
+                const uint32_t b = i - 1u;
+                const float* drow = &dbuf[b & 1u][g][0];
+                float4* out = &xb[b & 1u][0][lane];
+                float d[DP_BLK];
+#pragma unroll
+                for (int u = 0; u < DP_BLK / 4; ++u) {
+                    const float4 v = *reinterpret_cast<const float4*>(drow + 4 * u);
+                    d[4 * u] = v.x; d[4 * u + 1] = v.y; d[4 * u + 2] = v.z; d[4 * u + 3] = v.w;
+                }
+#pragma unroll
+                for (int u = 0; u < DP_BLK; u += 2) {
+                    step(d[u]); const v2f x0 = X;
+                    step(d[u + 1]);
+                    out[(u / 2) * 64] = make_float4(x0.x, x0.y, X.x, X.y);
+                }
+            }
+            dp_handover();
+        }
+        if (live) { st->xr[bin] = X.x; st->xi[bin] = X.y; }
+    } else {
+        // ---- A0 / A1: norms and running sums; A0 (role 2) owns the sums restarted at ticks = 0..3 (mod 5), A1 the one restarted
+        // at ticks = 4 (mod 5) and the one that runs from the stream start
+        const bool a0 = role == 2;
+        v2f s01 = a0 ? v2f{st->acc[0][bin], st->acc[1][bin]} : v2f{st->acc[4][bin], st->acc[5][bin]};
+        v2f s23 = a0 ? v2f{st->acc[2][bin], st->acc[3][bin]} : v2f{0.f, 0.f};
+        uint32_t phase = (uint32_t)(pos0 % TICK);
+        uint64_t tick = pos0 / TICK;
+        uint32_t row = 0;
+        float* tab = table + (size_t)c * ticks_cap * 12 + bin * 6;
+        const bool skip = flags & (a0 ? 64u : 128u);
+        for (uint32_t i = 0; i < NI; ++i) {
+            if (i >= 2u && i < NB + 2u && !skip) {
+                const uint32_t b = i - 2u;
+                const float4* in = &xb[b & 1u][0][lane];
+                if (phase == 0) {   // the sum that restarts with this tick
+                    const uint32_t j = (uint32_t)(tick % 5);
+                    if (a0) { if (j == 0) s01.x = 0.f; if (j == 1) s01.y = 0.f; if (j == 2) s23.x = 0.f; if (j == 3) s23.y = 0.f; }
+                    else if (j == 4) s01.x = 0.f;
+                }
+                auto acc = [&](float re, float im) {
+                    const v2f xx = {re, im};
+                    const v2f p = xx * xx;
+                    const float nrm = p.x + p.y;
+                    const v2f nn = {nrm, nrm};
+                    s01 = s01 + nn;
+                    if (a0) s23 = s23 + nn;
+                };
+#pragma unroll
+                for (int u = 0; u < DP_BLK / 2; ++u) {
+                    const float4 v = in[u * 64];
+                    acc(v.x, v.y);
+                    acc(v.z, v.w);
+                }
+                phase += DP_BLK;
+                if (phase == TICK) {
+                    if (live) {
+                        float* o = tab + (size_t)row * 12;
+                        if (a0) {
+                            *reinterpret_cast<float2*>(o) = make_float2(s01.x, s01.y);
+                            *reinterpret_cast<float2*>(o + 2) = make_float2(s23.x, s23.y);
+                        } else {
+                            *reinterpret_cast<float2*>(o + 4) = make_float2(s01.x, s01.y);
+                        }
+                    }
+                    phase = 0; ++tick; ++row;
+                }
+            }
+            dp_handover();
+        }
+        if (live) {
+            if (a0) { st->acc[0][bin] = s01.x; st->acc[1][bin] = s01.y; st->acc[2][bin] = s23.x; st->acc[3][bin] = s23.y; }
+            else { st->acc[4][bin] = s01.x; st->acc[5][bin] = s01.y; }
+        }
+    }
 }
 
 

@@ -44,7 +44,7 @@ struct GateExport {
 };
 
 struct GateParams {
-    const int16_t* x;
+    const void* x;            // the input rows: int16_t, or float for a float stream — the XT of the kernel the block is launched with
     size_t xpitch;
     const float* y;           // K1 output, read-only here
     size_t ypitch;
@@ -65,7 +65,7 @@ struct GateParams {
     uint32_t nblk;            // workgroups of the replay itself; the ones behind them fold deferred EVM operations (m17_state.hpp, evm_fold_pass)
     EvParams ev;
     const uint32_t* pol;      // optional [C]: the channels' polarity entries, 0 / 1 (m17hip_set_channel_polarity), XOR flags bit 0
-    // a float stream (limit_track_f32_kernel only; nullptr for int16): x names float rows, and the patch window's snapshots are floats
+    // a float stream (limit_track_kernel<float> only; nullptr for int16): x names float rows, and the patch window's snapshots are floats
     const float* hist_f;      // [C][HISTF_PITCH] SeqState::hist's twin
     const float* bnd_hist_f;  // [C][HISTF_PITCH] the twin of bnd's Boundary::hist
 };
@@ -259,7 +259,7 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
                 const bool eir = __shfl((int)end_in_run, src);
                 const int32_t et = __shfl(end_t, src);
                 const bool inv_cc = __shfl((int)invert, src) != 0;   // the whole wave works for channel cc here: ITS polarity, not each lane's own channel's
-                const XT* xrc = reinterpret_cast<const XT*>(P.x) + (size_t)cc * P.xpitch + XPRE + t0;
+                const XT* xrc = static_cast<const XT*>(P.x) + (size_t)cc * P.xpitch + XPRE + t0;
                 const Boundary* bsrc = (!from_chain && bnd_base) ? bnd_base + cc : nullptr;   // (both wave-uniform)
                 const XT* hist;
                 if constexpr (std::is_same<XT, float>::value) hist = (bsrc ? P.bnd_hist_f : P.hist_f) + (size_t)cc * HISTF_PITCH;
@@ -385,8 +385,9 @@ __device__ __forceinline__ void limit_track_pass(const GateParams& P, bool state
 }
 
 // (at most 128 VGPRs: a wave of it has to fit into what four K5 waves leave of a SIMD)
+// XT: int16_t, or float for a float stream: P.x names float rows, P.hist_f / P.bnd_hist_f the snapshots
 template <typename XT>
-__device__ __forceinline__ void limit_track_body(const GateParams& P)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_kernel(GateParams P)
 {
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     if (blockIdx.x >= P.nblk) {   // (a launch that runs beside K5 takes an earlier segment's EVM operations along: 64 channels per block)
@@ -406,9 +407,6 @@ __device__ __forceinline__ void limit_track_body(const GateParams& P)
     //  ignores the waves-per-SIMD attribute above)
     limit_track_pass<XT>(P, (P.flags & 2u) != 0, c, valid, P.chain_in != nullptr, P.only ? P.bnd : nullptr, lds_dyn);
 }
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_kernel(GateParams P) { limit_track_body<int16_t>(P); }
-// a float stream: P.x names float rows, P.hist_f / P.bnd_hist_f the snapshots
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void limit_track_f32_kernel(GateParams P) { limit_track_body<float>(P); }
 
 // =====================================================================================================
 // Gate-aware front end (m17hip_tune key 26): which samples of segment k + 2 can the carrier be ON for?

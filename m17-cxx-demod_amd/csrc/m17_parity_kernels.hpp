@@ -373,7 +373,7 @@ __global__ __launch_bounds__(64) void decode_seq_lane_kernel(DecodeSeqParams P)
     for (int k = 0; k < 30; ++k) P.lsf_io[(size_t)c * 30 + k] = (uint8_t)byte_at(L.lsf, 64, lane, k);
 }
 
-// one wave per channel; LDS as K5 lays a wave's decoder out (m17_wave_body.inc): stride 1, the cost words, the frame, the decisions, the output bytes, the LSF
+// one wave per channel; LDS as K5 lays a wave's decoder out (m17_wave_demod_kernel.hpp): stride 1, the cost words, the frame, the decisions, the output bytes, the LSF
 __global__ __launch_bounds__(64) void decode_seq_wave_kernel(DecodeSeqParams P)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[488 + 92 + 122 + 8 + 8];

@@ -125,7 +125,7 @@ struct GateTruth {
     uint32_t seg;
 };
 struct SeqParams {
-    const int16_t* x;
+    const void* x;            // the input rows: int16_t, or float for a float stream — the XT of the kernel the block is launched with
     size_t xpitch;
     const float* y;
     size_t ypitch;

@@ -1,5 +1,23 @@
-// The body of demod_wave_kernel<WPB, PROF, TIMED, KORDER> and demod_wave_f32_kernel<WPB, KORDER> (m17_wave_kernel.hpp): included into both, inside the
-// kernel's braces.  The including kernel names: WPB, PROF, TIMED, KORDER (constants); XT, the sample type of the input slab (int16_t or float); P.
+// K5 itself: demod_wave_kernel, one wave per channel.  The mapping, what the kernel consumes and the helpers it calls are in m17_wave_kernel.hpp.
+#pragma once
+
+#include "m17_wave_kernel.hpp"
+
+namespace m17 {
+
+// XT: the sample type of the input slab — int16_t, or float for a float stream (m17hip_upload_f32).  K5 reads raw samples in two places only, the window
+// rebuild of patch_run_start and the 149-sample snapshots; a float stream keeps the snapshots in SeqParams::hist_f / bnd_hist_f.
+// PROF: compile the 100 MHz section timers and counters in (diagnostics, tools/seq_ablate.py); the production
+// instantiation carries none of them.
+// TIMED: per-wave working time per segment (both only in the tools build, -DM17_TOOLS, and for int16 rows only: there are no float PROF / TIMED forms).
+// KORDER: the Kalman evaluation order as a compile-time constant (3 = the default order: its clock update is inlined and the kernel makes no
+// call at all: no stack, no scratch), or -1: the order of SeqParams at run time through the out-of-line variants (m17hip_set_kalman_order).
+// The int16 and the float kernel are ONE text, this kernel template (as K1 and K3 are templates over XT).  It has to be the __global__ function that is the
+// template: called as an inlined FUNCTION template from two kernels, the int16 kernel came out with eleven more spilled scalar registers (NOTES
+// 2026-10-18); instantiated as below, every form is instruction for instruction what it was as a body file included into hand-written kernels (NOTES 2026-10-20).
+template <typename XT, int WPB, bool PROF = false, bool TIMED = false, int KORDER = -1>
+__global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(SeqParams P)
+{
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     float* edges = reinterpret_cast<float*>(lds);                        // [64] llr table edges (43 used)
     for (int k = threadIdx.x; k < 43; k += 64 * WPB) edges[k] = P.llr_edges[k];
@@ -76,7 +94,7 @@
     uint32_t avail = 0;
 
     constexpr bool F32 = std::is_same<XT, float>::value;
-    const XT* xr = reinterpret_cast<const XT*>(P.x) + (size_t)c * P.xpitch + XPRE;
+    const XT* xr = static_cast<const XT*>(P.x) + (size_t)c * P.xpitch + XPRE;
     auto raw_hist = [&]() -> XT* {   // the channel's 149-sample snapshot (formed where it is used: nothing of it lives across the main loop)
         if constexpr (F32) return reinterpret_cast<XT*>(P.hist_f + (size_t)c * HISTF_PITCH);
         else return reinterpret_cast<XT*>(gs->hist);
@@ -1307,3 +1325,6 @@
         for (int k = cold_lane(); k < 75; k += 64) hd[k] = hs[k];
         }
     }
+}
+
+}  // namespace m17

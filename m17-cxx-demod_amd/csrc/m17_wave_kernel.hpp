@@ -123,28 +123,6 @@ __device__ __forceinline__ Hist3 nf_serve_limit(const float* yr, float* hr, M17_
                  __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, h2)))};
 }
 
-// PROF: compile the 100 MHz section timers and counters in (diagnostics, tools/seq_ablate.py); the production
-// instantiation carries none of them.
-// TIMED: per-wave working time per segment (both only in the tools build, -DM17_TOOLS).
-// KORDER: the Kalman evaluation order as a compile-time constant (3 = the default order: its clock update is inlined and the kernel makes no
-// call at all: no stack, no scratch), or -1: the order of SeqParams at run time through the out-of-line variants (m17hip_set_kalman_order).
-// XT: the sample type of the input slab — int16_t, or float for a float stream (m17hip_upload_f32).  K5 reads raw samples in two places only, the window
-// rebuild of patch_run_start and the 149-sample snapshots; a float stream keeps the snapshots in SeqParams::hist_f / bnd_hist_f.  Both kernels are ONE
-// text, m17_wave_body.inc, included into each (as K1 and K3 are built from their body files) — through an inlined function template the int16 kernel
-// came out with eleven more spilled scalar registers; included, it is the kernel it was.
-template <int WPB, bool PROF = false, bool TIMED = false, int KORDER = -1>
-__global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_kernel(SeqParams P)
-{
-    typedef int16_t XT;
-#include "m17_wave_body.inc"
-}
-// a float stream: the default-Kalman-order instantiation (KORDER = 3) and the run-time-order one (-1); the tools-only PROF / TIMED forms have no float twin
-template <int WPB, int KORDER = -1>
-__global__ __launch_bounds__(64 * WPB, M17_WAVE_MINW) void demod_wave_f32_kernel(SeqParams P)
-{
-    constexpr bool PROF = false, TIMED = false;
-    typedef float XT;
-#include "m17_wave_body.inc"
-}
+// (the kernel itself, demod_wave_kernel<XT, WPB, PROF, TIMED, KORDER>: m17_wave_demod_kernel.hpp)
 
 }  // namespace m17

@@ -12,7 +12,7 @@
 #include "m17_chan_kernels.hpp"
 #include "m17_chan_survey_kernels.hpp"
 #include "m17_state.hpp"
-#include "m17_wave_kernel.hpp"
+#include "m17_wave_demod_kernel.hpp"
 #include "m17_gate_kernel.hpp"
 #include "m17_mod_kernels.hpp"
 #include "m17_parity_kernels.hpp"
@@ -1067,18 +1067,10 @@ template <typename F> auto with_x(m17hip_ctx* c, int slot, F&& f)
 }
 // The kernels that read input rows, chosen by the rows' pointer: K1 and K3 for channels of one polarity (INV) or of mixed ones, K2, K5 (KORDER as
 // demod_wave_kernel has it).  The two forms of K3 take the same arguments.
-template <bool INV> auto fir_kernel(const int16_t*) { return fir_rrc150_skew_kernel<INV>; }
-template <bool INV> auto fir_kernel(const float*) { return fir_rrc150_skew_f32_kernel<INV>; }
-auto fir_mixed_kernel(const int16_t*) { return fir_rrc150_skew_mixed_kernel; }
-auto fir_mixed_kernel(const float*) { return fir_rrc150_skew_mixed_f32_kernel; }
-template <bool INV> auto dcd_kernel_of(const int16_t*, bool one_wave) { return one_wave ? dcd_kernel<INV> : dcd_pipe_kernel<INV>; }
-template <bool INV> auto dcd_kernel_of(const float*, bool one_wave) { return one_wave ? dcd_f32_kernel<INV> : dcd_pipe_f32_kernel<INV>; }
-auto dcd_mixed_kernel_of(const int16_t*, bool one_wave) { return one_wave ? dcd_mixed_kernel : dcd_pipe_mixed_kernel; }
-auto dcd_mixed_kernel_of(const float*, bool one_wave) { return one_wave ? dcd_mixed_f32_kernel : dcd_pipe_mixed_f32_kernel; }
-auto gate_kernel(const int16_t*) { return limit_track_kernel; }
-auto gate_kernel(const float*) { return limit_track_f32_kernel; }
-template <int KORDER> auto wave_kernel(const int16_t*) { return demod_wave_kernel<4, false, false, KORDER>; }
-template <int KORDER> auto wave_kernel(const float*) { return demod_wave_f32_kernel<4, KORDER>; }
+template <bool INV, bool MIXED, typename XT> auto fir_kernel(XT*) { return fir_rrc150_skew_kernel<XT, INV, MIXED>; }
+template <bool INV, bool MIXED, typename XT> auto dcd_kernel_of(XT*, bool one_wave) { return one_wave ? dcd_kernel<XT, INV, MIXED> : dcd_pipe_kernel<XT, INV, MIXED>; }
+template <typename XT> auto gate_kernel(XT*) { return limit_track_kernel<XT>; }
+template <int KORDER, typename XT> auto wave_kernel(XT*) { return demod_wave_kernel<XT, 4, false, false, KORDER>; }
 
 // t0: first sample of the slab to process (segment of a run); the kernels see the slab from there on
 constexpr size_t SEQ_LDS_BYTES_4 = 34816;   // see the K5 launch
@@ -1113,12 +1105,12 @@ int launch_fir(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, bool laten
         const uint32_t per = latency ? FIR_ITEMS_LATENCY : FIR_ITEMS_THROUGHPUT;
         const uint32_t cap = c->fir_grid ? c->fir_grid : std::max(FIR_GRID_PER_CU * c->n_cu, (items + per - 1) / per);
         const dim3 grid(std::min(items, cap));
-        const auto go = [&](auto kernel, auto... mixed) {
-            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, mixed...);
+        const auto go = [&](auto kernel) {   // (pol, flip: read by the mixed form only)
+            tm.launch(kernel, grid, dim3(FS_THREADS), 0, st, x + t0, c->xpitch, c->now().y + t0, c->ypitch, T, c->taps_skew, tiles, items, first_needed, pol, pol ? flags & 1u : 0u);
         };
-        if (pol) go(fir_mixed_kernel(x), pol, flags & 1u);
-        else if (flags & 1u) go(fir_kernel<true>(x));
-        else go(fir_kernel<false>(x));
+        if (pol) go(fir_kernel<false, true>(x));
+        else if (flags & 1u) go(fir_kernel<true, false>(x));
+        else go(fir_kernel<false, false>(x));
         HIPCHK(c, hipGetLastError());
         return M17HIP_OK;
     });
@@ -1133,12 +1125,12 @@ int launch_dcd(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, uint64_t p
     const bool one_wave = !latency || T % DP_BLK != 0 || (pos + t0) % DP_BLK != 0 || t0 % 8 != 0 || T < 4 * DP_BLK;
     const dim3 grid(one_wave ? (C + DCD_CPW * DCD_WPB - 1) / (DCD_CPW * DCD_WPB) : (C + DP_CPB - 1) / DP_CPB), block(one_wave ? 64 * DCD_WPB : 256);
     with_x(c, c->slot, [&](auto* x) {
-        const auto go = [&](auto kernel, auto... mixed) {
-            tm.launch(kernel, grid, block, 0, st, x + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, mixed...);
+        const auto go = [&](auto kernel) {   // (pol: read by the mixed form only)
+            tm.launch(kernel, grid, block, 0, st, x + t0, c->xpitch, c->dcd_state, c->now().dcd + row0 * 12, c->ticks_cap, C, T, pos + t0, c->coef, flags, pol);
         };
-        if (pol) go(dcd_mixed_kernel_of(x, one_wave), pol);
-        else if (flags & 1u) go(dcd_kernel_of<true>(x, one_wave));
-        else go(dcd_kernel_of<false>(x, one_wave));
+        if (pol) go(dcd_kernel_of<false, true>(x, one_wave));
+        else if (flags & 1u) go(dcd_kernel_of<true, false>(x, one_wave));
+        else go(dcd_kernel_of<false, false>(x, one_wave));
     });
     HIPCHK(c, hipGetLastError());
     return M17HIP_OK;
@@ -2661,12 +2653,9 @@ static int launch_gated_fir(m17hip_ctx* c, const RunPlan& p, uint32_t k)
 static EvParams ev_fold(const m17hip_ctx* c, const EvmFold::Pass& f, EvLast last) { return EvParams{f.ops, c->evm.pitch(), c->evm.state, c->diag.entries(), c->diag.room, c->seq_state, f.C, f.upto, last}; }
 static EvParams ev_no_fold(uint32_t C) { return EvParams{nullptr, 0, nullptr, nullptr, 0, nullptr, C, nullptr, 0u}; }
 
-// The parameter blocks of K2 and K5 (GateParams::x, SeqParams::x: filled in launch_gate_seg and seq_params, below) name the input rows as int16_t*
-// whatever they hold.  Float rows go in under that member here, and the float instantiations take them out again: reinterpret_cast<const XT*>(P.x) in
-// limit_track_body<XT> (m17_gate_kernel.hpp) and in the wave body (m17_wave_body.inc).  The kernel a block is launched with comes from the same typed
-// pointer (gate_kernel, wave_kernel), so the two cannot disagree.
-static const int16_t* param_rows(const int16_t* x) { return x; }
-static const int16_t* param_rows(const float* x) { return reinterpret_cast<const int16_t*>(x); }
+// The parameter blocks of K2 and K5 (GateParams::x, SeqParams::x: filled in launch_gate_seg and seq_params, below) name the input rows as const void*;
+// limit_track_kernel<XT> and demod_wave_kernel<XT, ...> read them as rows of XT.  The kernel a block is launched with comes from the same typed pointer
+// the block is filled from (gate_kernel, wave_kernel), so the two cannot disagree.
 
 // One launch of K2 over segment k of the run whose slabs the context names: the whole segment from K5's state (first segment), ahead of
 // K5 from K2's own state, or the redo of the channels K5 flagged in the previous segment.
@@ -2700,7 +2689,7 @@ static int launch_gate_seg(m17hip_ctx* c, const RunPlan& p, uint32_t k, hipStrea
         fold_blocks = f.blocks();
     }
     with_x(c, c->slot, [&](auto* x) {
-        G.x = param_rows(x + t0);
+        G.x = x + t0;
         if constexpr (std::is_same<decltype(x), float*>::value) { G.hist_f = c->hist_f; G.bnd_hist_f = redo ? by_parity(c->bnd_hist_f, k, c->maxC, HISTF_PITCH) : nullptr; }
         tm.launch(gate_kernel(x), dim3(G.nblk + fold_blocks), dim3(64), GT_LDS_FLOATS * sizeof(float), st, G);
     });
@@ -3134,7 +3123,7 @@ static SeqParams seq_params(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::R
     SeqParams P{};
     P.h = c->now().h + t0; P.final_h = by_parity(c->final_h, k, c->maxC, 4);
     P.dropped = by_parity(c->dropped, k, c->maxC);
-    P.x = param_rows(x + t0); P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
+    P.x = x + t0; P.xpitch = c->xpitch; P.y = c->now().y + t0; P.ypitch = c->ypitch;
     if constexpr (std::is_same<XT, float>::value) { P.hist_f = c->hist_f; P.bnd_hist_f = by_parity(c->bnd_hist_f, k + 1u, c->maxC, HISTF_PITCH); }
     P.dcd_table = c->now().dcd; P.ticks_cap = c->ticks_cap; P.state = c->seq_state;
     P.recs = rs.recs; P.rec_cap = c->rec_cap; P.rec_count = rs.rec_count; P.overflow = rs.ovf;
@@ -3207,8 +3196,8 @@ static int queue_chain(m17hip_ctx* c, const RunPlan& p, const m17hip_ctx::RecSet
         with_x(c, c->slot, [&](auto* x) {
             const SeqParams P = seq_params(c, p, rs, k, x);
 #ifdef M17_TOOLS   // (int16 rows only: run_format_check has refused these instantiations on a float stream)
-            if (c->profile) tm.launch((demod_wave_kernel<4, true>), grid, block, lds, c->stream, P);
-            else if (c->wave_times) tm.launch((demod_wave_kernel<4, false, true>), grid, block, lds, c->stream, P);
+            if (c->profile) tm.launch((demod_wave_kernel<int16_t, 4, true>), grid, block, lds, c->stream, P);
+            else if (c->wave_times) tm.launch((demod_wave_kernel<int16_t, 4, false, true>), grid, block, lds, c->stream, P);
             else
 #endif
             if (c->kalman_order == 3u) tm.launch(wave_kernel<3>(x), grid, block, lds, c->stream, P);   // (the default order: no call in the kernel)

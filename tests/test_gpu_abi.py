@@ -268,8 +268,9 @@ x = ol.generate_batch(p, 24, T, threads=8)
 recs, counts, _ = ol.demod_batch(x, cap=2 * (T // 1920 + 2) + 4, threads=8)
 exp = np.concatenate([recs[c, :counts[c]] for c in range(24)]).tobytes()
 c = m17hip.Context(24, T)
-defaults = {{4: 0, 5: 0, 11: 1, 12: 0, 14: 0, 21: 0, 25: 1}}
-for settings in ({{11: 0}}, {{5: 2}}, {{12: 3}}, {{14: 32640}}, {{4: 9600}}, {{5: 1, 12: 2, 4: 4800}}):
+defaults = {{1: 0, 4: 0, 5: 0, 11: 1, 12: 0, 14: 0, 19: 0, 21: 0, 25: 1}}
+# (keys 1 and 19: the PROF and the TIMED instantiation of the sequential kernel — counters and clocks beside the same records)
+for settings in ({{11: 0}}, {{5: 2}}, {{12: 3}}, {{14: 32640}}, {{4: 9600}}, {{5: 1, 12: 2, 4: 4800}}, {{1: 1}}, {{19: 1}}):
     for k, v in settings.items(): c.tune(k, v)
     c.upload(x); c.reset(); c.run()
     assert c.frames().tobytes() == exp, settings
