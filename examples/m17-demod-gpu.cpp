@@ -3,7 +3,9 @@
 // I,Q of the narrowband FM channel, int16 or float32, discriminated on the device with --iq-gain G, default 1; with --wide-i16 / --wide-f32 / --wide-u8
 // --decim R --offset-hz F: interleaved I,Q of a WIDEBAND feed at 48000 R samples per second, the channel F Hz from its centre tuned, filtered, decimated and
 // discriminated on the device — rtl_sdr -s 240000 ... | m17-demod-gpu --wide-u8 --decim 5 --offset-hz 12500; with --decim2 R2 as well the feed is at
-// 48000 R R2 and decimated in two stages — rtl_sdr -s 2400000 ... | m17-demod-gpu --wide-u8 --decim 10 --decim2 5 --offset-hz 12500; with --raster M --bin B in place of --offset-hz
+// 48000 R R2 and decimated in two stages — rtl_sdr -s 2400000 ... | m17-demod-gpu --wide-u8 --decim 10 --decim2 5 --offset-hz 12500; with --rate HZ in place of
+// --decim the feed runs at HZ samples per second, any rate m17hip_wide_resample_ratio has a shape for, and the second stage resamples —
+// rtl_sdr -s 2048000 ... | m17-demod-gpu --wide-u8 --rate 2048000 --offset-hz 12500 (--rate excludes --decim, --decim2 and --raster); with --raster M --bin B in place of --offset-hz
 // the feed at 48000 R (R up to 64) is split into M channels by the polyphase channeliser and bin B of them demodulated — rtl_sdr -s 2400000 ... |
 // m17-demod-gpu --wide-u8 --decim 50 --raster 192 --bin 1; with --scan STRIDE beside --raster every STRIDE-th output of the feed is surveyed on the device
 // and after each block the occupied bins — more than --scan-margin dB, default 20, over the median of the 192 — are printed to stderr: bin, Hz from the
@@ -47,6 +49,8 @@ int main(int argc, char** argv)
     int iq = 0;   // 1: int16 I,Q; 2: float32 I,Q
     int wide = 0;   // M17HIP_IQ_I16 / _F32 / _U8: a wideband feed of that format
     uint32_t decim = 1, decim2 = 0;   // (decim2 == 0: one stage)
+    bool decim_given = false;
+    unsigned long long rate = 0;      // (0: integer decimations)
     double offset_hz = 0.0;
     uint32_t raster = 0;   // (0: a tuner)
     long bin = 0;
@@ -61,7 +65,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--wide-i16")) wide = M17HIP_IQ_I16;
         else if (!std::strcmp(argv[i], "--wide-f32")) wide = M17HIP_IQ_F32;
         else if (!std::strcmp(argv[i], "--wide-u8")) wide = M17HIP_IQ_U8;
-        else if (!std::strcmp(argv[i], "--decim") && i + 1 < argc) decim = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
+        else if (!std::strcmp(argv[i], "--decim") && i + 1 < argc) { decim = (uint32_t)std::strtoul(argv[++i], nullptr, 10); decim_given = true; }
+        else if (!std::strcmp(argv[i], "--rate") && i + 1 < argc) { rate = std::strtoull(argv[++i], nullptr, 10); if (!rate) rate = ~0ull; }
         else if (!std::strcmp(argv[i], "--decim2") && i + 1 < argc) { decim2 = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!decim2) decim2 = 17; }
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) offset_hz = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(argv[i], "--raster") && i + 1 < argc) { raster = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!raster) raster = 257; }
@@ -69,13 +74,21 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--scan") && i + 1 < argc) { scan = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!scan) scan = 4097; }
         else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) scan_margin = std::strtod(argv[++i], nullptr);
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R] [--decim2 R2] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--iq-gain G] < samples\n");
             return 2;
         }
     }
     if (((iq || wide) && float_input) || (iq && wide) || !(iq_gain > 0.0f) || !std::isfinite(iq_gain)) { std::fprintf(stderr, "m17-demod-gpu: one input format, and a finite gain > 0\n"); return 2; }
-    const double half_hz = 24000.0 * decim * (decim2 ? decim2 : 1);
-    if (wide && raster) {
+    const double half_hz = rate ? 0.5 * (double)rate : 24000.0 * decim * (decim2 ? decim2 : 1);
+    if (rate) {
+        uint32_t d1, up, down;
+        if (!wide || decim_given || decim2 || raster || rate > 0xFFFFFFFFull || m17hip_wide_resample_ratio((uint32_t)rate, &d1, &up, &down) != M17HIP_OK ||
+            !(std::fabs(offset_hz) <= half_hz)) {
+            std::fprintf(stderr, "m17-demod-gpu: --rate HZ goes with a wideband format and without --decim, --decim2 and --raster; a rate of 48000 * decim1 * down / up "
+                                 "(decim1 to 16, up to 32, down to 125) and an offset inside the feed\n");
+            return 2;
+        }
+    } else if (wide && raster) {
         uint32_t m1, m2;
         if (decim < 1 || decim > 64 || decim2 || !core::chan_factor(raster, m1, m2) || bin < -(long)(raster / 2) || bin > (long)((raster - 1) / 2)) {
             std::fprintf(stderr, "m17-demod-gpu: a decimation of 1 to 64 in one stage, a raster that factors into two numbers up to 16, and a bin inside it\n");
@@ -103,7 +116,8 @@ int main(int argc, char** argv)
     }
     if (iq) return 0;
     if (wide) {   // a wideband feed: the tuner runs on the device
-        if (raster) demod.wide_raster(decim, raster, (int32_t)bin);
+        if (rate) demod.wide_rate((uint32_t)rate, offset_hz);
+        else if (raster) demod.wide_raster(decim, raster, (int32_t)bin);
         else if (decim2) demod.wide_config(decim, decim2, offset_hz);
         else demod.wide_config(decim, offset_hz);
         if (scan) {   // the occupied bins of the one source after each block: the floor is the median of the plane

@@ -220,9 +220,10 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: non-integer resampling, per-source sample counts, squelch / RSSI under a tuner (per bin of a raster: the survey,
+ * Out of scope, for a later pull request: per-source sample counts, squelch / RSSI under a tuner (per bin of a raster: the survey,
  * ABI 613, below).  (Sources above 16 x 48 kSPS: two stages,
- * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.) */
+ * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.  Rates that are no integer multiple of 48 kSPS: the resampling tuner,
+ * ABI 615, below.) */
 #define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
 /* The filter m17hip_wide_config takes by default — what a user of rtl_fm leaves to its built-in low-pass: ntaps = 32 * decim + 1, a Blackman-windowed
  * sinc with its cutoff at 5500 Hz of 48000 * decim, computed in double, scaled to unit DC gain and rounded to float.  No context is needed.  *ntaps is set
@@ -308,7 +309,7 @@ int m17hip_wide_config2(m17hip_ctx* ctx, uint32_t sources, uint32_t decim1, cons
  * is unchanged.  The twiddles exp(-2 pi j j / M) are DATA: made in one place, on the host, in double, rounded to float, exactly 0 / +-1 on the axes, and
  * tw[M - j] the conjugate of tw[j] to the bit; m17hip_wide_raster_twiddles returns the table the device is given, so a host computes the device's words
  * whatever its libm.
- * Out of scope, for a later pull request: a raster shifted by a fraction of a spacing, non-integer resampling, per-source sample counts.  (Which bins carry
+ * Out of scope, for a later pull request: a raster shifted by a fraction of a spacing, a raster in a source at a rational rate (the tuner for those: ABI 615, below), per-source sample counts.  (Which bins carry
  * anything — RSSI per bin: the raster survey, ABI 613, below.) */
 /* The default taps of m17hip_wide_raster: the formula of m17hip_wide_default_taps (32 * decim + 1 taps, Blackman-windowed sinc, cutoff 5500 Hz) for
  * decim 1..64, word for word that function's for decim <= 16.  No context is needed.  *ntaps is set whenever decim is valid; M17HIP_EINVAL if it is not, if
@@ -364,6 +365,49 @@ int m17hip_wide_survey(m17hip_ctx* ctx, uint32_t stride);
  * plane exists: the survey is off, no block (or, for back = 1, one block) since it was turned on, or none since m17hip_demod_reset, which starts the feeds
  * over.  M17HIP_EINVAL for back > 1, a NULL power_host or capacity (in floats) < sources * bins; nothing is written then. */
 int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* times, uint64_t* first_output);
+
+/* ---- wideband IQ input at rational sample rates: a resampling tuner (ABI 615) -------------------------------
+ * Every configuration above wants a source at an INTEGER multiple of 48 kSPS, and the rates receivers run at by default are not: rtl_sdr's 2.048 MSPS is
+ * 128/3 of it (1.024: 64/3, 2.56: 160/3), an Airspy's 2.5, 3, 6 and 10 MSPS 625/12, 125/2, 125 and 625/3, a HackRF's 8 and 20 MSPS 500/3 and 1250/3.  This
+ * is the two-stage tuner with a second stage that resamples by up / down: the source runs at 48000 * decim1 * down / up, decim1 1..16, up 1..32, down
+ * 1..125, up <= down and gcd(up, down) == 1.  With U = up, D = down, R1 = decim1, per channel, one kernel (csrc/m17_resample_kernels.hpp):
+ *     mixed[m] = x[m] * conj(nco(fcw * m))                             (as above; mixed[m] = 0 for m < 0)
+ *     u[p]     = sum_{i < ntaps1} taps1[i] * mixed[p R1 + R1 - 1 - i]  (the two-stage tuner's first stage, unchanged)
+ *     N_n      = n D + D - 1,   i0_n = N_n mod U,   b_n = N_n div U    (in 64 bits)
+ *     z[n]     = sum_{j : i0_n + U j < ntaps2} taps2[i0_n + U j] * u[b_n - j]
+ *     y[n]     = gain * arg(z[n] * conj(z[n-1]))
+ * — the u zero-stuffed by U, filtered with taps2 at 48000 * D, the sample at n D + D - 1 kept, with the products of the stuffed zeroes left out — in the
+ * arithmetic of ABI 609 (ddc_mix per input sample, ddc_tap chains from +0 with j ascending, fm_discriminate; core::ddc_resample is the host form of these
+ * words).  At U = 1 it is m17hip_wide_config2's definition, and the words are that tuner's.  n is counted WITHIN A BLOCK: every block holds a multiple of U
+ * outputs, so the phase i0 never depends on the feed's history.  The frequency word means fcw / 2^32 * 48000 * decim1 * down / up Hz.
+ * Out of scope: a rational-rate channeliser (a raster in a 2.048 MSPS source), sources of different rates in one context, interpolation (up > down), more
+ * than two stages, squelch or RSSI under a tuner. */
+/* The default taps of both stages.  Stage 1: 8 * decim1 + 1 taps of the Blackman-windowed sinc of m17hip_wide_default_taps2 with its cutoff at half the
+ * rate the stage leaves (0.5 / decim1 of the source's rate); one tap of 1 at decim1 == 1.  Stage 2: 32 * down + 1 taps of the same formula with the cutoff
+ * at 5500 Hz of 48000 * down, scaled in double to DC gain `up` — every one of the `up` branches taps2[r], taps2[r + up], ... then has unit gain within
+ * 1e-6 — and rounded; at up == 1 m17hip_wide_raster_default_taps(down) word for word where that exists.  No context is needed.  *ntaps1 and *ntaps2 are set
+ * whenever decim1, up and down are valid; M17HIP_EINVAL if they are not (up > down and a common factor included), if ntaps1 or ntaps2 is NULL, or if a taps
+ * pointer is NULL or its capacity too small (nothing written). */
+int m17hip_wide_resample_default_taps(uint32_t decim1, uint32_t up, uint32_t down, float* taps1, uint32_t cap1, uint32_t* ntaps1, float* taps2, uint32_t cap2,
+                                      uint32_t* ntaps2);
+/* What a user knows is the rate.  rate_hz / 48000 reduced to N / up; M17HIP_EINVAL if up > 32.  decim1 is the largest divisor of N that is <= 16 with
+ * N / decim1 <= 125 and N / decim1 >= 2 * up (the rate between the stages at or above 96 kSPS); failing that the largest with N / decim1 >= up; failing
+ * that M17HIP_EINVAL.  down = N / decim1.  2 048 000 -> 16, 3, 8;  2 400 000 -> 10, 1, 5;  2 500 000 -> 5, 12, 125;  3 000 000 -> 5, 2, 25;
+ * 6 000 000 -> 5, 1, 25;  10 000 000 -> 5, 3, 125;  250 000 -> 1, 24, 125;  48 000 -> 1, 1, 1.  No context is needed; nothing is written by a refused call. */
+int m17hip_wide_resample_ratio(uint32_t rate_hz, uint32_t* decim1, uint32_t* up, uint32_t* down);
+/* m17hip_wide_config2 with a resampling second stage: `sources` (1..256) at 48000 * decim1 * down / up, taps1[ntaps1] (1..256) and taps2[ntaps2] (1..4096),
+ * all finite; a NULL pointer with a count of 0 selects that stage's default taps.  M17HIP_EINVAL outside the limits, for up > down and for a common factor of
+ * the two.  In every other respect it is m17hip_wide_config2: it starts the feeds over, may be called again, waits for tuner launches in flight and never
+ * for a run, clears channels of sources that are gone, leaves the carries, returns M17HIP_ESTATE between m17hip_demod_front and its run, and turns the
+ * survey off.  The four configurations replace one another: whichever call was made last decides which kernel the next upload launches.
+ * m17hip_wide_channels serves it (it is a tuner: m17hip_wide_raster_channels and m17hip_wide_survey return M17HIP_ESTATE under it).
+ * m17hip_upload_wide*, all four ways in: `samples` must be a multiple of `up`, else M17HIP_EINVAL; every source row holds samples / up * down * decim1
+ * complex samples and pitch is at least that; a row of more than 2^32 - 1 complex samples is M17HIP_EINVAL on the arguments alone.
+ * THE FEED is the one described above.  Per source the last (ceil(ntaps2 / up) - 1) * decim1 + ntaps1 - 1 converted samples are carried; per channel the
+ * float2 carry (the last z); ONE running sample count; resets, retunes and the staged-block rule read as under the tuners.
+ * m17hip_timing_get index 13 is this tuner; m17hip_iq_bytes counts its memory by the two-stage tuner's rule with that history. */
+int m17hip_wide_resample(m17hip_ctx* ctx, uint32_t sources, uint32_t decim1, const float* taps1, uint32_t ntaps1, uint32_t up, uint32_t down, const float* taps2,
+                         uint32_t ntaps2, int iq_format);
 
 /* ---- per-operator batched entry points (config 2 parity) ---------------------------------------- */
 /* K1: sample scaling + BaseFirFilter<float,150> with the RRC taps, ungated, over the uploaded slab
@@ -865,7 +909,7 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 9 = tune (the tuner of m17hip_upload_wide* under m17hip_wide_config: one launch per wideband block),
  * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
  * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
- * entry per surveyed block). */
+ * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

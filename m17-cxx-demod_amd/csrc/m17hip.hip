@@ -9,6 +9,7 @@
 #include "m17_iq_kernels.hpp"
 #include "m17_wide_kernels.hpp"
 #include "m17_wide2_kernels.hpp"
+#include "m17_resample_kernels.hpp"
 #include "m17_chan_kernels.hpp"
 #include "m17_chan_survey_kernels.hpp"
 #include "m17_state.hpp"
@@ -36,7 +37,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -349,8 +350,9 @@ struct m17hip_ctx {
     struct Wide {
         uint32_t S = 0, R = 0, L = 0; int fmt = 0;   // S == 0: not configured
         uint32_t R2 = 0, L2 = 0;                     // R2 == 0: one stage (m17hip_wide_config); else R and L are stage 1's (m17hip_wide_config2: tune2_kernel)
-        uint32_t rate() const { return R2 ? R * R2 : R; }                       // wideband samples per output
-        uint32_t hlen() const { return R2 ? (L2 - 1) * R + L - 1 : L - 1; }     // converted samples a source carries
+        uint32_t U = 0, D = 0;                       // U != 0: the second stage resamples by U / D (m17hip_wide_resample: resample_kernel); R2 == 0, L2 its taps
+        uint64_t row(uint32_t T) const { return U ? (uint64_t)(T / U) * D * R : (uint64_t)T * (R2 ? R * R2 : R); }   // wideband samples under T outputs
+        uint32_t hlen() const { return U ? (wide2_j(L2, U) - 1) * R + L - 1 : R2 ? (L2 - 1) * R + L - 1 : L - 1; }   // converted samples a source carries
         uint32_t M = 0, M1 = 0, M2 = 0;              // M != 0: a raster of M bins (m17hip_wide_raster: chan_kernel); R and L are its decimation and taps, R2 == 0
         DevBuf<float> taps, taps2; DevBuf<float2> hist[2], znew, tw;
         int par = 0;
@@ -1209,7 +1211,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 614; }
+int m17hip_version(void) { return 615; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1640,8 +1642,8 @@ static int upload_iq(m17hip_ctx* c, const void* p, int iq_format, float gain, ui
 }
 
 // ---- wideband IQ input (ABI 609): the tuner in front of the float slab -----------------------------------------------------------------------
-// Blackman-windowed sinc of L taps, cutoff fc (cycles per sample), in double; unit DC gain, then rounded to float
-static void windowed_sinc(uint32_t L, double fc, float* taps)
+// Blackman-windowed sinc of L taps, cutoff fc (cycles per sample), in double; DC gain `gain` (1: the quotient as it is), then rounded to float
+static void windowed_sinc(uint32_t L, double fc, float* taps, double gain = 1.0)
 {
     const double pi = 3.14159265358979323846, mid = 0.5 * (L - 1);
     std::vector<double> h(L);
@@ -1653,7 +1655,7 @@ static void windowed_sinc(uint32_t L, double fc, float* taps)
         h[i] = sinc * w;
         sum += h[i];
     }
-    for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum);
+    for (uint32_t i = 0; i < L; ++i) taps[i] = (float)(h[i] / sum * gain);
 }
 // The channel filter: cutoff 5500 Hz at 48000 * decim, 32 * decim + 1 taps
 static void wide_default(uint32_t R, float* taps) { windowed_sinc(32 * R + 1, 5500.0 / (48000.0 * R), taps); }
@@ -1723,7 +1725,7 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
 {
     auto& w = c->wide;
     const IQT* src = static_cast<const IQT*>(dev);
-    const uint32_t W = T * w.rate(), H = w.hlen();   // (W fits: upload_wide has seen to it)
+    const uint32_t W = (uint32_t)w.row(T), H = w.hlen();   // (W fits: upload_wide has seen to it)
     if (w.dirty || !w.dev.live()) {   // the channel table, into the copy no queued launch reads
         uint32_t* staging = nullptr;
         HIPCHK(c, w.dev.begin_write(w.table.size(), &staging));
@@ -1732,7 +1734,13 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         w.dirty = false;
     }
     HIPCHK(c, w.dev.before_read(st));
-    if (w.R2) {
+    if (w.U) {
+        const uint32_t G = resample_groups(w.L, w.R, w.L2, w.U, w.D), Q = resample_q(w.L, w.R, w.L2, w.U, w.D, G);
+        TimedK tm(c, KT_RESAMPLE);
+        tm.launch(resample_kernel<IQT>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch,
+                  W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x,
+                  c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+    } else if (w.R2) {
         TimedK tm(c, KT_WIDE2);
         tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
                   w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
@@ -1796,7 +1804,8 @@ static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uin
     const auto own = [&] {
         if (!std::isfinite(gain) || !(gain > 0.0f)) return M17HIP_EINVAL;
         if (!c->wide.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
-        W = (uint64_t)T * c->wide.rate();
+        if (c->wide.U && T % c->wide.U) return M17HIP_EINVAL;   // (a block holds whole groups of `up` outputs: the phase never depends on the feed's history)
+        W = c->wide.row(T);
         return pitch < W || W > 0xFFFFFFFFull ? M17HIP_EINVAL : M17HIP_OK;   // (the kernels count a row's samples in 32 bits)
     };
     return upload_frame<float>(c, p, C, T, (how & IQ_STAGED) != 0, own, [&](float* x, hipStream_t st) -> int {
@@ -1878,9 +1887,10 @@ static void chan_twiddles(uint32_t M, float* tw)
     }
     if (M % 2 == 0) tw[M + 1] = 0.0f;   // (j = M / 2: -1, and its own conjugate)
 }
-// What the three configurations share, the arguments checked: h2 empty and decim2 == 0 is a single stage; bins != 0 the raster (a single stage, no oscillator).
+// What the four configurations share, the arguments checked: h2 empty and decim2 == 0 is a single stage; bins != 0 the raster (a single stage, no oscillator);
+// up != 0 the resampling tuner (h2 its second stage at up / down, decim2 == 0).
 static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t decim, const std::vector<float>& h, uint32_t decim2, const std::vector<float>& h2,
-                      uint32_t bins = 0)
+                      uint32_t bins = 0, uint32_t up = 0, uint32_t down = 0)
 {
     GUARD(c);
     if (c->front_queued) return M17HIP_ESTATE;
@@ -1890,18 +1900,18 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     if ((r = ensure_iq(c, st))) return r;
     HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (a block tuned with the configuration before may still be in flight: its buffers go)
     const uint32_t L = (uint32_t)h.size(), L2 = (uint32_t)h2.size();
-    const size_t hn = (size_t)sources * std::max<uint32_t>(decim2 ? (L2 - 1) * decim + L - 1 : L - 1, 1);
+    const size_t hn = (size_t)sources * std::max<uint32_t>(up ? (wide2_j(L2, up) - 1) * decim + L - 1 : decim2 ? (L2 - 1) * decim + L - 1 : L - 1, 1);
     w.S = 0;   // (not configured until all of it is there)
     w.sv.stride = 0; w.sv.forget();   // (the survey's plane has the configuration's shape: off, and its memory back)
     w.sv.scratch.release(&c->last_hip);
     for (auto& b : w.sv.plane) b.release(&c->last_hip);
     if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
-    if (decim2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
+    if (L2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
     else w.taps2.release(&c->last_hip);
     for (auto& b : w.hist) if ((r = alloc_code(c, b.alloc(hn)))) return r;
     if (!w.znew && (r = alloc_code(c, w.znew.alloc(c->maxC)))) return r;
     HIPCHK(c, hipMemcpy(w.taps, h.data(), L * sizeof(float), hipMemcpyHostToDevice));
-    if (decim2) HIPCHK(c, hipMemcpy(w.taps2, h2.data(), L2 * sizeof(float), hipMemcpyHostToDevice));
+    if (L2) HIPCHK(c, hipMemcpy(w.taps2, h2.data(), L2 * sizeof(float), hipMemcpyHostToDevice));
     if (bins) {
         std::vector<float> tw(2 * (size_t)bins);
         chan_twiddles(bins, tw.data());
@@ -1916,6 +1926,7 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.dirty = true;
     w.R = decim; w.L = L; w.R2 = decim2; w.L2 = L2; w.fmt = iq_format; w.par = 0; w.count = 0;
     w.M = bins; w.M1 = w.M2 = 0;
+    w.U = up; w.D = down;
     if (bins) core::chan_factor(bins, w.M1, w.M2);
     w.S = sources;
     return M17HIP_OK;
@@ -1949,6 +1960,49 @@ int m17hip_wide_config2(m17hip_ctx* c, uint32_t sources, uint32_t decim1, const 
     wide_default(decim2, h2.data());
     if (!wide_stage_taps(taps1, ntaps1, 256, h1) || !wide_stage_taps(taps2, ntaps2, 1024, h2)) return M17HIP_EINVAL;
     return wide_setup(c, sources, iq_format, decim1, h1, decim2, h2);
+}
+// ---- a resampling second stage (ABI 615): sources at 48000 * decim1 * down / up ----------------------------------------------------------------
+static uint32_t gcd_u32(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
+static bool resample_shape(uint32_t decim1, uint32_t up, uint32_t down)
+{
+    return decim1 >= 1 && decim1 <= 16 && up >= 1 && up <= 32 && down >= 1 && down <= 125 && up <= down && gcd_u32(up, down) == 1;
+}
+// Stage 2: the channel filter at 48000 * down — 32 * down + 1 taps, cutoff 5500 Hz — scaled in double to DC gain `up` (what the zero-stuffing takes), then
+// rounded: at up == 1 wide_default(down) word for word.  Stage 1: cutoff at half the rate it leaves, as wide_default1 has it.
+static void resample_default2(uint32_t up, uint32_t down, float* taps) { windowed_sinc(32 * down + 1, 5500.0 / (48000.0 * down), taps, (double)up); }
+int m17hip_wide_resample_default_taps(uint32_t decim1, uint32_t up, uint32_t down, float* taps1, uint32_t cap1, uint32_t* ntaps1, float* taps2, uint32_t cap2,
+                                      uint32_t* ntaps2)
+{
+    if (!resample_shape(decim1, up, down) || !ntaps1 || !ntaps2) return M17HIP_EINVAL;
+    *ntaps1 = decim1 == 1 ? 1 : 8 * decim1 + 1;
+    *ntaps2 = 32 * down + 1;
+    if (!taps1 || cap1 < *ntaps1 || !taps2 || cap2 < *ntaps2) return M17HIP_EINVAL;
+    wide_default1(decim1, 1, taps1);
+    resample_default2(up, down, taps2);
+    return M17HIP_OK;
+}
+int m17hip_wide_resample_ratio(uint32_t rate_hz, uint32_t* decim1, uint32_t* up, uint32_t* down)
+{
+    if (!rate_hz || !decim1 || !up || !down) return M17HIP_EINVAL;
+    const uint32_t g = gcd_u32(rate_hz, 48000), N = rate_hz / g, U = 48000 / g;   // rate / 48000 = N / U in lowest terms
+    if (U > 32) return M17HIP_EINVAL;
+    uint32_t best = 0;
+    for (uint32_t d = 16; d >= 1 && !best; --d) if (N % d == 0 && N / d <= 125 && N / d >= 2 * U) best = d;   // (the intermediate rate at or above 96 kSPS)
+    for (uint32_t d = 16; d >= 1 && !best; --d) if (N % d == 0 && N / d <= 125 && N / d >= U) best = d;
+    if (!best) return M17HIP_EINVAL;
+    *decim1 = best; *up = U; *down = N / best;
+    return M17HIP_OK;
+}
+int m17hip_wide_resample(m17hip_ctx* c, uint32_t sources, uint32_t decim1, const float* taps1, uint32_t ntaps1, uint32_t up, uint32_t down, const float* taps2,
+                         uint32_t ntaps2, int iq_format)
+{
+    if (!c || sources < 1 || sources > 256 || !resample_shape(decim1, up, down)) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    std::vector<float> h1(decim1 == 1 ? 1 : 8 * decim1 + 1), h2(32 * down + 1);
+    wide_default1(decim1, 1, h1.data());
+    resample_default2(up, down, h2.data());
+    if (!wide_stage_taps(taps1, ntaps1, 256, h1) || !wide_stage_taps(taps2, ntaps2, 4096, h2)) return M17HIP_EINVAL;
+    return wide_setup(c, sources, iq_format, decim1, h1, 0, h2, 0, up, down);
 }
 int m17hip_wide_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* fcw, uint32_t n)
 {

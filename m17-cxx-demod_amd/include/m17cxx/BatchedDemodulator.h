@@ -92,6 +92,18 @@ public:
     {
         check(m17hip_wide_config2(ctx_, sources, decim1, taps1, ntaps1, decim2, taps2, ntaps2, iq_format), "m17hip_wide_config2");
     }
+    // The same with a second stage that resamples by up / down, for sources whose rate is no integer multiple of 48 kSPS (m17hip_wide_resample):
+    // 48000 * decim1 * down / up samples per second (wide_resample_ratio finds the three for a rate), `samples` a multiple of `up`, every row
+    // samples / up * down * decim1 complex samples; frequency words are wide_fcw_rate(offset_hz, rate_hz).  It and the other configurations replace one another.
+    void wide_resample(uint32_t sources, uint32_t decim1, uint32_t up, uint32_t down, int iq_format = M17HIP_IQ_I16, const float* taps1 = nullptr,
+                       uint32_t ntaps1 = 0, const float* taps2 = nullptr, uint32_t ntaps2 = 0)
+    {
+        check(m17hip_wide_resample(ctx_, sources, decim1, taps1, ntaps1, up, down, taps2, ntaps2, iq_format), "m17hip_wide_resample");
+    }
+    static void wide_resample_ratio(uint32_t rate_hz, uint32_t& decim1, uint32_t& up, uint32_t& down)
+    {
+        if (m17hip_wide_resample_ratio(rate_hz, &decim1, &up, &down) != M17HIP_OK) throw std::invalid_argument("wide_resample_ratio: no configuration has this rate");
+    }
     // S sources split into `bins` channels each on a raster of 48000 * decim / bins Hz by the polyphase channeliser (m17hip_wide_raster; decim 1..64, every
     // row samples * decim complex samples); channels are named by wide_raster_channels(source, bin), wide_bin gives the bin of an offset.  It replaces
     // wide_config and wide_config2 and is replaced by them.
@@ -119,6 +131,12 @@ public:
         if (std::fabs(b - k) > 1e-9 * std::max(1.0, std::fabs(b)) || k < -(double)(bins / 2) || k > (double)((bins - 1) / 2))
             throw std::invalid_argument("wide_bin: the offset is not a channel of the raster");
         return (int32_t)k;
+    }
+    // ... at any rate: under wide_resample the source runs at 48000 * decim1 * down / up
+    static int32_t wide_fcw_rate(double offset_hz, double rate_hz)
+    {
+        const double w = std::nearbyint(offset_hz / rate_hz * 4294967296.0);
+        return (int32_t)(uint32_t)(int64_t)w;
     }
     void wide_channels(const uint32_t* source, const int32_t* fcw, uint32_t n) { check(m17hip_wide_channels(ctx_, source, fcw, n), "m17hip_wide_channels"); }
     // the frequency word of an offset in Hz from the source's centre, rounded to the nearest word

@@ -162,6 +162,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim;
         wide_r1_ = 0;
+        wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
         wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, decim);
         if (gpu_) {
@@ -197,6 +198,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim1 * decim2;
         wide_r1_ = decim1;
+        wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
         wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw(offset_hz, wide_decim_);
         if (gpu_) {
@@ -219,6 +221,43 @@ struct M17Demodulator
         }
         wide_u_.assign(2 * (wide_taps2_.size() - 1), 0.0f);   // (the u in front of the feed: made from that history with the first output)
     }
+    // The same out of a feed at ANY rate m17hip_wide_resample_ratio has a shape for (2.048 MSPS is 16 x 3 / 8): the second stage resamples by up / down
+    // (m17hip_wide_resample); empty taps: that stage's default taps (m17hip_wide_resample_default_taps).  Whole groups of down * decim1 samples — `up`
+    // outputs each — are buffered.  The host form is core::ddc_resample, a group at a time.  Throws std::invalid_argument for a rate without a shape.
+    void wide_rate(uint32_t rate_hz, double offset_hz, std::vector<float> taps1 = {}, std::vector<float> taps2 = {})
+    {
+        uint32_t decim1 = 0, up = 0, down = 0;
+        BatchedDemodulator::wide_resample_ratio(rate_hz, decim1, up, down);
+        if (taps1.empty() || taps2.empty()) {
+            uint32_t n1 = 0, n2 = 0;
+            std::vector<float> d1(8 * 16 + 1), d2(32 * 125 + 1);
+            if (m17hip_wide_resample_default_taps(decim1, up, down, d1.data(), (uint32_t)d1.size(), &n1, d2.data(), (uint32_t)d2.size(), &n2) != M17HIP_OK)
+                throw std::runtime_error("m17hip_wide_resample_default_taps");
+            if (taps1.empty()) taps1.assign(d1.begin(), d1.begin() + n1);
+            if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
+        }
+        wide_decim_ = decim1 * down;   // (the samples of a group)
+        wide_r1_ = decim1;
+        wide_up_ = up; wide_down_ = down;
+        raster_m_ = 0;
+        wide_fcw_ = (uint32_t)BatchedDemodulator::wide_fcw_rate(offset_hz, (double)rate_hz);
+        if (gpu_) {
+            flush();
+            const uint32_t source = 0;
+            const int32_t fcw = (int32_t)wide_fcw_;
+            gpu_->wide_resample(1, decim1, up, down, M17HIP_IQ_F32, taps1.data(), (uint32_t)taps1.size(), taps2.data(), (uint32_t)taps2.size());
+            gpu_->wide_channels(&source, &fcw, 1);
+            wide_buffer_.clear();
+            return;
+        }
+        wide_taps_ = std::move(taps1);
+        wide_taps2_ = std::move(taps2);
+        wide_m_ = 0;
+        const size_t J2 = (wide_taps2_.size() + up - 1) / up, H = (J2 - 1) * decim1 + wide_taps_.size() - 1;
+        wide_mixed_.assign(2 * H, 0.0f);   // the feed itself as (re, im) — ddc_resample mixes it — behind its zero history
+        wide_scratch_.resize(2 * (H + wide_decim_));
+        wide_u_.resize(2 * (J2 - 1 + down));
+    }
     // The same for a channel ON A RASTER of `bins` channels spaced 48000 * decim / bins Hz (decim 1..64; m17hip_wide_raster: the polyphase channeliser):
     // bin `bin`, -bins/2 <= bin < bins/2, of the feed; taps empty: the default taps (m17hip_wide_raster_default_taps).  The host form computes the same
     // words from detail/core.h (chan_fold, chan_pass1, chan_pass2) over the library's twiddle table.
@@ -234,6 +273,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim;
         wide_r1_ = 0;
+        wide_up_ = 1; wide_down_ = 0;
         if (gpu_) {
             flush();
             const uint32_t source = 0;
@@ -289,6 +329,19 @@ struct M17Demodulator
             demodState = (DemodState)cpu_->state();
             return;
         }
+        if (cpu_ && wide_down_) {   // a whole group of down * decim1 samples makes `up` outputs
+            wide_mixed_.push_back(i); wide_mixed_.push_back(q);
+            if (++wide_m_ % wide_decim_ != 0) return;
+            const uint32_t L1 = (uint32_t)wide_taps_.size(), L2 = (uint32_t)wide_taps2_.size();
+            const size_t H = (size_t)((L2 + wide_up_ - 1) / wide_up_ - 1) * wide_r1_ + L1 - 1;
+            float z[2 * 32], y[32];
+            core::ddc_resample(wide_taps_.data(), L1, wide_r1_, wide_taps2_.data(), L2, wide_up_, wide_down_, wide_mixed_.data() + wide_mixed_.size() - 2 * (size_t)wide_decim_,
+                               wide_fcw_, (uint32_t)(wide_m_ - wide_decim_), wide_up_, wide_scratch_.data(), wide_u_.data(), z, iq_prev_, iq_gain_, y);
+            if (wide_mixed_.size() > 2 * (H + 65536)) wide_mixed_.erase(wide_mixed_.begin(), wide_mixed_.end() - 2 * H);
+            for (uint32_t k = 0; k < wide_up_; ++k) cpu_->step((FloatType)y[k]);
+            demodState = (DemodState)cpu_->state();
+            return;
+        }
         if (cpu_) {
             float re, im;
             core::ddc_mix(i, q, wide_fcw_, (uint32_t)wide_m_, re, im);
@@ -323,7 +376,7 @@ struct M17Demodulator
         if (!buffer_.empty()) run_block();
         if (!iq_buffer_.empty()) run_iq_block();
         wide_buffer_.push_back({i, q});
-        if (wide_buffer_.size() == (size_t)block_ * wide_decim_) run_wide_block();
+        if (wide_buffer_.size() == (size_t)(block_ / wide_up_) * wide_decim_) run_wide_block();
     }
 
     // demodulate what is buffered (end of input); safe to call at any time (wideband samples short of one output stay buffered)
@@ -394,7 +447,7 @@ private:
     void run_wide_block()
     {
         const size_t n = wide_buffer_.size() / wide_decim_;
-        gpu_->upload_wide(wide_buffer_.data(), 1, (uint32_t)n, n * wide_decim_, iq_gain_);
+        gpu_->upload_wide(wide_buffer_.data(), 1, (uint32_t)(n * wide_up_), n * wide_decim_, iq_gain_);
         wide_buffer_.erase(wide_buffer_.begin(), wide_buffer_.begin() + n * wide_decim_);
         if (survey_stride_ && survey_report_) {   // (the plane of the block just uploaded: the fetch waits for its survey kernels, not for the run)
             survey_power_.resize(raster_m_);
@@ -433,6 +486,8 @@ private:
     std::vector<float> wide_taps2_, wide_u_;         // two stages: the second filter and the feed between the two
     uint32_t wide_decim_ = 0, wide_fcw_ = 0;         // (0: wide_config has not been called); wideband samples per output
     uint32_t wide_r1_ = 0;                           // the first stage's decimation (0: one stage)
+    uint32_t wide_up_ = 1, wide_down_ = 0;           // wide_rate: outputs per group of wide_decim_ samples, and the second stage's `down` (0: integer stages)
+    std::vector<float> wide_scratch_;                // wide_rate's host form: the mixed samples of one call
     uint32_t raster_m_ = 0, raster_m1_ = 0, raster_m2_ = 0, raster_k_ = 0;   // wide_raster: the bins (0: a tuner), their factors and the bin mod M
     uint32_t survey_stride_ = 0;                     // wide_survey: 0 = off
     survey_callback_t survey_report_;

@@ -149,6 +149,40 @@ M17_HD void ddc_fir2(const float* h1, uint32_t L1, uint32_t R1, const float* h2,
     for (int64_t p = -(int64_t)fresh; p < (int64_t)n * R2; ++p) ddc_fir(h1, L1, mixed + 2 * (p * R1 + R1 - 1), u[2 * p], u[2 * p + 1]);
     for (uint32_t m = 0; m < n; ++m) ddc_fir(h2, L2, u + 2 * ((int64_t)m * R2 + R2 - 1), z[2 * m], z[2 * m + 1]);
 }
+// A second stage that RESAMPLES by U / D (m17hip_wide_resample; U <= D, coprime): the u zero-stuffed by U, low-passed with h2 at 48000 D, the sample at
+// n D + D - 1 kept — with the products of the stuffed zeroes left out:
+//   N_n = n D + D - 1 (64 bits),  i0 = N_n mod U,  b = N_n div U,  z[n] = sum_{j : i0 + U j < L2} h2[i0 + U j] u[b - j]
+// the two chains of ddc_tap from +0, j ascending.  At U = 1 that is ddc_fir2's z word for word (i0 = 0, b = n D + D - 1).  n is counted within a block and a
+// block holds a multiple of U outputs — (n / U) D u —, so the phase never depends on the feed's history.
+// The whole host form of one block, composed of ddc_mix, ddc_tap and fm_discriminate and nothing else.  x: the block's converted samples (re, im), x[0] its
+// sample 0, with the H = (J2 - 1) R1 + L1 - 1 samples in front of it (J2 = ceil(L2 / U)), (n / U) D R1 behind; `count` the feed's index of sample 0.
+// Scratch: mixed [H + (n / U) D R1][2] and u [J2 - 1 + (n / U) D][2].  carry[2]: the z in front of output 0, on return the block's last z.  y[n]; z [n][2].
+M17_HD void ddc_resample(const float* h1, uint32_t L1, uint32_t R1, const float* h2, uint32_t L2, uint32_t U, uint32_t D, const float* x, uint32_t fcw,
+                         uint32_t count, uint32_t n, float* mixed, float* u, float* z, float* carry, float gain, float* y)
+{
+    const int64_t J2 = (L2 + U - 1) / U, H = (J2 - 1) * R1 + L1 - 1, NU = (int64_t)(n / U) * D;
+    float* mx = mixed + 2 * H;
+    float* uu = u + 2 * (J2 - 1);
+    for (int64_t k = -H; k < NU * R1; ++k) ddc_mix(x[2 * k], x[2 * k + 1], fcw, count + (uint32_t)k, mx[2 * k], mx[2 * k + 1]);
+    for (int64_t p = 1 - J2; p < NU; ++p) {
+        float re = 0.0f, im = 0.0f;
+        const float* newest = mx + 2 * (p * R1 + R1 - 1);
+        for (uint32_t i = 0; i < L1; ++i) ddc_tap(h1[i], newest[-2 * (int64_t)i], newest[-2 * (int64_t)i + 1], re, im);
+        uu[2 * p] = re; uu[2 * p + 1] = im;
+    }
+    float pre = carry[0], pim = carry[1];
+    for (uint32_t m = 0; m < n; ++m) {
+        const uint64_t N = (uint64_t)m * D + D - 1;
+        const int64_t b = (int64_t)(N / U);
+        float re = 0.0f, im = 0.0f;
+        int64_t j = 0;
+        for (uint32_t i = (uint32_t)(N % U); i < L2; i += U, ++j) ddc_tap(h2[i], uu[2 * (b - j)], uu[2 * (b - j) + 1], re, im);
+        z[2 * m] = re; z[2 * m + 1] = im;
+        y[m] = fm_discriminate(re, im, pre, pim, gain);
+        pre = re; pim = im;
+    }
+    carry[0] = pre; carry[1] = pim;
+}
 
 // ---- a-1c: the channeliser (m17hip_wide_raster): M channels on a raster, spaced rate / M.  The single-stage tuner's z with the oscillator exactly on the
 // raster, z_k[n] = sum_i h[i] x[m_n - i] exp(-2 pi j k (m_n - i) / M), computed as a FOLD of the taps into M partial sums — the phase of tap i depends on

@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -75,6 +75,7 @@ EXPORTS = [
     "m17hip_wide_default_taps2", "m17hip_wide_config2",
     "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
     "m17hip_wide_survey", "m17hip_wide_survey_fetch",
+    "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
@@ -186,6 +187,29 @@ def wide_raster_default_taps(decim):
     return taps[: n.value].copy()
 
 
+def wide_resample_default_taps(decim1, up, down):
+    """The default taps of wide_resample's two stages: (float32 [8 * decim1 + 1] — [1] at decim1 = 1 —, float32 [32 * down + 1] of DC gain `up`; at
+    up = 1 wide_raster_default_taps(down) word for word) — m17hip_wide_resample_default_taps (no context, no GPU)."""
+    n1, n2 = C.c_uint32(0), C.c_uint32(0)
+    t1, t2 = np.zeros(8 * 16 + 1, dtype=np.float32), np.zeros(32 * 125 + 1, dtype=np.float32)
+    code = load_library().m17hip_wide_resample_default_taps(C.c_uint32(decim1), C.c_uint32(up), C.c_uint32(down), _ptr(t1), C.c_uint32(t1.size),
+                                                            C.byref(n1), _ptr(t2), C.c_uint32(t2.size), C.byref(n2))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_resample_default_taps: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return t1[: n1.value].copy(), t2[: n2.value].copy()
+
+
+def wide_resample_ratio(rate_hz):
+    """(decim1, up, down) of wide_resample for a source of `rate_hz` samples per second: rate_hz = 48000 * decim1 * down / up —
+    m17hip_wide_resample_ratio (no context, no GPU).  Raises M17HipError for a rate no accepted configuration has."""
+    rate = int(rate_hz)
+    d1, up, down = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    code = load_library().m17hip_wide_resample_ratio(C.c_uint32(rate), C.byref(d1), C.byref(up), C.byref(down)) if 0 < rate < (1 << 32) else -1
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_resample_ratio: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return d1.value, up.value, down.value
+
+
 def wide_raster_twiddles(bins):
     """The channeliser's twiddle table for a raster of `bins`: complex64 [bins], exp(-2 pi j k / bins) made in double and rounded — the very words the
     device computes with; m17hip_wide_raster_twiddles (no context, no GPU)."""
@@ -228,7 +252,8 @@ def wide_raster_occupied(power, margin_db):
 
 
 def wide_fcw(offset_hz, decim):
-    """The signed 32-bit frequency word of an offset in Hz at 48000 * decim samples per second, rounded to the nearest word (wide_channels)."""
+    """The signed 32-bit frequency word of an offset in Hz at 48000 * decim samples per second, rounded to the nearest word (wide_channels).  `decim` need
+    not be an integer: under wide_resample it is decim1 * down / up."""
     w = int(round(float(offset_hz) / (48000.0 * decim) * 4294967296.0))
     return (w + (1 << 31)) % (1 << 32) - (1 << 31)
 
@@ -415,6 +440,7 @@ class Context:
         self._chk(self.lib.m17hip_wide_config(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_int(IQ_I16 if fmt is None else fmt), _ptr(t),
                                               C.c_uint32(0 if t is None else t.size)))
         self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+        self._wide_up = 1
 
     def wide_config2(self, sources, decim1, decim2, fmt=None, taps1=None, taps2=None):
         """`sources` wide IQ streams at 48000 * decim1 * decim2 samples per second (each 1..16) in format `fmt`, decimated in two stages: low-passed with
@@ -425,6 +451,20 @@ class Context:
         self._chk(self.lib.m17hip_wide_config2(self.h, C.c_uint32(sources), C.c_uint32(decim1), _ptr(t1), C.c_uint32(0 if t1 is None else t1.size),
                                                C.c_uint32(decim2), _ptr(t2), C.c_uint32(0 if t2 is None else t2.size), C.c_int(IQ_I16 if fmt is None else fmt)))
         self._wide = (int(sources), int(decim1) * int(decim2), IQ_I16 if fmt is None else int(fmt))
+        self._wide_up = 1
+
+    def wide_resample(self, sources, decim1, up, down, fmt=None, taps1=None, taps2=None):
+        """`sources` wide IQ streams at 48000 * decim1 * down / up samples per second (decim1 1..16, up 1..32, down 1..125, up <= down and coprime:
+        wide_resample_ratio finds them for a rate) in format `fmt`: low-passed with `taps1` and every decim1-th sample kept, then resampled by up / down
+        through `taps2` (None: that stage of wide_resample_default_taps(decim1, up, down)).  Replaces the other three configurations and is replaced by
+        them; the frequency words are wide_fcw(offset_hz, decim1 * down / up); a block holds a multiple of `up` outputs — m17hip_wide_resample."""
+        t1 = None if taps1 is None else np.ascontiguousarray(taps1, dtype=np.float32).reshape(-1)
+        t2 = None if taps2 is None else np.ascontiguousarray(taps2, dtype=np.float32).reshape(-1)
+        self._chk(self.lib.m17hip_wide_resample(self.h, C.c_uint32(sources), C.c_uint32(decim1), _ptr(t1), C.c_uint32(0 if t1 is None else t1.size),
+                                                C.c_uint32(up), C.c_uint32(down), _ptr(t2), C.c_uint32(0 if t2 is None else t2.size),
+                                                C.c_int(IQ_I16 if fmt is None else fmt)))
+        self._wide = (int(sources), int(decim1) * int(down), IQ_I16 if fmt is None else int(fmt))   # (samples per group of `up` outputs)
+        self._wide_up = int(up)
 
     def wide_raster(self, sources, decim, bins, fmt=None, taps=None):
         """`sources` wide IQ streams at 48000 * decim samples per second (decim 1..64) in format `fmt`, every one split into `bins` channels spaced
@@ -434,6 +474,7 @@ class Context:
         self._chk(self.lib.m17hip_wide_raster(self.h, C.c_uint32(sources), C.c_uint32(decim), C.c_uint32(bins), C.c_int(IQ_I16 if fmt is None else fmt),
                                               _ptr(t), C.c_uint32(0 if t is None else t.size)))
         self._wide = (int(sources), int(decim), IQ_I16 if fmt is None else int(fmt))
+        self._wide_up = 1
         self._wide_bins = int(bins)
 
     def wide_raster_channels(self, source, bin):
@@ -474,7 +515,8 @@ class Context:
         self._chk(self.lib.m17hip_wide_channels(self.h, _ptr(src) if src.size else None, w.ctypes.data_as(C.c_void_p) if w.size else None, C.c_uint32(src.size)))
 
     def upload_wide(self, x, gain=1.0, staged=False, channels=None):
-        """The input of the next run from one block of every source: numpy complex64 [S][W], int16 or uint8 [S][W][2] (W = outputs * decim; the dtype must
+        """The input of the next run from one block of every source: numpy complex64 [S][W], int16 or uint8 [S][W][2] (W = outputs * decim — under
+        wide_resample outputs / up * down * decim1: a whole number of groups of down * decim1 samples, each `up` outputs —; the dtype must
         be the configured format), or a torch tensor of those ON THE DEVICE, COMPLETE when this is called (see upload_iq).  `channels` (default: the
         context's) are tuned, filtered, decimated and discriminated into the float input slab.  staged: for the NEXT run, on the copy stream (host memory
         then has to be pinned and kept unmodified until upload_wait; so has a device tensor)."""
@@ -500,7 +542,7 @@ class Context:
             raise TypeError(f"a block of the configured format {fmt} with {S} sources and a multiple of {R} samples per source")
         self._keep = a   # (a staged block is read until upload_wait)
         name = "m17hip_upload_wide" + ("_device" if dev else "") + ("_async" if staged else "")
-        self._upload_wide_raw(name, ptr, self.max_channels if channels is None else channels, a.shape[1] // R, a.shape[1], gain)
+        self._upload_wide_raw(name, ptr, self.max_channels if channels is None else channels, a.shape[1] // R * getattr(self, "_wide_up", 1), a.shape[1], gain)
 
     def _upload_wide_raw(self, name, ptr, channels, samples, pitch, gain):
         self.C, self.T = int(channels), int(samples)

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --raster M [--survey STRIDE]] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -19,7 +19,12 @@ and no mixing term: there is no oscillator.
 With --survey STRIDE beside --raster the same blocks are then timed once more with the raster survey on (m17hip_wide_survey; chan_survey_kernel and
 chan_survey_sum_kernel, csrc/m17_chan_survey_kernels.hpp; library timer "survey"): the channeliser's time with the survey on and the survey's own, against
 the survey's floor, counted per source and SURVEY TIME (outputs / STRIDE of them): L packed fma for the fold, M M2 steps of 4 plain fma for pass 1 and
-M M1 for pass 2 — all M bins."""
+M M1 for pass 2 — all M bins.
+With --resample UP DOWN it is the resampling tuner of m17hip_wide_resample (resample_kernel, csrc/m17_resample_kernels.hpp; library timer "resample") at
+`decim` x DOWN / UP with the default taps of both stages (2.048 MSPS: --resample 3 8 ... 16); outputs are rounded down to a multiple of UP.  The filter term
+of its floor is C T (DOWN / UP L1 + L2 / UP) packed fma — DOWN / UP first-stage sums per output and the L2 / UP taps of the second stage that meet a sample —
+and the mixing term C T decim DOWN / UP samples.  In the same call the UNCHANGED tune2_kernel is then timed on the same buffer at the neighbouring integer
+shape decim x round(DOWN / UP) (at UP = 1 the very same shape, where the two kernels compute the same words): "neighbour" in the result."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -40,6 +45,12 @@ if "--raster" in ARGS:
     k = ARGS.index("--raster")
     RASTER = int(ARGS[k + 1])
     del ARGS[k:k + 2]
+UP = DOWN = 0   # (0: integer stages)
+if "--resample" in ARGS:
+    k = ARGS.index("--resample")
+    UP, DOWN = int(ARGS[k + 1]), int(ARGS[k + 2])
+    del ARGS[k:k + 3]
+    assert not R2 and not RASTER, "--resample UP DOWN goes without --decim2 and --raster"
 SURVEY = 0   # (0: not timed)
 if "--survey" in ARGS:
     k = ARGS.index("--survey")
@@ -56,6 +67,12 @@ L = 32 * R + 1
 RATE = R * (R2 if R2 else 1)   # wideband samples per output
 if R2:
     L, L2 = (t.size for t in m17hip.wide_default_taps2(R, R2))
+NEIGHBOUR = 0
+if UP:
+    T -= T % UP
+    L, L2 = (t.size for t in m17hip.wide_resample_default_taps(R, UP, DOWN))
+    NEIGHBOUR = min(max(int(round(DOWN / UP)), 1), 16)   # tune2's decim2 beside it
+ROW = T // UP * DOWN * R if UP else T * RATE   # wideband samples of a source row
 MIX_OPS = 40
 DEMOD_STEP_MS = (20.0, 23.0)   # the demodulation step of 4096 channels x 480 000 samples (README): scaled to this shape below
 
@@ -82,7 +99,8 @@ class Clocks(threading.Thread):
 ctx = m17hip.Context(C, T)
 stream = ctx.torch_stream()
 g = torch.Generator(device='cuda').manual_seed(609)
-x = torch.randint(-20000, 20000, (S, T * RATE, 2), dtype=torch.int16, device='cuda', generator=g)
+x = torch.randint(-20000, 20000, (S, max(ROW, T * R * NEIGHBOUR), 2), dtype=torch.int16, device='cuda', generator=g)
+PITCH = x.shape[1]
 torch.cuda.synchronize()
 rng = np.random.default_rng(609)
 if RASTER:
@@ -90,14 +108,17 @@ if RASTER:
     ctx.wide_raster_channels(np.repeat(np.arange(S), PER), np.concatenate([rng.permutation(RASTER)[:PER] - RASTER // 2 for _ in range(S)]))
 elif R2:
     ctx.wide_config2(S, R, R2, m17hip.IQ_I16)
+elif UP:
+    ctx.wide_resample(S, R, UP, DOWN, m17hip.IQ_I16)
 else:
     ctx.wide_config(S, R, m17hip.IQ_I16)
 if not RASTER:
-    ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATE) for f in rng.uniform(-24000.0 * RATE, 24000.0 * RATE, C)])
+    RATIO = R * DOWN / UP if UP else RATE
+    ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATIO) for f in rng.uniform(-24000.0 * RATIO, 24000.0 * RATIO, C)])
 
 
 def call():
-    ctx.upload_wide_device(x.data_ptr(), C, T, T * RATE)
+    ctx.upload_wide_device(x.data_ptr(), C, T, PITCH)
 
 
 clocks = Clocks()
@@ -113,7 +134,19 @@ for _ in range(REP):
     b.record(stream)
     b.synchronize()
     ev.append(a.elapsed_time(b))
-ms, n = ctx.timing_get("channelise" if RASTER else "tune2" if R2 else "tune")
+ms, n = ctx.timing_get("channelise" if RASTER else "tune2" if R2 else "resample" if UP else "tune")
+neighbour = {}
+if UP:   # tune2_kernel on the same buffer and table at decim x NEIGHBOUR: a warm-up block, then REP timed ones
+    ctx.wide_config2(S, R, NEIGHBOUR, m17hip.IQ_I16)
+    ctx.reset()
+    call()
+    ctx.timing_reset()
+    for _ in range(REP):
+        call()
+    ms2, n2 = ctx.timing_get("tune2")
+    l1n, l2n = (t.size for t in m17hip.wide_default_taps2(R, NEIGHBOUR))
+    neighbour = {"decim2": NEIGHBOUR, "taps": l1n, "taps2": l2n, "launches": n2, "kernel_ms": round(ms2 / n2, 3),
+                 "cycles": C * T * (NEIGHBOUR * l1n + l2n) / 64 * 4 + C * T * R * NEIGHBOUR * MIX_OPS / 64 * 2}
 survey = {}
 if SURVEY:   # the same blocks once more with the survey on: a warm-up block (the scratch and the planes are allocated), then REP timed ones
     ctx.wide_survey(SURVEY)
@@ -131,6 +164,9 @@ cus = torch.cuda.get_device_properties(0).multi_processor_count
 mhz = max(clocks.seen.values()) if clocks.seen else 2400
 FILTER = C * T * (R2 * L + L2 if R2 else L) / 64 * 4
 cycles = FILTER + C * T * RATE * MIX_OPS / 64 * 2
+if UP:
+    FILTER = C * T * (DOWN / UP * L + L2 / UP) / 64 * 4
+    cycles = FILTER + C * T * R * DOWN / UP * MIX_OPS / 64 * 2
 if RASTER:
     M2 = max(d for d in range(1, RASTER + 1) if RASTER % d == 0 and d * d <= RASTER)
     M1 = RASTER // M2
@@ -142,10 +178,13 @@ if SURVEY:
     survey["floor_ms"] = round(sc / (4 * cus * mhz * 1e6) * 1e3, 4)
     survey["survey_over_floor"] = round(survey["survey_ms"] / (sc / (4 * cus * mhz * 1e6) * 1e3), 2)
 kernel_ms = ms / n
+if UP:
+    nf = neighbour.pop("cycles") / (4 * cus * mhz * 1e6) * 1e3
+    neighbour.update(floor_ms=round(nf, 3), kernel_over_floor=round(neighbour["kernel_ms"] / nf, 2), resample_over_tune2=round(kernel_ms / neighbour["kernel_ms"], 3))
 step = [v * T / 480000.0 * C / 4096.0 for v in DEMOD_STEP_MS]
 print(json.dumps({
     "sources": S, "channels": C, "outputs": T, "decim": R, "taps": L, **({"decim2": R2, "taps2": L2} if R2 else {}),
-    **({"raster": RASTER} if RASTER else {}), "repeats": REP, "launches": n,
+    **({"raster": RASTER} if RASTER else {}), **({"up": UP, "down": DOWN, "taps2": L2, "neighbour": neighbour} if UP else {}), "repeats": REP, "launches": n,
     "kernel_ms": round(kernel_ms, 3), "stream_ms": [round(v, 3) for v in ev], "stream_ms_median": round(float(np.median(ev)), 3),
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
