@@ -6,6 +6,7 @@ words of the uncut feed.  6: the feature means something — three FM transmissi
 calls promise without a GPU."""
 import ctypes as C
 import os
+import shutil
 import subprocess
 from math import gcd
 
@@ -56,22 +57,34 @@ def test_up_1_gives_the_two_stage_tuners_words(case):
 #   |y_host - y_f64| (mod 2 pi) <= gain (2 bound / min|z| + 2^-20) wherever z[n] and z[n-1] of the reference both exceed 8 bound (wide_lib.f64_check_y's rule).
 # At most 1 % of a case's outputs may fall under that floor (tests/test_wide2_input.py's cap): asserted on the float64 reference alone.
 F64_CASES = [(8, 3, 16), (5, 12, 125), (5, 2, 25), (1, 24, 125)]   # (decim1, up, down)
+# (decim1, up, down, ntaps1, ntaps2) of tests/test_gpu_resample_tiles.py: every class with exactly 8 taps, and 32 classes of 8 or 9 taps behind a stage 1 that
+# does nothing.  Hamming windows (wide_lib.hamming_taps: the carrier is mixed to 0 Hz, inside any low-pass), the second one times `up` so that every branch has
+# a DC gain near 1
+F64_TAPPED = [(2, 3, 4, 9, 24), (1, 32, 33, 1, 265)]
 F64_N = 1200
 F64_GAIN = 1.25
 F64_WORDS = {"generic": -0x12345679, "+2^30": 1 << 30}
 F64_EXCLUDED_CAP = 0.01
 
 
+def _f64_taps(case):
+    if len(case) == 3:
+        return m17hip.wide_resample_default_taps(*case)
+    R1, U, D, L1, L2 = case
+    return wl.hamming_taps(L1), (U * wl.hamming_taps(L2).astype(np.float64)).astype(np.float32)
+
+
 def _f64_input(case, fcw, fmt=wl.IQ_I16):
-    R1, U, D = case
+    R1, U, D = case[:3]
     n = -(-F64_N // U) * U
     return wl.carriers(R1 * D, [fcw], n // U, fmt, seed=6151 + D), n
 
 
-@pytest.mark.parametrize("case", F64_CASES, ids=lambda c: "{}_{}over{}".format(*c))
+@pytest.mark.parametrize("case", F64_CASES + F64_TAPPED, ids=lambda c: "{}_{}over{}".format(*c) + ("_{}_{}".format(*c[3:]) if len(c) > 3 else ""))
 def test_the_resampler_is_within_derived_bounds_of_float64(case):
-    R1, U, D = case
-    taps1, taps2 = m17hip.wide_resample_default_taps(R1, U, D)
+    R1, U, D = case[:3]
+    taps1, taps2 = _f64_taps(case)
+    assert len(case) == 3 or (taps1.size, taps2.size) == case[3:]
     worst = [0.0, 0.0, 0.0]
     for name, fcw in F64_WORDS.items():
         x, n = _f64_input(case, fcw)
@@ -303,9 +316,22 @@ def test_python_refuses_a_block_that_is_no_whole_number_of_groups():
             ctx.upload_wide(bad)
 
 
+# (decim1, up, down, ntaps1, ntaps2) -> (G, Q, LDS bytes) of every shape the device tests of the tile's forms, of the count across 2^32 and of the calls under
+# the resampler rest on (tests/test_gpu_resample_tiles.py, test_gpu_wide_count_wrap.py, test_gpu_call_orders_resample.py): those choose their block sizes from
+# G, so a rule that gives another tile fails here and there, and does not go on passing without its edges.  The last but one takes every byte of the LDS.
+TILES = {(2, 2, 3, 5, 7): (255, 64, 14392), (3, 5, 6, 7, 11): (255, 64, 28696), (2, 2, 3, 5, 12): (255, 64, 14392), (2, 3, 4, 9, 24): (255, 64, 18520),
+         (1, 3, 4, 1, 25): (255, 64, 16440), (1, 3, 4, 1, 23): (255, 64, 16408),
+         (1, 32, 33, 1, 265): (121, 64, 65248), (1, 12, 31, 1, 249): (183, 64, 65264), (1, 12, 23, 1, 185): (226, 64, 65528), (1, 32, 91, 1, 729): (63, 64, 64784),
+         (16, 2, 115, 256, 4096): (19, 57, 65464), (16, 2, 15, 129, 4096): (116, 63, 65512), (16, 2, 7, 256, 4096): (243, 58, 65536),
+         (16, 3, 8, 33, 65): (255, 64, 55672), (16, 3, 8, 129, 257): (255, 64, 56952), (5, 12, 125, 41, 4001): (47, 64, 65088)}
+
+
 def test_the_restated_tile_rule():
     """resample_lib.tile against the figures the kernel's comment and NOTES.md record, and over every accepted shape at the longest filters: there is a tile,
-    it fits 64 KB, and a tile of one group with one u per chain would fit too."""
+    it fits 64 KB, and a tile of one group with one u per chain would fit too.  TILES: the shapes the device tests choose their edges from."""
+    for (R1, U, D, L1, L2), e in TILES.items():
+        assert rl.tile(L1, R1, L2, U, D) == e, (R1, U, D, L1, L2)
+    assert max(e[2] for e in TILES.values()) == rl.LDS_LIMIT
     table = {(16, 3, 8, 129, 257): (255, 64), (10, 1, 5, 81, 161): (255, 64), (5, 12, 125, 41, 4001): (47, 64), (16, 1, 125, 256, 4096): (13, 34),
              (16, 32, 125, 256, 4096): (22, 64)}
     for (R1, U, D, L1, L2), e in table.items():
@@ -315,6 +341,34 @@ def test_the_restated_tile_rule():
         for U in (u for u in range(1, min(D, 32) + 1) if gcd(u, D) == 1):
             G, Q, lds = rl.tile(256, 16, 4096, U, D)
             assert 1 <= G <= 255 and 1 <= Q <= 64 and lds <= 65536, (U, D, G, Q, lds)
+
+
+HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+
+
+@pytest.mark.skipif(HIPCC is None, reason="hipcc not present")
+def test_the_restated_tile_rule_is_the_librarys(tmp_path):
+    """resample_lib.tile is a RESTATEMENT, and the device tests choose their blocks' sizes from it: tests/cxx/resample_tile.cpp includes
+    csrc/m17_resample_kernels.hpp and prints what resample_groups, resample_q and resample_lds_bytes themselves give (host code, no HIP call).  Held against
+    the restatement over TILES, every accepted ratio at the longest filters, and 300 random accepted shapes."""
+    exe = tmp_path / "resample_tile"
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-I", os.path.join(iq.ROOT, "m17-cxx-demod_amd", "csrc"),
+                        "-I", os.path.join(iq.ROOT, "m17-cxx-demod_amd", "include"), "-I", os.path.join(iq.ROOT, "include"),
+                        os.path.join(iq.ROOT, "tests", "cxx", "resample_tile.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    shapes = list(TILES)
+    shapes += [(16, U, D, 256, 4096) for D in range(1, 126) for U in range(1, min(D, 32) + 1) if gcd(U, D) == 1]
+    rng = np.random.default_rng(6171)
+    swept = len(shapes)
+    while len(shapes) < swept + 300:
+        R1, U, D, L1, L2 = (int(rng.integers(lo, hi + 1)) for lo, hi in ((1, 16), (1, 32), (1, 125), (1, 256), (1, 4096)))
+        if U <= D and gcd(U, D) == 1:
+            shapes.append((R1, U, D, L1, L2))
+    out = subprocess.run([str(exe)] + [str(v) for s in shapes for v in s], capture_output=True, text=True, check=True).stdout.split("\n")
+    got = [tuple(int(v) for v in line.split()) for line in out if line.strip()]
+    assert len(got) == len(shapes)
+    for (R1, U, D, L1, L2), g in zip(shapes, got):
+        assert rl.tile(L1, R1, L2, U, D) == g, (R1, U, D, L1, L2, g)
 
 
 def test_example_takes_a_2048k_source_by_its_rate():
