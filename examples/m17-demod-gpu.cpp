@@ -9,7 +9,10 @@
 // the feed at 48000 R (R up to 64) is split into M channels by the polyphase channeliser and bin B of them demodulated — rtl_sdr -s 2400000 ... |
 // m17-demod-gpu --wide-u8 --decim 50 --raster 192 --bin 1; with --scan STRIDE beside --raster every STRIDE-th output of the feed is surveyed on the device
 // and after each block the occupied bins — more than --scan-margin dB, default 20, over the median of the 192 — are printed to stderr: bin, Hz from the
-// centre, dB over the floor), one line per frame callback on
+// centre, dB over the floor); with --spectrum N [--hop H, default N] under ANY wideband option the averaged N-point periodogram of each block is
+// computed on the device and the carriers it shows — the rule of m17hip's Python wide_spectrum_carriers: 9 kHz bands, more than --scan-margin dB over the
+// median floor — are printed to stderr with the offset in Hz that --offset-hz takes: rtl_sdr -s 2048000 ... | m17-demod-gpu --wide-u8 --rate 2048000
+// --spectrum 2048.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -42,6 +45,49 @@ static bool handle_frame(mobilinkd::M17FrameDecoder::output_buffer_t const& fram
     return true;
 }
 
+// The carriers of one source's spectrum plane at `rate` samples per second, as m17hip.wide_spectrum_carriers finds them (m17hip/__init__.py): band power
+// over `width` Hz, the floor the median times the band's bins, peaks greedily, strongest first, each excluding +-width around itself and a taken peak's
+// shoulders passed over, the offset refined to the centroid over the median.  (offset Hz, dB over the floor), strongest first.
+static std::vector<std::pair<double, double>> carriers(const std::vector<float>& power, double rate, double width, double margin_db)
+{
+    const long N = (long)power.size();
+    std::vector<std::pair<double, double>> out;
+    std::vector<double> sorted(power.begin(), power.end());
+    std::sort(sorted.begin(), sorted.end());
+    const double med = 0.5 * (sorted[(N - 1) / 2] + sorted[N / 2]);
+    if (!(med > 0.0) || !std::isfinite(med)) return out;
+    const double df = rate / N;
+    const long h = std::min<long>(std::lround(width / 2.0 / df), (N - 1) / 2), excl = (long)std::ceil(width / df);
+    const auto at = [&](long k) { return (double)power[(size_t)(((k % N) + N) % N)]; };
+    std::vector<double> band(N);
+    for (long k = 0; k < N; ++k) { double b = 0.0; for (long d = -h; d <= h; ++d) b += at(k + d); band[k] = b; }
+    const double floor = med * (2 * h + 1), need = floor * std::pow(10.0, margin_db / 10.0);
+    std::vector<char> free_(N);
+    for (long k = 0; k < N; ++k) free_[k] = std::isfinite(band[k]);
+    for (;;) {
+        long k = -1;
+        for (long i = 0; i < N; ++i) if (free_[i] && (k < 0 || band[i] > band[k])) k = i;
+        if (k < 0 || !(band[k] > need)) break;
+        long j = k;
+        for (;;) {   // uphill, half a band at a time
+            long m = j;
+            for (long d = -h; d <= h; ++d) { const long i = (((j + d) % N) + N) % N; if (band[i] > band[m]) m = i; }
+            if (m == j) break;
+            j = m;
+        }
+        if (j != k) { free_[k] = 0; continue; }
+        double sw = 0.0, sdw = 0.0;
+        for (long d = -h; d <= h; ++d) { const double w = std::max(at(k + d) - med, 0.0); sw += w; sdw += d * w; }
+        const double c = (double)(k < N / 2 ? k : k - N) + (sw > 0.0 ? sdw / sw : 0.0);
+        double hz = std::fmod(c * df + rate / 2.0, rate);
+        if (hz < 0.0) hz += rate;
+        out.emplace_back(hz - rate / 2.0, 10.0 * std::log10(band[k] / floor));
+        for (long d = -excl; d <= excl; ++d) free_[(size_t)((((k + d) % N) + N) % N)] = 0;
+    }
+    std::sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
+    return out;
+}
+
 int main(int argc, char** argv)
 {
     using namespace mobilinkd;
@@ -57,6 +103,8 @@ int main(int argc, char** argv)
     float iq_gain = 1.0f;
     uint32_t scan = 0;   // (0: no survey)
     double scan_margin = 20.0;
+    bool margin_given = false;
+    uint32_t spectrum = 0, hop = 0;   // (spectrum == 0: none; hop == 0: the points)
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -72,9 +120,11 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--raster") && i + 1 < argc) { raster = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!raster) raster = 257; }
         else if (!std::strcmp(argv[i], "--bin") && i + 1 < argc) bin = std::strtol(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--scan") && i + 1 < argc) { scan = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!scan) scan = 4097; }
-        else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) scan_margin = std::strtod(argv[++i], nullptr);
+        else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) { scan_margin = std::strtod(argv[++i], nullptr); margin_given = true; }
+        else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) { spectrum = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!spectrum) spectrum = 1; }
+        else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H]] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -99,6 +149,13 @@ int main(int argc, char** argv)
         return 2;
     }
     if (scan && (!(wide && raster) || scan > 4096)) { std::fprintf(stderr, "m17-demod-gpu: --scan STRIDE (1 to 4096) goes with --raster\n"); return 2; }
+    if (spectrum || hop) {
+        if (!hop) hop = spectrum;
+        if (!wide || spectrum < 64 || spectrum > 4096 || (spectrum & (spectrum - 1)) || hop > (1u << 24)) {
+            std::fprintf(stderr, "m17-demod-gpu: --spectrum N (a power of two, 64 to 4096) [--hop H (1 to 16777216)] goes with a wideband format\n");
+            return 2;
+        }
+    }
     M17Demodulator<float> demod(handle_frame);
     demod.diagnostics([](bool, float, float, float, bool, float, int, int, int, int) {});
     demod.iq_gain(iq_gain);
@@ -136,6 +193,14 @@ int main(int argc, char** argv)
                 }
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --scan needs the GPU path (the survey runs on the device); not surveying\n");
+        }
+        if (spectrum) {   // the carriers of the one source after each block
+            const double fs = 2.0 * half_hz, margin = margin_given ? scan_margin : 10.0;
+            const bool on = demod.wide_spectrum(spectrum, hop, [=](const std::vector<float>& power, uint32_t frames, uint64_t first_sample) {
+                std::fprintf(stderr, "spectrum: samples from %llu, %u frames\n", (unsigned long long)first_sample, frames);
+                for (const auto& c : carriers(power, fs, 9000.0, margin)) std::fprintf(stderr, "spectrum: carrier %+.1f Hz %.2f dB\n", c.first, c.second);
+            });
+            if (!on) std::fprintf(stderr, "m17-demod-gpu: --spectrum needs the GPU path (it runs on the device); no spectrum\n");
         }
         while (std::cin) {
             if (wide == M17HIP_IQ_I16) { int16_t s[2]; std::cin.read(reinterpret_cast<char*>(s), 4); if (std::cin) demod.wide((float)s[0], (float)s[1]); }

@@ -220,8 +220,8 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: per-source sample counts, squelch / RSSI under a tuner (per bin of a raster: the survey,
- * ABI 613, below).  (Sources above 16 x 48 kSPS: two stages,
+ * Out of scope, for a later pull request: per-source sample counts, squelching the demodulator, per-channel RSSI of a tuner's own z (per bin of a raster:
+ * the survey, ABI 613, below; which offsets of a source carry anything, under any configuration: the source spectrum, ABI 616, below).  (Sources above 16 x 48 kSPS: two stages,
  * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.  Rates that are no integer multiple of 48 kSPS: the resampling tuner,
  * ABI 615, below.) */
 #define M17HIP_IQ_U8 3    /* interleaved uint8 I,Q around 127.5 (rtl_sdr): (float)u - 127.5, exact.  Wideband input only: m17hip_upload_iq* refuses it */
@@ -352,8 +352,8 @@ int m17hip_wide_raster_channels(m17hip_ctx* ctx, const uint32_t* source, const i
  * (csrc/m17_chan_survey_kernels.hpp) on the block's own stream behind the channeliser: m17hip_upload_wait and the in-place forms' synchronisation cover
  * them, the floats the channels get are untouched, and with the survey off a block queues exactly what it queued under ABI 611.  m17hip_timing_get index 12
  * is the survey (both kernels, one entry per block); m17hip_iq_bytes counts its scratch and planes.
- * Out of scope, for a later pull request: a survey under the two tuners (they share no z), a waterfall of per-time spectra, channel assignment on the device,
- * squelching the demodulator itself. */
+ * Out of scope, for a later pull request: a waterfall of per-time spectra, channel assignment on the device, squelching the demodulator itself.  (Under
+ * the tuners, which share no z: the spectrum of the source block itself, ABI 616, below.) */
 /* stride 0 turns the survey off (the default); 1..4096 turns it on for the blocks uploaded AFTER the call — a block already staged is not surveyed
  * retroactively.  It never waits for anything in flight.  Planes of blocks surveyed before the call are no longer fetched.  M17HIP_ESTATE unless the last
  * wideband configuration is a raster, and between m17hip_demod_front and its run; M17HIP_EINVAL for a stride above 4096 or a NULL context.  Every
@@ -365,6 +365,58 @@ int m17hip_wide_survey(m17hip_ctx* ctx, uint32_t stride);
  * plane exists: the survey is off, no block (or, for back = 1, one block) since it was turned on, or none since m17hip_demod_reset, which starts the feeds
  * over.  M17HIP_EINVAL for back > 1, a NULL power_host or capacity (in floats) < sources * bins; nothing is written then. */
 int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* times, uint64_t* first_output);
+
+/* ---- the source spectrum: averaged periodogram of every wideband source, under every configuration (ABI 616) ---
+ * The three tuners take frequency words, and a user had to know every carrier's offset before m17hip_wide_channels was of any use: they share no z, so no
+ * survey serves them.  What every configuration shares is the source block.  With the spectrum on at N = `points` and `hop`, every wideband block uploaded
+ * is transformed beside whichever kernel the configuration launches:
+ *     c0 = the feed's 64-bit sample count at the block's start, W = the block's complex samples per source row, x = its samples as floats (int16 and float32
+ *     as they are, uint8 minus 127.5);
+ *     FRAME f starts at block sample a_f = first + f * hop, first = (hop - c0 mod hop) mod hop from all 64 bits of the count — where the feed's absolute
+ *     sample index is a multiple of hop: a property of the feed, not of how it is cut into blocks; J = the number of f with a_f + N <= W.  A frame that would
+ *     straddle a block's end is not taken (no history, no carried state), and J may be 0;
+ *     v[i] = (w[i] * re x[a_f + i], w[i] * im x[a_f + i]), two plain multiplies, w the window;
+ *     X = the N-point DFT of v, X[k] = sum_i v[i] exp(-2 pi j k i / N), evaluated as a radix-2 decimation-in-time FFT: v is loaded in bit-reversed order,
+ *     then stages s = 1 .. log2 N in ascending order; butterfly j < N / 2 of stage s pairs the elements i and i + h, h = 2^(s-1), i = 2 h (j div h) + j mod
+ *     h, with t = tw[(j mod h) * N / 2^s] as
+ *         (a, b) <- (a + b t, a - b t):   re' = fmaf(-b.im, t.im, fmaf(b.re, t.re, a.re)),  im' = fmaf(b.im, t.re, fmaf(b.re, t.im, a.im))
+ *     — core::chan_mac onto a, for the difference with (-t.re, -t.im) in t's place — ONE formula for every butterfly of every stage, the twiddles on the axes
+ *     included, so a non-finite sample gives the same words on host and device (it reaches every bin of its frame and of no other);
+ *     p = chan_power(X[k].re, X[k].im) = fmaf(re, re, im * im);
+ *     q_g = the chain from +0 of plain float adds of frame j's p, j = 16 g .. min(16 g + 15, J - 1), ascending (CHAN_SURVEY_GROUP = 16);
+ *     P[s][k] = the chain from +0 of plain float adds of q_g, g ascending.  With J = 0 every P is +0.
+ * P[s][k], k < N, belongs to the frequency k * Fs / N for k < N / 2 and (k - N) * Fs / N otherwise, measured from the source's centre at its sample rate Fs
+ * — the survey's index rule.  The twiddles tw[j] = exp(-2 pi j j / N), j < N / 2, are DATA: made on the host in double and rounded to float, exactly (1, 0)
+ * at j = 0 and (0, -1) at j = N / 4, and tw[N / 2 - j] = (-re, im) of tw[j] to the bit; m17hip_wide_spectrum_twiddles returns the table the device is
+ * given.  m17cxx/detail/core.h has spec_frames, spec_window, spec_bitrev, spec_butterfly and spec_item1 (and spec_item2: two stages in one pass, the same
+ * words), so a host computes the device's words.  Two kernels on the block's own stream (csrc/m17_spectrum_kernels.hpp; the second is the survey's
+ * chan_survey_sum_kernel) behind the configuration's kernel: they read the source block only, m17hip_upload_wait and the in-place forms' synchronisation
+ * cover them, the floats the channels get are untouched, and with the spectrum off a block queues exactly what it queued under ABI 615.
+ * m17hip_timing_get index 14 is the spectrum (both kernels, one entry per block); m17hip_iq_bytes counts its table, scratch and planes.  The scratch is
+ * sources * ceil(J / 16) * N floats: a hop far below N over a long block asks for as much memory as that says, and a block whose scratch cannot be had
+ * fails with M17HIP_ENOMEM.
+ * Out of scope, for a later pull request: a waterfall of per-frame spectra, frames that straddle blocks, per-channel RSSI of the tuners' own z, squelching
+ * the demodulator, assigning channels on the device. */
+/* points = 0 turns the spectrum off (the default).  Otherwise points is a power of two in 64..4096, hop is in 1..2^24 and window[nwindow] holds `points`
+ * finite floats; NULL with a count of 0 selects m17hip_wide_spectrum_default_window's.  It holds for the blocks uploaded AFTER the call and never waits for
+ * anything in flight: window and twiddles travel with the next block.  Planes of blocks transformed before the call are no longer fetched.  Legal under
+ * EVERY wideband configuration, the raster included, and independent of m17hip_wide_survey.  M17HIP_EINVAL outside the limits (a NULL context included),
+ * with nothing changed; M17HIP_ESTATE before any wideband configuration and between m17hip_demod_front and its run.  Every m17hip_wide_config,
+ * m17hip_wide_config2, m17hip_wide_raster or m17hip_wide_resample call turns it off: the plane has a row per source. */
+int m17hip_wide_spectrum(m17hip_ctx* ctx, uint32_t points, uint32_t hop, const float* window, uint32_t nwindow);
+/* The default window: the four-term minimum Blackman-Harris window in its periodic form, w[i] = 0.35875 - 0.48829 cos(2 pi i / N) + 0.14128 cos(4 pi i / N)
+ * - 0.01168 cos(6 pi i / N), computed in double and rounded to float.  No context is needed.  M17HIP_EINVAL for points that m17hip_wide_spectrum refuses
+ * (0 included), a NULL out or capacity (in floats) < points; nothing is written then. */
+int m17hip_wide_spectrum_default_window(uint32_t points, float* out, uint32_t capacity);
+/* The twiddle table as described above: points / 2 pairs (re, im), `points` floats.  No context is needed.  M17HIP_EINVAL as for the default window. */
+int m17hip_wide_spectrum_twiddles(uint32_t points, float* out, uint32_t capacity);
+/* The plane of the latest block uploaded with the spectrum on (back = 0) or of the block before it (back = 1; two planes and two events take turns):
+ * power_host[sources][points] floats; *frames = J and *first_sample = c0 + first of that block (either may be NULL).  It waits for that block's spectrum
+ * kernels only, on an event recorded behind the second of them, and copies on a stream of its own — never for a demodulation run or a later block.
+ * M17HIP_ESTATE if no such plane exists: the spectrum is off, no block (or, for back = 1, one block) since it was turned on, or none since
+ * m17hip_demod_reset, which starts the feeds over.  M17HIP_EINVAL for back > 1, a NULL power_host or capacity (in floats) < sources * points; nothing is
+ * written then. */
+int m17hip_wide_spectrum_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* frames, uint64_t* first_sample);
 
 /* ---- wideband IQ input at rational sample rates: a resampling tuner (ABI 615) -------------------------------
  * Every configuration above wants a source at an INTEGER multiple of 48 kSPS, and the rates receivers run at by default are not: rtl_sdr's 2.048 MSPS is
@@ -381,7 +433,7 @@ int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, 
  * words).  At U = 1 it is m17hip_wide_config2's definition, and the words are that tuner's.  n is counted WITHIN A BLOCK: every block holds a multiple of U
  * outputs, so the phase i0 never depends on the feed's history.  The frequency word means fcw / 2^32 * 48000 * decim1 * down / up Hz.
  * Out of scope: a rational-rate channeliser (a raster in a 2.048 MSPS source), sources of different rates in one context, interpolation (up > down), more
- * than two stages, squelch or RSSI under a tuner. */
+ * than two stages, squelching the demodulator, per-channel RSSI of the tuner's own z.  (Which offsets carry anything: the source spectrum, ABI 616, below.) */
 /* The default taps of both stages.  Stage 1: 8 * decim1 + 1 taps of the Blackman-windowed sinc of m17hip_wide_default_taps2 with its cutoff at half the
  * rate the stage leaves (0.5 / decim1 of the source's rate); one tap of 1 at decim1 == 1.  Stage 2: 32 * down + 1 taps of the same formula with the cutoff
  * at 5500 Hz of 48000 * down, scaled in double to DC gain `up` — every one of the `up` branches taps2[r], taps2[r + up], ... then has unit gain within
@@ -909,7 +961,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 9 = tune (the tuner of m17hip_upload_wide* under m17hip_wide_config: one launch per wideband block),
  * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
  * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
- * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block). */
+ * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block), 14 = spectrum (the two
+ * kernels of m17hip_wide_spectrum, one entry per transformed block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

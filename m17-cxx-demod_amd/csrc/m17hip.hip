@@ -12,6 +12,7 @@
 #include "m17_resample_kernels.hpp"
 #include "m17_chan_kernels.hpp"
 #include "m17_chan_survey_kernels.hpp"
+#include "m17_spectrum_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_demod_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -37,7 +38,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -379,10 +380,29 @@ struct m17hip_ctx {
             void forget() { valid[0] = valid[1] = false; }
             ~Survey() { if (fetch) (void)hipStreamDestroy(fetch); }
         } sv;
+        // The source spectrum (m17hip_wide_spectrum; csrc/m17_spectrum_kernels.hpp), under every configuration: points != 0 is on.  Planes [S][points],
+        // events and scratch [S][groups][points] as the survey's.  The window and the twiddles stay on the host until the next block brings them to the
+        // device as one table [window[points] | tw[points / 2][2]] (`dirty`), in the copy no queued launch reads.
+        struct Spectrum {
+            uint32_t points = 0, logn = 0, hop = 0;
+            std::vector<float> table;
+            bool dirty = true;
+            TurnTable dev;
+            DevBuf<float> scratch, plane[2];
+            Event ev[2];
+            bool valid[2] = {false, false};
+            uint32_t frames[2] = {0, 0};
+            uint64_t first_sample[2] = {0, 0};
+            int latest = 0;
+            hipStream_t fetch = nullptr;   // m17hip_wide_spectrum_fetch's copies: a stream of its own, behind nothing but the plane's event
+            void forget() { valid[0] = valid[1] = false; }
+            ~Spectrum() { if (fetch) (void)hipStreamDestroy(fetch); }
+        } sp;
         size_t bytes() const
         {
-            return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size()) * sizeof(float) +
-                   (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words()) * 4;
+            return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size() + sp.scratch.size() + sp.plane[0].size() +
+                    sp.plane[1].size()) * sizeof(float) +
+                   (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4;
         }
     } wide;
     Slab& now() { return slab[slot]; }         // the current / latest run's
@@ -1211,7 +1231,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 615; }
+int m17hip_version(void) { return 616; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1574,6 +1594,7 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
             for (auto& h : c->wide.hist) HIPCHK(c, hipMemsetAsync(h, 0, h.size() * sizeof(float2), st));
             c->wide.count = 0;
             c->wide.sv.forget();   // (the planes were blocks of the feed that ends here)
+            c->wide.sp.forget();
         }
     } else {
         std::vector<uint32_t> v(channels, channels + n);
@@ -1703,6 +1724,52 @@ static int launch_survey(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W
     sv.times[p] = J; sv.first_output[p] = N0; sv.valid[p] = true; sv.latest = p;
     return M17HIP_OK;
 }
+// The spectrum of one block (m17hip_wide_spectrum is on), on the block's stream: it reads src and w.count alone, and writes the plane whose turn it is.  A
+// block without a frame (J = 0) queues the second kernel alone: its plane is all +0.
+template <typename IQT>
+static int launch_spectrum(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, hipStream_t st)
+{
+    auto& w = c->wide;
+    auto& sp = w.sp;
+    const uint32_t N = sp.points;
+    uint32_t first, J;
+    core::spec_frames(w.count, W, N, sp.hop, first, J);
+    const uint32_t G = (J + core::CHAN_SURVEY_GROUP - 1) / core::CHAN_SURVEY_GROUP;
+    const int p = sp.latest ^ 1;
+    int r;
+    if (!sp.fetch) HIPCHK(c, hipStreamCreateWithFlags(&sp.fetch, hipStreamNonBlocking));
+    for (auto& e : sp.ev) if (!e) HIPCHK(c, e.create());
+    for (auto& b : sp.plane) if ((r = alloc_code(c, b.grow((size_t)w.S * N, &c->last_hip)))) return r;   // (released with every configuration: nothing reads them)
+    if (sp.scratch.size() < (size_t)w.S * G * N) {
+        HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be transformed)
+        if ((r = alloc_code(c, sp.scratch.grow((size_t)w.S * G * N, &c->last_hip)))) return r;
+    }
+    if (sp.dirty || !sp.dev.live()) {   // the window and the twiddles, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, sp.dev.begin_write(2 * 4096, &staging));
+        std::memcpy(staging, sp.table.data(), sp.table.size() * 4);
+        HIPCHK(c, sp.dev.publish(sp.table.size(), st));
+        sp.dirty = false;
+    }
+    HIPCHK(c, sp.dev.before_read(st));
+    sp.valid[p] = false;
+    {
+        Timed tm(c, KT_SPECTRUM, st);
+        if (G) {
+            const uint32_t F = spectrum_frames_per_pass(N);
+            const float* tab = reinterpret_cast<const float*>(sp.dev.dev());
+            hipLaunchKernelGGL(spectrum_kernel<IQT>, dim3(G, w.S), dim3(SPECTRUM_THREADS), spectrum_lds_bytes(N, F), st, src, pitch, tab,
+                               reinterpret_cast<const float2*>(tab + N), sp.logn, sp.hop, first, J, F, sp.scratch.get());
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(chan_survey_sum_kernel, dim3((w.S * N + 255) / 256), dim3(256), 0, st, sp.scratch.get(), G, N, w.S, sp.plane[p].get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, sp.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    HIPCHK(c, hipEventRecord(sp.ev[p], st));
+    sp.frames[p] = J; sp.first_sample[p] = w.count + first; sp.valid[p] = true; sp.latest = p;
+    return M17HIP_OK;
+}
 // What follows the tuner's or the channeliser's kernel on its stream `st`, for the next block: the channels' carries, the sources' histories (H converted
 // samples each, into the copy whose turn it is), the feed's sample count.  In between the survey of a raster's block, which reads what that kernel read.
 template <typename IQT>
@@ -1712,6 +1779,7 @@ static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_
     hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
     HIPCHK(c, hipGetLastError());
     if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;   // (m17hip_wide_survey: on under a raster only)
+    if (w.sp.points) if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;   // (m17hip_wide_spectrum: under every configuration)
     if (H) {
         hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
         HIPCHK(c, hipGetLastError());
@@ -1905,6 +1973,9 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.sv.stride = 0; w.sv.forget();   // (the survey's plane has the configuration's shape: off, and its memory back)
     w.sv.scratch.release(&c->last_hip);
     for (auto& b : w.sv.plane) b.release(&c->last_hip);
+    w.sp.points = 0; w.sp.forget();   // (the spectrum likewise: its plane has a row per source)
+    w.sp.scratch.release(&c->last_hip);
+    for (auto& b : w.sp.plane) b.release(&c->last_hip);
     if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
     if (L2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
     else w.taps2.release(&c->last_hip);
@@ -2075,6 +2146,87 @@ int m17hip_wide_survey_fetch(m17hip_ctx* c, uint32_t back, float* power_host, ui
     HIPCHK(c, hipStreamSynchronize(sv.fetch));
     if (times) *times = sv.times[p];
     if (first_output) *first_output = sv.first_output[p];
+    return M17HIP_OK;
+}
+// ---- the source spectrum (ABI 616): the averaged periodogram of every source, under every wideband configuration ------------------------------
+// 0 for anything but a power of two in 64..4096
+static uint32_t spectrum_logn(uint32_t points)
+{
+    for (uint32_t l = 6; l <= 12; ++l) if (points == 1u << l) return l;
+    return 0;
+}
+// four-term Blackman-Harris (the minimum 92 dB one), periodic: the N-point DFT sees one whole period
+static void spectrum_window(uint32_t N, float* w)
+{
+    const double pi = 3.14159265358979323846;
+    for (uint32_t i = 0; i < N; ++i) {
+        const double x = 2.0 * pi * i / N;
+        w[i] = (float)(0.35875 - 0.48829 * std::cos(x) + 0.14128 * std::cos(2.0 * x) - 0.01168 * std::cos(3.0 * x));
+    }
+}
+// tw[j] = exp(-2 pi j j / N) as (re, im), j < N / 2: cos and sin in double for j <= N / 4, rounded to float, exactly (1, 0) at 0 and (0, -1) at N / 4; the
+// second quarter is the first one's mirror to the bit, tw[N / 2 - j] = (-re, im) of tw[j]
+static void spectrum_twiddles(uint32_t N, float* tw)
+{
+    const double pi = 3.14159265358979323846;
+    tw[0] = 1.0f; tw[1] = 0.0f;
+    tw[2 * (N / 4)] = 0.0f; tw[2 * (N / 4) + 1] = -1.0f;
+    for (uint32_t j = 1; j < N / 4; ++j) {
+        const float re = (float)std::cos(2.0 * pi * j / N), im = (float)std::sin(2.0 * pi * j / N);
+        tw[2 * j] = re; tw[2 * j + 1] = -im;
+        tw[2 * (N / 2 - j)] = -re; tw[2 * (N / 2 - j) + 1] = -im;
+    }
+}
+int m17hip_wide_spectrum_default_window(uint32_t points, float* out, uint32_t capacity)
+{
+    if (!spectrum_logn(points) || !out || capacity < points) return M17HIP_EINVAL;
+    spectrum_window(points, out);
+    return M17HIP_OK;
+}
+int m17hip_wide_spectrum_twiddles(uint32_t points, float* out, uint32_t capacity)
+{
+    if (!spectrum_logn(points) || !out || capacity < points) return M17HIP_EINVAL;
+    spectrum_twiddles(points, out);
+    return M17HIP_OK;
+}
+int m17hip_wide_spectrum(m17hip_ctx* c, uint32_t points, uint32_t hop, const float* window, uint32_t nwindow)
+{
+    if (!c) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sp = w.sp;
+    if (points) {
+        if (!spectrum_logn(points) || hop < 1 || hop > (1u << 24)) return M17HIP_EINVAL;
+        if (window ? nwindow != points : nwindow != 0) return M17HIP_EINVAL;
+        for (uint32_t i = 0; window && i < points; ++i) if (!std::isfinite(window[i])) return M17HIP_EINVAL;
+    }
+    if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the planes have a row per source; the staged block belongs to the run being made)
+    sp.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
+    sp.points = points;
+    if (!points) return M17HIP_OK;
+    sp.logn = spectrum_logn(points); sp.hop = hop;
+    sp.table.resize(2 * (size_t)points);
+    if (window) std::copy(window, window + points, sp.table.begin());
+    else spectrum_window(points, sp.table.data());
+    spectrum_twiddles(points, sp.table.data() + points);
+    sp.dirty = true;
+    return M17HIP_OK;
+}
+int m17hip_wide_spectrum_fetch(m17hip_ctx* c, uint32_t back, float* power_host, uint64_t capacity, uint32_t* frames, uint64_t* first_sample)
+{
+    if (!c || back > 1 || !power_host) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sp = w.sp;
+    if (!w.S || !sp.points) return M17HIP_ESTATE;
+    const size_t n = (size_t)w.S * sp.points;
+    if (capacity < n) return M17HIP_EINVAL;
+    const int p = sp.latest ^ (int)back;
+    if (!sp.valid[p]) return M17HIP_ESTATE;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sp.ev[p]));   // (that block's spectrum and what its stream held in front of it: no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(power_host, sp.plane[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, sp.fetch));
+    HIPCHK(c, hipStreamSynchronize(sp.fetch));
+    if (frames) *frames = sp.frames[p];
+    if (first_sample) *first_sample = sp.first_sample[p];
     return M17HIP_OK;
 }
 int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }

@@ -123,6 +123,18 @@ public:
     {
         check(m17hip_wide_survey_fetch(ctx_, back, power, capacity, times, first_output), "m17hip_wide_survey_fetch");
     }
+    // The source spectrum (m17hip_wide_spectrum), under every wideband configuration: from the blocks uploaded after the call the frames of `points` samples
+    // (a power of two in 64..4096; 0: off) that begin where the feed's sample index is a multiple of `hop` (1..2^24) are windowed (nullptr with 0: the
+    // default window), transformed and their powers summed per source.  wide_spectrum_fetch: the plane [sources][points] of the latest such block (back = 0)
+    // or the one before (back = 1), its frames and the feed's sample index at its first frame; it waits for that block's spectrum kernels only.
+    void wide_spectrum(uint32_t points, uint32_t hop, const float* window = nullptr, uint32_t nwindow = 0)
+    {
+        check(m17hip_wide_spectrum(ctx_, points, hop, window, nwindow), "m17hip_wide_spectrum");
+    }
+    void wide_spectrum_fetch(uint32_t back, float* power, uint64_t capacity, uint32_t* frames = nullptr, uint64_t* first_sample = nullptr)
+    {
+        check(m17hip_wide_spectrum_fetch(ctx_, back, power, capacity, frames, first_sample), "m17hip_wide_spectrum_fetch");
+    }
     // the bin of an offset in Hz from the source's centre; throws where the offset is not on the raster or outside it
     static int32_t wide_bin(double offset_hz, uint32_t decim, uint32_t bins)
     {

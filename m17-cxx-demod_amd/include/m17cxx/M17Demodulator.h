@@ -161,6 +161,7 @@ struct M17Demodulator
             taps.resize(n);
         }
         wide_decim_ = decim;
+        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -197,6 +198,7 @@ struct M17Demodulator
             if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
         }
         wide_decim_ = decim1 * decim2;
+        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         wide_r1_ = decim1;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -237,6 +239,7 @@ struct M17Demodulator
             if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
         }
         wide_decim_ = decim1 * down;   // (the samples of a group)
+        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         wide_r1_ = decim1;
         wide_up_ = up; wide_down_ = down;
         raster_m_ = 0;
@@ -272,6 +275,7 @@ struct M17Demodulator
             taps.resize(n);
         }
         wide_decim_ = decim;
+        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         if (gpu_) {
@@ -304,6 +308,22 @@ struct M17Demodulator
         gpu_->wide_survey(stride);
         survey_stride_ = stride;
         survey_report_ = std::move(report);
+        return true;
+    }
+    // The source spectrum beside any wideband configuration on the GPU path (m17hip_wide_spectrum): the frames of `points` samples (a power of two in
+    // 64..4096; 0 turns it off) that begin where the feed's sample index is a multiple of `hop` are windowed (empty: the default Blackman-Harris window),
+    // transformed and their powers summed, and after each block `report` gets the plane — bin k at k rate / points below points / 2, (k - points) rate /
+    // points from there on —, the block's frames and the feed's sample index at its first frame.  Returns false, with nothing changed, on the host form: the
+    // spectrum is a device feature.  Any wide_config / wide_rate / wide_raster call turns it off.
+    using spectrum_callback_t = std::function<void(const std::vector<float>& power, uint32_t frames, uint64_t first_sample)>;
+    bool wide_spectrum(uint32_t points, uint32_t hop, spectrum_callback_t report, const std::vector<float>& window = {})
+    {
+        if (!gpu_) return false;
+        if (!wide_decim_) throw std::logic_error("M17Demodulator::wide_spectrum before wide_config");
+        flush();
+        gpu_->wide_spectrum(points, hop, window.empty() ? nullptr : window.data(), (uint32_t)window.size());
+        spectrum_points_ = points;
+        spectrum_report_ = std::move(report);
         return true;
     }
     // one wideband sample (wide_config or wide_raster first)
@@ -456,6 +476,13 @@ private:
             gpu_->wide_survey_fetch(0, survey_power_.data(), survey_power_.size(), &times, &first);
             survey_report_(survey_power_, times, first);
         }
+        if (spectrum_points_ && spectrum_report_) {   // (likewise: the fetch waits for the block's spectrum kernels)
+            spectrum_power_.resize(spectrum_points_);
+            uint32_t frames = 0;
+            uint64_t first = 0;
+            gpu_->wide_spectrum_fetch(0, spectrum_power_.data(), spectrum_power_.size(), &frames, &first);
+            spectrum_report_(spectrum_power_, frames, first);
+        }
         run_uploaded();
     }
     void run_uploaded()
@@ -492,6 +519,9 @@ private:
     uint32_t survey_stride_ = 0;                     // wide_survey: 0 = off
     survey_callback_t survey_report_;
     std::vector<float> survey_power_;
+    uint32_t spectrum_points_ = 0;                   // wide_spectrum: 0 = off
+    spectrum_callback_t spectrum_report_;
+    std::vector<float> spectrum_power_;
     std::vector<float> raster_tw_, raster_w_;        // the twiddle table; the partial sums and the first pass's sums of one output
     uint64_t wide_m_ = 0;
     uint32_t block_;

@@ -256,6 +256,62 @@ M17_HD void chan_pass2(const float* a, uint32_t M1, uint32_t M2, const float* tw
 constexpr uint32_t CHAN_SURVEY_GROUP = 16;
 M17_HD float chan_power(float re, float im) { return __builtin_fmaf(re, re, im * im); }
 
+// ---- a-1d: the source spectrum (m17hip_wide_spectrum): the averaged periodogram of a source block, whatever tunes or channelises it.  Frames of N = 2^logn
+// samples begin where the FEED's sample index is a multiple of `hop`; each is windowed (two plain multiplies per sample), transformed by a radix-2
+// decimation-in-time FFT over a bit-reversed load, and chan_power of every bin is summed over the block's frames on the survey's two levels
+// (CHAN_SURVEY_GROUP frames per group).  The twiddles tw[j] = exp(-2 pi j j / N), j < N / 2, are data (m17hip_wide_spectrum_twiddles).
+// The frames of a block of W samples that begins at sample c0 of the feed: frame f starts at block sample first + f hop, first = (hop - c0 mod hop) mod hop
+// from all 64 bits of the count, and J counts the f with first + f hop + N <= W — a frame that would straddle the block's end is not taken.
+M17_HD void spec_frames(uint64_t c0, uint32_t W, uint32_t N, uint32_t hop, uint32_t& first, uint32_t& J)
+{
+    first = (uint32_t)((hop - c0 % hop) % hop);
+    J = W >= N && first <= W - N ? (W - N - first) / hop + 1 : 0;
+}
+// the logn low bits of i in reverse order (logn 1..32)
+M17_HD uint32_t spec_bitrev(uint32_t i, uint32_t logn)
+{
+    i = (i >> 16) | (i << 16);
+    i = ((i & 0xFF00FF00u) >> 8) | ((i & 0x00FF00FFu) << 8);
+    i = ((i & 0xF0F0F0F0u) >> 4) | ((i & 0x0F0F0F0Fu) << 4);
+    i = ((i & 0xCCCCCCCCu) >> 2) | ((i & 0x33333333u) << 2);
+    i = ((i & 0xAAAAAAAAu) >> 1) | ((i & 0x55555555u) << 1);
+    return i >> (32 - logn);
+}
+// THE butterfly, one formula for every one of every stage, the twiddles on the axes included: (a, b) <- (a + b t, a - b t), each a chan_mac onto a — the
+// sum with t, the difference with -t (a negation is exact) — so a component is rounded twice.  A non-finite b reaches both outputs through the same four
+// fma on either side.  a, b, t: (re, im).
+M17_HD void spec_butterfly(float* a, float* b, const float* t)
+{
+    float pre = a[0], pim = a[1], mre = a[0], mim = a[1];
+    chan_mac(b[0], b[1], t[0], t[1], pre, pim);
+    chan_mac(b[0], b[1], -t[0], -t[1], mre, mim);
+    a[0] = pre; a[1] = pim; b[0] = mre; b[1] = mim;
+}
+// Stage s = 1 .. logn of the FFT over v[N][2] (bit-reversed on entry, in place), taken in ascending order of s; butterfly j < N / 2 of stage s pairs
+// v[i] and v[i + h], h = 2^(s-1), i = 2 h (j div h) + j mod h, with the twiddle tw[(j mod h) 2^(logn-s)].  The butterflies of a stage share no element.
+M17_HD void spec_item1(float* v, const float* tw, uint32_t logn, uint32_t s, uint32_t j)
+{
+    const uint32_t h = 1u << (s - 1), pos = j & (h - 1), i = ((j >> (s - 1)) << s) + pos;
+    spec_butterfly(v + 2 * i, v + 2 * (i + h), tw + 2 * (pos << (logn - s)));
+}
+// Stages s and s + 1 in one pass: item q < N / 4 takes the four butterflies among v[i], v[i + h], v[i + 2h], v[i + 3h], i = 4 h (q div h) + q mod h, that
+// spec_item1 takes in those two stages, stage s first — the same words, with the four elements in registers in between.
+M17_HD void spec_item2(float* v, const float* tw, uint32_t logn, uint32_t s, uint32_t q)
+{
+    const uint32_t h = 1u << (s - 1), pos = q & (h - 1), i = ((q >> (s - 1)) << (s + 1)) + pos;
+    float e0[2] = {v[2 * i], v[2 * i + 1]}, e1[2] = {v[2 * (i + h)], v[2 * (i + h) + 1]};
+    float e2[2] = {v[2 * (i + 2 * h)], v[2 * (i + 2 * h) + 1]}, e3[2] = {v[2 * (i + 3 * h)], v[2 * (i + 3 * h) + 1]};
+    const float* t = tw + 2 * (pos << (logn - s));
+    spec_butterfly(e0, e1, t);
+    spec_butterfly(e2, e3, t);
+    spec_butterfly(e0, e2, tw + 2 * (pos << (logn - s - 1)));
+    spec_butterfly(e1, e3, tw + 2 * ((pos + h) << (logn - s - 1)));
+    v[2 * i] = e0[0]; v[2 * i + 1] = e0[1]; v[2 * (i + h)] = e1[0]; v[2 * (i + h) + 1] = e1[1];
+    v[2 * (i + 2 * h)] = e2[0]; v[2 * (i + 2 * h) + 1] = e2[1]; v[2 * (i + 3 * h)] = e3[0]; v[2 * (i + 3 * h) + 1] = e3[1];
+}
+// One windowed sample on its way into the FFT: two plain multiplies.
+M17_HD void spec_window(float w, float xre, float xim, float& re, float& im) { re = w * xre; im = w * xim; }
+
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).
 constexpr int RRC_TAPS = 150;

@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -76,6 +76,7 @@ EXPORTS = [
     "m17hip_wide_raster_default_taps", "m17hip_wide_raster_twiddles", "m17hip_wide_raster", "m17hip_wide_raster_channels",
     "m17hip_wide_survey", "m17hip_wide_survey_fetch",
     "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
+    "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
@@ -247,6 +248,77 @@ def wide_raster_occupied(power, margin_db):
             db = 10.0 * np.log10(p[s].astype(np.float64) / floor)
         for k in np.nonzero(db > float(margin_db))[0]:
             out.append((s, int(k) if k <= (M - 1) // 2 else int(k) - M, float(db[k])))
+    out.sort(key=lambda e: -e[2])
+    return out
+
+
+def wide_spectrum_default_window(points):
+    """The default window of Context.wide_spectrum: float32 [points], the periodic four-term Blackman-Harris window made in double and rounded —
+    m17hip_wide_spectrum_default_window (no context, no GPU)."""
+    w = np.zeros(max(int(points), 1), dtype=np.float32)
+    code = load_library().m17hip_wide_spectrum_default_window(C.c_uint32(points), _ptr(w), C.c_uint32(w.size))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_spectrum_default_window: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return w
+
+
+def wide_spectrum_twiddles(points):
+    """The spectrum's twiddle table: complex64 [points / 2], exp(-2 pi j k / points) made in double and rounded — the very words the device computes with;
+    m17hip_wide_spectrum_twiddles (no context, no GPU)."""
+    tw = np.zeros(max(int(points) // 2, 1), dtype=np.complex64)
+    code = load_library().m17hip_wide_spectrum_twiddles(C.c_uint32(points), tw.ctypes.data_as(C.c_void_p), C.c_uint32(2 * tw.size))
+    if code != 0:
+        raise M17HipError(f"m17hip_wide_spectrum_twiddles: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return tw
+
+
+def wide_spectrum_carriers(power, rate_hz, width_hz=9000.0, margin_db=10.0):
+    """The carriers of a spectrum plane (Context.wide_spectrum_fetch) of sources at `rate_hz` samples per second.  Per source: the BAND POWER of bin k is the
+    circular sum of the 2 h + 1 bins around it, h = round(width_hz / 2 / (rate_hz / N)); the floor is the row's median times 2 h + 1; peaks of the band
+    power are picked greedily, strongest first, while they stand more than `margin_db` dB over the floor, and each excludes the bins within width_hz of
+    itself — a bin from which the band power still rises, half a band at a time, into what a taken peak excludes is that peak's shoulder and is passed
+    over; a peak's offset is the centroid over its band of what the bins hold above the row's median.  Returns (source, offset in Hz from the source's
+    centre, signed in [-rate_hz / 2, rate_hz / 2), dB of the band power over the floor), strongest first — wide_fcw takes the offset as it is.  A row whose
+    median is 0 or not finite reports nothing.  Pure numpy."""
+    p = np.asarray(power, dtype=np.float64)
+    if p.ndim == 1:
+        p = p[None, :]
+    N = p.shape[1]
+    df = float(rate_hz) / N
+    h = min(int(round(float(width_hz) / 2.0 / df)), (N - 1) // 2)
+    nb = 2 * h + 1
+    excl = int(np.ceil(float(width_hz) / df))
+    d = np.arange(-h, h + 1)
+    out = []
+    for s in range(p.shape[0]):
+        med = float(np.median(p[s]))
+        if not np.isfinite(med) or med <= 0.0:
+            continue
+        with np.errstate(invalid="ignore"):
+            cs = np.concatenate([[0.0], np.cumsum(np.concatenate([p[s, N - h:], p[s], p[s, :h]]))])
+            band = cs[nb:] - cs[:-nb]   # band[k]: bins k - h .. k + h, circular
+        floor = med * nb
+        free = np.isfinite(band)
+        need = floor * 10.0 ** (float(margin_db) / 10.0)
+        while free.any():
+            k = int(np.argmax(np.where(free, band, -np.inf)))
+            if not band[k] > need:
+                break
+            j = k   # (uphill within half a band at a time: a shoulder of a peak already taken ends inside what that peak excludes, and is no peak)
+            while True:
+                near = (j + d) % N
+                m = int(near[np.argmax(band[near])])
+                if not band[m] > band[j]:
+                    break
+                j = m
+            if j != k:
+                free[k] = False
+                continue
+            w = np.maximum(p[s, (k + d) % N] - med, 0.0)
+            c = (k if k < N // 2 else k - N) + (float((d * w).sum() / w.sum()) if w.sum() > 0.0 else 0.0)
+            hz = (c * df + float(rate_hz) / 2.0) % float(rate_hz) - float(rate_hz) / 2.0
+            out.append((s, hz, 10.0 * float(np.log10(band[k] / floor))))
+            free[(k + np.arange(-excl, excl + 1)) % N] = False
     out.sort(key=lambda e: -e[2])
     return out
 
@@ -505,6 +577,27 @@ class Context:
         self._chk(self.lib.m17hip_wide_survey_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(cap), C.byref(times), C.byref(first)))
         S, M = self._wide[0], self._wide_bins   # (the call succeeded: wide_raster has set both)
         return buf[: S * M].reshape(S, M).copy(), int(times.value), int(first.value)
+
+    def wide_spectrum(self, points, hop, window=None):
+        """The source spectrum: from the blocks uploaded after this call, every source block's frames of `points` samples (a power of two in 64..4096; 0:
+        off, the default) that begin where the feed's sample index is a multiple of `hop` (1..2^24) are windowed (float32 [points]; None: the default
+        Blackman-Harris window), transformed, and their powers summed into the block's plane — m17hip_wide_spectrum.  Legal under every wideband
+        configuration; any wide_config / wide_config2 / wide_raster / wide_resample call turns it off."""
+        w = None if window is None else np.ascontiguousarray(np.asarray(window, dtype=np.float32).reshape(-1))
+        self._chk(self.lib.m17hip_wide_spectrum(self.h, C.c_uint32(points), C.c_uint32(hop), _ptr(w), C.c_uint32(0 if w is None else w.size)))
+        self._spectrum_points = int(points)
+
+    def wide_spectrum_fetch(self, back=0):
+        """(power float32 [sources][points] — bin k at k * rate / points below points / 2, (k - points) * rate / points from there on —, frames in the block,
+        the feed's sample index at the block's first frame) of the latest block uploaded with the spectrum on (back = 0) or the one before it (back = 1);
+        waits for that block's spectrum kernels only — m17hip_wide_spectrum_fetch.  wide_spectrum_carriers reads the plane."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_spectrum_fetch: back is 0 or 1")
+        S, N = getattr(self, "_wide", (0,))[0], getattr(self, "_spectrum_points", 0)   # (0 where wide_spectrum was never called: the library then refuses)
+        buf = np.zeros(max(S * N, 1), dtype=np.float32)
+        frames, first = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self.lib.m17hip_wide_spectrum_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(S * N), C.byref(frames), C.byref(first)))
+        return buf.reshape(S, N), int(frames.value), int(first.value)
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -24,7 +24,11 @@ With --resample UP DOWN it is the resampling tuner of m17hip_wide_resample (resa
 `decim` x DOWN / UP with the default taps of both stages (2.048 MSPS: --resample 3 8 ... 16); outputs are rounded down to a multiple of UP.  The filter term
 of its floor is C T (DOWN / UP L1 + L2 / UP) packed fma — DOWN / UP first-stage sums per output and the L2 / UP taps of the second stage that meet a sample —
 and the mixing term C T decim DOWN / UP samples.  In the same call the UNCHANGED tune2_kernel is then timed on the same buffer at the neighbouring integer
-shape decim x round(DOWN / UP) (at UP = 1 the very same shape, where the two kernels compute the same words): "neighbour" in the result."""
+shape decim x round(DOWN / UP) (at UP = 1 the very same shape, where the two kernels compute the same words): "neighbour" in the result.
+With --spectrum N --hop H under any of them the same blocks are then timed once more with the source spectrum on (m17hip_wide_spectrum; spectrum_kernel,
+csrc/m17_spectrum_kernels.hpp, and chan_survey_sum_kernel; library timer "spectrum"): the configuration's own kernel with the spectrum on beside its time
+with it off, the spectrum's own time, a device-to-device copy of the same block bytes as the memory yardstick, and the spectrum's floor — 5 N log2 N
+flops per frame at the packed rate, 64 per clock and SIMD."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -57,6 +61,15 @@ if "--survey" in ARGS:
     SURVEY = int(ARGS[k + 1])
     del ARGS[k:k + 2]
     assert RASTER and SURVEY >= 1, "--survey STRIDE goes with --raster M"
+SPECTRUM = HOP = 0   # (0: not timed)
+if "--spectrum" in ARGS:
+    k = ARGS.index("--spectrum")
+    SPECTRUM = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+    assert "--hop" in ARGS, "--spectrum N goes with --hop H"
+    k = ARGS.index("--hop")
+    HOP = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
 T = int(ARGS[2]) if len(ARGS) > 2 else 48000
@@ -135,6 +148,31 @@ for _ in range(REP):
     b.synchronize()
     ev.append(a.elapsed_time(b))
 ms, n = ctx.timing_get("channelise" if RASTER else "tune2" if R2 else "resample" if UP else "tune")
+OWN = "channelise" if RASTER else "tune2" if R2 else "resample" if UP else "tune"
+spectrum = {}
+if SPECTRUM:   # the same blocks once more with the spectrum on: a warm-up block (table, scratch and planes), then REP timed ones; then the copy
+    ctx.wide_spectrum(SPECTRUM, HOP)
+    call()
+    ctx.timing_reset()
+    frames = 0
+    for _ in range(REP):
+        call()
+        frames += ctx.wide_spectrum_fetch()[1]
+    (ms_o, n_o), (ms_p, n_p) = ctx.timing_get(OWN), ctx.timing_get("spectrum")
+    ctx.wide_spectrum(0, 0)
+    y = torch.empty_like(x[:, :ROW])
+    y.copy_(x[:, :ROW])
+    torch.cuda.synchronize()
+    cp = []
+    for _ in range(REP):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); y.copy_(x[:, :ROW]); b.record()
+        b.synchronize()
+        cp.append(a.elapsed_time(b))
+    del y
+    spectrum = {"points": SPECTRUM, "hop": HOP, "launches": n_p, "frames_per_block": frames / REP, "own_kernel_ms_spectrum_off": round(ms / n, 3),
+                "own_kernel_ms_spectrum_on": round(ms_o / n_o, 3), "spectrum_ms": round(ms_p / n_p, 3), "copy_ms_median": round(float(np.median(cp)), 3),
+                "block_bytes": S * ROW * 4}
 neighbour = {}
 if UP:   # tune2_kernel on the same buffer and table at decim x NEIGHBOUR: a warm-up block, then REP timed ones
     ctx.wide_config2(S, R, NEIGHBOUR, m17hip.IQ_I16)
@@ -177,6 +215,11 @@ if SURVEY:
     sc = S * survey["times_per_block"] * (L / 64 * 4 + (RASTER * M2 + RASTER * M1) * 4 / 64 * 2)
     survey["floor_ms"] = round(sc / (4 * cus * mhz * 1e6) * 1e3, 4)
     survey["survey_over_floor"] = round(survey["survey_ms"] / (sc / (4 * cus * mhz * 1e6) * 1e3), 2)
+if SPECTRUM:
+    pc = S * spectrum["frames_per_block"] * 5 * SPECTRUM * (SPECTRUM.bit_length() - 1) / 64
+    pf = pc / (4 * cus * mhz * 1e6) * 1e3
+    spectrum.update(floor_ms=round(pf, 4), spectrum_over_floor=round(spectrum["spectrum_ms"] / pf, 2) if pf else None,
+                    spectrum_over_copy=round(spectrum["spectrum_ms"] / spectrum["copy_ms_median"], 2))
 kernel_ms = ms / n
 if UP:
     nf = neighbour.pop("cycles") / (4 * cus * mhz * 1e6) * 1e3
@@ -189,6 +232,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
