@@ -418,6 +418,71 @@ int m17hip_wide_spectrum_twiddles(uint32_t points, float* out, uint32_t capacity
  * written then. */
 int m17hip_wide_spectrum_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* frames, uint64_t* first_sample);
 
+/* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
+ * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
+ * it, an FM exciter — as rtl_fm is attached in front of the receiver —, is this family: every int16 baseband of a context's input slab (uploaded, or made
+ * by m17hip_synth_i16 / _tx_i16 / _sweep_i16: what m17hip_download_i16 would return) is FM-modulated and put at an offset into one of a few wide IQ streams,
+ * at the rates the receive side accepts, in memory the CALLER supplies.  A TX context makes the multiplex; an RX context takes it through
+ * m17hip_upload_wide_device.  The TX context's stream stays an int16 stream; no existing kernel, launch, stream rule or format rule changes.
+ * THE DEFINITION (ring arithmetic in uint64 and uint32, wrapping):
+ *     RATE AND BLOCK: a source runs at 48000 P / Q samples per second, P in 1..2000, Q in 1..32, gcd(P, Q) = 1, P >= Q — under m17hip_wide_config P = decim,
+ *     under m17hip_wide_config2 P = decim1 decim2, under m17hip_wide_resample P = decim1 down and Q = up.  A block of `samples` baseband samples (a multiple
+ *     of Q) gives W = samples / Q * P wideband samples per source.
+ *     INDICES: c0 = the feed's 64-bit sample count at the block's start (a multiple of P; it begins at the configuration's first_sample); block sample m has
+ *     the absolute index M = c0 + m; k = (m Q) div P and r = (m Q) mod P in 64 bits; b[k] = sample k of the channel's baseband row, b[-1] = the last
+ *     baseband sample of the block before, 0 at the feed's start.
+ *     PHASE: the exact integral of the baseband interpolated linearly between b[k-1] and b[k] — the baseband is delayed by one sample, so no block needs
+ *     its successor:
+ *         A2[k] = A2_carry + sum_{i<k} (b[i-1] + b[i]),   E(m) = A2[k] P^2 + 2 b[k-1] r P + (b[k] - b[k-1]) r^2,   theta(m) = K E(m) mod 2^64.
+ *     K is the configuration's deviation word: 2^64 turns per unit of E, times the deviation per int16 unit and baseband sample, divided by 2 P^2
+ *     (m17hip_synth_wide_k).  Every operation is an integer ring operation: any summation order, scan or tiling gives the same theta, and nothing per
+ *     wideband sample is carried.
+ *     CARRIER AND SUM: p = (uint32)(theta(m) >> 32) + fcw_c (uint32)M + phase0_c; (cos, sin) = core::nco(p); a channel's term is (amplitude_c cos,
+ *     amplitude_c sin), two plain multiplies; x_s[m] = the chain of plain float adds from +0 over the channels of source s among the call's `channels`, in
+ *     ascending channel index (a term of amplitude 0 is a zero of either sign and leaves the chain's words as they are); a source nobody transmits on is
+ *     +0.  fcw means what m17hip_wide_channels means by it at the same rate, and the count enters as in core::ddc_mix: a receiver fed from count 0 sees a
+ *     constant carrier phase.
+ *     NOISE, with sigma > 0: re += (float)(unit_noise(ns_s, 2 M) * (double)sigma), im += the same with 2 M + 1; unit_noise = core::mod_unit_noise, the
+ *     modulator's, M from all 64 bits; ns_s = mod_splitmix64(seed ^ mod_splitmix64(s * 0x9E3779B97F4A7C15 + 0x57494445)) (core::wtx_noise_stream).
+ *     OUTPUT: M17HIP_IQ_F32 the floats as they are; M17HIP_IQ_I16 rintf, clamped to [-32768, 32767]; M17HIP_IQ_U8 rintf(fmaf(v, 1/128, 127.5)), clamped to
+ *     [0, 255]; interleaved I,Q, the row pitch in complex samples — exactly what m17hip_upload_wide* reads.
+ *     CARRIES: per channel A2 (uint64) and the last baseband sample; the context keeps one sample count.  m17hip_synth_wide_config starts count and
+ *     carries over, and so does m17hip_demod_reset on the TX context (the count at the configuration's first_sample again).
+ * m17cxx/detail/core.h has wtx_index, wtx_step, wtx_within, wtx_theta, wtx_phase, wtx_add, wtx_noise, wtx_i16 and wtx_u8, so a host computes the device's
+ * words.  Two kernels on the context's main stream (csrc/m17_wide_tx_kernels.hpp): wide_tx_prefix_kernel writes K P^2 A2[k] per baseband sample to a scratch
+ * plane and advances the carries, wide_tx_mux_kernel makes the streams.  The SCRATCH is 8 bytes per baseband sample of the block, channels * samples * 8
+ * bytes (1.5 GB at 4096 channels of one second): allocated with the first call and grown on demand, M17HIP_ENOMEM where it cannot be had — like the
+ * spectrum's scratch above, it is as large as that says.  The host form keeps the block's output on the device as well (sources * W samples).
+ * m17hip_timing_get index 15 is the generator (both kernels, one entry per block); m17hip_iq_bytes counts its tables, carries and scratch.
+ * Out of scope, for a later pull request: pre-emphasis, interpolation better than linear, per-channel deviation, an async device form, more than one
+ * rate per context. */
+typedef struct m17_wide_tx { uint32_t source; int32_t fcw; uint32_t phase0; float amplitude; } m17_wide_tx; /* 16 bytes */
+/* The deviation word K = 2^63 hz_per_unit / (48000 p^2) for a deviation of hz_per_unit Hz per int16 unit of the baseband; hz_per_unit 0 selects M17's,
+ * 2400 / (3 * 7168) (the outer symbols +-3 x 7168 deviate +-2400 Hz).  Computed in integers and rounded half up: a nonzero hz_per_unit is taken as the
+ * exact binary fraction the double holds, the default as the quotient of integers it is.  No context is needed.  M17HIP_EINVAL for p outside 1..2000, a
+ * NULL k, a negative or non-finite hz_per_unit, or a K that would be 0 or 2^63 and more (half a turn per unit of E); nothing is written then. */
+int m17hip_synth_wide_k(double hz_per_unit, uint32_t p, uint64_t* k);
+/* Configures the generator: sources 1..256 at 48000 p / q (p 1..2000, q 1..32, coprime, p >= q), output of iq_format (M17HIP_IQ_I16, _F32 or _U8), the
+ * deviation word k, noise of noise_sigma (finite, >= 0; 0: none) from `seed`, the feed's count beginning at first_sample (a multiple of p).  The table
+ * is fresh afterwards (every amplitude 0), the carries zero.  It never waits.  M17HIP_EINVAL outside the limits, with nothing changed; M17HIP_ESTATE
+ * between m17hip_demod_front and its run. */
+int m17hip_synth_wide_config(m17hip_ctx* ctx, uint32_t sources, uint32_t p, uint32_t q, int iq_format, uint64_t k, float noise_sigma, uint64_t seed,
+                             uint64_t first_sample);
+/* Channel c < n transmits on tx[c].source at the frequency word tx[c].fcw with the start phase tx[c].phase0 and the amplitude tx[c].amplitude (in output
+ * units: int16 units for M17HIP_IQ_I16 and _U8, which scales by 1/128); entries >= n keep theirs.  It holds from the next m17hip_synth_wide call and
+ * never waits: the table takes turns in two device copies.  M17HIP_EINVAL for n above the context's channels, a NULL tx, a source at or above
+ * `sources`, an amplitude that is negative or not finite — nothing is changed then; M17HIP_ESTATE before the configuration and between
+ * m17hip_demod_front and its run. */
+int m17hip_synth_wide_channels(m17hip_ctx* ctx, const m17_wide_tx* tx, uint32_t n);
+/* One block: the `channels` x `samples` int16 input the slab holds becomes dst[sources][pitch] complex samples of the configured format, W = samples / q * p
+ * of them written per row; dst is host memory (m17hip_synth_wide) or device memory (m17hip_synth_wide_device).  Both are complete when they return — the
+ * completeness m17hip_upload_wide_device asks of its producer.  M17HIP_EINVAL for a NULL pointer, channels or samples of 0 or above the context's,
+ * samples not a multiple of q, W above 2^32 - 1, pitch < W; M17HIP_ESTATE before the configuration, on a float stream, where the slab holds no int16
+ * input of channels x samples, and between m17hip_demod_front and its run; M17HIP_ENOMEM if the scratch cannot be had.  Nothing is written and no
+ * carry moves on a refusal. */
+int m17hip_synth_wide(m17hip_ctx* ctx, void* dst_host, uint32_t channels, uint32_t samples, size_t pitch);
+int m17hip_synth_wide_device(m17hip_ctx* ctx, void* dst_dev, uint32_t channels, uint32_t samples, size_t pitch);
+
 /* ---- wideband IQ input at rational sample rates: a resampling tuner (ABI 615) -------------------------------
  * Every configuration above wants a source at an INTEGER multiple of 48 kSPS, and the rates receivers run at by default are not: rtl_sdr's 2.048 MSPS is
  * 128/3 of it (1.024: 64/3, 2.56: 160/3), an Airspy's 2.5, 3, 6 and 10 MSPS 625/12, 125/2, 125 and 625/3, a HackRF's 8 and 20 MSPS 500/3 and 1250/3.  This
@@ -962,7 +1027,7 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
  * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
  * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block), 14 = spectrum (the two
- * kernels of m17hip_wide_spectrum, one entry per transformed block). */
+ * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -23,13 +23,8 @@ struct ModParams {   // layout of m17_synth_params (include/m17hip.h)
     double lead_sigma, noise_sigma, dc_offset, gain, tail_sigma;
 };
 
-__host__ __device__ inline uint64_t mod_splitmix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+using core::mod_splitmix64;   // (the hash and the noise are defined once for host and device: m17cxx/detail/core.h)
+using core::mod_unit_noise;
 __device__ inline uint64_t mod_channel_seed(uint64_t base, uint64_t cc) { return base ^ mod_splitmix64(cc * 0x9E3779B97F4A7C15ull + 1); }
 
 // M17Randomizer.h:16-22 (decorrelation sequence)
@@ -352,16 +347,6 @@ __global__ __launch_bounds__(64) void mod_symbols_tx_kernel(const ModTx* tx, con
     out[48u * (npre + slot) + lane] = word;
 }
 
-// Zero-mean unit-variance noise for (stream, n): sum of 8 uniform u16 from two splitmix64 words, exact in double
-__device__ inline double mod_unit_noise(uint64_t stream, uint64_t n)
-{
-    const uint64_t h = mod_splitmix64(stream ^ (n * 0xD1342543DE82EF95ull));
-    const uint64_t g = mod_splitmix64(h);
-    int64_t sum = 0;
-    for (int k = 0; k < 4; ++k) { sum += (int64_t)((h >> (16 * k)) & 0xFFFF); sum += (int64_t)((g >> (16 * k)) & 0xFFFF); }
-    const double inv_sigma = 1.0 / 53510.38419625641;
-    return (double)(2 * sum - 8 * 65535) * 0.5 * inv_sigma;
-}
 __device__ inline int16_t mod_sat16(double v)
 {
     double r = rint(v);

@@ -13,6 +13,7 @@
 #include "m17_chan_kernels.hpp"
 #include "m17_chan_survey_kernels.hpp"
 #include "m17_spectrum_kernels.hpp"
+#include "m17_wide_tx_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_demod_kernel.hpp"
 #include "m17_gate_kernel.hpp"
@@ -38,7 +39,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -405,6 +406,26 @@ struct m17hip_ctx {
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4;
         }
     } wide;
+    // THE WIDEBAND SIGNAL GENERATOR (m17hip_synth_wide_config, m17hip_synth_wide; csrc/m17_wide_tx_kernels.hpp): the int16 input slab's rows FM-modulated into
+    // S wide streams at 48000 P / Q in the caller's memory.  Of its own: the channel table — on the host [maxC] entries, on the device a turn-taking copy of
+    // the per-source lists made for the channels of a call —, the carries (A2 per channel; the last baseband sample in two copies that take turns, `par` names
+    // the one to read), the scratch plane of phase bases (8 bytes per baseband sample of the largest block so far) and, for the host form, the block's
+    // output before it is copied out.  Every call is complete when it returns, so nothing here is ever in flight between calls.
+    struct WideTx {
+        uint32_t S = 0, P = 0, Q = 0; int fmt = 0;   // S == 0: not configured
+        uint64_t K = 0, seed = 0, first = 0, count = 0;
+        float sigma = 0.0f;
+        std::vector<m17_wide_tx> table;   // [maxC]
+        bool dirty = true;
+        TurnTable dev;
+        uint32_t dev_C = 0;
+        DevBuf<uint64_t> a2, plane;       // [maxC]; [channels][samples] of the largest block
+        DevBuf<int32_t> last;             // [2][maxC]
+        DevBuf<char> out;                 // the host form's block
+        int par = 0;
+        bool fresh = true;                // the carries are zeroed in front of the next block (a feed's start)
+        size_t bytes() const { return (a2.size() + plane.size()) * 8 + last.size() * 4 + out.size() + dev.words() * 4; }
+    } wtx;
     Slab& now() { return slab[slot]; }         // the current / latest run's
     Slab& other() { return slab[slot ^ 1]; }   // the staging pair (the run before the latest one's)
     bool foreign_streams[4] = {false, false, false, false};   // tools build, keys 40-43: side / side2 / side3 / copy belong to the experiment, not to the context
@@ -1231,7 +1252,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 616; }
+int m17hip_version(void) { return 617; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1920,7 +1941,7 @@ int m17hip_upload_iq_device_async(m17hip_ctx* c, const void* dev, int iq_format,
 int m17hip_iq_bytes(m17hip_ctx* c, uint64_t* bytes)
 {
     if (!c || !bytes) return M17HIP_EINVAL;
-    *bytes = c->iq_carry.size() * sizeof(float2) + c->iq_raw.size() + c->wide.bytes();
+    *bytes = c->iq_carry.size() * sizeof(float2) + c->iq_raw.size() + c->wide.bytes() + c->wtx.bytes();
     return M17HIP_OK;
 }
 
@@ -2367,6 +2388,126 @@ int m17hip_synth_tx_i16(m17hip_ctx* c, const m17_synth_params* base, const m17_t
     return M17HIP_OK;
 }
 
+// ---- the wideband signal generator (ABI 617): FM-multiplex basebands of the int16 input slab ---------------------------------------------------
+static uint32_t wtx_gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
+// K = 2^63 hz_per_unit / (48000 p^2), rounded half up, in integers: hz_per_unit is mant 2^(e - 53) exactly (frexp), the default 2400 / 21504 a quotient of
+// integers.  Refused: a K of 0 or of 2^63 and more, a numerator that does not fit 128 bits.
+int m17hip_synth_wide_k(double hz_per_unit, uint32_t p, uint64_t* k)
+{
+    if (!k || p < 1 || p > 2000 || !std::isfinite(hz_per_unit) || hz_per_unit < 0.0) return M17HIP_EINVAL;
+    typedef unsigned __int128 u128;
+    u128 num, den = (u128)48000u * p * p;
+    if (hz_per_unit == 0.0) { num = (u128)2400u << 63; den *= 21504u; }
+    else {
+        int e = 0;
+        const double f = std::frexp(hz_per_unit, &e);   // hz_per_unit = f 2^e, 0.5 <= f < 1
+        const uint64_t mant = (uint64_t)std::ldexp(f, 53);
+        const int sh = e + 10;   // 2^63 mant 2^(e - 53) = mant 2^(e + 10)
+        if (sh > 74) return M17HIP_EINVAL;
+        if (sh >= 0) num = (u128)mant << sh;
+        else { if (-sh > 64) return M17HIP_EINVAL; num = mant; den <<= -sh; }
+    }
+    const u128 q = (num + den / 2) / den;
+    if (q == 0 || q >= ((u128)1 << 63)) return M17HIP_EINVAL;
+    *k = (uint64_t)q;
+    return M17HIP_OK;
+}
+int m17hip_synth_wide_config(m17hip_ctx* c, uint32_t sources, uint32_t p, uint32_t q, int iq_format, uint64_t k, float noise_sigma, uint64_t seed,
+                             uint64_t first_sample)
+{
+    if (!c || sources < 1 || sources > 256 || p < 1 || p > 2000 || q < 1 || q > 32 || p < q || wtx_gcd(p, q) != 1) return M17HIP_EINVAL;
+    if (iq_format != M17HIP_IQ_I16 && iq_format != M17HIP_IQ_F32 && iq_format != M17HIP_IQ_U8) return M17HIP_EINVAL;
+    if (!std::isfinite(noise_sigma) || noise_sigma < 0.0f || first_sample % p) return M17HIP_EINVAL;
+    if (c->front_queued) return M17HIP_ESTATE;
+    auto& w = c->wtx;
+    w.S = sources; w.P = p; w.Q = q; w.fmt = iq_format; w.K = k; w.sigma = noise_sigma; w.seed = seed; w.first = w.count = first_sample;
+    w.table.assign(c->maxC, m17_wide_tx{0u, 0, 0u, 0.0f});   // (a fresh table: nobody transmits)
+    w.dirty = true; w.fresh = true;
+    return M17HIP_OK;
+}
+int m17hip_synth_wide_channels(m17hip_ctx* c, const m17_wide_tx* tx, uint32_t n)
+{
+    if (!c || !tx || n > c->maxC) return M17HIP_EINVAL;
+    auto& w = c->wtx;
+    if (!w.S || c->front_queued) return M17HIP_ESTATE;
+    for (uint32_t i = 0; i < n; ++i)
+        if (tx[i].source >= w.S || !std::isfinite(tx[i].amplitude) || tx[i].amplitude < 0.0f) return M17HIP_EINVAL;
+    std::copy(tx, tx + n, w.table.begin());
+    w.dirty = true;
+    return M17HIP_OK;
+}
+static int synth_wide(m17hip_ctx* c, void* dst, uint32_t C, uint32_t T, size_t pitch, bool host)
+{
+    if (!c || !dst || C == 0 || T == 0 || C > c->maxC || T > c->maxT) return M17HIP_EINVAL;
+    auto& w = c->wtx;
+    if (!w.S || c->front_queued || c->stream_fmt == M17HIP_FORMAT_F32) return M17HIP_ESTATE;
+    if (!c->uploaded || c->slab_fmt[c->slot] != M17HIP_FORMAT_I16 || c->now().C != C || c->now().T != T) return M17HIP_ESTATE;   // (no such int16 input there)
+    if (T % w.Q) return M17HIP_EINVAL;
+    const uint64_t W64 = (uint64_t)(T / w.Q) * w.P;
+    if (W64 > 0xFFFFFFFFull || pitch < W64) return M17HIP_EINVAL;
+    const uint32_t W = (uint32_t)W64;
+    GUARD(c);
+    const hipStream_t st = c->stream;
+    const size_t sb = iq_sample_bytes(w.fmt);
+    int r;
+    if (!w.a2 && (r = alloc_code(c, w.a2.alloc(c->maxC)))) return r;
+    if (!w.last && (r = alloc_code(c, w.last.alloc(2 * (size_t)c->maxC)))) return r;
+    if ((r = alloc_code(c, w.plane.grow((size_t)C * T, &c->last_hip)))) return r;   // (every earlier block is complete: nothing reads the one it outgrew)
+    if (host && (r = alloc_code(c, w.out.grow((size_t)w.S * W * sb, &c->last_hip)))) return r;
+    if (w.fresh) {
+        HIPCHK(c, hipMemsetAsync(w.a2, 0, w.a2.size() * 8, st));
+        HIPCHK(c, hipMemsetAsync(w.last, 0, w.last.size() * 4, st));
+        w.fresh = false;
+    }
+    if (w.dirty || !w.dev.live() || w.dev_C != C) {   // the lists by source of the channels < C that transmit, into the copy no queued launch reads
+        uint32_t* t = nullptr;
+        HIPCHK(c, w.dev.begin_write(wtx_table_words(256, c->maxC), &t));
+        uint32_t* first = t;
+        std::fill(first, first + w.S + 1, 0u);
+        for (uint32_t ch = 0; ch < C; ++ch) if (w.table[ch].amplitude > 0.0f) ++first[w.table[ch].source + 1];   // (a term of amplitude 0 is a zero: +0 + -0 = +0)
+        for (uint32_t s = 0; s < w.S; ++s) first[s + 1] += first[s];
+        std::vector<uint32_t> at(first, first + w.S);
+        uint32_t* ent = t + w.S + 1;
+        for (uint32_t ch = 0; ch < C; ++ch) {
+            const m17_wide_tx& e = w.table[ch];
+            if (!(e.amplitude > 0.0f)) continue;
+            uint32_t* o = ent + WTX_ENTRY * (size_t)at[e.source]++;
+            o[0] = ch; o[1] = (uint32_t)e.fcw; o[2] = e.phase0;
+            std::memcpy(o + 3, &e.amplitude, 4);
+        }
+        HIPCHK(c, w.dev.publish(wtx_table_words(w.S, first[w.S]), st));
+        w.dirty = false; w.dev_C = C;
+    }
+    HIPCHK(c, w.dev.before_read(st));
+    const int32_t* last_in = w.last.get() + (size_t)w.par * c->maxC;
+    int32_t* last_out = w.last.get() + (size_t)(w.par ^ 1) * c->maxC;
+    const uint32_t NK = wtx_span(w.P, w.Q), CH = wtx_chunk(NK);
+    void* out = host ? (void*)w.out.get() : dst;
+    const size_t opitch = host ? (size_t)W : pitch;
+    {
+        Timed tm(c, KT_WIDE_TX, st);
+        hipLaunchKernelGGL(wide_tx_prefix_kernel, dim3(c->maxC), dim3(64), 0, st, c->now().x.get(), c->xpitch, C, T, w.K * w.P * w.P, w.a2.get(), last_in,
+                           last_out, w.plane.get(), (size_t)T);
+        HIPCHK(c, hipGetLastError());
+        r = with_iq_type(w.fmt, [&](auto s) -> int {
+            hipLaunchKernelGGL(wide_tx_mux_kernel<decltype(s)>, dim3((W + WTX_TILE - 1) / WTX_TILE, w.S), dim3(WTX_THREADS), wtx_lds_bytes(NK, CH), st,
+                               c->now().x.get(), c->xpitch, w.plane.get(), (size_t)T, last_in, w.dev.dev(), w.S, w.P, w.Q, w.K, W, w.count, NK, CH, w.sigma,
+                               w.seed, static_cast<decltype(s)*>(out), opitch);
+            HIPCHK(c, hipGetLastError());
+            return M17HIP_OK;
+        });
+        if (r) return r;
+    }
+    HIPCHK(c, w.dev.after_read(RD_MAIN, st));
+    if (host) HIPCHK(c, hipMemcpy2DAsync(dst, pitch * sb, out, opitch * sb, (size_t)W * sb, w.S, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // complete when it returns: what m17hip_upload_wide_device asks of its producer
+    w.par ^= 1;
+    w.count += W;
+    return M17HIP_OK;
+}
+int m17hip_synth_wide(m17hip_ctx* c, void* dst_host, uint32_t C, uint32_t T, size_t pitch) { return synth_wide(c, dst_host, C, T, pitch, true); }
+int m17hip_synth_wide_device(m17hip_ctx* c, void* dst_dev, uint32_t C, uint32_t T, size_t pitch) { return synth_wide(c, dst_dev, C, T, pitch, false); }
+
 int m17hip_fir_rrc150(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t flags, float* out_host)
 {
     if (!c || C == 0 || T == 0 || C > c->maxC || T > c->maxT || (flags & ~M17HIP_FLAG_INVERT)) return M17HIP_EINVAL;
@@ -2666,6 +2807,7 @@ int m17hip_demod_reset(m17hip_ctx* c)
         HIPCHK(c, hipMemsetAsync(c->hist_f, 0, c->hist_f.size() * sizeof(float), c->stream));
     }
     if (int r = iq_fresh_feed(c, nullptr, 0)) return r;   // (a context that has seen IQ input: every channel's feed starts over)
+    c->wtx.count = c->wtx.first; c->wtx.fresh = true;   // (a generator's feed likewise: count and carries as m17hip_synth_wide_config left them)
     HIPCHK(c, hipMemset2DAsync(c->now().h, c->ypitch * sizeof(float), 0, YPRE * sizeof(float), c->maxC, c->stream));
     if (int r = c->bert.reset(c, c->stream)) return r;
     if (int r = c->packets.reset(c, c->stream)) return r;

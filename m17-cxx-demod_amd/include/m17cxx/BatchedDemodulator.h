@@ -135,6 +135,27 @@ public:
     {
         check(m17hip_wide_spectrum_fetch(ctx_, back, power, capacity, frames, first_sample), "m17hip_wide_spectrum_fetch");
     }
+    // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
+    // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
+    // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,
+    // complete on return: an RX object's upload_wide_device may take it at once.
+    static uint64_t wide_tx_k(uint32_t p, double hz_per_unit = 0.0)
+    {
+        uint64_t k = 0;
+        if (m17hip_synth_wide_k(hz_per_unit, p, &k) != M17HIP_OK) throw std::invalid_argument("m17hip_synth_wide_k: no such deviation word");
+        return k;
+    }
+    void synth_wide_config(uint32_t sources, uint32_t p, uint32_t q, int iq_format, uint64_t k = 0, float noise_sigma = 0.0f, uint64_t seed = 0,
+                           uint64_t first_sample = 0)
+    {
+        check(m17hip_synth_wide_config(ctx_, sources, p, q, iq_format, k ? k : wide_tx_k(p), noise_sigma, seed, first_sample), "m17hip_synth_wide_config");
+    }
+    void synth_wide_channels(const m17_wide_tx* tx, uint32_t n) { check(m17hip_synth_wide_channels(ctx_, tx, n), "m17hip_synth_wide_channels"); }
+    void synth_wide(void* dst, uint32_t channels, uint32_t samples, size_t pitch, bool device = false)
+    {
+        check(device ? m17hip_synth_wide_device(ctx_, dst, channels, samples, pitch) : m17hip_synth_wide(ctx_, dst, channels, samples, pitch),
+              "m17hip_synth_wide");
+    }
     // the bin of an offset in Hz from the source's centre; throws where the offset is not on the raster or outside it
     static int32_t wide_bin(double offset_hz, uint32_t decim, uint32_t bins)
     {

@@ -312,6 +312,82 @@ M17_HD void spec_item2(float* v, const float* tw, uint32_t logn, uint32_t s, uin
 // One windowed sample on its way into the FFT: two plain multiplies.
 M17_HD void spec_window(float w, float xre, float xim, float& re, float& im) { re = w * xre; im = w * xim; }
 
+// ---- t1: the wideband signal generator (m17hip_synth_wide, ABI 617): FM-modulate int16 basebands and put them at offsets into wide IQ streams -------
+// No reference file: the reference's users attach an FM exciter behind its modulator.  Written here, once, so that the kernels and the host form give the
+// same words.  Everything up to the oscillator's argument is INTEGER RING arithmetic (uint64 / uint32, wrapping), so any summation order, scan or tiling
+// gives the same phase; nothing per wideband sample is carried.
+// The generator's and the modulator's hash and noise (the modulator's kernels, csrc/m17_mod_kernels.hpp, use these): splitmix64, and zero-mean
+// unit-variance noise for (stream, n) — the sum of 8 uniform u16 from two splitmix64 words, exact in double.
+M17_HD uint64_t mod_splitmix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+M17_HD double mod_unit_noise(uint64_t stream, uint64_t n)
+{
+    const uint64_t h = mod_splitmix64(stream ^ (n * 0xD1342543DE82EF95ull));
+    const uint64_t g = mod_splitmix64(h);
+    int64_t sum = 0;
+    for (int k = 0; k < 4; ++k) { sum += (int64_t)((h >> (16 * k)) & 0xFFFF); sum += (int64_t)((g >> (16 * k)) & 0xFFFF); }
+    const double inv_sigma = 1.0 / 53510.38419625641;
+    return (double)(2 * sum - 8 * 65535) * 0.5 * inv_sigma;
+}
+// the noise stream of source s under the configuration's seed
+M17_HD uint64_t wtx_noise_stream(uint64_t seed, uint32_t s) { return mod_splitmix64(seed ^ mod_splitmix64((uint64_t)s * 0x9E3779B97F4A7C15ull + 0x57494445ull)); }
+// Block sample m of a source at 48000 P / Q: baseband sample k = (m Q) div P and the place r = (m Q) mod P inside it, from a 64-bit product.
+M17_HD void wtx_index(uint32_t m, uint32_t P, uint32_t Q, uint32_t& k, uint32_t& r)
+{
+    const uint64_t t = (uint64_t)m * Q;
+    k = (uint32_t)(t / P);
+    r = (uint32_t)(t % P);
+}
+// A2[k + 1] - A2[k] = b[k - 1] + b[k]: twice the integral of the linearly interpolated baseband over baseband sample k (int16 values as int32)
+M17_HD uint64_t wtx_step(int32_t bp, int32_t b) { return (uint64_t)(int64_t)(bp + b); }
+// E(m) - A2[k] P^2 = 2 b[k-1] r P + (b[k] - b[k-1]) r^2, as r (2 b[k-1] P + (b[k] - b[k-1]) r): with P <= 2000 the inner sum is below 2^28 in magnitude
+// (int32), its product with r < P a 32 x 32 -> 64 bit one
+M17_HD uint64_t wtx_within(int32_t bp, int32_t b, uint32_t r, uint32_t P)
+{
+    const int32_t t = 2 * bp * (int32_t)P + (b - bp) * (int32_t)r;
+    return (uint64_t)((int64_t)t * (int64_t)(int32_t)r);
+}
+// The oscillator's argument: the top 32 bits of theta = K E = base + K within, base = K P^2 A2[k], plus the carrier's fcw (uint32)M + phase0 — the
+// count enters as in ddc_mix, so a receiver fed from count 0 sees a constant carrier phase.
+M17_HD uint64_t wtx_theta(uint64_t base, uint64_t K, uint64_t within) { return base + K * within; }
+M17_HD uint32_t wtx_phase(uint64_t theta, uint32_t fcw, uint32_t M, uint32_t phase0) { return (uint32_t)(theta >> 32) + fcw * M + phase0; }
+// One channel's term onto the source's sum: nco, two plain multiplies, two plain adds.
+M17_HD void wtx_add(float amplitude, uint32_t p, float& re, float& im)
+{
+    float c, s;
+    nco(p, c, s);
+    const float tr = amplitude * c, ti = amplitude * s;
+    re = re + tr;
+    im = im + ti;
+}
+// sigma > 0: noise from all 64 bits of the feed's sample index M, words 2 M and 2 M + 1 of the source's stream
+M17_HD void wtx_noise(uint64_t ns, uint64_t M, float sigma, float& re, float& im)
+{
+    re = re + (float)(mod_unit_noise(ns, 2 * M) * (double)sigma);
+    im = im + (float)(mod_unit_noise(ns, 2 * M + 1) * (double)sigma);
+}
+// The output formats: M17HIP_IQ_I16 rintf clamped to [-32768, 32767]; M17HIP_IQ_U8 rintf(fmaf(v, 1/128, 127.5)) clamped to [0, 255] (a NaN — only
+// infinities of both signs can make one — takes the upper limit on both sides of the boundary).
+M17_HD int16_t wtx_i16(float v)
+{
+    float r = __builtin_rintf(v);
+    r = r < 32767.0f ? r : 32767.0f;
+    r = r > -32768.0f ? r : -32768.0f;
+    return (int16_t)(int32_t)r;
+}
+M17_HD uint8_t wtx_u8(float v)
+{
+    float r = __builtin_rintf(__builtin_fmaf(v, 0.0078125f, 127.5f));
+    r = r < 255.0f ? r : 255.0f;
+    r = r > 0.0f ? r : 0.0f;
+    return (uint8_t)(int32_t)r;
+}
+
 // ---- a2: RRC matched filter taps (M17Demodulator.h:79-118): alpha = 0.5, 10 samples per symbol, 149 symmetric taps and
 // a trailing 0.0; the double literals narrowed to float.  FIR order: FirFilter.h:36-40 (newest sample first, i = 0..149).
 constexpr int RRC_TAPS = 150;

@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -54,6 +54,7 @@ CHAN_STAT_DTYPE = np.dtype([("channel", "<u4"), ("point", "<u4"), ("bits", "<u4"
 assert IMPAIRMENT_DTYPE.itemsize == 32 and CHAN_STAT_DTYPE.itemsize == 32
 MAX_SWEEP_POINTS = 4096
 TX_DTYPE = np.dtype([("kind", "<u4"), ("n_frames", "<u4"), ("first_row", "<u4"), ("reserved", "<u4")])   # m17_tx
+WIDE_TX_DTYPE = np.dtype([("source", "<u4"), ("fcw", "<i4"), ("phase0", "<u4"), ("amplitude", "<f4")])   # m17_wide_tx
 TX_BERT, TX_STREAM, TX_PACKET = 0, 1, 2
 
 EXPORTS = [
@@ -77,6 +78,7 @@ EXPORTS = [
     "m17hip_wide_survey", "m17hip_wide_survey_fetch",
     "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
+    "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
 FORMAT_I16, FORMAT_F32 = 1, 2   # M17HIP_FORMAT_*
@@ -321,6 +323,16 @@ def wide_spectrum_carriers(power, rate_hz, width_hz=9000.0, margin_db=10.0):
             free[(k + np.arange(-excl, excl + 1)) % N] = False
     out.sort(key=lambda e: -e[2])
     return out
+
+
+def synth_wide_k(hz_per_unit=0.0, p=1):
+    """The deviation word of Context.synth_wide_config for a deviation of hz_per_unit Hz per int16 unit of the baseband at 48000 * p / q samples per
+    second: 2^63 hz_per_unit / (48000 p^2) rounded half up; 0 selects M17's 2400 / (3 * 7168) — m17hip_synth_wide_k (no context, no GPU)."""
+    k = C.c_uint64(0)
+    code = load_library().m17hip_synth_wide_k(C.c_double(hz_per_unit), C.c_uint32(p), C.byref(k))
+    if code != 0:
+        raise M17HipError(f"m17hip_synth_wide_k: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
+    return int(k.value)
 
 
 def wide_fcw(offset_hz, decim):
@@ -709,6 +721,52 @@ class Context:
         self._chk(self.lib.m17hip_synth_tx_i16(self.h, C.byref(base), _ptr(tx), _ptr(lsf), _ptr(rows_arr), C.c_uint32(len(rows)),
                                                C.c_uint32(len(transmissions)), C.c_uint32(int(samples)), C.c_uint32(chan0)))
         self.C, self.T = len(transmissions), int(samples)
+
+    def synth_wide_config(self, sources, p, q=1, fmt=IQ_I16, k=None, noise_sigma=0.0, seed=0, first_sample=0):
+        """Configure the wideband signal generator: `sources` streams at 48000 * p / q samples per second in the format `fmt`, the deviation word k (None:
+        synth_wide_k(0, p), M17's deviation), noise of noise_sigma from `seed`, the feed's sample count beginning at first_sample (a multiple of p) —
+        m17hip_synth_wide_config.  The table is fresh afterwards: nobody transmits."""
+        k = synth_wide_k(0.0, p) if k is None else int(k)
+        self._chk(self.lib.m17hip_synth_wide_config(self.h, C.c_uint32(sources), C.c_uint32(p), C.c_uint32(q), C.c_int(fmt), C.c_uint64(k),
+                                                    C.c_float(noise_sigma), C.c_uint64(seed), C.c_uint64(first_sample)))
+        self._wide_tx = (int(sources), int(p), int(q), int(fmt))
+
+    def synth_wide_channels(self, source, fcw, phase0=0, amplitude=0.0):
+        """Channel c transmits on source[c] at the frequency word fcw[c] (wide_fcw at the generator's rate, p / q) with the start phase phase0[c] and the
+        amplitude amplitude[c] (scalars hold for every channel) from the next synth_wide call; channels past the sequences keep theirs —
+        m17hip_synth_wide_channels.  A WIDE_TX_DTYPE array as `source` is taken as the table itself."""
+        if isinstance(source, np.ndarray) and source.dtype == WIDE_TX_DTYPE:
+            tx = np.ascontiguousarray(source.reshape(-1))
+        else:
+            src = np.asarray(source, dtype=np.uint32).reshape(-1)
+            tx = np.zeros(src.size, dtype=WIDE_TX_DTYPE)
+            tx["source"] = src
+            tx["fcw"] = np.broadcast_to(np.asarray(fcw, dtype=np.int64), src.shape).astype(np.int32)
+            tx["phase0"] = np.broadcast_to(np.asarray(phase0, dtype=np.int64) & 0xFFFFFFFF, src.shape).astype(np.uint32)
+            tx["amplitude"] = np.broadcast_to(np.asarray(amplitude, dtype=np.float32), src.shape)
+        self._chk(self.lib.m17hip_synth_wide_channels(self.h, tx.ctypes.data_as(C.c_void_p), C.c_uint32(tx.size)))
+
+    def synth_wide(self, samples=None, out=None, channels=None):
+        """One block of the generator from the int16 input the slab holds (`channels` x `samples`, default: the last input's; samples a multiple of q):
+        W = samples / q * p complex samples per source.  out = None: a numpy array complex64 [S][W], or int16 / uint8 [S][W][2] — m17hip_synth_wide.
+        out = a torch tensor ON THE DEVICE of that dtype and at least that shape ([S][pitch] complex64 or [S][pitch][2]), contiguous: filled in place,
+        complete when this returns (what upload_wide / upload_wide_device ask of their producer) — m17hip_synth_wide_device."""
+        S, P, Q, fmt = getattr(self, "_wide_tx", (0, 1, 1, IQ_I16))
+        n = int(self.T if samples is None else samples)
+        ch = int(self.C if channels is None else channels)
+        W = n // Q * P
+        if out is None:
+            shape = (max(S, 1), max(W, 1))
+            a = np.zeros(shape, dtype=np.complex64) if fmt == IQ_F32 else np.zeros(shape + (2,), dtype=np.int16 if fmt == IQ_I16 else np.uint8)
+            self._chk(self.lib.m17hip_synth_wide(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint32(ch), C.c_uint32(n), C.c_size_t(a.shape[1])))
+            return a[:S, :W]
+        kinds = {"torch.complex64": IQ_F32, "torch.int16": IQ_I16, "torch.uint8": IQ_U8}
+        if not (hasattr(out, "data_ptr") and out.is_cuda and out.is_contiguous()) or kinds.get(str(out.dtype)) != fmt:
+            raise TypeError("out is a contiguous device tensor of the configured format")
+        if out.dim() != (2 if fmt == IQ_F32 else 3) or out.shape[0] < S or (fmt != IQ_F32 and out.shape[2] != 2):
+            raise TypeError("out is complex64 [S][pitch], or int16 / uint8 [S][pitch][2]")
+        self._chk(self.lib.m17hip_synth_wide_device(self.h, C.c_void_p(out.data_ptr()), C.c_uint32(ch), C.c_uint32(n), C.c_size_t(out.shape[1])))
+        return out
 
     def download(self, channels=None):
         """The input slab's first `channels` rows (default: all of the last input)."""
