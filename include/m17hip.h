@@ -399,7 +399,9 @@ int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, 
  * the demodulator, assigning channels on the device. */
 /* points = 0 turns the spectrum off (the default).  Otherwise points is a power of two in 64..4096, hop is in 1..2^24 and window[nwindow] holds `points`
  * finite floats; NULL with a count of 0 selects m17hip_wide_spectrum_default_window's.  It holds for the blocks uploaded AFTER the call and never waits for
- * anything in flight: window and twiddles travel with the next block.  Planes of blocks transformed before the call are no longer fetched.  Legal under
+ * anything in flight: window and twiddles travel with the next block.  (What a change can cost is paid by that NEXT upload, not by this call: where
+ * `points` has risen the upload regrows the two planes, and where the block needs more scratch than any before it the scratch; either waits on the host
+ * for the blocks still in flight.)  Planes of blocks transformed before the call are no longer fetched.  Legal under
  * EVERY wideband configuration, the raster included, and independent of m17hip_wide_survey.  M17HIP_EINVAL outside the limits (a NULL context included),
  * with nothing changed; M17HIP_ESTATE before any wideband configuration and between m17hip_demod_front and its run.  Every m17hip_wide_config,
  * m17hip_wide_config2, m17hip_wide_raster or m17hip_wide_resample call turns it off: the plane has a row per source. */

@@ -1760,7 +1760,12 @@ static int launch_spectrum(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t
     int r;
     if (!sp.fetch) HIPCHK(c, hipStreamCreateWithFlags(&sp.fetch, hipStreamNonBlocking));
     for (auto& e : sp.ev) if (!e) HIPCHK(c, e.create());
-    for (auto& b : sp.plane) if ((r = alloc_code(c, b.grow((size_t)w.S * N, &c->last_hip)))) return r;   // (released with every configuration: nothing reads them)
+    // The planes are regrown where `points` has risen since they were made (m17hip_wide_spectrum never frees: its call waits for nothing).  The block before
+    // may still be writing the old ones then — its sum kernel is the last but one of its chain, and `st` has only been put behind ev_iq, the host has not
+    // waited.  What orders the release behind that writer is hipFree itself, which synchronises the device before it frees (documented in
+    // hip_runtime_api.h): this upload then returns no earlier than the block before ends (tests/test_gpu_call_orders_spectrum.py: 9.3 - 9.7 ms with a
+    // tuner of 7.5 ms in flight).  A release that does not wait (a pool, hipFreeAsync) needs hipEventSynchronize(c->ev_iq) here, as the scratch below has.
+    for (auto& b : sp.plane) if ((r = alloc_code(c, b.grow((size_t)w.S * N, &c->last_hip)))) return r;
     if (sp.scratch.size() < (size_t)w.S * G * N) {
         HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be transformed)
         if ((r = alloc_code(c, sp.scratch.grow((size_t)w.S * G * N, &c->last_hip)))) return r;
