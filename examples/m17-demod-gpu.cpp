@@ -12,7 +12,8 @@
 // centre, dB over the floor); with --spectrum N [--hop H, default N] under ANY wideband option the averaged N-point periodogram of each block is
 // computed on the device and the carriers it shows — the rule of m17hip's Python wide_spectrum_carriers: 9 kHz bands, more than --scan-margin dB over the
 // median floor — are printed to stderr with the offset in Hz that --offset-hz takes: rtl_sdr -s 2048000 ... | m17-demod-gpu --wide-u8 --rate 2048000
-// --spectrum 2048.  One line per frame callback on
+// --spectrum 2048; with --meter W (16 to 65536 outputs; 1920 is one M17 frame) under ANY wideband option the channel's level, its carrier's offset from
+// the tuned frequency and its deviation are measured on the device per window of W outputs and printed to stderr after each block.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -105,6 +106,7 @@ int main(int argc, char** argv)
     double scan_margin = 20.0;
     bool margin_given = false;
     uint32_t spectrum = 0, hop = 0;   // (spectrum == 0: none; hop == 0: the points)
+    uint32_t meter = 0;               // (0: no meter)
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -122,9 +124,10 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--scan") && i + 1 < argc) { scan = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!scan) scan = 4097; }
         else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) { scan_margin = std::strtod(argv[++i], nullptr); margin_given = true; }
         else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) { spectrum = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!spectrum) spectrum = 1; }
+        else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) { meter = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!meter) meter = 1; }
         else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H]] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H]] [--meter W] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -149,6 +152,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (scan && (!(wide && raster) || scan > 4096)) { std::fprintf(stderr, "m17-demod-gpu: --scan STRIDE (1 to 4096) goes with --raster\n"); return 2; }
+    if (meter && (!wide || meter < 16 || meter > 65536)) { std::fprintf(stderr, "m17-demod-gpu: --meter W (16 to 65536 outputs) goes with a wideband format\n"); return 2; }
     if (spectrum || hop) {
         if (!hop) hop = spectrum;
         if (!wide || spectrum < 64 || spectrum > 4096 || (spectrum & (spectrum - 1)) || hop > (1u << 24)) {
@@ -201,6 +205,13 @@ int main(int argc, char** argv)
                 for (const auto& c : carriers(power, fs, 9000.0, margin)) std::fprintf(stderr, "spectrum: carrier %+.1f Hz %.2f dB\n", c.first, c.second);
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --spectrum needs the GPU path (it runs on the device); no spectrum\n");
+        }
+        if (meter) {   // level, offset and deviation of the one channel per window of the feed (a window a block cuts comes in two pieces)
+            const bool on = demod.wide_meter(meter, [](uint64_t window, uint32_t outputs, double level_db, double offset_hz, double deviation_hz) {
+                std::fprintf(stderr, "meter: window %llu, %u outputs: level %.2f dB, offset %+.1f Hz, deviation %.1f Hz\n", (unsigned long long)window, outputs,
+                             level_db, offset_hz, deviation_hz);
+            });
+            if (!on) std::fprintf(stderr, "m17-demod-gpu: --meter needs the GPU path (it runs on the device); no meter\n");
         }
         while (std::cin) {
             if (wide == M17HIP_IQ_I16) { int16_t s[2]; std::cin.read(reinterpret_cast<char*>(s), 4); if (std::cin) demod.wide((float)s[0], (float)s[1]); }

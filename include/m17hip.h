@@ -220,7 +220,7 @@ int m17hip_iq_bytes(m17hip_ctx* ctx, uint64_t* bytes);
  * rtl_fm or a channeliser for, the half of that job in front of the discriminator of ABI 608.  The arithmetic is the project's own, defined once for host
  * and device (m17cxx/detail/core.h: nco — a float32 oscillator within 2^-21 of cos / sin, exactly on the axes at the four quarter phases —, ddc_mix, ddc_tap:
  * two fma chains from +0 in the order i = 0 .. ntaps - 1), so a host can compute the very words the device computes.
- * Out of scope, for a later pull request: per-source sample counts, squelching the demodulator, per-channel RSSI of a tuner's own z (per bin of a raster:
+ * Out of scope, for a later pull request: per-source sample counts, squelching the demodulator (per-channel level of a tuner's own z: the channel meter, ABI 618, below; per bin of a raster:
  * the survey, ABI 613, below; which offsets of a source carry anything, under any configuration: the source spectrum, ABI 616, below).  (Sources above 16 x 48 kSPS: two stages,
  * ABI 610, below.  Channels on a raster: the polyphase channeliser, ABI 611, below.  Rates that are no integer multiple of 48 kSPS: the resampling tuner,
  * ABI 615, below.) */
@@ -395,7 +395,7 @@ int m17hip_wide_survey_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, 
  * m17hip_timing_get index 14 is the spectrum (both kernels, one entry per block); m17hip_iq_bytes counts its table, scratch and planes.  The scratch is
  * sources * ceil(J / 16) * N floats: a hop far below N over a long block asks for as much memory as that says, and a block whose scratch cannot be had
  * fails with M17HIP_ENOMEM.
- * Out of scope, for a later pull request: a waterfall of per-frame spectra, frames that straddle blocks, per-channel RSSI of the tuners' own z, squelching
+ * Out of scope, for a later pull request: a waterfall of per-frame spectra, frames that straddle blocks, squelching
  * the demodulator, assigning channels on the device. */
 /* points = 0 turns the spectrum off (the default).  Otherwise points is a power of two in 64..4096, hop is in 1..2^24 and window[nwindow] holds `points`
  * finite floats; NULL with a count of 0 selects m17hip_wide_spectrum_default_window's.  It holds for the blocks uploaded AFTER the call and never waits for
@@ -419,6 +419,46 @@ int m17hip_wide_spectrum_twiddles(uint32_t points, float* out, uint32_t capacity
  * m17hip_demod_reset, which starts the feeds over.  M17HIP_EINVAL for back > 1, a NULL power_host or capacity (in floats) < sources * points; nothing is
  * written then. */
 int m17hip_wide_spectrum_fetch(m17hip_ctx* ctx, uint32_t back, float* power_host, uint64_t capacity, uint32_t* frames, uint64_t* first_sample);
+
+/* ---- the channel meter: level, offset and deviation sums per wideband channel, under every configuration (ABI 618) ---
+ * The discriminator keeps arg(z[n] conj z[n-1]) and throws |z| away; the survey and the spectrum describe the SOURCE.  With the meter on at `window` (in
+ * outputs, 16..65536) every wideband block uploaded under m17hip_wide_config, _config2, _wide_raster or _wide_resample leaves three sums per channel and per
+ * stretch of time, taken where z and y already exist:
+ *     T = the block's outputs per channel; N0 = the 64-bit number of outputs the feed produced before the block (0 after m17hip_demod_reset or a
+ *     configuration); a0 = N0 mod window, taken on the host from all 64 bits; K = (a0 + T - 1) div window + 1;
+ *     PIECE k < K of the block holds the outputs n with (a0 + n) div window == k: m_k outputs, lo_k .. lo_k + m_k - 1.  Windows are a property of the feed,
+ *     not of its blocks: a window that a block boundary cuts is reported in two pieces, one per block, and nothing is carried;
+ *     for channel c and output n: p = chan_power(z.re, z.im) = fmaf(re, re, im * im) of the very z[n] the configuration's kernel discriminates; y = the float
+ *     that kernel stores into the input slab (before any polarity, with the gain of the upload call); e = y * y, one rounded multiply, not contracted;
+ *     for each quantity v in (p, y, e) and each piece: q_g = the chain from +0 of plain float adds of v over the outputs lo_k + 16 g .. min(lo_k + 16 g + 15,
+ *     lo_k + m_k - 1), ascending; V[c][k] = the chain from +0 of plain adds of q_g, g ascending — the survey's two levels and CHAN_SURVEY_GROUP; the order
+ *     is part of the definition.
+ * The plane of a block is [3][C][K] floats (sum p, sum y, sum e), C the upload call's channel count.  m17cxx/detail/core.h has meter_pieces, meter_piece,
+ * meter_sq and meter_sum, so a host computes the device's words.  sum p / m is the channel's power (amplitude^2 in the units of the source's samples, through
+ * the configuration's filter); (sum y / m) * 48000 / (2 pi gain) is the carrier's offset in Hz from the channel's frequency word; the variance of y, by the
+ * same factor, is the deviation (an M17 carrier: its +-2400 Hz; an empty FM channel: discriminator noise several times wider — the classic noise squelch).
+ * On the device the configuration's kernel runs in a metered instantiation that stores p beside y (one more float per output, into a scratch [C][T]), and
+ * wide_meter_kernel (csrc/m17_meter_kernels.hpp) follows on the block's own stream: m17hip_upload_wait and the in-place forms' synchronisation cover it,
+ * the floats the channels get are untouched, and with the meter off a block queues exactly what it queued under ABI 617.  m17hip_timing_get index 16 is the
+ * meter kernel (one entry per block; the metered tuner keeps its own index); m17hip_iq_bytes counts the scratch and the planes.  A block whose scratch
+ * cannot be had fails with M17HIP_ENOMEM.
+ * Out of scope, for a later pull request: squelching the demodulator or the gate-aware front end from the meter, retuning a channel on the device from its
+ * offset, a level per call in the call log, a peak-hold or a histogram, windows carried across blocks; tests of the meter under other calls in flight beyond one
+ * staged and one in-place block. */
+/* window = 0 turns the meter off (the default); 16..65536 turns it on for the blocks uploaded AFTER the call.  It never waits for anything in flight.
+ * Planes of blocks measured before the call are no longer fetched.  M17HIP_EINVAL for 1..15, above 65536 or a NULL context; M17HIP_ESTATE before any
+ * wideband configuration and between m17hip_demod_front and its run.  Every m17hip_wide_config, m17hip_wide_config2, m17hip_wide_raster or
+ * m17hip_wide_resample call turns it off; m17hip_demod_reset keeps it on and starts N0 over; m17hip_demod_reset_channels does not touch it. */
+int m17hip_wide_meter(m17hip_ctx* ctx, uint32_t window);
+/* The shape of the latest block uploaded with the meter on (back = 0) or of the one before it (back = 1): C, K, N0 div window (the feed's window that piece
+ * 0 belongs to), N0 and T.  Any pointer may be NULL.  It does not wait.  M17HIP_ESTATE if no such plane exists: the meter is off, no block (or, for
+ * back = 1, one block) since it was turned on, or none since m17hip_demod_reset.  M17HIP_EINVAL for back > 1 or a NULL context; nothing is written then. */
+int m17hip_wide_meter_shape(m17hip_ctx* ctx, uint32_t back, uint32_t* channels, uint32_t* pieces, uint64_t* first_window, uint64_t* first_output,
+                            uint32_t* outputs);
+/* The plane of that block: planes_host[3][C][K] floats.  It waits for that block's meter kernel only, on an event recorded behind it, and copies on a stream
+ * of its own — never for a demodulation run or a later block.  M17HIP_ESTATE as for the shape; M17HIP_EINVAL for back > 1, a NULL context or planes_host,
+ * or capacity (in floats) < 3 C K; nothing is written then. */
+int m17hip_wide_meter_fetch(m17hip_ctx* ctx, uint32_t back, float* planes_host, uint64_t capacity);
 
 /* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
  * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
@@ -500,7 +540,8 @@ int m17hip_synth_wide_device(m17hip_ctx* ctx, void* dst_dev, uint32_t channels, 
  * words).  At U = 1 it is m17hip_wide_config2's definition, and the words are that tuner's.  n is counted WITHIN A BLOCK: every block holds a multiple of U
  * outputs, so the phase i0 never depends on the feed's history.  The frequency word means fcw / 2^32 * 48000 * decim1 * down / up Hz.
  * Out of scope: a rational-rate channeliser (a raster in a 2.048 MSPS source), sources of different rates in one context, interpolation (up > down), more
- * than two stages, squelching the demodulator, per-channel RSSI of the tuner's own z.  (Which offsets carry anything: the source spectrum, ABI 616, below.) */
+ * than two stages, squelching the demodulator.  (Which offsets carry anything: the source spectrum, ABI 616, below; a channel's own level, offset and deviation: the
+ * channel meter, ABI 618, above.) */
 /* The default taps of both stages.  Stage 1: 8 * decim1 + 1 taps of the Blackman-windowed sinc of m17hip_wide_default_taps2 with its cutoff at half the
  * rate the stage leaves (0.5 / decim1 of the source's rate); one tap of 1 at decim1 == 1.  Stage 2: 32 * down + 1 taps of the same formula with the cutoff
  * at 5500 Hz of 48000 * down, scaled in double to DC gain `up` — every one of the `up` branches taps2[r], taps2[r + up], ... then has unit gain within
@@ -1029,7 +1070,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 10 = tune2 (the two-stage tuner of m17hip_upload_wide* under m17hip_wide_config2: likewise),
  * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
  * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block), 14 = spectrum (the two
- * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block). */
+ * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block),
+ * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -46,12 +46,13 @@ __host__ __device__ inline size_t chan_table_words(uint32_t S, uint32_t P) { ret
 // 5. The store, an item per ((bin, channel) pair, time) with the time fastest, so a wave writes runs of TT consecutive floats; the block's last z goes to
 //    znew[channel] (wide_carry_kernel follows, as behind the tuners).
 // `cm` is the feed's sample count at the block's start mod M, taken by the host from all 64 bits.  Vector stores only, no atomics.
-template <typename IQT>
+// METER: as tune_kernel's, per (bin, channel) pair: two channels on one bin get the same power.
+template <typename IQT, bool METER = false, typename... PW>
 __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                             const float* __restrict__ taps, uint32_t L, uint32_t R, uint32_t M1, uint32_t M2,
                                                             const float2* __restrict__ tw, const uint32_t* __restrict__ table, uint32_t S, uint32_t cm,
                                                             uint32_t TT, uint32_t C, float* __restrict__ dst, size_t dpitch, uint32_t T,
-                                                            const float2* __restrict__ carry, float2* __restrict__ znew, float gain)
+                                                            const float2* __restrict__ carry, float2* __restrict__ znew, float gain, PW... pw)
 {
     extern __shared__ float2 chan_lds[];
     const uint32_t s = blockIdx.y, tid = threadIdx.x, n0 = blockIdx.x * TT, M = M1 * M2, H = L - 1;
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const IQT* __restric
         const uint32_t n = n0 + g - 1;
         const float2 z = wz[k * NW + g], b = n == 0 ? carry[c] : wz[k * NW + g - 1];
         dst[(size_t)c * dpitch + XPRE + n] = core::fm_discriminate(z.x, z.y, b.x, b.y, gain);
+        if constexpr (METER) meter_put(c, n, z, pw...);
         if (n == T - 1) znew[c] = z;
     }
 }

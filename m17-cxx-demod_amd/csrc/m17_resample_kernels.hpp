@@ -100,12 +100,14 @@ __device__ __forceinline__ void resample_chains(const float2* base, uint32_t lan
 // 3. Output n = g0 U + w - 1 is z w against z w - 1, lanes over consecutive w; the block's last z goes to znew[c] for wide_carry_kernel.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.  Every z is the same
 // chain whatever G and Q are: the result does not depend on the tile rule.
-template <typename IQT>
+// METER: as tune_kernel's.
+template <typename IQT, bool METER = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void resample_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                                 const float* __restrict__ taps1, uint32_t L1, uint32_t R1, const float* __restrict__ taps2,
                                                                 uint32_t L2, uint32_t U, uint32_t D, uint32_t G, uint32_t Q,
                                                                 const uint32_t* __restrict__ table, uint32_t maxC, uint32_t count, float* __restrict__ dst,
-                                                                size_t dpitch, uint32_t T, const float2* __restrict__ carry, float2* __restrict__ znew, float gain)
+                                                                size_t dpitch, uint32_t T, const float2* __restrict__ carry, float2* __restrict__ znew, float gain,
+                                                                PW... pw)
 {
     extern __shared__ float2 resample_lds[];
     const uint32_t lane = threadIdx.x;
@@ -202,6 +204,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void resample_kernel(const IQT* __res
         const uint32_t n = g0 * U + w - 1;
         const float2 a = zbuf[w], b = zbuf[w - 1];
         d[n] = core::fm_discriminate(a.x, a.y, b.x, b.y, gain);
+        if constexpr (METER) meter_put(c, n, a, pw...);
         if (n == T - 1) znew[c] = a;
     }
 }

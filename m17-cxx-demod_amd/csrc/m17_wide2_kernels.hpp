@@ -72,12 +72,13 @@ __device__ __forceinline__ void wide_chains(const float2* base, uint32_t P, uint
 // 2. Stage 2 is tune_kernel's step 2 over the u planes with (L2, R2), and 3. the z go through LDS into the discriminator as there: the block's output 0 has
 //    the channel's carry in front, a later tile recomputes the z in front of it, the block's last z goes to znew[c] for wide_carry_kernel.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.
-template <typename IQT>
+// METER: as tune_kernel's.
+template <typename IQT, bool METER = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void tune2_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                              const float* __restrict__ taps1, uint32_t L1, uint32_t R1, const float* __restrict__ taps2,
                                                              uint32_t L2, uint32_t R2, uint32_t Q, const uint32_t* __restrict__ table, uint32_t maxC,
                                                              uint32_t count, float* __restrict__ dst, size_t dpitch, uint32_t T,
-                                                             const float2* __restrict__ carry, float2* __restrict__ znew, float gain)
+                                                             const float2* __restrict__ carry, float2* __restrict__ znew, float gain, PW... pw)
 {
     extern __shared__ float2 wide2_lds[];
     // the workgroups in launch order go through the CHANNELS of one tile before the next tile: those in flight together read the same stretch of the few
@@ -168,6 +169,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune2_kernel(const IQT* __restri
         if (n >= T) continue;
         const float2 b = zbuf[w - 1];
         d[n] = core::fm_discriminate(z[q].x, z[q].y, b.x, b.y, gain);
+        if constexpr (METER) meter_put(c, n, z[q], pw...);
         if (n == T - 1) znew[c] = z[q];
     }
 }

@@ -12,6 +12,11 @@ namespace m17 {
 // a wideband sample as two floats (all exact): int16 and float32 as iq_float has them, uint8 in rtl_sdr's convention
 __device__ __forceinline__ float2 iq_float(uchar2 v) { return make_float2(core::ddc_u8(v.x), core::ddc_u8(v.y)); }
 
+// The power scratch of a metered launch (m17hip_wide_meter; csrc/m17_meter_kernels.hpp): [channels][pitch] floats, chan_power of the z of output n of
+// channel c at p[c * pitch + n].  The metered instantiations of the four wideband kernels take one as their last argument; the others have no such argument.
+struct MeterOut { float* p; size_t pitch; };
+__device__ __forceinline__ void meter_put(uint32_t c, uint32_t n, float2 z, MeterOut m) { m.p[(size_t)c * m.pitch + n] = core::chan_power(z.x, z.y); }
+
 constexpr int WIDE_THREADS = 64;                        // one wave per workgroup
 constexpr int WIDE_PER_LANE = 4;                        // filter sums in flight per lane: lane l has z number l, l + 64, l + 128, l + 192 of the tile
 constexpr int WIDE_Z = WIDE_THREADS * WIDE_PER_LANE;    // z per tile: the one in front of the tile's first output and one per output
@@ -33,11 +38,12 @@ __host__ __device__ inline size_t wide_lds_bytes(uint32_t L, uint32_t R) { retur
 //    block before; zero for a fresh feed); in front of a later tile's first output the z is recomputed (one in 256).  The block's last z goes to znew[c]:
 //    tile 0 of this launch reads carry[c], so the carry itself is written by wide_carry_kernel behind this launch.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.
-template <typename IQT>
+// METER (m17hip_wide_meter is on): the launch has one more argument, a MeterOut, and every output's chan_power(z) goes to it beside the output's y.
+template <typename IQT, bool METER = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                             const float* __restrict__ taps, uint32_t L, uint32_t R, const uint32_t* __restrict__ table,
                                                             uint32_t maxC, uint32_t count, float* __restrict__ dst, size_t dpitch, uint32_t T,
-                                                            const float2* __restrict__ carry, float2* __restrict__ znew, float gain)
+                                                            const float2* __restrict__ carry, float2* __restrict__ znew, float gain, PW... pw)
 {
     extern __shared__ float2 wide_lds[];
     const uint32_t c = blockIdx.y, lane = threadIdx.x;
@@ -100,6 +106,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restric
         if (n >= T) continue;
         const float2 b = zbuf[w - 1];
         d[n] = core::fm_discriminate(z[q].x, z[q].y, b.x, b.y, gain);
+        if constexpr (METER) meter_put(c, n, z[q], pw...);
         if (n == T - 1) znew[c] = z[q];
     }
 }

@@ -13,6 +13,7 @@
 #include "m17_chan_kernels.hpp"
 #include "m17_chan_survey_kernels.hpp"
 #include "m17_spectrum_kernels.hpp"
+#include "m17_meter_kernels.hpp"
 #include "m17_wide_tx_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_demod_kernel.hpp"
@@ -39,7 +40,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -399,10 +400,29 @@ struct m17hip_ctx {
             void forget() { valid[0] = valid[1] = false; }
             ~Spectrum() { if (fetch) (void)hipStreamDestroy(fetch); }
         } sp;
+        // The channel meter (m17hip_wide_meter; csrc/m17_meter_kernels.hpp), under every configuration: window != 0 is on.  `outputs` is the feed's output
+        // count (N0 of the next block), kept whether the meter is on or off.  The power scratch [C][T] is written by the metered instantiation of the
+        // block's kernel and read by wide_meter_kernel behind it on the same stream; it is every block's, like the survey's: the next block's kernel runs
+        // behind ev_iq, which is recorded behind this block's meter kernel.  Two planes [3][C][K] take turns, each with its own shape, event and capacity:
+        // only the plane whose turn it is is ever regrown, so the block before keeps its words.
+        struct Meter {
+            uint32_t window = 0;
+            uint64_t outputs = 0;
+            DevBuf<float> scratch, plane[2];
+            Event ev[2];
+            bool valid[2] = {false, false};
+            uint32_t C[2] = {0, 0}, K[2] = {0, 0}, T[2] = {0, 0};
+            uint64_t N0[2] = {0, 0};
+            uint32_t win[2] = {0, 0};
+            int latest = 0;
+            hipStream_t fetch = nullptr;   // m17hip_wide_meter_fetch's copies: a stream of its own, behind nothing but the plane's event
+            void forget() { valid[0] = valid[1] = false; }
+            ~Meter() { if (fetch) (void)hipStreamDestroy(fetch); }
+        } mt;
         size_t bytes() const
         {
             return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size() + sp.scratch.size() + sp.plane[0].size() +
-                    sp.plane[1].size()) * sizeof(float) +
+                    sp.plane[1].size() + mt.scratch.size() + mt.plane[0].size() + mt.plane[1].size()) * sizeof(float) +
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4;
         }
     } wide;
@@ -1252,7 +1272,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 617; }
+int m17hip_version(void) { return 618; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1616,6 +1636,8 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
             c->wide.count = 0;
             c->wide.sv.forget();   // (the planes were blocks of the feed that ends here)
             c->wide.sp.forget();
+            c->wide.mt.forget();   // (the meter stays on: its windows start over with the feed)
+            c->wide.mt.outputs = 0;
         }
     } else {
         std::vector<uint32_t> v(channels, channels + n);
@@ -1798,12 +1820,49 @@ static int launch_spectrum(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t
 }
 // What follows the tuner's or the channeliser's kernel on its stream `st`, for the next block: the channels' carries, the sources' histories (H converted
 // samples each, into the copy whose turn it is), the feed's sample count.  In between the survey of a raster's block, which reads what that kernel read.
+// The power scratch of a metered block, in front of the block's kernel: [C][T] floats.  Regrown behind everything that may still read the old one.
+static int meter_scratch(m17hip_ctx* c, uint32_t C, uint32_t T)
+{
+    auto& mt = c->wide.mt;
+    if (mt.scratch.size() >= (size_t)C * T) return M17HIP_OK;
+    HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the block before may still be metered)
+    return alloc_code(c, mt.scratch.grow((size_t)C * T, &c->last_hip));
+}
+// The meter of one block (m17hip_wide_meter is on), on the block's stream behind its kernel: it reads the power scratch and the rows of `x` that kernel
+// wrote, and writes the plane whose turn it is.
+static int launch_meter(m17hip_ctx* c, const float* x, uint32_t T, uint32_t C, hipStream_t st)
+{
+    auto& mt = c->wide.mt;
+    uint32_t a0, K;
+    core::meter_pieces(mt.outputs, T, mt.window, a0, K);
+    const int p = mt.latest ^ 1;
+    int r;
+    if (!mt.fetch) HIPCHK(c, hipStreamCreateWithFlags(&mt.fetch, hipStreamNonBlocking));
+    for (auto& e : mt.ev) if (!e) HIPCHK(c, e.create());
+    mt.valid[p] = false;
+    if (mt.plane[p].size() < (size_t)3 * C * K) {   // (this plane alone: the other one is the block before's, which keeps its words)
+        HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (its last writer, two blocks back, is in front of that)
+        if ((r = alloc_code(c, mt.plane[p].grow((size_t)3 * C * K, &c->last_hip)))) return r;
+    }
+    {
+        Timed tm(c, KT_METER, st);
+        const uint32_t PP = meter_pieces_per_wg(mt.window);
+        hipLaunchKernelGGL(wide_meter_kernel, dim3((K + PP - 1) / PP, C), dim3(METER_THREADS), 0, st, mt.scratch.get(), (size_t)T, x, c->xpitch, a0, T,
+                           mt.window, K, C, mt.plane[p].get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(mt.ev[p], st));
+    mt.C[p] = C; mt.K[p] = K; mt.T[p] = T; mt.N0[p] = mt.outputs; mt.win[p] = mt.window; mt.valid[p] = true; mt.latest = p;
+    return M17HIP_OK;
+}
 template <typename IQT>
-static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, uint32_t H, uint32_t C, hipStream_t st)
+static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, uint32_t H, uint32_t C, const float* x, hipStream_t st)
 {
     auto& w = c->wide;
     hipLaunchKernelGGL(wide_carry_kernel, dim3((C + 63) / 64), dim3(64), 0, st, w.znew.get(), c->iq_carry.get(), C);
     HIPCHK(c, hipGetLastError());
+    if (w.mt.window) if (int r = launch_meter(c, x, T, C, st)) return r;   // (m17hip_wide_meter: under every configuration)
+    w.mt.outputs += T;
     if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;   // (m17hip_wide_survey: on under a raster only)
     if (w.sp.points) if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;   // (m17hip_wide_spectrum: under every configuration)
     if (H) {
@@ -1828,25 +1887,43 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         w.dirty = false;
     }
     HIPCHK(c, w.dev.before_read(st));
+    const bool meter = w.mt.window != 0;   // (the metered instantiations: one more argument and one more store per output, otherwise the same launch)
+    if (meter) if (int r = meter_scratch(c, C, T)) return r;
+    const MeterOut mo{w.mt.scratch.get(), (size_t)T};
     if (w.U) {
         const uint32_t G = resample_groups(w.L, w.R, w.L2, w.U, w.D), Q = resample_q(w.L, w.R, w.L2, w.U, w.D, G);
         TimedK tm(c, KT_RESAMPLE);
+        if (meter)
+            tm.launch(resample_kernel<IQT, true, MeterOut>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st,
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count,
+                      x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
+        else
         tm.launch(resample_kernel<IQT>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch,
                   W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x,
                   c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else if (w.R2) {
         TimedK tm(c, KT_WIDE2);
+        if (meter)
+            tm.launch(tune2_kernel<IQT, true, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src,
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
+                      (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
+        else
         tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
                   w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
                   (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else {
         TimedK tm(c, KT_WIDE);
+        if (meter)
+            tm.launch(tune_kernel<IQT, true, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W,
+                      w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(),
+                      gain, mo);
+        else
         tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
                   w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, w.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));   // (two readers: the main stream and the copy stream)
-    return wide_after_block(c, src, pitch, W, T, H, C, st);
+    return wide_after_block(c, src, pitch, W, T, H, C, x, st);
 }
 // The channeliser's launch (m17hip_wide_raster): the same frame, one workgroup per source and tile of output times.
 template <typename IQT>
@@ -1880,16 +1957,23 @@ static int launch_chan(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         w.dirty = false; w.rdev_C = C;
     }
     HIPCHK(c, w.rdev.before_read(st));
+    const bool meter = w.mt.window != 0;
+    if (meter) if (int r = meter_scratch(c, C, T)) return r;
     {
         const uint32_t TT = chan_tile(w.L, w.R, w.M);
         TimedK tm(c, KT_CHAN);
+        if (meter)
+            tm.launch(chan_kernel<IQT, true, MeterOut>, dim3((T + TT - 1) / TT, w.S), dim3(CHAN_THREADS), chan_lds_bytes(w.L, w.R, w.M, TT), st, src, pitch, W,
+                      w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.M1, w.M2, w.tw.get(), w.rdev.dev(), w.S, (uint32_t)(w.count % w.M), TT, C, x, c->xpitch, T,
+                      c->iq_carry.get(), w.znew.get(), gain, MeterOut{w.mt.scratch.get(), (size_t)T});
+        else
         tm.launch(chan_kernel<IQT>, dim3((T + TT - 1) / TT, w.S), dim3(CHAN_THREADS), chan_lds_bytes(w.L, w.R, w.M, TT), st, src, pitch, W, w.hist[w.par].get(),
                   w.taps.get(), w.L, w.R, w.M1, w.M2, w.tw.get(), w.rdev.dev(), w.S, (uint32_t)(w.count % w.M), TT, C, x, c->xpitch, T, c->iq_carry.get(),
                   w.znew.get(), gain);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, w.rdev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
-    return wide_after_block(c, src, pitch, W, T, H, C, st);
+    return wide_after_block(c, src, pitch, W, T, H, C, x, st);
 }
 // The four ways in, as upload_iq has them: the tuner or the channeliser takes the place of the copy.  `p`: [sources][pitch] samples of the configured format.
 static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uint32_t T, size_t pitch, int how)
@@ -2002,6 +2086,9 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.sp.points = 0; w.sp.forget();   // (the spectrum likewise: its plane has a row per source)
     w.sp.scratch.release(&c->last_hip);
     for (auto& b : w.sp.plane) b.release(&c->last_hip);
+    w.mt.window = 0; w.mt.forget(); w.mt.outputs = 0;   // (the meter likewise: a new feed)
+    w.mt.scratch.release(&c->last_hip);
+    for (auto& b : w.mt.plane) b.release(&c->last_hip);
     if ((r = alloc_code(c, w.taps.alloc(L)))) return r;
     if (L2) { if ((r = alloc_code(c, w.taps2.alloc(L2)))) return r; }
     else w.taps2.release(&c->last_hip);
@@ -2253,6 +2340,51 @@ int m17hip_wide_spectrum_fetch(m17hip_ctx* c, uint32_t back, float* power_host, 
     HIPCHK(c, hipStreamSynchronize(sp.fetch));
     if (frames) *frames = sp.frames[p];
     if (first_sample) *first_sample = sp.first_sample[p];
+    return M17HIP_OK;
+}
+// ---- the channel meter (ABI 618): level, offset and deviation sums per channel and window, under every wideband configuration --------------------
+int m17hip_wide_meter(m17hip_ctx* c, uint32_t window)
+{
+    if (!c || (window && (window < 16 || window > 65536))) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the staged block belongs to the run being made)
+    w.mt.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
+    w.mt.window = window;
+    return M17HIP_OK;
+}
+// the plane `back` names, or -1
+static int meter_plane(const m17hip_ctx* c, uint32_t back)
+{
+    const auto& mt = c->wide.mt;
+    if (!c->wide.S || !mt.window) return -1;
+    const int p = mt.latest ^ (int)back;
+    return mt.valid[p] ? p : -1;
+}
+int m17hip_wide_meter_shape(m17hip_ctx* c, uint32_t back, uint32_t* channels, uint32_t* pieces, uint64_t* first_window, uint64_t* first_output, uint32_t* outputs)
+{
+    if (!c || back > 1) return M17HIP_EINVAL;
+    const int p = meter_plane(c, back);
+    if (p < 0) return M17HIP_ESTATE;
+    const auto& mt = c->wide.mt;
+    if (channels) *channels = mt.C[p];
+    if (pieces) *pieces = mt.K[p];
+    if (first_window) *first_window = mt.N0[p] / mt.win[p];
+    if (first_output) *first_output = mt.N0[p];
+    if (outputs) *outputs = mt.T[p];
+    return M17HIP_OK;
+}
+int m17hip_wide_meter_fetch(m17hip_ctx* c, uint32_t back, float* planes_host, uint64_t capacity)
+{
+    if (!c || back > 1 || !planes_host) return M17HIP_EINVAL;
+    const int p = meter_plane(c, back);
+    if (p < 0) return M17HIP_ESTATE;
+    auto& mt = c->wide.mt;
+    const size_t n = (size_t)3 * mt.C[p] * mt.K[p];
+    if (capacity < n) return M17HIP_EINVAL;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(mt.ev[p]));   // (that block's meter kernel and what its stream held in front of it: no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(planes_host, mt.plane[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, mt.fetch));
+    HIPCHK(c, hipStreamSynchronize(mt.fetch));
     return M17HIP_OK;
 }
 int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }

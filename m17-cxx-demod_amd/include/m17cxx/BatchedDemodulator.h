@@ -135,6 +135,21 @@ public:
     {
         check(m17hip_wide_spectrum_fetch(ctx_, back, power, capacity, frames, first_sample), "m17hip_wide_spectrum_fetch");
     }
+    // The channel meter (m17hip_wide_meter), under every wideband configuration: from the blocks uploaded after the call the sums of chan_power(z), of the
+    // discriminator's y and of y * y per channel and per window of `window` outputs of the feed (16..65536; 0: off).  wide_meter_fetch: the planes
+    // [3][channels][pieces] of the latest such block (back = 0) or the one before (back = 1), resized to fit, with the block's shape — piece k belongs to
+    // window first_window + k of the feed; it waits for that block's meter kernel only.
+    void wide_meter(uint32_t window) { check(m17hip_wide_meter(ctx_, window), "m17hip_wide_meter"); }
+    void wide_meter_fetch(uint32_t back, std::vector<float>& planes, uint32_t* channels = nullptr, uint32_t* pieces = nullptr, uint64_t* first_window = nullptr,
+                          uint64_t* first_output = nullptr, uint32_t* outputs = nullptr)
+    {
+        uint32_t c = 0, k = 0;
+        check(m17hip_wide_meter_shape(ctx_, back, &c, &k, first_window, first_output, outputs), "m17hip_wide_meter_shape");
+        planes.resize((size_t)3 * c * k);
+        check(m17hip_wide_meter_fetch(ctx_, back, planes.data(), planes.size()), "m17hip_wide_meter_fetch");
+        if (channels) *channels = c;
+        if (pieces) *pieces = k;
+    }
     // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
     // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
     // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,

@@ -162,6 +162,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        meter_window_ = 0;      // (and the meter)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -199,6 +200,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim1 * decim2;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        meter_window_ = 0;      // (and the meter)
         wide_r1_ = decim1;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -240,6 +242,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim1 * down;   // (the samples of a group)
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        meter_window_ = 0;      // (and the meter)
         wide_r1_ = decim1;
         wide_up_ = up; wide_down_ = down;
         raster_m_ = 0;
@@ -276,6 +279,7 @@ struct M17Demodulator
         }
         wide_decim_ = decim;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        meter_window_ = 0;      // (and the meter)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         if (gpu_) {
@@ -324,6 +328,22 @@ struct M17Demodulator
         gpu_->wide_spectrum(points, hop, window.empty() ? nullptr : window.data(), (uint32_t)window.size());
         spectrum_points_ = points;
         spectrum_report_ = std::move(report);
+        return true;
+    }
+    // The channel meter beside any wideband configuration on the GPU path (m17hip_wide_meter): per window of `window` outputs of the feed (16..65536; 0
+    // turns it off; 1920 is one M17 frame) the channel's level, its carrier's offset from the channel's frequency and its deviation, and after each block
+    // `report` gets them for every piece of a window the block holds: the feed's window number, the piece's outputs, 10 log10 of the mean power of z (dB
+    // over an amplitude of 1 in the source's units), the mean of the discriminator's output in Hz and its standard deviation in Hz.  Returns false, with
+    // nothing changed, on the host form: the meter is a device feature.  Any wide_config / wide_rate / wide_raster call turns it off.
+    using meter_callback_t = std::function<void(uint64_t window, uint32_t outputs, double level_db, double offset_hz, double deviation_hz)>;
+    bool wide_meter(uint32_t window, meter_callback_t report)
+    {
+        if (!gpu_) return false;
+        if (!wide_decim_) throw std::logic_error("M17Demodulator::wide_meter before wide_config");
+        flush();
+        gpu_->wide_meter(window);
+        meter_window_ = window;
+        meter_report_ = std::move(report);
         return true;
     }
     // one wideband sample (wide_config or wide_raster first)
@@ -483,6 +503,20 @@ private:
             gpu_->wide_spectrum_fetch(0, spectrum_power_.data(), spectrum_power_.size(), &frames, &first);
             spectrum_report_(spectrum_power_, frames, first);
         }
+        if (meter_window_ && meter_report_) {   // (likewise: the fetch waits for the block's meter kernel)
+            uint32_t pieces = 0, outputs = 0;
+            uint64_t first_window = 0, first_output = 0;
+            gpu_->wide_meter_fetch(0, meter_planes_, nullptr, &pieces, &first_window, &first_output, &outputs);
+            const double hz = 48000.0 / (2.0 * 3.14159265358979323846 * (double)iq_gain_);
+            const uint64_t a0 = first_output % meter_window_;
+            for (uint32_t k = 0; k < pieces; ++k) {   // (one channel: planes [3][1][pieces])
+                const uint64_t lo = (uint64_t)k * meter_window_ > a0 ? (uint64_t)k * meter_window_ - a0 : 0;
+                const uint64_t hi = std::min<uint64_t>((uint64_t)(k + 1) * meter_window_ - a0, outputs);
+                const double m = (double)(hi - lo), mean = meter_planes_[pieces + k] / m;
+                meter_report_(first_window + k, (uint32_t)(hi - lo), 10.0 * std::log10(meter_planes_[k] / m), mean * hz,
+                              std::sqrt(std::max(meter_planes_[2 * pieces + k] / m - mean * mean, 0.0)) * hz);
+            }
+        }
         run_uploaded();
     }
     void run_uploaded()
@@ -522,6 +556,9 @@ private:
     uint32_t spectrum_points_ = 0;                   // wide_spectrum: 0 = off
     spectrum_callback_t spectrum_report_;
     std::vector<float> spectrum_power_;
+    uint32_t meter_window_ = 0;                      // wide_meter: 0 = off
+    meter_callback_t meter_report_;
+    std::vector<float> meter_planes_;
     std::vector<float> raster_tw_, raster_w_;        // the twiddle table; the partial sums and the first pass's sums of one output
     uint64_t wide_m_ = 0;
     uint32_t block_;

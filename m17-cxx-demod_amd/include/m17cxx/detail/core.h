@@ -312,6 +312,41 @@ M17_HD void spec_item2(float* v, const float* tw, uint32_t logn, uint32_t s, uin
 // One windowed sample on its way into the FFT: two plain multiplies.
 M17_HD void spec_window(float w, float xre, float xim, float& re, float& im) { re = w * xre; im = w * xim; }
 
+// ---- a-1e: the channel meter (m17hip_wide_meter): per channel and per WINDOW of `window` outputs of the feed, the sums of p = chan_power(z), of the
+// discriminator's y and of e = y * y (meter_sq: one rounded multiply), under every wideband configuration.  Windows are a property of the FEED: with N0 the
+// 64-bit number of outputs in front of a block of T outputs, a0 = N0 mod window (from all 64 bits) and PIECE k of the block holds the outputs n with
+// (a0 + n) div window == k, k < K = (a0 + T - 1) div window + 1 — a window that a block boundary cuts is reported in two pieces, and nothing is carried.
+// A piece's sum is the survey's sum on two levels: q_g over the piece's outputs 16 g .. min(16 g + 15, m - 1), then the q_g, all chains of plain adds from +0.
+M17_HD void meter_pieces(uint64_t N0, uint32_t T, uint32_t window, uint32_t& a0, uint32_t& K)
+{
+    a0 = (uint32_t)(N0 % window);
+    K = (uint32_t)(((uint64_t)a0 + T - 1) / window) + 1;
+}
+// piece k < K of a block of T >= 1 outputs: its first output lo and its count m >= 1
+M17_HD void meter_piece(uint32_t a0, uint32_t T, uint32_t window, uint32_t k, uint32_t& lo, uint32_t& m)
+{
+    const uint64_t b = (uint64_t)k * window, e = b + window - a0;   // the window's first output and the one behind its last, counted from the block's output -a0 / 0
+    lo = b > a0 ? (uint32_t)(b - a0) : 0u;
+    m = (e < T ? (uint32_t)e : T) - lo;
+}
+M17_HD float meter_sq(float y) { return y * y; }
+// the chain of plain float adds of v[0 .. n - 1] onto acc, ascending: both levels are this
+M17_HD float meter_chain(float acc, const float* v, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) acc = acc + v[i];
+    return acc;
+}
+// a piece's sum over v[0 .. n - 1]: first-level chains from +0 over CHAN_SURVEY_GROUP values each, the second-level chain from +0 over those
+M17_HD float meter_sum(const float* v, uint32_t n)
+{
+    float acc = 0.0f;
+    for (uint32_t g = 0; g < n; g += CHAN_SURVEY_GROUP) {
+        const float q = meter_chain(0.0f, v + g, n - g < CHAN_SURVEY_GROUP ? n - g : CHAN_SURVEY_GROUP);
+        acc = acc + q;
+    }
+    return acc;
+}
+
 // ---- t1: the wideband signal generator (m17hip_synth_wide, ABI 617): FM-modulate int16 basebands and put them at offsets into wide IQ streams -------
 // No reference file: the reference's users attach an FM exciter behind its modulator.  Written here, once, so that the kernels and the host form give the
 // same words.  Everything up to the oscillator's argument is INTEGER RING arithmetic (uint64 / uint32, wrapping), so any summation order, scan or tiling

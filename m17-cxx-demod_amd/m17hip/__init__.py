@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -78,6 +78,7 @@ EXPORTS = [
     "m17hip_wide_survey", "m17hip_wide_survey_fetch",
     "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
+    "m17hip_wide_meter", "m17hip_wide_meter_shape", "m17hip_wide_meter_fetch",
     "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
@@ -333,6 +334,35 @@ def synth_wide_k(hz_per_unit=0.0, p=1):
     if code != 0:
         raise M17HipError(f"m17hip_synth_wide_k: {load_library().m17hip_strerror(C.c_int(code)).decode()}")
     return int(k.value)
+
+
+def wide_meter_counts(first_output, outputs, window):
+    """m_k, the outputs in every piece of a metered block (Context.wide_meter_fetch): the block of `outputs` outputs that begins at output `first_output`
+    of the feed, cut where the feed's output index is a multiple of `window`.  int64 [K]; pure Python integers, any 64-bit first_output."""
+    n0, t, w = int(first_output), int(outputs), int(window)
+    if t < 1 or w < 1 or n0 < 0:
+        raise ValueError("wide_meter_counts: outputs and window are at least 1, first_output at least 0")
+    a0 = n0 % w
+    k = (a0 + t - 1) // w + 1
+    return np.array([min((j + 1) * w - a0, t) - max(j * w - a0, 0) for j in range(k)], dtype=np.int64)
+
+
+def wide_meter_report(planes, counts, gain):
+    """What the sums of a metered block mean, in float64: planes [3][C][K] (Context.wide_meter_fetch), counts [K] (wide_meter_counts) and the `gain` of the
+    upload call give a dict of three [C][K] arrays —
+        level_db      10 log10(sum p / m): the power of the channel's z, dB over an amplitude of 1 in the units of the source's samples
+        offset_hz     (sum y / m) * 48000 / (2 pi gain): the carrier's offset from the channel's frequency word
+        deviation_hz  sqrt(max(sum e / m - (sum y / m)^2, 0)) * 48000 / (2 pi gain): the spread of the discriminator's output, as a frequency
+    A piece of a window gives that piece's figures; add the planes and the counts of a window's two pieces before the call for the window's."""
+    pl = np.asarray(planes, dtype=np.float64)
+    m = np.asarray(counts, dtype=np.float64).reshape(1, -1)
+    if pl.ndim != 3 or pl.shape[0] != 3 or pl.shape[2] != m.shape[1]:
+        raise ValueError("wide_meter_report: planes is [3][C][K] and counts [K]")
+    hz = 48000.0 / (2.0 * np.pi * float(gain))
+    mean_y = pl[1] / m
+    with np.errstate(divide="ignore", invalid="ignore"):
+        level = 10.0 * np.log10(pl[0] / m)
+    return {"level_db": level, "offset_hz": mean_y * hz, "deviation_hz": np.sqrt(np.maximum(pl[2] / m - mean_y * mean_y, 0.0)) * hz}
 
 
 def wide_fcw(offset_hz, decim):
@@ -610,6 +640,27 @@ class Context:
         frames, first = C.c_uint32(0), C.c_uint64(0)
         self._chk(self.lib.m17hip_wide_spectrum_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(S * N), C.byref(frames), C.byref(first)))
         return buf.reshape(S, N), int(frames.value), int(first.value)
+
+    def wide_meter(self, window):
+        """The channel meter: from the blocks uploaded after this call, the sums of chan_power(z), of the discriminator's y and of y * y per channel and per
+        window of `window` outputs of the feed (16..65536; 0: off, the default) — m17hip_wide_meter.  Legal under every wideband configuration; any
+        wide_config / wide_config2 / wide_raster / wide_resample call turns it off; reset() keeps it on and starts the windows over."""
+        self._chk(self.lib.m17hip_wide_meter(self.h, C.c_uint32(window)))
+
+    def wide_meter_fetch(self, back=0):
+        """(planes float32 [3][C][K] — sum p, sum y, sum y * y of channel c over piece k —, first_window, first_output, outputs) of the latest block
+        uploaded with the meter on (back = 0) or the one before it (back = 1): piece k belongs to window first_window + k of the feed, the block began at
+        output first_output and holds `outputs` outputs per channel (wide_meter_counts gives the pieces' counts, wide_meter_report the meaning).  Waits
+        for that block's meter kernel only — m17hip_wide_meter_shape, m17hip_wide_meter_fetch."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_meter_fetch: back is 0 or 1")
+        ch, k, t = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        fw, fo = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.m17hip_wide_meter_shape(self.h, C.c_uint32(back), C.byref(ch), C.byref(k), C.byref(fw), C.byref(fo), C.byref(t)))
+        n = 3 * ch.value * k.value
+        buf = np.zeros(max(n, 1), dtype=np.float32)
+        self._chk(self.lib.m17hip_wide_meter_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(n)))
+        return buf[:n].reshape(3, ch.value, k.value), int(fw.value), int(fo.value), int(t.value)
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -28,7 +28,11 @@ shape decim x round(DOWN / UP) (at UP = 1 the very same shape, where the two ker
 With --spectrum N --hop H under any of them the same blocks are then timed once more with the source spectrum on (m17hip_wide_spectrum; spectrum_kernel,
 csrc/m17_spectrum_kernels.hpp, and chan_survey_sum_kernel; library timer "spectrum"): the configuration's own kernel with the spectrum on beside its time
 with it off, the spectrum's own time, a device-to-device copy of the same block bytes as the memory yardstick, and the spectrum's floor — 5 N log2 N
-flops per frame at the packed rate, 64 per clock and SIMD."""
+flops per frame at the packed rate, 64 per clock and SIMD.
+With --meter W under any of them the same blocks are then timed once more with the channel meter on (m17hip_wide_meter; the METERED instantiation of the
+configuration's kernel, which stores chan_power of every z, and wide_meter_kernel, csrc/m17_meter_kernels.hpp; library timer "meter"): the metered kernel
+beside the unmetered one of the same call, the meter kernel's own time, and a device-to-device copy of the bytes it reads — 2 x 4 bytes per channel and
+output — as the memory yardstick."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -69,6 +73,11 @@ if "--spectrum" in ARGS:
     assert "--hop" in ARGS, "--spectrum N goes with --hop H"
     k = ARGS.index("--hop")
     HOP = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+METER = 0   # (0: not timed)
+if "--meter" in ARGS:
+    k = ARGS.index("--meter")
+    METER = int(ARGS[k + 1])
     del ARGS[k:k + 2]
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
@@ -173,6 +182,32 @@ if SPECTRUM:   # the same blocks once more with the spectrum on: a warm-up block
     spectrum = {"points": SPECTRUM, "hop": HOP, "launches": n_p, "frames_per_block": frames / REP, "own_kernel_ms_spectrum_off": round(ms / n, 3),
                 "own_kernel_ms_spectrum_on": round(ms_o / n_o, 3), "spectrum_ms": round(ms_p / n_p, 3), "copy_ms_median": round(float(np.median(cp)), 3),
                 "block_bytes": S * ROW * 4}
+meter = {}
+if METER:   # the same blocks once more with the meter on: a warm-up block (scratch and planes), then REP timed ones; then the copy of what the meter reads
+    ctx.wide_meter(METER)
+    call(); call()
+    ctx.timing_reset()
+    pieces = 0
+    for _ in range(REP):
+        call()
+        pieces = ctx.wide_meter_fetch()[0].shape[2]
+    (ms_o, n_o), (ms_m, n_m) = ctx.timing_get(OWN), ctx.timing_get("meter")
+    ctx.wide_meter(0)
+    src = torch.empty((2, C, T), dtype=torch.float32, device='cuda')
+    dst = torch.empty_like(src)
+    dst.copy_(src)
+    torch.cuda.synchronize()
+    cp = []
+    for _ in range(REP):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); dst.copy_(src); b.record()
+        b.synchronize()
+        cp.append(a.elapsed_time(b))
+    del src, dst
+    meter = {"window": METER, "launches": n_m, "pieces_per_block": pieces, "own_kernel_ms_unmetered": round(ms / n, 3),
+             "own_kernel_ms_metered": round(ms_o / n_o, 3), "metered_over_unmetered": round(ms_o / n_o / (ms / n), 4), "meter_ms": round(ms_m / n_m, 3),
+             "copy_ms_median": round(float(np.median(cp)), 3), "bytes_read": 2 * 4 * C * T,
+             "meter_over_copy": round(ms_m / n_m / float(np.median(cp)), 2)}
 neighbour = {}
 if UP:   # tune2_kernel on the same buffer and table at decim x NEIGHBOUR: a warm-up block, then REP timed ones
     ctx.wide_config2(S, R, NEIGHBOUR, m17hip.IQ_I16)
@@ -232,6 +267,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
