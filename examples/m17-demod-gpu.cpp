@@ -13,7 +13,10 @@
 // computed on the device and the carriers it shows — the rule of m17hip's Python wide_spectrum_carriers: 9 kHz bands, more than --scan-margin dB over the
 // median floor — are printed to stderr with the offset in Hz that --offset-hz takes: rtl_sdr -s 2048000 ... | m17-demod-gpu --wide-u8 --rate 2048000
 // --spectrum 2048; with --meter W (16 to 65536 outputs; 1920 is one M17 frame) under ANY wideband option the channel's level, its carrier's offset from
-// the tuned frequency and its deviation are measured on the device per window of W outputs and printed to stderr after each block.  One line per frame callback on
+// the tuned frequency and its deviation are measured on the device per window of W outputs and printed to stderr after each block; with --squelch DB
+// [--hang N] beside --spectrum and a tuner (not --raster) the first block runs unsquelched, its plane's median sets the floor of a 9 kHz band, and from
+// the second block on the channel is tuned only while its band stands DB dB over that floor (it stays open down to DB - 3 dB and for N more blocks), and
+// is fed zeros otherwise; each decision is printed to stderr.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -107,6 +110,9 @@ int main(int argc, char** argv)
     bool margin_given = false;
     uint32_t spectrum = 0, hop = 0;   // (spectrum == 0: none; hop == 0: the points)
     uint32_t meter = 0;               // (0: no meter)
+    double squelch_db = 0.0;          // (--squelch: dB over the floor; hang in blocks)
+    bool squelch = false;
+    uint32_t hang = 0;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -125,9 +131,11 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--scan-margin") && i + 1 < argc) { scan_margin = std::strtod(argv[++i], nullptr); margin_given = true; }
         else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) { spectrum = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!spectrum) spectrum = 1; }
         else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) { meter = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!meter) meter = 1; }
+        else if (!std::strcmp(argv[i], "--squelch") && i + 1 < argc) { squelch_db = std::strtod(argv[++i], nullptr); squelch = true; }
+        else if (!std::strcmp(argv[i], "--hang") && i + 1 < argc) hang = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H]] [--meter W] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N]]] [--meter W] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -153,6 +161,10 @@ int main(int argc, char** argv)
     }
     if (scan && (!(wide && raster) || scan > 4096)) { std::fprintf(stderr, "m17-demod-gpu: --scan STRIDE (1 to 4096) goes with --raster\n"); return 2; }
     if (meter && (!wide || meter < 16 || meter > 65536)) { std::fprintf(stderr, "m17-demod-gpu: --meter W (16 to 65536 outputs) goes with a wideband format\n"); return 2; }
+    if ((squelch || hang) && (!squelch || !spectrum || raster || !(squelch_db > 0.0) || hang > 65535)) {
+        std::fprintf(stderr, "m17-demod-gpu: --squelch DB (above 0) [--hang N (0 to 65535 blocks)] goes with --spectrum and a tuner, not with --raster\n");
+        return 2;
+    }
     if (spectrum || hop) {
         if (!hop) hop = spectrum;
         if (!wide || spectrum < 64 || spectrum > 4096 || (spectrum & (spectrum - 1)) || hop > (1u << 24)) {
@@ -205,6 +217,14 @@ int main(int argc, char** argv)
                 for (const auto& c : carriers(power, fs, 9000.0, margin)) std::fprintf(stderr, "spectrum: carrier %+.1f Hz %.2f dB\n", c.first, c.second);
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --spectrum needs the GPU path (it runs on the device); no spectrum\n");
+        }
+        if (squelch) {   // the first block unsquelched: its plane sets the levels
+            const double fs = 2.0 * half_hz;
+            const uint32_t h = std::min<uint32_t>((uint32_t)std::lrint(9000.0 / 2.0 / (fs / spectrum)), std::min<uint32_t>(64u, spectrum / 2 - 1));
+            const bool on = demod.wide_squelch(h, squelch_db, squelch_db - 3.0, hang, [](bool open, uint32_t hold, float band, uint32_t frames) {
+                std::fprintf(stderr, "squelch: %s, hold %u, band %.6g over %u frames\n", open ? "open" : "closed", hold, (double)band, frames);
+            });
+            if (!on) std::fprintf(stderr, "m17-demod-gpu: --squelch needs the GPU path (it runs on the device); no squelch\n");
         }
         if (meter) {   // level, offset and deviation of the one channel per window of the feed (a window a block cuts comes in two pieces)
             const bool on = demod.wide_meter(meter, [](uint64_t window, uint32_t outputs, double level_db, double offset_hz, double deviation_hz) {

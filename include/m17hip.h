@@ -460,6 +460,52 @@ int m17hip_wide_meter_shape(m17hip_ctx* ctx, uint32_t back, uint32_t* channels, 
  * or capacity (in floats) < 3 C K; nothing is written then. */
 int m17hip_wide_meter_fetch(m17hip_ctx* ctx, uint32_t back, float* planes_host, uint64_t capacity);
 
+/* ---- the spectrum squelch: the three tuners skip the channels whose band holds no carrier (ABI 619) -------------
+ * m17hip_wide_config, _config2 and _wide_resample tune every channel of every block, transmitting or not.  What can say beforehand that a channel is silent
+ * is the source spectrum (ABI 616): it reads the source block alone and costs a hundredth of a tuner.  With the squelch on, per block uploaded:
+ *     N = the spectrum's points, J = the spectrum's frame count of THIS block, P = its plane [sources][N], B = half_bins;
+ *     for channel c with source s and frequency word fcw (signed 32 bit):
+ *     k_c = (((int64)fcw + 2^(31 - log2 N)) >> (32 - log2 N)) & (N - 1), the shift arithmetic (a floor): the spectrum's index rule — bin k belongs to
+ *     k Fs / N — in integers, to the nearest bin; it holds for all three tuners, because the word is relative to the source's own rate;
+ *     b_c = the chain from +0 of plain float adds of P[s][(k_c + d) & (N - 1)], d = -B .. B ascending;
+ *     to = open_level[s] * (float)J and tc = close_level[s] * (float)J, one rounded multiply each.  The levels are per SOURCE: dongles differ in gain;
+ *     h = the channel's hold count before the block: 0 after a configuration, after m17hip_wide_squelch, after m17hip_demod_reset and, for the listed
+ *     channels, after m17hip_demod_reset_channels; a retune by m17hip_wide_channels keeps it;
+ *     J == 0: the channel is OPEN and h' = h (a block too short for a frame is never silenced for want of a measurement);
+ *     else !(b_c < to): h' = hang + 1; else h > 0 and !(b_c < tc): h' = hang + 1; else h' = h > 0 ? h - 1 : 0; the channel is open iff h' > 0.
+ *     The comparisons are negated so that a NaN band opens the channel as well.
+ * m17cxx/detail/core.h has squelch_bin, squelch_band, squelch_level and squelch_step, so a host computes the device's words.
+ * An OPEN channel gets exactly the words the unsquelched kernel gives it from the same carry.  A CLOSED channel gets y = +0.0f for all T outputs of the
+ * block, +0 in the meter's power scratch where the meter is on, and (0, 0) as its carry for the next block: the first output after a reopening is
+ * fm_discriminate against a zero z, +0 (the zero-product rule), and every later output is the unsquelched word, since the sources' histories are kept
+ * regardless.
+ * On the device the block's spectrum moves IN FRONT of the tuner on the block's stream, wide_squelch_kernel (csrc/m17_squelch_kernels.hpp, a lane per
+ * channel) follows it, and the tuner runs in a squelched instantiation whose workgroups read the channel's state word first: a closed workgroup stores its
+ * tile's zeros and returns before it mixes a sample.  What m17hip_wide_spectrum_fetch returns and waits for does not change.  With the squelch off a block
+ * queues exactly what it queued under ABI 618.  m17hip_timing_get index 17 is the squelch kernel (the spectrum and the tuner keep theirs); m17hip_iq_bytes
+ * counts the levels, the hold counts and the fetch planes.
+ * A transmission that begins in a block's last moments — behind the last frame the spectrum takes, or too short in it to lift the band over the level — is
+ * not heard until the next block: its start is lost.  The loss is bounded by one block, so a receiver that must keep a transmission's link setup frame
+ * (40 ms) uploads blocks no longer than the preamble it can count on, covers the block with frames (hop <= points), and sets the open level low enough
+ * that a carrier present for one frame in J lifts the band over it: open_level * J below floor * (J - 1) + carrier.
+ * Out of scope, for a later pull request: a floor estimated on the device (the median); squelch under the raster; driving the demodulator's gate-aware front
+ * end or its frame cycle from the squelch; a look-back that re-tunes the block before an opening; compacting the grid to open channels; AFC; tests of the
+ * squelch under deep in-flight call orders beyond one staged and one in-place block. */
+/* open_level == NULL with nlevels == 0 turns the squelch off (the default).  Otherwise half_bins is in 0..64 and below points / 2, the levels are finite
+ * with 0 < close_level[s] <= open_level[s], nlevels == sources and hang is in 0..65535 (blocks a channel stays open behind the last block whose band held
+ * it open).  It holds for the blocks uploaded AFTER the call and never waits for anything in flight: the levels travel to the device with the next block, in
+ * a copy that no queued launch reads.  M17HIP_EINVAL outside the limits or for a NULL context, with nothing changed.  M17HIP_ESTATE, with nothing changed:
+ * before any wideband configuration; between m17hip_demod_front and its run; and, when turning it on, with the spectrum off or under m17hip_wide_raster
+ * (the channeliser's work is shared by a source's channels: there is nothing per channel to save, and the raster survey serves that case).  Every
+ * m17hip_wide_spectrum call and every m17hip_wide_config, m17hip_wide_config2, m17hip_wide_raster or m17hip_wide_resample call turns it off. */
+int m17hip_wide_squelch(m17hip_ctx* ctx, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang);
+/* The decision of the latest block uploaded with the squelch on (back = 0) or of the one before it (back = 1): state_host[c] = h' | open << 31 and
+ * band_host[c] = b_c for the block's channels; *channels their number, *frames the block's J (either may be NULL).  Two planes and two events take turns.  It
+ * waits for that block's squelch kernel only — not for its tuner, a run or a later block — and copies on a stream of its own.  M17HIP_ESTATE if no such
+ * plane exists: the squelch is off, no block (or, for back = 1, one block) since it was turned on, or none since m17hip_demod_reset.  M17HIP_EINVAL for
+ * back > 1, a NULL context, state_host or band_host, or capacity (in channels) below the block's channel count; nothing is written then. */
+int m17hip_wide_squelch_fetch(m17hip_ctx* ctx, uint32_t back, uint32_t* state_host, float* band_host, uint64_t capacity, uint32_t* channels, uint32_t* frames);
+
 /* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
  * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
  * it, an FM exciter — as rtl_fm is attached in front of the receiver —, is this family: every int16 baseband of a context's input slab (uploaded, or made
@@ -1071,7 +1117,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 11 = channelise (the channeliser of m17hip_upload_wide* under m17hip_wide_raster: likewise), 12 = survey (the two kernels of m17hip_wide_survey, one
  * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block), 14 = spectrum (the two
  * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block),
- * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index). */
+ * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index),
+ * 17 = squelch (wide_squelch_kernel of m17hip_wide_squelch, one entry per squelched block; its spectrum and its tuner keep their own indices). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

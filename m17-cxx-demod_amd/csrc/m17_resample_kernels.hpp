@@ -100,8 +100,8 @@ __device__ __forceinline__ void resample_chains(const float2* base, uint32_t lan
 // 3. Output n = g0 U + w - 1 is z w against z w - 1, lanes over consecutive w; the block's last z goes to znew[c] for wide_carry_kernel.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.  Every z is the same
 // chain whatever G and Q are: the result does not depend on the tile rule.
-// METER: as tune_kernel's.
-template <typename IQT, bool METER = false, typename... PW>
+// METER, SQUELCH: as tune_kernel's (a closed workgroup's tile is its groups' outputs).
+template <typename IQT, bool METER = false, bool SQUELCH = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void resample_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                                 const float* __restrict__ taps1, uint32_t L1, uint32_t R1, const float* __restrict__ taps2,
                                                                 uint32_t L2, uint32_t U, uint32_t D, uint32_t G, uint32_t Q,
@@ -113,6 +113,12 @@ __global__ __launch_bounds__(WIDE_THREADS) void resample_kernel(const IQT* __res
     const uint32_t lane = threadIdx.x;
     const uint64_t wg = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const uint32_t c = (uint32_t)(wg % gridDim.y), g0 = (uint32_t)(wg / gridDim.y) * G;
+    if constexpr (SQUELCH) {
+        if (squelch_closed(c, pw...)) {
+            squelch_zero(c, g0 * U, (T / U - g0 < G ? T / U : g0 + G) * U, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
+            return;
+        }
+    }
     const uint32_t s = table[c], fcw = table[maxC + c];
     const uint32_t J1 = wide2_j(L1, R1), J2 = wide2_j(L2, U), JD = wide2_j(J2, D), P2 = G + JD, K = WIDE_PER_LANE * Q, P1 = K + J1 - 1;
     const uint32_t H = (J2 - 1) * R1 + L1 - 1;

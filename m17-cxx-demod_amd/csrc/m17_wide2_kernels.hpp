@@ -72,8 +72,8 @@ __device__ __forceinline__ void wide_chains(const float2* base, uint32_t P, uint
 // 2. Stage 2 is tune_kernel's step 2 over the u planes with (L2, R2), and 3. the z go through LDS into the discriminator as there: the block's output 0 has
 //    the channel's carry in front, a later tile recomputes the z in front of it, the block's last z goes to znew[c] for wide_carry_kernel.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.
-// METER: as tune_kernel's.
-template <typename IQT, bool METER = false, typename... PW>
+// METER, SQUELCH: as tune_kernel's.
+template <typename IQT, bool METER = false, bool SQUELCH = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void tune2_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                              const float* __restrict__ taps1, uint32_t L1, uint32_t R1, const float* __restrict__ taps2,
                                                              uint32_t L2, uint32_t R2, uint32_t Q, const uint32_t* __restrict__ table, uint32_t maxC,
@@ -86,6 +86,12 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune2_kernel(const IQT* __restri
     const uint32_t lane = threadIdx.x;
     const uint64_t wg = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const uint32_t c = (uint32_t)(wg % gridDim.y), n0 = (uint32_t)(wg / gridDim.y) * WIDE_TILE;
+    if constexpr (SQUELCH) {
+        if (squelch_closed(c, pw...)) {
+            squelch_zero(c, n0, T - n0 < (uint32_t)WIDE_TILE ? T : n0 + WIDE_TILE, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
+            return;
+        }
+    }
     const uint32_t s = table[c], fcw = table[maxC + c];
     const uint32_t J1 = wide2_j(L1, R1), J2 = wide2_j(L2, R2), P2 = WIDE_TILE + J2, K = WIDE_PER_LANE * Q, P1 = K + J1 - 1;
     const uint32_t H = (L2 - 1) * R1 + L1 - 1;

@@ -26,6 +26,28 @@ constexpr int WIDE_TAPS = 8;                            // taps fetched together
 __host__ __device__ inline uint32_t wide_plane(uint32_t L, uint32_t R) { return WIDE_TILE + (L + R - 1) / R; }
 __host__ __device__ inline size_t wide_lds_bytes(uint32_t L, uint32_t R) { return ((size_t)R * wide_plane(L, R) + WIDE_Z) * sizeof(float2); }   // <= 42880 (R = 16, L = 1024)
 
+// What a squelched launch of a tuner takes as its last argument (m17hip_wide_squelch; csrc/m17_squelch_kernels.hpp): the block's state words, [channels] of
+// h' | open << 31.
+struct SquelchIn { const uint32_t* state; };
+__device__ __forceinline__ bool squelch_closed(uint32_t c, SquelchIn q) { return !(q.state[c] & core::SQUELCH_OPEN); }
+__device__ __forceinline__ bool squelch_closed(uint32_t c, MeterOut, SquelchIn q) { return squelch_closed(c, q); }
+// (the metered and squelched instantiations carry both: the power goes where the meter's argument says)
+__device__ __forceinline__ void meter_put(uint32_t c, uint32_t n, float2 z, MeterOut m, SquelchIn) { meter_put(c, n, z, m); }
+__device__ __forceinline__ void squelch_power(uint32_t, uint32_t, SquelchIn) {}
+__device__ __forceinline__ void squelch_power(uint32_t c, uint32_t n, MeterOut m, SquelchIn) { m.p[(size_t)c * m.pitch + n] = 0.0f; }
+
+// A closed channel's workgroup: the outputs n0 .. n1 - 1 of the block (n1 <= T) get +0, the meter's power scratch likewise where there is one, and the
+// workgroup that holds output T - 1 leaves (0, 0) as the channel's carry.  No LDS, no barrier.
+template <typename... PW>
+__device__ __forceinline__ void squelch_zero(uint32_t c, uint32_t n0, uint32_t n1, uint32_t T, float* __restrict__ d, float2* __restrict__ znew, PW... pw)
+{
+    for (uint32_t n = n0 + threadIdx.x; n < n1; n += WIDE_THREADS) {
+        d[n] = 0.0f;
+        squelch_power(c, n, pw...);
+        if (n == T - 1) znew[c] = make_float2(0.0f, 0.0f);
+    }
+}
+
 // Grid (tiles of WIDE_TILE outputs, channels).  Channel c listens to source table[c] at the frequency word table[maxC + c].
 // 1. The workgroup mixes the (WIDE_TILE + J) R input samples under its tile ONCE into LDS (the oscillator costs as much as ten taps: never per output).
 //    Sample k of the block (k < 0: the source's carried history of H = L - 1 converted samples; below that and behind the row's end: zero, which no stored
@@ -39,7 +61,10 @@ __host__ __device__ inline size_t wide_lds_bytes(uint32_t L, uint32_t R) { retur
 //    tile 0 of this launch reads carry[c], so the carry itself is written by wide_carry_kernel behind this launch.
 // Samples are read one by one (a sample is aligned to its own size, nothing more is asked of the rows); vector stores only, no atomics.
 // METER (m17hip_wide_meter is on): the launch has one more argument, a MeterOut, and every output's chan_power(z) goes to it beside the output's y.
-template <typename IQT, bool METER = false, typename... PW>
+// SQUELCH (m17hip_wide_squelch is on): the launch's last argument is a SquelchIn, and the workgroups of a channel whose state word says closed store +0 for
+// their tile's outputs (and powers), (0, 0) for the carry where they hold output T - 1, and return — before any LDS traffic, barrier or mixing.  The flag is
+// the channel's, so the return is uniform for the workgroup.
+template <typename IQT, bool METER = false, bool SQUELCH = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                             const float* __restrict__ taps, uint32_t L, uint32_t R, const uint32_t* __restrict__ table,
                                                             uint32_t maxC, uint32_t count, float* __restrict__ dst, size_t dpitch, uint32_t T,
@@ -48,6 +73,12 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restric
     extern __shared__ float2 wide_lds[];
     const uint32_t c = blockIdx.y, lane = threadIdx.x;
     const uint32_t n0 = blockIdx.x * WIDE_TILE;
+    if constexpr (SQUELCH) {
+        if (squelch_closed(c, pw...)) {
+            squelch_zero(c, n0, T - n0 < (uint32_t)WIDE_TILE ? T : n0 + WIDE_TILE, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
+            return;
+        }
+    }
     const uint32_t s = table[c], fcw = table[maxC + c];
     const uint32_t J = (L + R - 1) / R, P = WIDE_TILE + J, H = L - 1;
     float2* zbuf = wide_lds + (size_t)R * P;

@@ -14,6 +14,7 @@
 #include "m17_chan_survey_kernels.hpp"
 #include "m17_spectrum_kernels.hpp"
 #include "m17_meter_kernels.hpp"
+#include "m17_squelch_kernels.hpp"
 #include "m17_wide_tx_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_demod_kernel.hpp"
@@ -40,7 +41,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -419,11 +420,33 @@ struct m17hip_ctx {
             void forget() { valid[0] = valid[1] = false; }
             ~Meter() { if (fetch) (void)hipStreamDestroy(fetch); }
         } mt;
+        // The spectrum squelch of the three tuners (m17hip_wide_squelch; csrc/m17_squelch_kernels.hpp): `on` needs the spectrum on and no raster.  The
+        // levels [open[S] | close[S]] stay on the host until the next block brings them to the device in a turn-taking table (`dirty`).  The hold counts
+        // [maxC] are the feed's, ordered across the two streams by ev_iq like the carries; `fresh` says that the next squelched block zeroes the whole
+        // array on its own stream in front of its kernel, so neither m17hip_wide_squelch nor m17hip_demod_reset touches a stream for them.  Two planes of state words and band
+        // powers [maxC] take turns, each with the event recorded behind the block's wide_squelch_kernel; the block's tuner reads its own state plane.
+        struct Squelch {
+            bool on = false, fresh = true;
+            uint32_t B = 0, hang = 0;
+            std::vector<float> levels;
+            bool dirty = true;
+            TurnTable dev;
+            DevBuf<uint32_t> hold, state[2];
+            DevBuf<float> band[2];
+            Event ev[2];
+            bool valid[2] = {false, false};
+            uint32_t C[2] = {0, 0}, frames[2] = {0, 0};
+            int latest = 0;
+            hipStream_t fetch = nullptr;   // m17hip_wide_squelch_fetch's copies: a stream of its own, behind nothing but the plane's event
+            void forget() { valid[0] = valid[1] = false; }
+            ~Squelch() { if (fetch) (void)hipStreamDestroy(fetch); }
+        } sq;
         size_t bytes() const
         {
             return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size() + sp.scratch.size() + sp.plane[0].size() +
                     sp.plane[1].size() + mt.scratch.size() + mt.plane[0].size() + mt.plane[1].size()) * sizeof(float) +
-                   (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4;
+                   (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4 +
+                   (sq.dev.words() + sq.hold.size() + sq.state[0].size() + sq.state[1].size() + sq.band[0].size() + sq.band[1].size()) * 4;
         }
     } wide;
     // THE WIDEBAND SIGNAL GENERATOR (m17hip_synth_wide_config, m17hip_synth_wide; csrc/m17_wide_tx_kernels.hpp): the int16 input slab's rows FM-modulated into
@@ -1272,7 +1295,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 618; }
+int m17hip_version(void) { return 619; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1638,14 +1661,21 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
             c->wide.sp.forget();
             c->wide.mt.forget();   // (the meter stays on: its windows start over with the feed)
             c->wide.mt.outputs = 0;
+            c->wide.sq.forget();   // (the squelch stays on: every channel's hold count starts over)
+            c->wide.sq.fresh = true;
         }
     } else {
+        auto& sq = c->wide.sq;
+        // the listed channels' hold counts as well.  Not while `fresh` is set: the next squelched block then zeroes the WHOLE array on its stream before its
+        // kernel reads a count (launch_squelch), so nothing that stands in it now is ever read
+        const bool hold = c->wide.S && sq.hold && !sq.fresh;
         std::vector<uint32_t> v(channels, channels + n);
         std::sort(v.begin(), v.end());
         for (size_t i = 0; i < v.size();) {
             size_t j = i + 1;
             while (j < v.size() && v[j] <= v[j - 1] + 1u) ++j;
             HIPCHK(c, hipMemsetAsync(c->iq_carry.get() + v[i], 0, (size_t)(v[j - 1] - v[i] + 1u) * sizeof(float2), st));
+            if (hold) HIPCHK(c, hipMemsetAsync(sq.hold.get() + v[i], 0, (size_t)(v[j - 1] - v[i] + 1u) * sizeof(uint32_t), st));
             i = j;
         }
     }
@@ -1855,6 +1885,47 @@ static int launch_meter(m17hip_ctx* c, const float* x, uint32_t T, uint32_t C, h
     mt.C[p] = C; mt.K[p] = K; mt.T[p] = T; mt.N0[p] = mt.outputs; mt.win[p] = mt.window; mt.valid[p] = true; mt.latest = p;
     return M17HIP_OK;
 }
+// The squelch of one block (m17hip_wide_squelch is on), on the block's stream between its spectrum and its tuner: it reads the plane launch_spectrum has
+// just queued, the channel table the tuner is about to read and the levels, steps the hold counts and writes the state and band planes whose turn it is.
+// The state plane is what the block's tuner reads: its next writer, two blocks on, is behind that tuner through ev_iq.
+static int launch_squelch(m17hip_ctx* c, uint32_t C, hipStream_t st)
+{
+    auto& w = c->wide;
+    auto& sq = w.sq;
+    const int p = sq.latest ^ 1, ps = w.sp.latest;
+    int r;
+    if (!sq.fetch) HIPCHK(c, hipStreamCreateWithFlags(&sq.fetch, hipStreamNonBlocking));
+    for (auto& e : sq.ev) if (!e) HIPCHK(c, e.create());
+    if (!sq.hold) {   // ([maxC] each, once per configuration: never regrown)
+        if ((r = alloc_code(c, sq.hold.alloc(c->maxC)))) return r;
+        for (auto& b : sq.state) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
+        for (auto& b : sq.band) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
+        sq.fresh = true;
+    }
+    if (sq.dirty || !sq.dev.live()) {   // the levels, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, sq.dev.begin_write(2 * 256, &staging));
+        std::memcpy(staging, sq.levels.data(), sq.levels.size() * 4);
+        HIPCHK(c, sq.dev.publish(sq.levels.size(), st));
+        sq.dirty = false;
+    }
+    HIPCHK(c, sq.dev.before_read(st));
+    sq.valid[p] = false;
+    // A fresh feed of decisions: every count of the array is 0, not only those of this block's channels — a later block may carry more channels than this
+    // one.  On the block's stream, which iq_order has put behind whatever read or wrote the array last: nothing is waited for.
+    if (sq.fresh) HIPCHK(c, hipMemsetAsync(sq.hold.get(), 0, (size_t)c->maxC * sizeof(uint32_t), st));
+    {
+        Timed tm(c, KT_SQUELCH, st);
+        hipLaunchKernelGGL(wide_squelch_kernel, dim3((C + SQUELCH_THREADS - 1) / SQUELCH_THREADS), dim3(SQUELCH_THREADS), 0, st, w.sp.plane[ps].get(), w.sp.logn,
+                           w.sp.frames[ps], w.dev.dev(), c->maxC, reinterpret_cast<const float*>(sq.dev.dev()), w.S, sq.B, sq.hang, sq.hold.get(), sq.state[p].get(), sq.band[p].get(), C);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    HIPCHK(c, hipEventRecord(sq.ev[p], st));
+    sq.fresh = false;
+    sq.C[p] = C; sq.frames[p] = w.sp.frames[ps]; sq.valid[p] = true; sq.latest = p;
+    return M17HIP_OK;
+}
 template <typename IQT>
 static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, uint32_t H, uint32_t C, const float* x, hipStream_t st)
 {
@@ -1864,7 +1935,7 @@ static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_
     if (w.mt.window) if (int r = launch_meter(c, x, T, C, st)) return r;   // (m17hip_wide_meter: under every configuration)
     w.mt.outputs += T;
     if (w.sv.stride) if (int r = launch_survey<IQT>(c, src, pitch, W, T, st)) return r;   // (m17hip_wide_survey: on under a raster only)
-    if (w.sp.points) if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;   // (m17hip_wide_spectrum: under every configuration)
+    if (w.sp.points && !w.sq.on) if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;   // (m17hip_wide_spectrum: under every configuration; a squelched block's went in front of its tuner)
     if (H) {
         hipLaunchKernelGGL(wide_hist_kernel<IQT>, dim3((H + 63) / 64, w.S), dim3(64), 0, st, src, pitch, W, w.hist[w.par].get(), w.hist[w.par ^ 1].get(), H);
         HIPCHK(c, hipGetLastError());
@@ -1890,11 +1961,27 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     const bool meter = w.mt.window != 0;   // (the metered instantiations: one more argument and one more store per output, otherwise the same launch)
     if (meter) if (int r = meter_scratch(c, C, T)) return r;
     const MeterOut mo{w.mt.scratch.get(), (size_t)T};
+    // The squelched instantiations (m17hip_wide_squelch): the block's spectrum and the squelch kernel go IN FRONT of the tuner on its stream, and the tuner's
+    // last argument is the state plane that kernel has written.  With the squelch off nothing moves: the spectrum follows in wide_after_block.
+    const bool squelch = w.sq.on;
+    if (squelch) {
+        if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;
+        if (int r = launch_squelch(c, C, st)) return r;
+    }
+    const SquelchIn qi{squelch ? w.sq.state[w.sq.latest].get() : nullptr};
     if (w.U) {
         const uint32_t G = resample_groups(w.L, w.R, w.L2, w.U, w.D), Q = resample_q(w.L, w.R, w.L2, w.U, w.D, G);
         TimedK tm(c, KT_RESAMPLE);
-        if (meter)
-            tm.launch(resample_kernel<IQT, true, MeterOut>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st,
+        if (squelch && meter)
+            tm.launch(resample_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
+                      resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
+                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
+        else if (squelch)
+            tm.launch(resample_kernel<IQT, false, true, SquelchIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
+                      resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
+                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
+        else if (meter)
+            tm.launch(resample_kernel<IQT, true, false, MeterOut>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st,
                       src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count,
                       x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
         else
@@ -1903,8 +1990,16 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
                   c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else if (w.R2) {
         TimedK tm(c, KT_WIDE2);
-        if (meter)
-            tm.launch(tune2_kernel<IQT, true, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src,
+        if (squelch && meter)
+            tm.launch(tune2_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
+                      wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
+                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
+        else if (squelch)
+            tm.launch(tune2_kernel<IQT, false, true, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
+                      wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
+                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
+        else if (meter)
+            tm.launch(tune2_kernel<IQT, true, false, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src,
                       pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
                       (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
         else
@@ -1913,8 +2008,16 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
                   (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else {
         TimedK tm(c, KT_WIDE);
-        if (meter)
-            tm.launch(tune_kernel<IQT, true, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W,
+        if (squelch && meter)
+            tm.launch(tune_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st,
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      w.znew.get(), gain, mo, qi);
+        else if (squelch)
+            tm.launch(tune_kernel<IQT, false, true, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src,
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      w.znew.get(), gain, qi);
+        else if (meter)
+            tm.launch(tune_kernel<IQT, true, false, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W,
                       w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(),
                       gain, mo);
         else
@@ -2086,6 +2189,10 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.sp.points = 0; w.sp.forget();   // (the spectrum likewise: its plane has a row per source)
     w.sp.scratch.release(&c->last_hip);
     for (auto& b : w.sp.plane) b.release(&c->last_hip);
+    w.sq.on = false; w.sq.forget();   // (the squelch goes with the spectrum)
+    w.sq.hold.release(&c->last_hip);
+    for (auto& b : w.sq.state) b.release(&c->last_hip);
+    for (auto& b : w.sq.band) b.release(&c->last_hip);
     w.mt.window = 0; w.mt.forget(); w.mt.outputs = 0;   // (the meter likewise: a new feed)
     w.mt.scratch.release(&c->last_hip);
     for (auto& b : w.mt.plane) b.release(&c->last_hip);
@@ -2314,6 +2421,7 @@ int m17hip_wide_spectrum(m17hip_ctx* c, uint32_t points, uint32_t hop, const flo
     }
     if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the planes have a row per source; the staged block belongs to the run being made)
     sp.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
+    w.sq.on = false; w.sq.forget();   // (the squelch's bins are this call's to redefine: off until m17hip_wide_squelch is called again)
     sp.points = points;
     if (!points) return M17HIP_OK;
     sp.logn = spectrum_logn(points); sp.hop = hop;
@@ -2385,6 +2493,51 @@ int m17hip_wide_meter_fetch(m17hip_ctx* c, uint32_t back, float* planes_host, ui
     HIPCHK(c, hipEventSynchronize(mt.ev[p]));   // (that block's meter kernel and what its stream held in front of it: no run, no later block)
     HIPCHK(c, hipMemcpyAsync(planes_host, mt.plane[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, mt.fetch));
     HIPCHK(c, hipStreamSynchronize(mt.fetch));
+    return M17HIP_OK;
+}
+// ---- the spectrum squelch (ABI 619): the three tuners skip the channels whose band of the block's spectrum holds no carrier ----------------------------
+int m17hip_wide_squelch(m17hip_ctx* c, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang)
+{
+    if (!c) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sq = w.sq;
+    const bool off = !open_level && nlevels == 0;
+    if (!off) {
+        if (!open_level || !close_level || nlevels < 1 || nlevels > 256 || half_bins > 64 || hang > 65535) return M17HIP_EINVAL;
+        for (uint32_t s = 0; s < nlevels; ++s)
+            if (!std::isfinite(open_level[s]) || !std::isfinite(close_level[s]) || !(close_level[s] > 0.0f) || !(close_level[s] <= open_level[s])) return M17HIP_EINVAL;
+    }
+    if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the staged block belongs to the run being made)
+    if (!off) {
+        if (w.M || !w.sp.points) return M17HIP_ESTATE;   // (a raster's channels share their work; the decision is read from the block's spectrum)
+        if (nlevels != w.S || half_bins >= w.sp.points / 2) return M17HIP_EINVAL;
+    }
+    sq.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
+    sq.fresh = true;
+    sq.on = !off;
+    if (off) return M17HIP_OK;
+    sq.B = half_bins; sq.hang = hang;
+    sq.levels.assign(open_level, open_level + nlevels);
+    sq.levels.insert(sq.levels.end(), close_level, close_level + nlevels);
+    sq.dirty = true;
+    return M17HIP_OK;
+}
+int m17hip_wide_squelch_fetch(m17hip_ctx* c, uint32_t back, uint32_t* state_host, float* band_host, uint64_t capacity, uint32_t* channels, uint32_t* frames)
+{
+    if (!c || back > 1 || !state_host || !band_host) return M17HIP_EINVAL;
+    auto& sq = c->wide.sq;
+    if (!c->wide.S || !sq.on) return M17HIP_ESTATE;
+    const int p = sq.latest ^ (int)back;
+    if (!sq.valid[p]) return M17HIP_ESTATE;
+    const size_t n = sq.C[p];
+    if (capacity < n) return M17HIP_EINVAL;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sq.ev[p]));   // (that block's squelch kernel and what its stream held in front of it: not its tuner, no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(state_host, sq.state[p].get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, sq.fetch));
+    HIPCHK(c, hipMemcpyAsync(band_host, sq.band[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, sq.fetch));
+    HIPCHK(c, hipStreamSynchronize(sq.fetch));
+    if (channels) *channels = (uint32_t)n;
+    if (frames) *frames = sq.frames[p];
     return M17HIP_OK;
 }
 int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }

@@ -150,6 +150,26 @@ public:
         if (channels) *channels = c;
         if (pieces) *pieces = k;
     }
+    // The spectrum squelch of the three tuners (m17hip_wide_squelch; the spectrum must be on): from the blocks uploaded after the call a channel whose band
+    // of 2 half_bins + 1 bins of the block's spectrum lies below open_level[source] x frames is not tuned (its floats are +0); an open one stays open down
+    // to close_level[source] x frames and for `hang` blocks behind that.  One level pair per source; wide_squelch_off turns it off.  wide_squelch_fetch:
+    // per channel of the latest such block (back = 0) or the one before (back = 1) the word h' | open << 31 and the band power, resized to fit; it waits for
+    // that block's squelch kernel only.
+    void wide_squelch(uint32_t half_bins, const std::vector<float>& open_level, const std::vector<float>& close_level, uint32_t hang = 0)
+    {
+        if (open_level.size() != close_level.size()) throw std::invalid_argument("wide_squelch: one open and one close level per source");
+        check(m17hip_wide_squelch(ctx_, half_bins, open_level.data(), close_level.data(), (uint32_t)open_level.size(), hang), "m17hip_wide_squelch");
+    }
+    void wide_squelch_off() { check(m17hip_wide_squelch(ctx_, 0, nullptr, nullptr, 0, 0), "m17hip_wide_squelch"); }
+    void wide_squelch_fetch(uint32_t back, std::vector<uint32_t>& state, std::vector<float>& band, uint32_t* frames = nullptr)
+    {
+        state.resize(channels_);
+        band.resize(channels_);
+        uint32_t n = 0;
+        check(m17hip_wide_squelch_fetch(ctx_, back, state.data(), band.data(), state.size(), &n, frames), "m17hip_wide_squelch_fetch");
+        state.resize(n);
+        band.resize(n);
+    }
     // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
     // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
     // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,

@@ -163,6 +163,7 @@ struct M17Demodulator
         wide_decim_ = decim;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         meter_window_ = 0;      // (and the meter)
+        squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -201,6 +202,7 @@ struct M17Demodulator
         wide_decim_ = decim1 * decim2;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         meter_window_ = 0;      // (and the meter)
+        squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = decim1;
         wide_up_ = 1; wide_down_ = 0;
         raster_m_ = 0;
@@ -243,6 +245,7 @@ struct M17Demodulator
         wide_decim_ = decim1 * down;   // (the samples of a group)
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         meter_window_ = 0;      // (and the meter)
+        squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = decim1;
         wide_up_ = up; wide_down_ = down;
         raster_m_ = 0;
@@ -280,6 +283,7 @@ struct M17Demodulator
         wide_decim_ = decim;
         spectrum_points_ = 0;   // (every configuration turns the spectrum off)
         meter_window_ = 0;      // (and the meter)
+        squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = 0;
         wide_up_ = 1; wide_down_ = 0;
         if (gpu_) {
@@ -328,6 +332,26 @@ struct M17Demodulator
         gpu_->wide_spectrum(points, hop, window.empty() ? nullptr : window.data(), (uint32_t)window.size());
         spectrum_points_ = points;
         spectrum_report_ = std::move(report);
+        squelch_mode_ = 0;   // (every wide_spectrum call turns the squelch off)
+        return true;
+    }
+    // The spectrum squelch beside wide_config / wide_rate on the GPU path (m17hip_wide_squelch; wide_spectrum first): the NEXT block runs unsquelched, and
+    // its plane gives the levels — the median of the plane times 2 half_bins + 1, per frame, times 10^(open_db / 10) and 10^(close_db / 10), the rule of
+    // m17hip's Python wide_squelch_levels —; from the block after it the channel is tuned only while its band of the block's spectrum holds a carrier (and
+    // for `hang` blocks behind that), and gets +0 otherwise.  After each squelched block `report`, if any, gets the decision: open, the hold count, the band
+    // power and the block's frames.  Returns false, with nothing changed, on the host form.  Any wide_config / wide_rate / wide_raster / wide_spectrum
+    // call turns it off.
+    using squelch_callback_t = std::function<void(bool open, uint32_t hold, float band, uint32_t frames)>;
+    bool wide_squelch(uint32_t half_bins, double open_db, double close_db, uint32_t hang = 0, squelch_callback_t report = {})
+    {
+        if (!gpu_) return false;
+        if (!wide_decim_ || raster_m_ || !spectrum_points_) throw std::logic_error("M17Demodulator::wide_squelch needs wide_config or wide_rate, and wide_spectrum");
+        if (half_bins > 64 || half_bins >= spectrum_points_ / 2 || hang > 65535 || !(close_db <= open_db)) throw std::invalid_argument("M17Demodulator::wide_squelch");
+        flush();
+        gpu_->wide_squelch_off();
+        squelch_half_ = half_bins; squelch_open_db_ = open_db; squelch_close_db_ = close_db; squelch_hang_ = hang;
+        squelch_report_ = std::move(report);
+        squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
         return true;
     }
     // The channel meter beside any wideband configuration on the GPU path (m17hip_wide_meter): per window of `window` outputs of the feed (16..65536; 0
@@ -496,12 +520,28 @@ private:
             gpu_->wide_survey_fetch(0, survey_power_.data(), survey_power_.size(), &times, &first);
             survey_report_(survey_power_, times, first);
         }
-        if (spectrum_points_ && spectrum_report_) {   // (likewise: the fetch waits for the block's spectrum kernels)
+        const bool squelched = squelch_mode_ == 2;   // (this block was uploaded with the squelch on)
+        if (spectrum_points_ && (spectrum_report_ || squelch_mode_ == 1)) {   // (likewise: the fetch waits for the block's spectrum kernels)
             spectrum_power_.resize(spectrum_points_);
             uint32_t frames = 0;
             uint64_t first = 0;
             gpu_->wide_spectrum_fetch(0, spectrum_power_.data(), spectrum_power_.size(), &frames, &first);
-            spectrum_report_(spectrum_power_, frames, first);
+            if (spectrum_report_) spectrum_report_(spectrum_power_, frames, first);
+            if (squelch_mode_ == 1 && frames) {   // (the levels from this block's plane; the squelch holds from the next block on)
+                std::vector<float> v(spectrum_power_);
+                std::sort(v.begin(), v.end());
+                const double floor = 0.5 * ((double)v[v.size() / 2 - 1] + (double)v[v.size() / 2]) * (2.0 * squelch_half_ + 1.0) / (double)frames;
+                const float open = (float)(floor * std::pow(10.0, squelch_open_db_ / 10.0)), close = (float)(floor * std::pow(10.0, squelch_close_db_ / 10.0));
+                if (std::isfinite(open) && close > 0.0f) {   // (a plane of zeros sets nothing: the next block tries again)
+                    gpu_->wide_squelch(squelch_half_, {open}, {close}, squelch_hang_);
+                    squelch_mode_ = 2;
+                }
+            }
+        }
+        if (squelched && squelch_report_) {   // (likewise: the fetch waits for the block's squelch kernel)
+            uint32_t frames = 0;
+            gpu_->wide_squelch_fetch(0, squelch_state_, squelch_band_, &frames);
+            squelch_report_((squelch_state_[0] >> 31) != 0, squelch_state_[0] & 0x7FFFFFFFu, squelch_band_[0], frames);
         }
         if (meter_window_ && meter_report_) {   // (likewise: the fetch waits for the block's meter kernel)
             uint32_t pieces = 0, outputs = 0;
@@ -559,6 +599,12 @@ private:
     uint32_t meter_window_ = 0;                      // wide_meter: 0 = off
     meter_callback_t meter_report_;
     std::vector<float> meter_planes_;
+    int squelch_mode_ = 0;                           // wide_squelch: 0 = off, 1 = armed (the next block's plane sets the levels), 2 = on
+    uint32_t squelch_half_ = 0, squelch_hang_ = 0;
+    double squelch_open_db_ = 0.0, squelch_close_db_ = 0.0;
+    squelch_callback_t squelch_report_;
+    std::vector<uint32_t> squelch_state_;
+    std::vector<float> squelch_band_;
     std::vector<float> raster_tw_, raster_w_;        // the twiddle table; the partial sums and the first pass's sums of one output
     uint64_t wide_m_ = 0;
     uint32_t block_;

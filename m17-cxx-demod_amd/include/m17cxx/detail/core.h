@@ -347,6 +347,36 @@ M17_HD float meter_sum(const float* v, uint32_t n)
     return acc;
 }
 
+// ---- a-1f: the spectrum squelch (m17hip_wide_squelch): per block and channel of the three tuners, whether the channel's workgroups tune the block at all,
+// decided from the block's own spectrum plane P[source][N] of J frames.  The channel's bin is the spectrum's index rule in integers — bin k belongs to
+// k Fs / N, the frequency word to fcw Fs / 2^32 —, rounded to the nearest bin, a word half way between two bins to the upper one, circular.
+M17_HD uint32_t squelch_bin(int32_t fcw, uint32_t logn)
+{
+    const int64_t v = ((int64_t)fcw + ((int64_t)1 << (31 - logn))) >> (32 - logn);   // (arithmetic: the floor)
+    return (uint32_t)v & ((1u << logn) - 1u);
+}
+// the band power: the chain from +0 of plain float adds of row[(k + d) & (N - 1)], d = -B .. B ascending (B < N / 2)
+M17_HD float squelch_band(const float* row, uint32_t N, uint32_t k, uint32_t B)
+{
+    float acc = 0.0f;
+    for (uint32_t i = 0; i <= 2 * B; ++i) acc = acc + row[(k + N - B + i) & (N - 1)];
+    return acc;
+}
+// a threshold of the block: the source's level per frame times the block's frames, one rounded multiply
+M17_HD float squelch_level(float level, uint32_t J) { return level * (float)J; }
+// One block's step of a channel: h the hold count in front of it, b its band power, to / tc the open and close thresholds, J the block's frames.  Returns
+// h' | open << 31.  A block without a frame leaves the channel open and h as it is; the comparisons are negated so that a NaN band opens as well.
+constexpr uint32_t SQUELCH_OPEN = 0x80000000u;
+M17_HD uint32_t squelch_step(uint32_t h, float b, float to, float tc, uint32_t hang, uint32_t J)
+{
+    if (J == 0) return h | SQUELCH_OPEN;
+    uint32_t hn;
+    if (!(b < to)) hn = hang + 1u;
+    else if (h > 0u && !(b < tc)) hn = hang + 1u;
+    else hn = h > 0u ? h - 1u : 0u;
+    return hn | (hn > 0u ? SQUELCH_OPEN : 0u);
+}
+
 // ---- t1: the wideband signal generator (m17hip_synth_wide, ABI 617): FM-modulate int16 basebands and put them at offsets into wide IQ streams -------
 // No reference file: the reference's users attach an FM exciter behind its modulator.  Written here, once, so that the kernels and the host form give the
 // same words.  Everything up to the oscillator's argument is INTEGER RING arithmetic (uint64 / uint32, wrapping), so any summation order, scan or tiling

@@ -30,7 +30,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16, "squelch": 17}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -79,6 +79,7 @@ EXPORTS = [
     "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
     "m17hip_wide_meter", "m17hip_wide_meter_shape", "m17hip_wide_meter_fetch",
+    "m17hip_wide_squelch", "m17hip_wide_squelch_fetch",
     "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
@@ -363,6 +364,28 @@ def wide_meter_report(planes, counts, gain):
     with np.errstate(divide="ignore", invalid="ignore"):
         level = 10.0 * np.log10(pl[0] / m)
     return {"level_db": level, "offset_hz": mean_y * hz, "deviation_hz": np.sqrt(np.maximum(pl[2] / m - mean_y * mean_y, 0.0)) * hz}
+
+
+def wide_squelch_half_bins(width_hz, rate_hz, points):
+    """half_bins of Context.wide_squelch for a band of width_hz around a channel's word in a spectrum of `points` bins of sources at rate_hz samples per
+    second: round(width_hz / 2 / (rate_hz / points)) — the h of wide_spectrum_carriers —, at most (points - 1) // 2 and at most 64, the limit of
+    m17hip_wide_squelch: at fine bins (9 kHz at 4096 points and 240 kSPS would be 77) the band is then narrower than asked for; take fewer points."""
+    n = int(points)
+    return min(int(round(float(width_hz) / 2.0 / (float(rate_hz) / n))), (n - 1) // 2, 64)
+
+
+def wide_squelch_levels(power, frames, half_bins, open_db, close_db):
+    """(open_level, close_level) float32 [sources] of Context.wide_squelch from a fetched spectrum plane (Context.wide_spectrum_fetch: power [sources][points]
+    of `frames` frames): per source the floor of a band of 2 half_bins + 1 bins PER FRAME — the row's median times 2 half_bins + 1, divided by frames —
+    times 10^(open_db / 10) and 10^(close_db / 10).  The median is the floor while fewer than half the bins hold a carrier.  Computed in float64 and rounded
+    to float32 once.  Pure numpy."""
+    p = np.asarray(power, dtype=np.float64)
+    if p.ndim == 1:
+        p = p[None, :]
+    if int(frames) < 1:
+        raise ValueError("wide_squelch_levels: a plane of at least one frame")
+    floor = np.median(p, axis=1) * (2 * int(half_bins) + 1) / float(int(frames))
+    return ((floor * 10.0 ** (float(open_db) / 10.0)).astype(np.float32), (floor * 10.0 ** (float(close_db) / 10.0)).astype(np.float32))
 
 
 def wide_fcw(offset_hz, decim):
@@ -661,6 +684,37 @@ class Context:
         buf = np.zeros(max(n, 1), dtype=np.float32)
         self._chk(self.lib.m17hip_wide_meter_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(n)))
         return buf[:n].reshape(3, ch.value, k.value), int(fw.value), int(fo.value), int(t.value)
+
+    def wide_squelch(self, half_bins, open_level, close_level=None, hang=0):
+        """The spectrum squelch of the three tuners (wide_config, wide_config2, wide_resample; the spectrum must be on): from the blocks uploaded after this
+        call a channel whose band — the 2 half_bins + 1 bins of the block's spectrum around its frequency word — lies below open_level[source] x frames is
+        not tuned: its floats are +0.  A channel that was open stays open while the band is at least close_level x frames (None: the open level) and for
+        `hang` blocks after that.  Scalars broadcast to all sources; open_level None turns it off (the default) — m17hip_wide_squelch.  Every wide_spectrum
+        call and every configuration call turns it off; reset() keeps it on and clears the hold counts."""
+        if open_level is None:
+            self._chk(self.lib.m17hip_wide_squelch(self.h, C.c_uint32(0), None, None, C.c_uint32(0), C.c_uint32(0)))
+            return
+        S = getattr(self, "_wide", (0,))[0]
+        o = np.asarray(open_level, dtype=np.float32).reshape(-1)
+        cl = o if close_level is None else np.asarray(close_level, dtype=np.float32).reshape(-1)
+        o = np.ascontiguousarray(np.repeat(o, S) if o.size == 1 and S > 1 else o)
+        cl = np.ascontiguousarray(np.repeat(cl, S) if cl.size == 1 and S > 1 else cl)
+        if o.size != cl.size:
+            raise ValueError("one open and one close level per source")
+        self._chk(self.lib.m17hip_wide_squelch(self.h, C.c_uint32(half_bins), _ptr(o), _ptr(cl), C.c_uint32(o.size), C.c_uint32(hang)))
+
+    def wide_squelch_fetch(self, back=0):
+        """(open bool [C], hold uint32 [C], band float32 [C], frames) of the latest block uploaded with the squelch on (back = 0) or the one before it
+        (back = 1): whether the block's channel was tuned, its hold count behind the block, the band power the decision was made from and the spectrum's
+        frame count of the block.  Waits for that block's squelch kernel only — m17hip_wide_squelch_fetch."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_squelch_fetch: back is 0 or 1")
+        cap = max(self.max_channels, 1)
+        state, band = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.float32)
+        n, frames = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.lib.m17hip_wide_squelch_fetch(self.h, C.c_uint32(back), _ptr(state), _ptr(band), C.c_uint64(cap), C.byref(n), C.byref(frames)))
+        state, band = state[: n.value], band[: n.value].copy()
+        return (state >> 31).astype(bool), state & np.uint32(0x7FFFFFFF), band, int(frames.value)
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

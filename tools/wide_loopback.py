@@ -3,7 +3,7 @@
 m17hip_upload_wide_device under a named configuration and runs; the tool counts the channels whose good records (Viterbi cost below 30, no LICH) hold the
 content sent.
     python tools/wide_loopback.py [--decim R | --decim2 R1 R2 | --raster R M | --rate HZ] [--channels C] [--sources S] [--outputs T] [--amplitude A]
-                                  [--sigma SIGMA] [--spacing HZ]
+                                  [--sigma SIGMA] [--spacing HZ] [--squelch DB [--points N] [--blocks K] [--hang H]]
 --decim R        one-stage tuner (m17hip_wide_config) at 48000 R                      (the default: --decim 5)
 --decim2 R1 R2   two-stage tuner (m17hip_wide_config2) at 48000 R1 R2                 (2.4 MSPS: --decim2 10 5)
 --raster R M     polyphase channeliser (m17hip_wide_raster) at 48000 R, M bins        (2.4 MSPS, 12.5 kHz: --raster 50 192)
@@ -12,6 +12,10 @@ Defaults: 4096 channels on 64 sources, 48 000 outputs, int16 streams.  A source'
 spacing) around its centre, as many as fit between +-0.45 of the rate; channels that do not fit wrap onto the same offsets again — they then share a
 carrier and cannot decode, which the count shows: 64 channels of 12.5 kHz need 800 kHz.  The amplitude defaults to the largest for which
 n A + 8 sigma <= 32767 with n channels on a source, so no sample clips.
+With --squelch DB (a tuner, not --raster) the same streams are received once more with the spectrum squelch on (m17hip_wide_squelch): one unsquelched block's
+spectrum plane (--points N, default 2048, hop N) gives the levels — m17hip.wide_squelch_levels: a 9 kHz band, open DB and close DB - 3 dB over the median
+floor —, then the outputs go in --blocks K equal blocks (default 1), each a run of its own, and the channels decoded from the squelched feed are counted
+beside those of the unsquelched one: the difference is what the squelch costs in lost lead-ins.
 Printed, as one JSON line: the channels decoded — beside how many of the same basebands decode when the TX context demodulates its own slab, with no
 multiplex in between, and how many do both ways —, the generator's time (library timer "synth_wide": both kernels) beside its instruction-count floor and the
 time of a device-to-device copy of the same output bytes, and the receive kernel's time (its library timer).
@@ -54,7 +58,12 @@ T = int(take(ARGS, "--outputs", 1, 48000))
 SIGMA = float(take(ARGS, "--sigma", 1, 100.0))
 AMP = take(ARGS, "--amplitude", 1, None)
 SPACING = float(take(ARGS, "--spacing", 1, 12500.0))
+SQUELCH = take(ARGS, "--squelch", 1, None)
+POINTS = int(take(ARGS, "--points", 1, 2048))
+BLOCKS = int(take(ARGS, "--blocks", 1, 1))
+HANG = int(take(ARGS, "--hang", 1, 0))
 assert not ARGS, f"unknown arguments {ARGS}"
+assert SQUELCH is None or not RASTER, "--squelch goes with a tuner"
 assert sum(v is not None for v in (DECIM2, RASTER, RATE, DECIM)) <= 1, "one configuration"
 assert C_ALL % S == 0, "the same number of channels on every source"
 PER = C_ALL // S
@@ -173,6 +182,29 @@ rx.upload_wide_device(out.data_ptr(), C_ALL, T, W)
 rx.run()
 recs = rx.frames()
 rx_ms, rx_n = rx.timing_get(timer)
+squelched = None
+if SQUELCH is not None:   # the same streams once more, squelched: levels from one unsquelched block's plane, then K blocks, each a run
+    assert T % (BLOCKS * Q) == 0, "--blocks K: equal blocks of whole groups"
+    Tb = T // BLOCKS
+    Wb = Tb // Q * P
+    half = m17hip.wide_squelch_half_bins(9000.0, RATE_HZ, POINTS)
+    rx.reset()
+    rx.wide_spectrum(POINTS, POINTS)
+    rx.upload_wide_device(out.data_ptr(), C_ALL, T, W)
+    power, frames, _ = rx.wide_spectrum_fetch()
+    levels = m17hip.wide_squelch_levels(power, frames, half, float(SQUELCH), float(SQUELCH) - 3.0)
+    rx.reset()
+    rx.wide_squelch(half, levels[0], levels[1], HANG)
+    rx.timing_reset()
+    parts, opened = [], []
+    for k in range(BLOCKS):
+        rx.upload_wide_device(out.data_ptr() + k * Wb * 4, C_ALL, Tb, W)
+        rx.run()
+        parts.append(rx.frames().copy())
+        opened.append(int(rx.wide_squelch_fetch()[0].sum()))
+    squelched = {"margin_db": float(SQUELCH), "points": POINTS, "half_bins": half, "blocks": BLOCKS, "hang": HANG, "open_channels_per_block": opened,
+                 "records": np.concatenate(parts), "tuner_ms": rx.timing_get(timer)[0] / BLOCKS, "spectrum_ms": rx.timing_get("spectrum")[0] / BLOCKS,
+                 "squelch_kernel_ms": rx.timing_get("squelch")[0] / BLOCKS}
 rx.close()
 
 
@@ -184,6 +216,10 @@ def failures(recs):
 
 
 bad, bad_direct = failures(recs), failures(direct)
+if squelched is not None:
+    bad_sq = failures(squelched.pop("records"))
+    squelched.update(decoded=C_ALL - len(bad_sq), decoded_unsquelched=C_ALL - len(bad), lost_to_the_squelch=len(set(bad_sq) - set(bad)),
+                     first_lost=sorted(set(bad_sq) - set(bad))[:16])
 cus = torch.cuda.get_device_properties(0).multi_processor_count
 mhz = 2400.0   # (the highest shader clock level the driver lists, read only; 2400 where it lists none)
 for path in sorted(glob.glob('/sys/class/drm/card*/device/pp_dpm_sclk')):
@@ -202,4 +238,4 @@ print(json.dumps({
     "decoded_from_the_basebands_directly": C_ALL - len(bad_direct), "decoded_by_both": C_ALL - len(set(bad) | set(bad_direct)),
     "generator_ms": gen_ms / max(gen_n, 1), "generator_floor_ms": floor_ms, "generator_x_floor": gen_ms / max(gen_n, 1) / floor_ms,
     "copy_same_bytes_ms": copy_ms, "output_bytes": int(out.numel() * 2), "generator_device_bytes": tx_bytes,
-    "receive_kernel": timer, "receive_ms": rx_ms / max(rx_n, 1), "cus": cus, "shader_mhz_max_level": mhz}))
+    "receive_kernel": timer, "receive_ms": rx_ms / max(rx_n, 1), **({"squelched": squelched} if squelched is not None else {}), "cus": cus, "shader_mhz_max_level": mhz}))

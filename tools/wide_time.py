@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -32,7 +32,13 @@ flops per frame at the packed rate, 64 per clock and SIMD.
 With --meter W under any of them the same blocks are then timed once more with the channel meter on (m17hip_wide_meter; the METERED instantiation of the
 configuration's kernel, which stores chan_power of every z, and wide_meter_kernel, csrc/m17_meter_kernels.hpp; library timer "meter"): the metered kernel
 beside the unmetered one of the same call, the meter kernel's own time, and a device-to-device copy of the bytes it reads — 2 x 4 bytes per channel and
-output — as the memory yardstick."""
+output — as the memory yardstick.
+With --squelch FRACTION[,FRACTION...] beside --spectrum under one of the three tuners a source of weak noise is made with a carrier on that fraction of the
+channels (a random choice among every source's channels: the first ones of every source put the open workgroups at a fixed period of the grid, which was
+measured 4 x slower per open workgroup under the two-stage tuners), one unsquelched block's plane gives the levels (m17hip.wide_squelch_levels: a 9 kHz band, open 10 dB and
+close 6 dB over the median floor), and the squelched launch — the spectrum, wide_squelch_kernel (library timer "squelch") and the squelched instantiation of
+the tuner — is timed per fraction beside the unsquelched tuner and spectrum on the same source in the same call.  Fraction 0 is a grid of all-closed
+workgroups: the floor of the design."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -79,6 +85,16 @@ if "--meter" in ARGS:
     k = ARGS.index("--meter")
     METER = int(ARGS[k + 1])
     del ARGS[k:k + 2]
+SQUELCH = []   # (empty: not timed)
+PLACE = "random"
+if "--squelch-first" in ARGS:   # (the carriers on the FIRST channels of every source instead: the regular placement, kept for the comparison)
+    ARGS.remove("--squelch-first")
+    PLACE = "first"
+if "--squelch" in ARGS:
+    k = ARGS.index("--squelch")
+    SQUELCH = [float(v) for v in ARGS[k + 1].split(",")]
+    del ARGS[k:k + 2]
+    assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in SQUELCH), "--squelch FRACTION (0 to 1) goes with --spectrum N --hop H and a tuner"
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
 T = int(ARGS[2]) if len(ARGS) > 2 else 48000
@@ -136,7 +152,8 @@ else:
     ctx.wide_config(S, R, m17hip.IQ_I16)
 if not RASTER:
     RATIO = R * DOWN / UP if UP else RATE
-    ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATIO) for f in rng.uniform(-24000.0 * RATIO, 24000.0 * RATIO, C)])
+    OFFSETS = rng.uniform(-24000.0 * RATIO, 24000.0 * RATIO, C)
+    ctx.wide_channels(np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATIO) for f in OFFSETS])
 
 
 def call():
@@ -208,6 +225,51 @@ if METER:   # the same blocks once more with the meter on: a warm-up block (scra
              "own_kernel_ms_metered": round(ms_o / n_o, 3), "metered_over_unmetered": round(ms_o / n_o / (ms / n), 4), "meter_ms": round(ms_m / n_m, 3),
              "copy_ms_median": round(float(np.median(cp)), 3), "bytes_read": 2 * 4 * C * T,
              "meter_over_copy": round(ms_m / n_m / float(np.median(cp)), 2)}
+squelch = []
+if SQUELCH:   # per fraction: a source with carriers on that share of the channels; unsquelched (spectrum + tuner), then squelched (spectrum + squelch + tuner)
+    half = m17hip.wide_squelch_half_bins(9000.0, 48000.0 * RATIO, SPECTRUM)   # (at most 64: a narrower band at fine bins)
+    n64 = torch.arange(ROW, dtype=torch.float64, device='cuda')
+    for frac in SQUELCH:
+        on = int(round(frac * PER))
+        xs = torch.randint(-200, 201, (S, ROW, 2), dtype=torch.int16, device='cuda', generator=g)
+        for s_ in range(S):   # 300 exp(2 pi i f n / Fs) for `on` of the source's channels, chosen at random (at most 64 x 300 < 32767 - 200)
+            pick = np.sort(rng.permutation(PER)[:on]) if PLACE == "random" else np.arange(on)
+            f = torch.tensor(OFFSETS[s_ * PER + pick] / (48000.0 * RATIO), dtype=torch.float64, device='cuda')
+            for k0 in range(0, on, 8):
+                ph = 2.0 * np.pi * torch.remainder(f[k0:k0 + 8, None] * n64[None, :], 1.0)
+                xs[s_, :, 0] += torch.round(300.0 * torch.cos(ph).sum(0)).to(torch.int16)
+                xs[s_, :, 1] += torch.round(300.0 * torch.sin(ph).sum(0)).to(torch.int16)
+        torch.cuda.synchronize()
+
+        def call_s():
+            ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
+
+        ctx.reset()
+        ctx.wide_spectrum(SPECTRUM, HOP)
+        call_s(); call_s()
+        power, frames, _ = ctx.wide_spectrum_fetch()
+        levels = m17hip.wide_squelch_levels(power, frames, half, 10.0, 6.0)
+        ctx.timing_reset()
+        for _ in range(REP):
+            call_s()
+        ctx.wide_spectrum_fetch()
+        (ms_u, n_u), (ms_pu, n_pu) = ctx.timing_get(OWN), ctx.timing_get("spectrum")
+        ctx.wide_squelch(half, levels[0], levels[1], 0)
+        call_s(); call_s()
+        ctx.timing_reset()
+        for _ in range(REP):
+            call_s()
+        opened = int(ctx.wide_squelch_fetch()[0].sum())
+        (ms_q, n_q), (ms_pq, n_pq), (ms_k, n_k) = ctx.timing_get(OWN), ctx.timing_get("spectrum"), ctx.timing_get("squelch")
+        ctx.wide_squelch(0, None)
+        ctx.wide_spectrum(0, 0)
+        uns, sq_ = ms_u / n_u, ms_q / n_q + ms_pq / n_pq + ms_k / n_k
+        squelch.append({"fraction": frac, "placement": PLACE, "carriers": on * S, "open_channels": opened, "half_bins": half, "frames_per_block": frames,
+                        "unsquelched_tuner_ms": round(uns, 3), "unsquelched_spectrum_ms": round(ms_pu / n_pu, 3), "squelched_tuner_ms": round(ms_q / n_q, 3),
+                        "squelched_spectrum_ms": round(ms_pq / n_pq, 3), "squelch_kernel_ms": round(ms_k / n_k, 4), "squelched_launch_ms": round(sq_, 3),
+                        "squelched_launch_over_unsquelched_tuner": round(sq_ / uns, 4)})
+        del xs
+    ctx.reset()
 neighbour = {}
 if UP:   # tune2_kernel on the same buffer and table at decim x NEIGHBOUR: a warm-up block, then REP timed ones
     ctx.wide_config2(S, R, NEIGHBOUR, m17hip.IQ_I16)
@@ -267,6 +329,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
