@@ -16,7 +16,9 @@
 // the tuned frequency and its deviation are measured on the device per window of W outputs and printed to stderr after each block; with --squelch DB
 // [--hang N] beside --spectrum and a tuner (not --raster) the first block runs unsquelched, its plane's median sets the floor of a 9 kHz band, and from
 // the second block on the channel is tuned only while its band stands DB dB over that floor (it stays open down to DB - 3 dB and for N more blocks), and
-// is fed zeros otherwise; each decision is printed to stderr.  One line per frame callback on
+// is fed zeros otherwise; each decision is printed to stderr; with --slots [--lead N] beside --squelch the decision is taken per slot of 16 frames of the
+// block's spectrum and the tuner skips per tile of its outputs (--hang then counts slots, --lead N opens the tiles up to N slots in front of an opening),
+// so a transmission that begins inside a block is kept from its start; the tiles tuned are printed per block.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -113,6 +115,8 @@ int main(int argc, char** argv)
     double squelch_db = 0.0;          // (--squelch: dB over the floor; hang in blocks)
     bool squelch = false;
     uint32_t hang = 0;
+    bool slots = false;               // (--slots: per slot and tile; --lead in slots)
+    uint32_t lead = 0;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -133,9 +137,11 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) { meter = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!meter) meter = 1; }
         else if (!std::strcmp(argv[i], "--squelch") && i + 1 < argc) { squelch_db = std::strtod(argv[++i], nullptr); squelch = true; }
         else if (!std::strcmp(argv[i], "--hang") && i + 1 < argc) hang = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
+        else if (!std::strcmp(argv[i], "--slots")) slots = true;
+        else if (!std::strcmp(argv[i], "--lead") && i + 1 < argc) { lead = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!lead) lead = ~0u; }
         else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N]]] [--meter W] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N] [--slots [--lead N]]]] [--meter W] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -163,6 +169,10 @@ int main(int argc, char** argv)
     if (meter && (!wide || meter < 16 || meter > 65536)) { std::fprintf(stderr, "m17-demod-gpu: --meter W (16 to 65536 outputs) goes with a wideband format\n"); return 2; }
     if ((squelch || hang) && (!squelch || !spectrum || raster || !(squelch_db > 0.0) || hang > 65535)) {
         std::fprintf(stderr, "m17-demod-gpu: --squelch DB (above 0) [--hang N (0 to 65535 blocks)] goes with --spectrum and a tuner, not with --raster\n");
+        return 2;
+    }
+    if ((slots || lead) && (!squelch || !slots || (lead && lead > 255))) {
+        std::fprintf(stderr, "m17-demod-gpu: --slots [--lead N (1 to 255 slots)] goes with --squelch\n");
         return 2;
     }
     if (spectrum || hop) {
@@ -221,7 +231,9 @@ int main(int argc, char** argv)
         if (squelch) {   // the first block unsquelched: its plane sets the levels
             const double fs = 2.0 * half_hz;
             const uint32_t h = std::min<uint32_t>((uint32_t)std::lrint(9000.0 / 2.0 / (fs / spectrum)), std::min<uint32_t>(64u, spectrum / 2 - 1));
-            const bool on = demod.wide_squelch(h, squelch_db, squelch_db - 3.0, hang, [](bool open, uint32_t hold, float band, uint32_t frames) {
+            const bool on = slots ? demod.wide_squelch_slots(h, squelch_db, squelch_db - 3.0, hang, lead, [](uint32_t open_tiles, uint32_t tiles, uint32_t nslots, uint32_t frames) {
+                std::fprintf(stderr, "squelch: %u of %u tiles open, %u slots over %u frames\n", open_tiles, tiles, nslots, frames);
+            }) : demod.wide_squelch(h, squelch_db, squelch_db - 3.0, hang, [](bool open, uint32_t hold, float band, uint32_t frames) {
                 std::fprintf(stderr, "squelch: %s, hold %u, band %.6g over %u frames\n", open ? "open" : "closed", hold, (double)band, frames);
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --squelch needs the GPU path (it runs on the device); no squelch\n");

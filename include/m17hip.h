@@ -489,8 +489,9 @@ int m17hip_wide_meter_fetch(m17hip_ctx* ctx, uint32_t back, float* planes_host, 
  * (40 ms) uploads blocks no longer than the preamble it can count on, covers the block with frames (hop <= points), and sets the open level low enough
  * that a carrier present for one frame in J lifts the band over it: open_level * J below floor * (J - 1) + carrier.
  * Out of scope, for a later pull request: a floor estimated on the device (the median); squelch under the raster; driving the demodulator's gate-aware front
- * end or its frame cycle from the squelch; a look-back that re-tunes the block before an opening; compacting the grid to open channels; AFC; tests of the
- * squelch under deep in-flight call orders beyond one staged and one in-place block. */
+ * end or its frame cycle from the squelch; a look-back ACROSS a block boundary that re-tunes the block before an opening (within a block,
+ * m17hip_wide_squelch_slots below decides per slot and has a lead); compacting the grid to open channels; AFC; tests of the squelch under deep in-flight call
+ * orders beyond one staged and one in-place block. */
 /* open_level == NULL with nlevels == 0 turns the squelch off (the default).  Otherwise half_bins is in 0..64 and below points / 2, the levels are finite
  * with 0 < close_level[s] <= open_level[s], nlevels == sources and hang is in 0..65535 (blocks a channel stays open behind the last block whose band held
  * it open).  It holds for the blocks uploaded AFTER the call and never waits for anything in flight: the levels travel to the device with the next block, in
@@ -505,6 +506,44 @@ int m17hip_wide_squelch(m17hip_ctx* ctx, uint32_t half_bins, const float* open_l
  * plane exists: the squelch is off, no block (or, for back = 1, one block) since it was turned on, or none since m17hip_demod_reset.  M17HIP_EINVAL for
  * back > 1, a NULL context, state_host or band_host, or capacity (in channels) below the block's channel count; nothing is written then. */
 int m17hip_wide_squelch_fetch(m17hip_ctx* ctx, uint32_t back, uint32_t* state_host, float* band_host, uint64_t capacity, uint32_t* channels, uint32_t* frames);
+
+/* ---- the time-resolved squelch: a decision per SLOT of a block, a skip per TILE of the tuner's outputs (ABI 620) --------------------------------------
+ * m17hip_wide_squelch takes one decision per channel and block, so a carrier keyed for part of a block is diluted by the silent part (12 dB over the floor
+ * for a fifth of the block lifts the block's band by 6 dB), and a strong one opens the whole block.  This second mode, exclusive with that one, decides per
+ * group of 16 frames of the block's spectrum and lets the tuners skip per tile.  Per block uploaded with it on, N, hop, first and J as for the spectrum:
+ *     SLOTS.  G = ceil(J / 16); slot g holds J_g = min(16, J - 16 g) frames; its row Q[s][g][.] is the spectrum's first-level sum for source s: the chain from
+ *     +0 of chan_power over the slot's frames, ascending (what spectrum_kernel leaves in its scratch).  The plane m17hip_wide_spectrum_fetch returns is the same.
+ *     BAND AND THRESHOLDS.  For channel c with source s: k_c = squelch_bin(fcw, log2 N), b_{c,g} = squelch_band(Q[s][g], N, k_c, B), and the thresholds are
+ *     squelch_level(open_level[s], J_g) and squelch_level(close_level[s], J_g): the four functions of ABI 619, unchanged.
+ *     RECURRENCE.  w_g = squelch_step(h_{g-1}, b_{c,g}, to_g, tc_g, hang, J_g), g = 0 .. G - 1; h_g is the low 31 bits of w_g, open_g its top bit; h_{-1} is the
+ *     channel's hold count carried from the block before: 0 after a configuration, after either squelch call, after m17hip_demod_reset and, for the listed
+ *     channels, after m17hip_demod_reset_channels; a retune keeps it.  hang counts SLOTS.  The block leaves h_{G-1} as the hold count and w_{G-1} as the
+ *     channel's state word.  J == 0: every tile of the block is open, the hold count stays and the state word is h | 1 << 31.
+ *     TILES.  TO = the tuner's outputs per workgroup: 255 under m17hip_wide_config and _config2, groups x up under m17hip_wide_resample.  Tile t holds the
+ *     outputs [t TO, min((t + 1) TO, T)) of the block's T and spans the block samples [a_t, e_t), a_t = floor(t TO W / T), e_t = floor(min((t + 1) TO, T) W / T)
+ *     of the block's W, in 64 bits.  slot(x) = 0 for x < first, else min((x - first) / (16 hop), G - 1).  Tile t is OPEN iff open_g holds for some g in
+ *     slot(a_t) .. min(slot(e_t - 1) + lead, G - 1).  `lead` opens the tiles in front of an opening WITHIN the block: it cannot reach back into the block
+ *     before, which has left the device's hands.
+ * m17cxx/detail/core.h has squelch_slots, squelch_slot_frames, squelch_slot_of, squelch_tile_span and squelch_tile_open: one text for host and device.
+ * An OPEN tile gets exactly the words the unsquelched kernel gives it from the same carry; a tile behind a closed one recomputes the z in front of its first
+ * output as every tile does, so its first output is the unsquelched word.  A CLOSED tile gets +0 for its outputs, +0 in the meter's power scratch where the
+ * meter is on, and (0, 0) as the carry where it holds output T - 1: the zero-product rule shows only at output 0 of a block whose predecessor's last tile
+ * was closed.
+ * On the device the block's spectrum goes in front of the tuner as under ABI 619; three kernels follow it (csrc/m17_squelch_kernels.hpp: the bands, a lane per
+ * channel and slot; the recurrence, a lane per channel; the tile mask, a lane per channel and 32 tiles) and the tuner runs in a tile-squelched
+ * instantiation.  m17hip_timing_get index 18 is the three kernels, one entry per block; m17hip_iq_bytes counts the planes, which grow with the block's shape
+ * (M17HIP_ENOMEM from the upload when they cannot be had).
+ * Arguments, limits, refusals and what turns it off are m17hip_wide_squelch's, plus lead in 0..255.  NULL / 0 levels turn the squelch off whichever mode was
+ * on; each of the two calls replaces the other's mode and starts the hold counts over. */
+int m17hip_wide_squelch_slots(m17hip_ctx* ctx, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang,
+                              uint32_t lead);
+/* The decisions of the latest block uploaded in slot mode (back = 0) or of the one before it (back = 1): state_host[c] = w_{G-1}, bands_host[c * G + g] =
+ * b_{c,g}, mask_host[c * ceil(tiles / 32) + (t >> 5)] bit t & 31 = tile t open; *channels, *slots = G, *tiles and *frames = J (each may be NULL).  Two plane
+ * sets and two events take turns.  It waits for that block's squelch kernels only and copies on the fetch stream.  M17HIP_ESTATE if no such plane exists
+ * (as m17hip_wide_squelch_fetch, or the block mode is on; m17hip_wide_squelch_fetch returns it under slot mode).  M17HIP_EINVAL for back > 1, a NULL
+ * context, state_host, bands_host or mask_host, cap_channels < C, cap_bands < C G or cap_mask_words < C ceil(tiles / 32); nothing is written then. */
+int m17hip_wide_squelch_slots_fetch(m17hip_ctx* ctx, uint32_t back, uint32_t* state_host, float* bands_host, uint32_t* mask_host, uint64_t cap_channels,
+                                    uint64_t cap_bands, uint64_t cap_mask_words, uint32_t* channels, uint32_t* slots, uint32_t* tiles, uint32_t* frames);
 
 /* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
  * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
@@ -1118,7 +1157,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * entry per surveyed block), 13 = resample (the resampling tuner of m17hip_upload_wide* under m17hip_wide_resample: one launch per wideband block), 14 = spectrum (the two
  * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block),
  * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index),
- * 17 = squelch (wide_squelch_kernel of m17hip_wide_squelch, one entry per squelched block; its spectrum and its tuner keep their own indices). */
+ * 17 = squelch (wide_squelch_kernel of m17hip_wide_squelch, one entry per squelched block; its spectrum and its tuner keep their own indices),
+ * 18 = squelch_slots (the three kernels of m17hip_wide_squelch_slots, one entry per squelched block; likewise). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void resample_kernel(const IQT* __res
     const uint64_t wg = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const uint32_t c = (uint32_t)(wg % gridDim.y), g0 = (uint32_t)(wg / gridDim.y) * G;
     if constexpr (SQUELCH) {
-        if (squelch_closed(c, pw...)) {
+        if (squelch_closed(c, (uint32_t)(wg / gridDim.y), pw...)) {
             squelch_zero(c, g0 * U, (T / U - g0 < G ? T / U : g0 + G) * U, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
             return;
         }

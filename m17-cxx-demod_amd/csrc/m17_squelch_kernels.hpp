@@ -33,4 +33,69 @@ __global__ __launch_bounds__(SQUELCH_THREADS) void wide_squelch_kernel(const flo
     band[c] = b;
 }
 
+// ---- the time-resolved squelch (m17hip_wide_squelch_slots): a decision per SLOT — a group of core::CHAN_SURVEY_GROUP frames, whose sums spectrum_kernel has
+// left in its scratch[S][G][N] — and a skip per TILE of the tuner's outputs.  Three kernels on the block's stream behind spectrum_kernel; the words are
+// core::squelch_slot_frames, squelch_slot_of, squelch_tile_span and squelch_tile_open's beside the four above.  Vector stores only, no atomics.
+__host__ __device__ inline uint32_t squelch_slot_words(uint32_t G) { return G ? (G + 31u) / 32u : 1u; }   // words of a channel's slot flags
+__host__ __device__ inline uint32_t squelch_tile_words(uint32_t tiles) { return (tiles + 31u) / 32u; }   // words of a channel's tile mask (tiles >= 1)
+
+// 1. A lane per (channel, slot): band[c][g] = the band of scratch[source][g] around the channel's bin.  G >= 1.
+__global__ __launch_bounds__(SQUELCH_THREADS) void squelch_slots_band_kernel(const float* __restrict__ scratch, uint32_t logn, uint32_t G,
+                                                                             const uint32_t* __restrict__ table, uint32_t maxC, uint32_t B,
+                                                                             float* __restrict__ band, uint32_t C)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * SQUELCH_THREADS + threadIdx.x;
+    if (i >= (uint64_t)C * G) return;
+    const uint32_t c = (uint32_t)(i / G), g = (uint32_t)(i % G);
+    const uint32_t s = table[c], N = 1u << logn;
+    const uint32_t k = core::squelch_bin((int32_t)table[maxC + c], logn);
+    band[i] = core::squelch_band(scratch + (((size_t)s * G + g) << logn), N, k, B);
+}
+
+// 2. A lane per channel: the recurrence over the block's slots from hold[c].  Writes hold[c], state[c] = the last slot's word (h | open << 31 where the block
+// has no slot) and the slots' open flags, bits[c][squelch_slot_words(G)], bit g & 31 of word g >> 5.
+__global__ __launch_bounds__(SQUELCH_THREADS) void squelch_slots_step_kernel(const float* __restrict__ band, uint32_t G, uint32_t J,
+                                                                             const uint32_t* __restrict__ table, const float* __restrict__ levels, uint32_t S,
+                                                                             uint32_t hang, uint32_t* __restrict__ hold, uint32_t* __restrict__ state,
+                                                                             uint32_t* __restrict__ bits, uint32_t C)
+{
+    const uint32_t c = blockIdx.x * SQUELCH_THREADS + threadIdx.x;
+    if (c >= C) return;
+    const uint32_t s = table[c], SW = squelch_slot_words(G);
+    const float lo = levels[s], lc = levels[S + s];
+    uint32_t word = core::squelch_step(hold[c], 0.0f, 0.0f, 0.0f, hang, 0);   // (G == 0: open, the count as it is)
+    uint32_t h = word & ~core::SQUELCH_OPEN, acc = 0;
+    const float* b = band + (size_t)c * G;
+    uint32_t* o = bits + (size_t)c * SW;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t Jg = core::squelch_slot_frames(J, g);
+        word = core::squelch_step(h, b[g], core::squelch_level(lo, Jg), core::squelch_level(lc, Jg), hang, Jg);
+        h = word & ~core::SQUELCH_OPEN;
+        acc |= (word >> 31) << (g & 31u);
+        if ((g & 31u) == 31u) { o[g >> 5] = acc; acc = 0; }
+    }
+    if (G == 0 || (G & 31u)) o[G >> 5] = acc;
+    hold[c] = h;
+    state[c] = word;
+}
+
+// 3. A lane per (channel, word of 32 tiles): mask[c][MW], bit t & 31 of word t >> 5 set where tile t of TO outputs (of T, made from W block samples) is
+// tuned; the bits beyond the block's last tile are 0.
+__global__ __launch_bounds__(SQUELCH_THREADS) void squelch_slots_tile_kernel(const uint32_t* __restrict__ bits, uint32_t G, uint32_t first, uint32_t hop,
+                                                                             uint32_t lead, uint32_t TO, uint32_t T, uint32_t W, uint32_t tiles, uint32_t MW,
+                                                                             uint32_t* __restrict__ mask, uint32_t C)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * SQUELCH_THREADS + threadIdx.x;
+    if (i >= (uint64_t)C * MW) return;
+    const uint32_t c = (uint32_t)(i / MW), m = (uint32_t)(i % MW);
+    const uint32_t* o = bits + (size_t)c * squelch_slot_words(G);
+    uint32_t word = 0;
+    for (uint32_t j = 0; j < 32u && m * 32u + j < tiles; ++j) {
+        uint32_t a, e;
+        core::squelch_tile_span(m * 32u + j, TO, T, W, a, e);
+        word |= (core::squelch_tile_open(o, G, first, hop, lead, a, e) ? 1u : 0u) << j;
+    }
+    mask[i] = word;
+}
+
 }  // namespace m17

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune2_kernel(const IQT* __restri
     const uint64_t wg = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const uint32_t c = (uint32_t)(wg % gridDim.y), n0 = (uint32_t)(wg / gridDim.y) * WIDE_TILE;
     if constexpr (SQUELCH) {
-        if (squelch_closed(c, pw...)) {
+        if (squelch_closed(c, (uint32_t)(wg / gridDim.y), pw...)) {
             squelch_zero(c, n0, T - n0 < (uint32_t)WIDE_TILE ? T : n0 + WIDE_TILE, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
             return;
         }

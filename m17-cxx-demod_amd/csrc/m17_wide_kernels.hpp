@@ -29,12 +29,19 @@ __host__ __device__ inline size_t wide_lds_bytes(uint32_t L, uint32_t R) { retur
 // What a squelched launch of a tuner takes as its last argument (m17hip_wide_squelch; csrc/m17_squelch_kernels.hpp): the block's state words, [channels] of
 // h' | open << 31.
 struct SquelchIn { const uint32_t* state; };
-__device__ __forceinline__ bool squelch_closed(uint32_t c, SquelchIn q) { return !(q.state[c] & core::SQUELCH_OPEN); }
-__device__ __forceinline__ bool squelch_closed(uint32_t c, MeterOut, SquelchIn q) { return squelch_closed(c, q); }
+// A tile-squelched launch (m17hip_wide_squelch_slots) takes the block's tile mask instead: [channels][words], bit t & 31 of word t >> 5 set where the
+// channel's tile t is tuned.  SQUELCH stays one template flag: the type of the trailing argument says which decision a workgroup reads.
+struct SquelchTilesIn { const uint32_t* mask; uint32_t words; };
+__device__ __forceinline__ bool squelch_closed(uint32_t c, uint32_t, SquelchIn q) { return !(q.state[c] & core::SQUELCH_OPEN); }
+__device__ __forceinline__ bool squelch_closed(uint32_t c, uint32_t tile, SquelchTilesIn q) { return !((q.mask[(size_t)c * q.words + (tile >> 5)] >> (tile & 31u)) & 1u); }
+template <typename Q> __device__ __forceinline__ bool squelch_closed(uint32_t c, uint32_t tile, MeterOut, Q q) { return squelch_closed(c, tile, q); }
 // (the metered and squelched instantiations carry both: the power goes where the meter's argument says)
 __device__ __forceinline__ void meter_put(uint32_t c, uint32_t n, float2 z, MeterOut m, SquelchIn) { meter_put(c, n, z, m); }
+__device__ __forceinline__ void meter_put(uint32_t c, uint32_t n, float2 z, MeterOut m, SquelchTilesIn) { meter_put(c, n, z, m); }
 __device__ __forceinline__ void squelch_power(uint32_t, uint32_t, SquelchIn) {}
+__device__ __forceinline__ void squelch_power(uint32_t, uint32_t, SquelchTilesIn) {}
 __device__ __forceinline__ void squelch_power(uint32_t c, uint32_t n, MeterOut m, SquelchIn) { m.p[(size_t)c * m.pitch + n] = 0.0f; }
+__device__ __forceinline__ void squelch_power(uint32_t c, uint32_t n, MeterOut m, SquelchTilesIn) { m.p[(size_t)c * m.pitch + n] = 0.0f; }
 
 // A closed channel's workgroup: the outputs n0 .. n1 - 1 of the block (n1 <= T) get +0, the meter's power scratch likewise where there is one, and the
 // workgroup that holds output T - 1 leaves (0, 0) as the channel's carry.  No LDS, no barrier.
@@ -63,7 +70,8 @@ __device__ __forceinline__ void squelch_zero(uint32_t c, uint32_t n0, uint32_t n
 // METER (m17hip_wide_meter is on): the launch has one more argument, a MeterOut, and every output's chan_power(z) goes to it beside the output's y.
 // SQUELCH (m17hip_wide_squelch is on): the launch's last argument is a SquelchIn, and the workgroups of a channel whose state word says closed store +0 for
 // their tile's outputs (and powers), (0, 0) for the carry where they hold output T - 1, and return — before any LDS traffic, barrier or mixing.  The flag is
-// the channel's, so the return is uniform for the workgroup.
+// the channel's, so the return is uniform for the workgroup.  Under m17hip_wide_squelch_slots the last argument is a SquelchTilesIn instead and the flag is
+// the (channel, tile)'s — the workgroup's own bit of the block's tile mask —, read in the same place: SQUELCH stays one flag.
 template <typename IQT, bool METER = false, bool SQUELCH = false, typename... PW>
 __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restrict__ src, size_t spitch, uint32_t W, const float2* __restrict__ hist,
                                                             const float* __restrict__ taps, uint32_t L, uint32_t R, const uint32_t* __restrict__ table,
@@ -74,7 +82,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void tune_kernel(const IQT* __restric
     const uint32_t c = blockIdx.y, lane = threadIdx.x;
     const uint32_t n0 = blockIdx.x * WIDE_TILE;
     if constexpr (SQUELCH) {
-        if (squelch_closed(c, pw...)) {
+        if (squelch_closed(c, blockIdx.x, pw...)) {
             squelch_zero(c, n0, T - n0 < (uint32_t)WIDE_TILE ? T : n0 + WIDE_TILE, T, dst + (size_t)c * dpitch + XPRE, znew, pw...);
             return;
         }

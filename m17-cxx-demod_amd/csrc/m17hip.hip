@@ -41,7 +41,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_SQUELCH_SLOTS, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -438,6 +438,15 @@ struct m17hip_ctx {
             uint32_t C[2] = {0, 0}, frames[2] = {0, 0};
             int latest = 0;
             hipStream_t fetch = nullptr;   // m17hip_wide_squelch_fetch's copies: a stream of its own, behind nothing but the plane's event
+            // The time-resolved mode (m17hip_wide_squelch_slots; `slots`, exclusive with the block mode above): hold, state, levels, events and the fetch
+            // stream serve as they do there.  Of its own: the slots' open flags of the block being queued (read by its tile kernel alone, on the same
+            // stream), and two band planes [C][G] and two tile masks [C][ceil(tiles / 32)] that take turns with the state planes and grow with the
+            // block's shape; the block's tuner reads its own mask.
+            bool slots = false;
+            uint32_t lead = 0;
+            DevBuf<uint32_t> sbits, mask[2];
+            DevBuf<float> sband[2];
+            uint32_t G[2] = {0, 0}, tiles[2] = {0, 0};
             void forget() { valid[0] = valid[1] = false; }
             ~Squelch() { if (fetch) (void)hipStreamDestroy(fetch); }
         } sq;
@@ -446,7 +455,8 @@ struct m17hip_ctx {
             return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size() + sp.scratch.size() + sp.plane[0].size() +
                     sp.plane[1].size() + mt.scratch.size() + mt.plane[0].size() + mt.plane[1].size()) * sizeof(float) +
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4 +
-                   (sq.dev.words() + sq.hold.size() + sq.state[0].size() + sq.state[1].size() + sq.band[0].size() + sq.band[1].size()) * 4;
+                   (sq.dev.words() + sq.hold.size() + sq.state[0].size() + sq.state[1].size() + sq.band[0].size() + sq.band[1].size() +
+                    sq.sbits.size() + sq.mask[0].size() + sq.mask[1].size() + sq.sband[0].size() + sq.sband[1].size()) * 4;
         }
     } wide;
     // THE WIDEBAND SIGNAL GENERATOR (m17hip_synth_wide_config, m17hip_synth_wide; csrc/m17_wide_tx_kernels.hpp): the int16 input slab's rows FM-modulated into
@@ -1295,7 +1305,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 619; }
+int m17hip_version(void) { return 620; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1926,6 +1936,63 @@ static int launch_squelch(m17hip_ctx* c, uint32_t C, hipStream_t st)
     sq.C[p] = C; sq.frames[p] = w.sp.frames[ps]; sq.valid[p] = true; sq.latest = p;
     return M17HIP_OK;
 }
+// The time-resolved squelch of one block (m17hip_wide_squelch_slots is on), in launch_squelch's place: it reads the group sums spectrum_kernel has just left
+// in the spectrum's scratch — the next writer of that scratch is the next block's spectrum_kernel, behind this stream through ev_iq, and a regrowth waits
+// for ev_iq first —, the channel table and the levels, steps the hold counts through the block's slots and writes the band plane, the state plane and the
+// tile mask whose turn it is.  TO: the outputs of a tile of the tuner that follows; tiles: their number.
+static int launch_squelch_slots(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t W, uint32_t TO, uint32_t tiles, hipStream_t st)
+{
+    auto& w = c->wide;
+    auto& sq = w.sq;
+    const int p = sq.latest ^ 1;
+    uint32_t first, J;
+    core::spec_frames(w.count, W, w.sp.points, w.sp.hop, first, J);   // (what launch_spectrum has just transformed)
+    const uint32_t G = core::squelch_slots(J), SW = squelch_slot_words(G), MW = squelch_tile_words(tiles);
+    int r;
+    if (!sq.fetch) HIPCHK(c, hipStreamCreateWithFlags(&sq.fetch, hipStreamNonBlocking));
+    for (auto& e : sq.ev) if (!e) HIPCHK(c, e.create());
+    if (!sq.hold) {   // ([maxC] each, once per configuration: never regrown)
+        if ((r = alloc_code(c, sq.hold.alloc(c->maxC)))) return r;
+        for (auto& b : sq.state) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
+        for (auto& b : sq.band) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
+        sq.fresh = true;
+    }
+    sq.valid[p] = false;
+    if (sq.sbits.size() < (size_t)C * SW || sq.sband[p].size() < (size_t)C * G || sq.mask[p].size() < (size_t)C * MW) {   // (the block's shape has grown)
+        HIPCHK(c, hipEventSynchronize(c->ev_iq));   // (the last reader of these — the tuner two blocks back, the tile kernel of the block before — is in front of that)
+        if ((r = alloc_code(c, sq.sbits.grow((size_t)C * SW, &c->last_hip)))) return r;
+        if ((r = alloc_code(c, sq.sband[p].grow((size_t)C * G, &c->last_hip)))) return r;
+        if ((r = alloc_code(c, sq.mask[p].grow((size_t)C * MW, &c->last_hip)))) return r;
+    }
+    if (sq.dirty || !sq.dev.live()) {   // the levels, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, sq.dev.begin_write(2 * 256, &staging));
+        std::memcpy(staging, sq.levels.data(), sq.levels.size() * 4);
+        HIPCHK(c, sq.dev.publish(sq.levels.size(), st));
+        sq.dirty = false;
+    }
+    HIPCHK(c, sq.dev.before_read(st));
+    if (sq.fresh) HIPCHK(c, hipMemsetAsync(sq.hold.get(), 0, (size_t)c->maxC * sizeof(uint32_t), st));   // (as launch_squelch does)
+    {
+        Timed tm(c, KT_SQUELCH_SLOTS, st);
+        if (G) {
+            hipLaunchKernelGGL(squelch_slots_band_kernel, dim3((uint32_t)(((uint64_t)C * G + SQUELCH_THREADS - 1) / SQUELCH_THREADS)), dim3(SQUELCH_THREADS), 0, st,
+                               w.sp.scratch.get(), w.sp.logn, G, w.dev.dev(), c->maxC, sq.B, sq.sband[p].get(), C);
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(squelch_slots_step_kernel, dim3((C + SQUELCH_THREADS - 1) / SQUELCH_THREADS), dim3(SQUELCH_THREADS), 0, st, sq.sband[p].get(), G, J,
+                           w.dev.dev(), reinterpret_cast<const float*>(sq.dev.dev()), w.S, sq.hang, sq.hold.get(), sq.state[p].get(), sq.sbits.get(), C);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(squelch_slots_tile_kernel, dim3((uint32_t)(((uint64_t)C * MW + SQUELCH_THREADS - 1) / SQUELCH_THREADS)), dim3(SQUELCH_THREADS), 0, st,
+                           sq.sbits.get(), G, first, w.sp.hop, sq.lead, TO, T, W, tiles, MW, sq.mask[p].get(), C);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    HIPCHK(c, hipEventRecord(sq.ev[p], st));
+    sq.fresh = false;
+    sq.C[p] = C; sq.frames[p] = J; sq.G[p] = G; sq.tiles[p] = tiles; sq.valid[p] = true; sq.latest = p;
+    return M17HIP_OK;
+}
 template <typename IQT>
 static int wide_after_block(m17hip_ctx* c, const IQT* src, size_t pitch, uint32_t W, uint32_t T, uint32_t H, uint32_t C, const float* x, hipStream_t st)
 {
@@ -1963,16 +2030,28 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
     const MeterOut mo{w.mt.scratch.get(), (size_t)T};
     // The squelched instantiations (m17hip_wide_squelch): the block's spectrum and the squelch kernel go IN FRONT of the tuner on its stream, and the tuner's
     // last argument is the state plane that kernel has written.  With the squelch off nothing moves: the spectrum follows in wide_after_block.
-    const bool squelch = w.sq.on;
-    if (squelch) {
+    // The tile-squelched instantiations (m17hip_wide_squelch_slots) take the block's tile mask in the state plane's place; everything else is the same.
+    const bool slots = w.sq.on && w.sq.slots, squelch = w.sq.on && !slots;
+    const uint32_t RG = w.U ? resample_groups(w.L, w.R, w.L2, w.U, w.D) : 0;
+    const uint32_t tiles = w.U ? (T / w.U + RG - 1) / RG : (T + WIDE_TILE - 1) / WIDE_TILE;
+    if (squelch || slots) {
         if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;
-        if (int r = launch_squelch(c, C, st)) return r;
+        if (int r = slots ? launch_squelch_slots(c, C, T, W, w.U ? RG * w.U : (uint32_t)WIDE_TILE, tiles, st) : launch_squelch(c, C, st)) return r;
     }
     const SquelchIn qi{squelch ? w.sq.state[w.sq.latest].get() : nullptr};
+    const SquelchTilesIn ti{slots ? w.sq.mask[w.sq.latest].get() : nullptr, squelch_tile_words(tiles)};
     if (w.U) {
-        const uint32_t G = resample_groups(w.L, w.R, w.L2, w.U, w.D), Q = resample_q(w.L, w.R, w.L2, w.U, w.D, G);
+        const uint32_t G = RG, Q = resample_q(w.L, w.R, w.L2, w.U, w.D, G);
         TimedK tm(c, KT_RESAMPLE);
-        if (squelch && meter)
+        if (slots && meter)
+            tm.launch(resample_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
+                      resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
+                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
+        else if (slots)
+            tm.launch(resample_kernel<IQT, false, true, SquelchTilesIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
+                      resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
+                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
+        else if (squelch && meter)
             tm.launch(resample_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
                       resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
                       w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
@@ -1990,7 +2069,15 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
                   c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else if (w.R2) {
         TimedK tm(c, KT_WIDE2);
-        if (squelch && meter)
+        if (slots && meter)
+            tm.launch(tune2_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
+                      wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
+                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
+        else if (slots)
+            tm.launch(tune2_kernel<IQT, false, true, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
+                      wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
+                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
+        else if (squelch && meter)
             tm.launch(tune2_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
                       wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
                       wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
@@ -2008,7 +2095,15 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
                   (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else {
         TimedK tm(c, KT_WIDE);
-        if (squelch && meter)
+        if (slots && meter)
+            tm.launch(tune_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st,
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      w.znew.get(), gain, mo, ti);
+        else if (slots)
+            tm.launch(tune_kernel<IQT, false, true, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src,
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      w.znew.get(), gain, ti);
+        else if (squelch && meter)
             tm.launch(tune_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st,
                       src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
                       w.znew.get(), gain, mo, qi);
@@ -2193,6 +2288,9 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.sq.hold.release(&c->last_hip);
     for (auto& b : w.sq.state) b.release(&c->last_hip);
     for (auto& b : w.sq.band) b.release(&c->last_hip);
+    w.sq.sbits.release(&c->last_hip);
+    for (auto& b : w.sq.mask) b.release(&c->last_hip);
+    for (auto& b : w.sq.sband) b.release(&c->last_hip);
     w.mt.window = 0; w.mt.forget(); w.mt.outputs = 0;   // (the meter likewise: a new feed)
     w.mt.scratch.release(&c->last_hip);
     for (auto& b : w.mt.plane) b.release(&c->last_hip);
@@ -2496,14 +2594,16 @@ int m17hip_wide_meter_fetch(m17hip_ctx* c, uint32_t back, float* planes_host, ui
     return M17HIP_OK;
 }
 // ---- the spectrum squelch (ABI 619): the three tuners skip the channels whose band of the block's spectrum holds no carrier ----------------------------
-int m17hip_wide_squelch(m17hip_ctx* c, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang)
+// Both modes' call: `slots` says which one the levels turn on (m17hip_wide_squelch: hang in blocks, lead 0; m17hip_wide_squelch_slots: hang in slots).
+static int squelch_set(m17hip_ctx* c, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang, bool slots,
+                       uint32_t lead)
 {
     if (!c) return M17HIP_EINVAL;
     auto& w = c->wide;
     auto& sq = w.sq;
     const bool off = !open_level && nlevels == 0;
     if (!off) {
-        if (!open_level || !close_level || nlevels < 1 || nlevels > 256 || half_bins > 64 || hang > 65535) return M17HIP_EINVAL;
+        if (!open_level || !close_level || nlevels < 1 || nlevels > 256 || half_bins > 64 || hang > 65535 || lead > 255) return M17HIP_EINVAL;
         for (uint32_t s = 0; s < nlevels; ++s)
             if (!std::isfinite(open_level[s]) || !std::isfinite(close_level[s]) || !(close_level[s] > 0.0f) || !(close_level[s] <= open_level[s])) return M17HIP_EINVAL;
     }
@@ -2516,17 +2616,48 @@ int m17hip_wide_squelch(m17hip_ctx* c, uint32_t half_bins, const float* open_lev
     sq.fresh = true;
     sq.on = !off;
     if (off) return M17HIP_OK;
-    sq.B = half_bins; sq.hang = hang;
+    sq.B = half_bins; sq.hang = hang; sq.slots = slots; sq.lead = lead;
     sq.levels.assign(open_level, open_level + nlevels);
     sq.levels.insert(sq.levels.end(), close_level, close_level + nlevels);
     sq.dirty = true;
+    return M17HIP_OK;
+}
+int m17hip_wide_squelch(m17hip_ctx* c, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang)
+{
+    return squelch_set(c, half_bins, open_level, close_level, nlevels, hang, false, 0);
+}
+// ---- the time-resolved squelch (ABI 620): a decision per slot of 16 frames, a skip per tile of the tuner's outputs --------------------------------------
+int m17hip_wide_squelch_slots(m17hip_ctx* c, uint32_t half_bins, const float* open_level, const float* close_level, uint32_t nlevels, uint32_t hang, uint32_t lead)
+{
+    return squelch_set(c, half_bins, open_level, close_level, nlevels, hang, true, lead);
+}
+int m17hip_wide_squelch_slots_fetch(m17hip_ctx* c, uint32_t back, uint32_t* state_host, float* bands_host, uint32_t* mask_host, uint64_t cap_channels,
+                                    uint64_t cap_bands, uint64_t cap_mask_words, uint32_t* channels, uint32_t* slots, uint32_t* tiles, uint32_t* frames)
+{
+    if (!c || back > 1 || !state_host || !bands_host || !mask_host) return M17HIP_EINVAL;
+    auto& sq = c->wide.sq;
+    if (!c->wide.S || !sq.on || !sq.slots) return M17HIP_ESTATE;
+    const int p = sq.latest ^ (int)back;
+    if (!sq.valid[p]) return M17HIP_ESTATE;
+    const size_t n = sq.C[p], nb = n * sq.G[p], nm = n * squelch_tile_words(sq.tiles[p]);
+    if (cap_channels < n || cap_bands < nb || cap_mask_words < nm) return M17HIP_EINVAL;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sq.ev[p]));   // (that block's squelch kernels and what its stream held in front of them: not its tuner, no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(state_host, sq.state[p].get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, sq.fetch));
+    if (nb) HIPCHK(c, hipMemcpyAsync(bands_host, sq.sband[p].get(), nb * sizeof(float), hipMemcpyDeviceToHost, sq.fetch));
+    HIPCHK(c, hipMemcpyAsync(mask_host, sq.mask[p].get(), nm * sizeof(uint32_t), hipMemcpyDeviceToHost, sq.fetch));
+    HIPCHK(c, hipStreamSynchronize(sq.fetch));
+    if (channels) *channels = (uint32_t)n;
+    if (slots) *slots = sq.G[p];
+    if (tiles) *tiles = sq.tiles[p];
+    if (frames) *frames = sq.frames[p];
     return M17HIP_OK;
 }
 int m17hip_wide_squelch_fetch(m17hip_ctx* c, uint32_t back, uint32_t* state_host, float* band_host, uint64_t capacity, uint32_t* channels, uint32_t* frames)
 {
     if (!c || back > 1 || !state_host || !band_host) return M17HIP_EINVAL;
     auto& sq = c->wide.sq;
-    if (!c->wide.S || !sq.on) return M17HIP_ESTATE;
+    if (!c->wide.S || !sq.on || sq.slots) return M17HIP_ESTATE;   // (the slot mode's planes are m17hip_wide_squelch_slots_fetch's)
     const int p = sq.latest ^ (int)back;
     if (!sq.valid[p]) return M17HIP_ESTATE;
     const size_t n = sq.C[p];

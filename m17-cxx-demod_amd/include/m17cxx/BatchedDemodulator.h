@@ -170,6 +170,36 @@ public:
         state.resize(n);
         band.resize(n);
     }
+    // The time-resolved mode of the squelch (m17hip_wide_squelch_slots), exclusive with wide_squelch's: a decision per slot of 16 frames of the block's
+    // spectrum, `hang` in slots, and the tuners skip per tile of outputs; `lead` (0..255) opens the tiles in front of an opening within the block.
+    // wide_squelch_off turns either mode off.  wide_squelch_slots_fetch: per channel the state word behind the block, the slots' band powers [channels][slots]
+    // and the tile mask [channels][ceil(tiles / 32)] of the latest such block (back = 0) or the one before; it waits for that block's squelch kernels only.
+    // The planes' sizes are the block's: the vectors are grown while the library refuses their capacity.
+    void wide_squelch_slots(uint32_t half_bins, const std::vector<float>& open_level, const std::vector<float>& close_level, uint32_t hang = 0, uint32_t lead = 0)
+    {
+        if (open_level.size() != close_level.size()) throw std::invalid_argument("wide_squelch_slots: one open and one close level per source");
+        check(m17hip_wide_squelch_slots(ctx_, half_bins, open_level.data(), close_level.data(), (uint32_t)open_level.size(), hang, lead), "m17hip_wide_squelch_slots");
+    }
+    void wide_squelch_slots_fetch(uint32_t back, std::vector<uint32_t>& state, std::vector<float>& bands, std::vector<uint32_t>& mask, uint32_t* slots = nullptr,
+                                  uint32_t* tiles = nullptr, uint32_t* frames = nullptr)
+    {
+        state.resize(channels_);
+        uint32_t n = 0, g = 0, t = 0, j = 0;
+        int rc = M17HIP_EINVAL;
+        for (size_t per = 64; per <= ((size_t)1 << 22); per *= 8) {
+            bands.resize(channels_ * per);
+            mask.resize(channels_ * per);
+            rc = m17hip_wide_squelch_slots_fetch(ctx_, back, state.data(), bands.data(), mask.data(), state.size(), bands.size(), mask.size(), &n, &g, &t, &j);
+            if (rc != M17HIP_EINVAL || back > 1) break;
+        }
+        check(rc, "m17hip_wide_squelch_slots_fetch");
+        state.resize(n);
+        bands.resize((size_t)n * g);
+        mask.resize((size_t)n * ((t + 31) / 32));
+        if (slots) *slots = g;
+        if (tiles) *tiles = t;
+        if (frames) *frames = j;
+    }
     // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
     // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
     // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,

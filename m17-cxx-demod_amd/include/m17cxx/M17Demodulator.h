@@ -351,6 +351,26 @@ struct M17Demodulator
         gpu_->wide_squelch_off();
         squelch_half_ = half_bins; squelch_open_db_ = open_db; squelch_close_db_ = close_db; squelch_hang_ = hang;
         squelch_report_ = std::move(report);
+        squelch_slots_ = false;
+        squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
+        return true;
+    }
+    // The time-resolved mode of the same (m17hip_wide_squelch_slots), in wide_squelch's place: armed and levelled in the same way, but the decision is taken per
+    // slot of 16 frames of the block's spectrum (`hang` counts slots) and the tuner skips per tile of its outputs; `lead` opens the tiles in front of an
+    // opening within the block, so a transmission that begins inside a block keeps its start.  After each squelched block `report`, if any, gets the tiles
+    // tuned, the block's tiles, its slots and its frames.
+    using squelch_slots_callback_t = std::function<void(uint32_t open_tiles, uint32_t tiles, uint32_t slots, uint32_t frames)>;
+    bool wide_squelch_slots(uint32_t half_bins, double open_db, double close_db, uint32_t hang = 0, uint32_t lead = 0, squelch_slots_callback_t report = {})
+    {
+        if (!gpu_) return false;
+        if (!wide_decim_ || raster_m_ || !spectrum_points_) throw std::logic_error("M17Demodulator::wide_squelch_slots needs wide_config or wide_rate, and wide_spectrum");
+        if (half_bins > 64 || half_bins >= spectrum_points_ / 2 || hang > 65535 || lead > 255 || !(close_db <= open_db))
+            throw std::invalid_argument("M17Demodulator::wide_squelch_slots");
+        flush();
+        gpu_->wide_squelch_off();
+        squelch_half_ = half_bins; squelch_open_db_ = open_db; squelch_close_db_ = close_db; squelch_hang_ = hang; squelch_lead_ = lead;
+        squelch_slots_report_ = std::move(report);
+        squelch_slots_ = true;
         squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
         return true;
     }
@@ -533,12 +553,19 @@ private:
                 const double floor = 0.5 * ((double)v[v.size() / 2 - 1] + (double)v[v.size() / 2]) * (2.0 * squelch_half_ + 1.0) / (double)frames;
                 const float open = (float)(floor * std::pow(10.0, squelch_open_db_ / 10.0)), close = (float)(floor * std::pow(10.0, squelch_close_db_ / 10.0));
                 if (std::isfinite(open) && close > 0.0f) {   // (a plane of zeros sets nothing: the next block tries again)
-                    gpu_->wide_squelch(squelch_half_, {open}, {close}, squelch_hang_);
+                    if (squelch_slots_) gpu_->wide_squelch_slots(squelch_half_, {open}, {close}, squelch_hang_, squelch_lead_);
+                    else gpu_->wide_squelch(squelch_half_, {open}, {close}, squelch_hang_);
                     squelch_mode_ = 2;
                 }
             }
         }
-        if (squelched && squelch_report_) {   // (likewise: the fetch waits for the block's squelch kernel)
+        if (squelched && squelch_slots_ && squelch_slots_report_) {   // (likewise: the fetch waits for the block's squelch kernels)
+            uint32_t slots = 0, tiles = 0, frames = 0, open_tiles = 0;
+            gpu_->wide_squelch_slots_fetch(0, squelch_state_, squelch_band_, squelch_mask_, &slots, &tiles, &frames);
+            for (uint32_t t = 0; t < tiles; ++t) open_tiles += (squelch_mask_[t >> 5] >> (t & 31u)) & 1u;
+            squelch_slots_report_(open_tiles, tiles, slots, frames);
+        }
+        if (squelched && !squelch_slots_ && squelch_report_) {   // (likewise: the fetch waits for the block's squelch kernel)
             uint32_t frames = 0;
             gpu_->wide_squelch_fetch(0, squelch_state_, squelch_band_, &frames);
             squelch_report_((squelch_state_[0] >> 31) != 0, squelch_state_[0] & 0x7FFFFFFFu, squelch_band_[0], frames);
@@ -600,7 +627,10 @@ private:
     meter_callback_t meter_report_;
     std::vector<float> meter_planes_;
     int squelch_mode_ = 0;                           // wide_squelch: 0 = off, 1 = armed (the next block's plane sets the levels), 2 = on
-    uint32_t squelch_half_ = 0, squelch_hang_ = 0;
+    bool squelch_slots_ = false;                     // wide_squelch_slots in wide_squelch's place
+    uint32_t squelch_half_ = 0, squelch_hang_ = 0, squelch_lead_ = 0;
+    squelch_slots_callback_t squelch_slots_report_;
+    std::vector<uint32_t> squelch_mask_;
     double squelch_open_db_ = 0.0, squelch_close_db_ = 0.0;
     squelch_callback_t squelch_report_;
     std::vector<uint32_t> squelch_state_;

@@ -376,6 +376,40 @@ M17_HD uint32_t squelch_step(uint32_t h, float b, float to, float tc, uint32_t h
     else hn = h > 0u ? h - 1u : 0u;
     return hn | (hn > 0u ? SQUELCH_OPEN : 0u);
 }
+// ---- a-1g: the time-resolved squelch (m17hip_wide_squelch_slots): the same four functions per SLOT of a block — a group of CHAN_SURVEY_GROUP frames of the
+// block's spectrum, whose row is the spectrum's first-level sum — and the tuners skip per TILE of outputs.  A block of J frames has squelch_slots(J) slots;
+// slot g holds squelch_slot_frames(J, g) frames and is stepped with squelch_step(h, band, level x frames, ..., hang, frames): hang counts slots.
+M17_HD uint32_t squelch_slots(uint32_t J) { return J / CHAN_SURVEY_GROUP + (J % CHAN_SURVEY_GROUP ? 1u : 0u); }
+M17_HD uint32_t squelch_slot_frames(uint32_t J, uint32_t g)   // (g < squelch_slots(J))
+{
+    return J - CHAN_SURVEY_GROUP * g < CHAN_SURVEY_GROUP ? J - CHAN_SURVEY_GROUP * g : CHAN_SURVEY_GROUP;
+}
+// the slot of block sample x (G >= 1 slots): the samples in front of the first frame belong to slot 0, those behind the last slot's span to slot G - 1
+M17_HD uint32_t squelch_slot_of(uint32_t x, uint32_t first, uint32_t hop, uint32_t G)
+{
+    if (x < first) return 0u;
+    const uint64_t g = (uint64_t)(x - first) / ((uint64_t)CHAN_SURVEY_GROUP * hop);
+    return g < G - 1u ? (uint32_t)g : G - 1u;
+}
+// the block samples [a, e) under tile t of TO outputs of a block of T outputs made from W samples: floors of 64-bit products
+M17_HD void squelch_tile_span(uint32_t t, uint32_t TO, uint32_t T, uint32_t W, uint32_t& a, uint32_t& e)
+{
+    const uint64_t n0 = (uint64_t)t * TO, n1 = n0 + TO < T ? n0 + TO : T;
+    a = (uint32_t)(n0 * W / T);
+    e = (uint32_t)(n1 * W / T);
+}
+// Whether the tile over block samples [a, e) is tuned: some slot from the one of a to the one of e - 1 plus `lead` (within the block) is open.  bits holds
+// the slots' open flags, bit g & 31 of word g >> 5.  A block without a slot (G == 0) is all open.
+M17_HD bool squelch_tile_open(const uint32_t* bits, uint32_t G, uint32_t first, uint32_t hop, uint32_t lead, uint32_t a, uint32_t e)
+{
+    if (G == 0u) return true;
+    const uint32_t g0 = squelch_slot_of(a, first, hop, G);
+    uint32_t g1 = squelch_slot_of(e > a ? e - 1u : a, first, hop, G);
+    g1 = G - 1u - g1 < lead ? G - 1u : g1 + lead;
+    for (uint32_t g = g0; g <= g1; ++g)
+        if ((bits[g >> 5] >> (g & 31u)) & 1u) return true;
+    return false;
+}
 
 // ---- t1: the wideband signal generator (m17hip_synth_wide, ABI 617): FM-modulate int16 basebands and put them at offsets into wide IQ streams -------
 // No reference file: the reference's users attach an FM exciter behind its modulator.  Written here, once, so that the kernels and the host form give the

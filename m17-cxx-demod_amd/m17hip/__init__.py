@@ -30,7 +30,8 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
-           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16, "squelch": 17}
+           "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16, "squelch": 17,
+           "squelch_slots": 18}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -79,7 +80,7 @@ EXPORTS = [
     "m17hip_wide_resample_default_taps", "m17hip_wide_resample_ratio", "m17hip_wide_resample",
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
     "m17hip_wide_meter", "m17hip_wide_meter_shape", "m17hip_wide_meter_fetch",
-    "m17hip_wide_squelch", "m17hip_wide_squelch_fetch",
+    "m17hip_wide_squelch", "m17hip_wide_squelch_fetch", "m17hip_wide_squelch_slots", "m17hip_wide_squelch_slots_fetch",
     "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
@@ -715,6 +716,45 @@ class Context:
         self._chk(self.lib.m17hip_wide_squelch_fetch(self.h, C.c_uint32(back), _ptr(state), _ptr(band), C.c_uint64(cap), C.byref(n), C.byref(frames)))
         state, band = state[: n.value], band[: n.value].copy()
         return (state >> 31).astype(bool), state & np.uint32(0x7FFFFFFF), band, int(frames.value)
+
+    def wide_squelch_slots(self, half_bins, open_level, close_level=None, hang=0, lead=0):
+        """The time-resolved mode of the squelch, exclusive with wide_squelch's: the decision is taken per SLOT of a block — 16 frames of its spectrum — with
+        `hang` counted in slots, and the tuners skip per TILE of outputs (255, or groups x up under wide_resample); `lead` (0..255) opens the tiles in front
+        of an opening within the block.  Levels as wide_squelch's (wide_squelch_levels serves: they are per frame); open_level None turns the squelch off
+        whichever mode was on — m17hip_wide_squelch_slots."""
+        if open_level is None:
+            self._chk(self.lib.m17hip_wide_squelch_slots(self.h, C.c_uint32(0), None, None, C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)))
+            return
+        S = getattr(self, "_wide", (0,))[0]
+        o = np.asarray(open_level, dtype=np.float32).reshape(-1)
+        cl = o if close_level is None else np.asarray(close_level, dtype=np.float32).reshape(-1)
+        o = np.ascontiguousarray(np.repeat(o, S) if o.size == 1 and S > 1 else o)
+        cl = np.ascontiguousarray(np.repeat(cl, S) if cl.size == 1 and S > 1 else cl)
+        if o.size != cl.size:
+            raise ValueError("one open and one close level per source")
+        self._chk(self.lib.m17hip_wide_squelch_slots(self.h, C.c_uint32(half_bins), _ptr(o), _ptr(cl), C.c_uint32(o.size), C.c_uint32(hang), C.c_uint32(lead)))
+
+    def wide_squelch_slots_fetch(self, back=0):
+        """(state uint32 [C], bands float32 [C][G], mask uint32 [C][ceil(tiles / 32)], tiles, frames) of the latest block uploaded in slot mode (back = 0) or the
+        one before it (back = 1): the channels' state words behind the block (hold | open << 31 of the last slot), the band power of every slot, the tile
+        mask the tuner read (bit t & 31 of word t >> 5 set: tile t tuned) and the block's tile and frame counts.  Waits for that block's squelch kernels only —
+        m17hip_wide_squelch_slots_fetch.  The plane sizes are the block's, so the call is repeated with larger buffers while the library refuses them."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_squelch_slots_fetch: back is 0 or 1")
+        cap = max(self.max_channels, 1)
+        per = 64
+        while True:
+            state, bands, mask = np.zeros(cap, dtype=np.uint32), np.zeros(cap * per, dtype=np.float32), np.zeros(cap * per, dtype=np.uint32)
+            n, g, t, frames = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+            rc = self.lib.m17hip_wide_squelch_slots_fetch(self.h, C.c_uint32(back), _ptr(state), _ptr(bands), _ptr(mask), C.c_uint64(cap), C.c_uint64(cap * per),
+                                                          C.c_uint64(cap * per), C.byref(n), C.byref(g), C.byref(t), C.byref(frames))
+            if rc == -1 and per < (1 << 22):   # (M17HIP_EINVAL: the only argument that can be wrong here is a capacity)
+                per *= 8
+                continue
+            self._chk(rc)
+            break
+        c, mw = n.value, (t.value + 31) // 32
+        return (state[:c].copy(), bands[: c * g.value].reshape(c, g.value).copy(), mask[: c * mw].reshape(c, mw).copy(), int(t.value), int(frames.value))
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]] [--slots KEYED[,KEYED...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -38,7 +38,12 @@ channels (a random choice among every source's channels: the first ones of every
 measured 4 x slower per open workgroup under the two-stage tuners), one unsquelched block's plane gives the levels (m17hip.wide_squelch_levels: a 9 kHz band, open 10 dB and
 close 6 dB over the median floor), and the squelched launch — the spectrum, wide_squelch_kernel (library timer "squelch") and the squelched instantiation of
 the tuner — is timed per fraction beside the unsquelched tuner and spectrum on the same source in the same call.  Fraction 0 is a grid of all-closed
-workgroups: the floor of the design."""
+workgroups: the floor of the design.
+With --slots KEYED[,KEYED...] beside --spectrum under one of the three tuners EVERY channel has a carrier, keyed for the first KEYED (0 to 1) of each block
+over weak noise; the levels come from the plane of a block of that noise alone (10 and 6 dB over the median floor, a 9 kHz band).  Per value the same
+source is timed in the same call unsquelched (tuner and spectrum), under the block squelch (m17hip_wide_squelch: spectrum, "squelch", tuner) and under the
+slot squelch (m17hip_wide_squelch_slots at lead 1, hang 1: spectrum, "squelch_slots", tuner), with the share of tiles the slot mode left open.  KEYED 1 is
+the slot mode's overhead against the block mode's launch; KEYED 0.2 is what it is for."""
 import glob, json, os, sys, threading, time
 if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
     os.environ["GPU_MAX_HW_QUEUES"] = "16"   # (before torch initialises the HIP runtime: a context's streams must not share hardware queues)
@@ -95,6 +100,12 @@ if "--squelch" in ARGS:
     SQUELCH = [float(v) for v in ARGS[k + 1].split(",")]
     del ARGS[k:k + 2]
     assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in SQUELCH), "--squelch FRACTION (0 to 1) goes with --spectrum N --hop H and a tuner"
+SLOTS = []   # (empty: not timed)
+if "--slots" in ARGS:
+    k = ARGS.index("--slots")
+    SLOTS = [float(v) for v in ARGS[k + 1].split(",")]
+    del ARGS[k:k + 2]
+    assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in SLOTS), "--slots KEYED (0 to 1) goes with --spectrum N --hop H and a tuner"
 S = int(ARGS[0]) if len(ARGS) > 0 else 64
 PER = int(ARGS[1]) if len(ARGS) > 1 else 64
 T = int(ARGS[2]) if len(ARGS) > 2 else 48000
@@ -270,6 +281,59 @@ if SQUELCH:   # per fraction: a source with carriers on that share of the channe
                         "squelched_launch_over_unsquelched_tuner": round(sq_ / uns, 4)})
         del xs
     ctx.reset()
+slots = []
+if SLOTS:   # per keyed share: unsquelched, block squelch, slot squelch on one source whose every channel has a carrier for the first part of each block
+    assert PER * 300 + 200 <= 32767, "--slots: at most 108 channels per source (300 per carrier)"
+    half = m17hip.wide_squelch_half_bins(9000.0, 48000.0 * RATIO, SPECTRUM)
+    n64 = torch.arange(ROW, dtype=torch.float64, device='cuda')
+    quiet = torch.randint(-200, 201, (S, ROW, 2), dtype=torch.int16, device='cuda', generator=g)
+    torch.cuda.synchronize()
+    ctx.reset()
+    ctx.wide_spectrum(SPECTRUM, HOP)
+    ctx.upload_wide_device(quiet.data_ptr(), C, T, ROW)
+    power, frames, _ = ctx.wide_spectrum_fetch()
+    levels = m17hip.wide_squelch_levels(power, frames, half, 10.0, 6.0)
+    del quiet
+    for keyed in SLOTS:
+        on = int(round(keyed * ROW))
+        xs = torch.randint(-200, 201, (S, ROW, 2), dtype=torch.int16, device='cuda', generator=g)
+        for s_ in range(S):   # 300 exp(2 pi i f n / Fs) for every channel of the source over the block's first `on` samples
+            f = torch.tensor(OFFSETS[s_ * PER:(s_ + 1) * PER] / (48000.0 * RATIO), dtype=torch.float64, device='cuda')
+            for k0 in range(0, PER if on else 0, 8):
+                ph = 2.0 * np.pi * torch.remainder(f[k0:k0 + 8, None] * n64[None, :on], 1.0)
+                xs[s_, :on, 0] += torch.round(300.0 * torch.cos(ph).sum(0)).to(torch.int16)
+                xs[s_, :on, 1] += torch.round(300.0 * torch.sin(ph).sum(0)).to(torch.int16)
+        torch.cuda.synchronize()
+
+        def timed(extra):
+            ctx.upload_wide_device(xs.data_ptr(), C, T, ROW); ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
+            ctx.timing_reset()
+            for _ in range(REP):
+                ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
+            ctx.wide_spectrum_fetch()
+            return sum(ctx.timing_get(name)[0] / max(ctx.timing_get(name)[1], 1) for name in (OWN, "spectrum") + extra), ctx.timing_get(OWN)[0] / REP
+
+        ctx.reset()
+        ctx.wide_spectrum(SPECTRUM, HOP)
+        uns, uns_tuner = timed(())
+        ctx.wide_squelch(half, levels[0], levels[1], 0)
+        blk, blk_tuner = timed(("squelch",))
+        blk_open = int(ctx.wide_squelch_fetch()[0].sum())
+        ctx.wide_squelch_slots(half, levels[0], levels[1], 1, 1)
+        slt, slt_tuner = timed(("squelch_slots",))
+        state, bands, mask, tiles, frames = ctx.wide_squelch_slots_fetch()
+        open_tiles = int(sum(bin(int(w)).count("1") for w in mask.reshape(-1)))
+        kern = ctx.timing_get("squelch_slots")
+        ctx.wide_squelch(0, None)
+        ctx.wide_spectrum(0, 0)
+        slots.append({"keyed": keyed, "half_bins": half, "frames_per_block": frames, "slots_per_block": int(bands.shape[1]), "tiles_per_channel": tiles,
+                      "open_tile_share": round(open_tiles / float(tiles * C), 4), "block_mode_open_channels": blk_open,
+                      "unsquelched_tuner_ms": round(uns_tuner, 3), "unsquelched_tuner_and_spectrum_ms": round(uns, 3),
+                      "block_squelch_launch_ms": round(blk, 3), "block_squelch_tuner_ms": round(blk_tuner, 3),
+                      "slot_squelch_launch_ms": round(slt, 3), "slot_squelch_tuner_ms": round(slt_tuner, 3),
+                      "slot_kernels_ms": round(kern[0] / max(kern[1], 1), 4), "slot_over_block_launch": round(slt / blk, 4)})
+        del xs
+    ctx.reset()
 neighbour = {}
 if UP:   # tune2_kernel on the same buffer and table at decim x NEIGHBOUR: a warm-up block, then REP timed ones
     ctx.wide_config2(S, R, NEIGHBOUR, m17hip.IQ_I16)
@@ -329,6 +393,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}), **({"slots": slots} if SLOTS else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
