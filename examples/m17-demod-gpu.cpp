@@ -18,7 +18,9 @@
 // the second block on the channel is tuned only while its band stands DB dB over that floor (it stays open down to DB - 3 dB and for N more blocks), and
 // is fed zeros otherwise; each decision is printed to stderr; with --slots [--lead N] beside --squelch the decision is taken per slot of 16 frames of the
 // block's spectrum and the tuner skips per tile of its outputs (--hang then counts slots, --lead N opens the tiles up to N slots in front of an opening),
-// so a transmission that begins inside a block is kept from its start; the tiles tuned are printed per block.  One line per frame callback on
+// so a transmission that begins inside a block is kept from its start; the tiles tuned are printed per block; with --auto-floor [--rise A] [--fall A]
+// beside --squelch the floor is taken on the device from every block's own plane and tracked (towards a higher floor by A, towards a lower one by A, each
+// in (0, 1], default 1), so the first block is squelched too and a floor that moves is followed; the floor is printed in dB per block.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -117,6 +119,9 @@ int main(int argc, char** argv)
     uint32_t hang = 0;
     bool slots = false;               // (--slots: per slot and tile; --lead in slots)
     uint32_t lead = 0;
+    bool auto_floor = false;          // (--auto-floor: the floor from each block's plane, on the device; --rise and --fall track it)
+    float rise = 1.0f, fall = 1.0f;
+    bool track_given = false;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -139,9 +144,12 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--hang") && i + 1 < argc) hang = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (!std::strcmp(argv[i], "--slots")) slots = true;
         else if (!std::strcmp(argv[i], "--lead") && i + 1 < argc) { lead = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!lead) lead = ~0u; }
+        else if (!std::strcmp(argv[i], "--auto-floor")) auto_floor = true;
+        else if (!std::strcmp(argv[i], "--rise") && i + 1 < argc) { rise = std::strtof(argv[++i], nullptr); track_given = true; }
+        else if (!std::strcmp(argv[i], "--fall") && i + 1 < argc) { fall = std::strtof(argv[++i], nullptr); track_given = true; }
         else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N] [--slots [--lead N]]]] [--meter W] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N] [--slots [--lead N]] [--auto-floor [--rise A] [--fall A]]]] [--meter W] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -173,6 +181,10 @@ int main(int argc, char** argv)
     }
     if ((slots || lead) && (!squelch || !slots || (lead && lead > 255))) {
         std::fprintf(stderr, "m17-demod-gpu: --slots [--lead N (1 to 255 slots)] goes with --squelch\n");
+        return 2;
+    }
+    if ((auto_floor || track_given) && (!squelch || !auto_floor || !(rise > 0.0f) || !(rise <= 1.0f) || !(fall > 0.0f) || !(fall <= 1.0f))) {
+        std::fprintf(stderr, "m17-demod-gpu: --auto-floor [--rise A] [--fall A] (each above 0, 1 at the most) goes with --squelch\n");
         return 2;
     }
     if (spectrum || hop) {
@@ -228,7 +240,7 @@ int main(int argc, char** argv)
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --spectrum needs the GPU path (it runs on the device); no spectrum\n");
         }
-        if (squelch) {   // the first block unsquelched: its plane sets the levels
+        if (squelch) {   // the first block unsquelched: its plane sets the levels (--auto-floor: none is, the device takes every block's floor)
             const double fs = 2.0 * half_hz;
             const uint32_t h = std::min<uint32_t>((uint32_t)std::lrint(9000.0 / 2.0 / (fs / spectrum)), std::min<uint32_t>(64u, spectrum / 2 - 1));
             const bool on = slots ? demod.wide_squelch_slots(h, squelch_db, squelch_db - 3.0, hang, lead, [](uint32_t open_tiles, uint32_t tiles, uint32_t nslots, uint32_t frames) {
@@ -237,6 +249,11 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "squelch: %s, hold %u, band %.6g over %u frames\n", open ? "open" : "closed", hold, (double)band, frames);
             });
             if (!on) std::fprintf(stderr, "m17-demod-gpu: --squelch needs the GPU path (it runs on the device); no squelch\n");
+            if (on && auto_floor)   // the floor of every block on the device: the first block is squelched too
+                demod.wide_squelch_floor(squelch_db, squelch_db - 3.0, rise, fall, [](float floor, float open_level, float, uint32_t frames) {
+                    std::fprintf(stderr, "floor: %.2f dB per frame and band, open at %.2f dB, %u frames\n", 10.0 * std::log10((double)floor),
+                                 10.0 * std::log10((double)open_level), frames);
+                });
         }
         if (meter) {   // level, offset and deviation of the one channel per window of the feed (a window a block cuts comes in two pieces)
             const bool on = demod.wide_meter(meter, [](uint64_t window, uint32_t outputs, double level_db, double offset_hz, double deviation_hz) {

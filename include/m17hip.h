@@ -488,7 +488,7 @@ int m17hip_wide_meter_fetch(m17hip_ctx* ctx, uint32_t back, float* planes_host, 
  * not heard until the next block: its start is lost.  The loss is bounded by one block, so a receiver that must keep a transmission's link setup frame
  * (40 ms) uploads blocks no longer than the preamble it can count on, covers the block with frames (hop <= points), and sets the open level low enough
  * that a carrier present for one frame in J lifts the band over it: open_level * J below floor * (J - 1) + carrier.
- * Out of scope, for a later pull request: a floor estimated on the device (the median); squelch under the raster; driving the demodulator's gate-aware front
+ * Out of scope here: a floor estimated on the device (the median: m17hip_wide_squelch_floor below, ABI 621); squelch under the raster; driving the demodulator's gate-aware front
  * end or its frame cycle from the squelch; a look-back ACROSS a block boundary that re-tunes the block before an opening (within a block,
  * m17hip_wide_squelch_slots below decides per slot and has a lead); compacting the grid to open channels; AFC; tests of the squelch under deep in-flight call
  * orders beyond one staged and one in-place block. */
@@ -544,6 +544,51 @@ int m17hip_wide_squelch_slots(m17hip_ctx* ctx, uint32_t half_bins, const float* 
  * context, state_host, bands_host or mask_host, cap_channels < C, cap_bands < C G or cap_mask_words < C ceil(tiles / 32); nothing is written then. */
 int m17hip_wide_squelch_slots_fetch(m17hip_ctx* ctx, uint32_t back, uint32_t* state_host, float* bands_host, uint32_t* mask_host, uint64_t cap_channels,
                                     uint64_t cap_bands, uint64_t cap_mask_words, uint32_t* channels, uint32_t* slots, uint32_t* tiles, uint32_t* frames);
+
+/* ---- the sources' noise floor on the device: both squelch modes' levels from the block's own plane (ABI 621) ------------------------------------------
+ * Both modes above compare against levels the caller supplies, which a receiver gets by fetching a plane, taking its median on the host and calling the
+ * squelch again: a round trip, and levels that are wrong as soon as the floor moves (a rise by more than the open margin opens every channel of the source
+ * in every block; a fall loses the weak carriers).  With this mode on, a kernel in front of the squelch kernels makes the block's levels from the block's
+ * plane, so the floor applies to the very block it was measured on and no host takes part.  Per block uploaded with it on: N the spectrum's points, J the
+ * block's frames, P[s][N] the block's plane (what m17hip_wide_spectrum_fetch returns; under the slot mode the same second-level sum, not a slot's row),
+ * B = half_bins of the squelch mode that is on:
+ *     KEY.  squelch_floor_key(x) = x != x ? 0xFFFFFFFF : bits(x).  Powers are sums of chan_power from +0, so no non-NaN value has its sign bit set: ascending
+ *     key order is ascending value order, every NaN last.
+ *     MEDIAN.  med_s = the row's UPPER MEDIAN: the element whose key has rank N / 2 (0-based) among the row's N keys in ascending order; where that key is
+ *     0xFFFFFFFF, the quiet NaN 0x7FC00000.  A selection, not an average of two: every correct algorithm gives the same word.  It is deliberately NOT
+ *     np.median's mean of the two middle values in float64 (m17hip.wide_squelch_levels takes that one).  With N / 2 - 1 bins raised by carriers the median
+ *     is still a floor bin; with N / 2 or more it is a raised one.
+ *     FLOOR.  f = squelch_floor(med, B, J) = (med * (float)(2 B + 1)) / (float)J, two rounded operations, then f = f < floor_min ? floor_min : f; a NaN
+ *     stays a NaN.  Only taken for J >= 1.
+ *     TRACK.  F = the source's carried floor, a NaN in front of the first block.  squelch_track(F, f, rise, fall): F is a NaN -> f, whatever it is; else f
+ *     not finite -> F; else a = f > F ? rise : fall and a >= 1 ? f : fmaf(a, f - F, F).  A block with J == 0 leaves F as it is.
+ *     LEVELS.  open_level[s] = F' * open_ratio, close_level[s] = F' * close_ratio, one rounded multiply each; they are per frame, and squelch_level(level, J)
+ *     and squelch_level(level, J_g) of the two modes take them as they take given levels.  A NaN level opens every channel of the source (squelch_step's
+ *     comparisons are negated: the fail-open rule): the state in front of the first block with a frame.
+ * m17cxx/detail/core.h has squelch_floor_key, squelch_floor_median, squelch_floor, squelch_track and squelch_floor_level: one text for host and device.
+ * On the device squelch_floor_kernel (csrc/m17_squelch_kernels.hpp; a workgroup per source, the keys in LDS, a radix select in four 8-bit passes over an LDS
+ * histogram of integer counts) goes between the block's spectrum and the mode's kernels, which are unchanged and read the open | close rows of the floor
+ * plane in place of the table of given levels; that table is neither uploaded nor read while the mode is on and serves again when it is turned off.  The
+ * carry F[sources] is the feed's, ordered across the two streams like the hold counts, and starts over (NaN) wherever those are zeroed: after a
+ * configuration, either squelch call, this call and m17hip_demod_reset.  m17hip_demod_reset_channels zeroes the listed hold counts and leaves the floor; a
+ * retune keeps both.  m17hip_timing_get index 19 is the kernel, one entry per block; m17hip_iq_bytes counts the carry and the two floor planes.
+ * The call needs one of the two squelch modes on; half_bins, hang and lead stay that mode's and its given levels are set aside.  It holds for the blocks
+ * uploaded after it and never waits for anything in flight; it starts the hold counts and the floor over, as either squelch call does.  open_ratio == 0 &&
+ * close_ratio == 0 turns it off: the given levels serve again from the next block.  Every m17hip_wide_squelch and _squelch_slots call (they carry levels)
+ * turns it off, and so does everything that turns the squelch itself off.  m17hip.wide_squelch_ratio(dB) = 10^(dB / 10).
+ * M17HIP_EINVAL, nothing changed: a NULL context; a non-finite argument; ratios outside 0 < close_ratio <= open_ratio, the off pair excepted; rise or fall
+ * outside (0, 1]; floor_min < 0.  M17HIP_ESTATE, nothing changed: no wideband configuration; between m17hip_demod_front and its run; turning it on with no
+ * squelch mode on.
+ * OUT OF SCOPE: a floor per slot, or one that ignores bins already known to hold carriers; percentiles other than the median; per-source ratios; the
+ * carrier list (wide_spectrum_carriers) and channel assignment on the device; the raster; the demodulator's behaviour on long runs of exact zeros
+ * (NOTES.md; unchanged here); compacting the grid; AFC. */
+int m17hip_wide_squelch_floor(m17hip_ctx* ctx, float open_ratio, float close_ratio, float rise, float fall, float floor_min);
+/* The floor plane of the latest block uploaded with the mode on (back = 0) or of the one before it (back = 1): plane_host[4][sources] = med | F' | open_level |
+ * close_level; *sources and *frames = J (each may be NULL).  Two planes take turns with the squelch's state planes and share their events: a plane whose
+ * turn it is not keeps its words.  It waits for that block's floor and squelch kernels only — not for its tuner, a run or a later block — and copies on the
+ * squelch's fetch stream.  M17HIP_ESTATE if no such plane exists: the mode is off, not enough blocks since it was turned on, or none since
+ * m17hip_demod_reset.  M17HIP_EINVAL for back > 1, a NULL context or plane_host, or capacity (in floats) below 4 x sources; nothing is written then. */
+int m17hip_wide_squelch_floor_fetch(m17hip_ctx* ctx, uint32_t back, float* plane_host, uint64_t capacity, uint32_t* sources, uint32_t* frames);
 
 /* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
  * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
@@ -1158,7 +1203,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * kernels of m17hip_wide_spectrum, one entry per transformed block), 15 = synth_wide (the two kernels of m17hip_synth_wide*, one entry per block),
  * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index),
  * 17 = squelch (wide_squelch_kernel of m17hip_wide_squelch, one entry per squelched block; its spectrum and its tuner keep their own indices),
- * 18 = squelch_slots (the three kernels of m17hip_wide_squelch_slots, one entry per squelched block; likewise). */
+ * 18 = squelch_slots (the three kernels of m17hip_wide_squelch_slots, one entry per squelched block; likewise),
+ * 19 = squelch_floor (squelch_floor_kernel of m17hip_wide_squelch_floor, one entry per block uploaded with that mode on; none with it off). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

@@ -98,4 +98,58 @@ __global__ __launch_bounds__(SQUELCH_THREADS) void squelch_slots_tile_kernel(con
     mask[i] = word;
 }
 
+// ---- the sources' noise floor (m17hip_wide_squelch_floor): the levels of either mode above made on the device from the block's own plane, in front of the
+// mode's kernels on the block's stream.  A workgroup per source.  The row's keys (core::squelch_floor_key) go to LDS once — 16 KB at 4096 points —, and the
+// key of rank N / 2 is selected by radix, the most significant byte first: four passes, each counting the keys that still share the selected prefix in a
+// 256-entry LDS histogram (integer LDS adds: the counts do not depend on their order) and choosing the one bucket that holds the rank.  Every lane scans the
+// histogram with wave-uniform reads, so the bucket needs no reduction; lane b owns bucket b.  The barriers: behind the keys and the zeroed histogram, behind
+// the counts, and behind the choice (which is also in front of the next pass's zeroes).  One lane then applies core::squelch_floor and squelch_track to the
+// source's carry F[s] — read and written in stream order like hold[] — and writes F[s] and out[4][S] = med | F' | open | close.  A block without a frame
+// (J == 0) leaves F as it is.  Vector stores only, no float atomics, no global atomics.  64 points leave three quarters of the lanes without a key: they
+// still zero, scan and meet every barrier.
+constexpr int SQUELCH_FLOOR_THREADS = 256;
+constexpr uint32_t SQUELCH_FLOOR_MAX_POINTS = 4096;
+
+__global__ __launch_bounds__(SQUELCH_FLOOR_THREADS) void squelch_floor_kernel(const float* __restrict__ plane, uint32_t logn, uint32_t J, uint32_t B,
+                                                                              float open_ratio, float close_ratio, float rise, float fall, float floor_min,
+                                                                              float* __restrict__ carry, float* __restrict__ out, uint32_t S)
+{
+    __shared__ uint32_t keys[SQUELCH_FLOOR_MAX_POINTS];
+    __shared__ uint32_t hist[SQUELCH_FLOOR_THREADS];
+    __shared__ uint32_t sel[2];   // the selected prefix (in place, the bits below it 0) and the rank among the keys that share it
+    const uint32_t s = blockIdx.x, t = threadIdx.x, N = 1u << logn;
+    if (s >= S || N > SQUELCH_FLOOR_MAX_POINTS) return;   // (uniform over the workgroup)
+    const float* row = plane + (size_t)s * N;
+    for (uint32_t i = t; i < N; i += SQUELCH_FLOOR_THREADS) keys[i] = core::squelch_floor_key(row[i]);
+    uint32_t prefix = 0, mask = 0, rank = N / 2;
+    for (uint32_t shift = 24;; shift -= 8) {
+        hist[t] = 0;
+        __syncthreads();
+        for (uint32_t i = t; i < N; i += SQUELCH_FLOOR_THREADS) {
+            const uint32_t k = keys[i];
+            if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        uint32_t below = 0, mine = 0;
+        for (uint32_t b = 0; b < (uint32_t)SQUELCH_FLOOR_THREADS; ++b) {
+            const uint32_t n = hist[b];
+            below += b < t ? n : 0u;
+            mine = b == t ? n : mine;
+        }
+        if (below <= rank && rank - below < mine) { sel[0] = prefix | (t << shift); sel[1] = rank - below; }   // (one lane: the buckets' counts sum to more than rank)
+        __syncthreads();
+        prefix = sel[0]; rank = sel[1]; mask |= 255u << shift;
+        if (shift == 0) break;
+    }
+    if (t != 0) return;
+    const float med = core::squelch_floor_value(prefix);
+    float F = carry[s];
+    if (J) F = core::squelch_track(F, core::squelch_floor(med, B, J, floor_min), rise, fall);
+    carry[s] = F;
+    out[s] = med;
+    out[S + s] = F;
+    out[2 * (size_t)S + s] = core::squelch_floor_level(F, open_ratio);
+    out[3 * (size_t)S + s] = core::squelch_floor_level(F, close_ratio);
+}
+
 }  // namespace m17

@@ -41,7 +41,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_SQUELCH_SLOTS, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_SQUELCH_SLOTS, KT_SQUELCH_FLOOR, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -447,6 +447,15 @@ struct m17hip_ctx {
             DevBuf<uint32_t> sbits, mask[2];
             DevBuf<float> sband[2];
             uint32_t G[2] = {0, 0}, tiles[2] = {0, 0};
+            // The floor on the device (m17hip_wide_squelch_floor; `floor`, beside either mode above): squelch_floor_kernel in front of the mode's kernels makes
+            // the block's levels from its plane, and those kernels read them from the floor plane whose turn it is in place of the table of given levels,
+            // which is then neither uploaded nor read and keeps what it holds.  The carry [256] is the feed's, ordered by ev_iq like `hold`; `fresh` fills it
+            // with NaNs where it zeroes `hold`.  Two planes [4][S] = med | floor | open | close take turns with the state planes and share their events;
+            // has_floor says which of those blocks wrote one.  Only squelch_set turns `on` on, and it turns `floor` off: nothing else has to.
+            bool floor = false;
+            float f_open = 0.0f, f_close = 0.0f, f_rise = 1.0f, f_fall = 1.0f, f_min = 0.0f;
+            DevBuf<float> fcarry, fplane[2];
+            bool has_floor[2] = {false, false};
             void forget() { valid[0] = valid[1] = false; }
             ~Squelch() { if (fetch) (void)hipStreamDestroy(fetch); }
         } sq;
@@ -456,7 +465,8 @@ struct m17hip_ctx {
                     sp.plane[1].size() + mt.scratch.size() + mt.plane[0].size() + mt.plane[1].size()) * sizeof(float) +
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4 +
                    (sq.dev.words() + sq.hold.size() + sq.state[0].size() + sq.state[1].size() + sq.band[0].size() + sq.band[1].size() +
-                    sq.sbits.size() + sq.mask[0].size() + sq.mask[1].size() + sq.sband[0].size() + sq.sband[1].size()) * 4;
+                    sq.sbits.size() + sq.mask[0].size() + sq.mask[1].size() + sq.sband[0].size() + sq.sband[1].size() + sq.fcarry.size() + sq.fplane[0].size() +
+                    sq.fplane[1].size()) * 4;
         }
     } wide;
     // THE WIDEBAND SIGNAL GENERATOR (m17hip_synth_wide_config, m17hip_synth_wide; csrc/m17_wide_tx_kernels.hpp): the int16 input slab's rows FM-modulated into
@@ -1305,7 +1315,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 620; }
+int m17hip_version(void) { return 621; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1895,6 +1905,53 @@ static int launch_meter(m17hip_ctx* c, const float* x, uint32_t T, uint32_t C, h
     mt.C[p] = C; mt.K[p] = K; mt.T[p] = T; mt.N0[p] = mt.outputs; mt.win[p] = mt.window; mt.valid[p] = true; mt.latest = p;
     return M17HIP_OK;
 }
+// The levels of one squelched block, in front of its squelch kernels on its stream `st`: with m17hip_wide_squelch_floor on, squelch_floor_kernel makes them
+// from the plane launch_spectrum has just queued (J frames) into floor plane `p`; otherwise the table of given levels is brought up to date.  `fresh` also
+// starts the hold counts and the floor carry over here.  *levels is what the squelch kernel reads; squelch_levels_done follows that kernel.
+static int squelch_levels(m17hip_ctx* c, int p, uint32_t J, hipStream_t st, const float** levels)
+{
+    auto& w = c->wide;
+    auto& sq = w.sq;
+    int r;
+    if (sq.floor && !sq.fcarry) {   // ([256] and [4][256], once per configuration: never regrown)
+        if ((r = alloc_code(c, sq.fcarry.alloc(256)))) return r;
+        for (auto& b : sq.fplane) if ((r = alloc_code(c, b.alloc(4 * 256)))) return r;
+        sq.fresh = true;
+    }
+    if (!sq.floor) {
+        if (sq.dirty || !sq.dev.live()) {   // the levels, into the copy no queued launch reads
+            uint32_t* staging = nullptr;
+            HIPCHK(c, sq.dev.begin_write(2 * 256, &staging));
+            std::memcpy(staging, sq.levels.data(), sq.levels.size() * 4);
+            HIPCHK(c, sq.dev.publish(sq.levels.size(), st));
+            sq.dirty = false;
+        }
+        HIPCHK(c, sq.dev.before_read(st));
+    }
+    // A fresh feed of decisions: every count of the array is 0, not only those of this block's channels — a later block may carry more channels than this
+    // one — and every source's floor is forgotten.  On the block's stream, which iq_order has put behind whatever read or wrote the arrays last: nothing
+    // is waited for.
+    if (sq.fresh) {
+        HIPCHK(c, hipMemsetAsync(sq.hold.get(), 0, (size_t)c->maxC * sizeof(uint32_t), st));
+        if (sq.fcarry) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sq.fcarry.get()), (int)core::SQUELCH_FLOOR_NAN, 256, st));
+    }
+    sq.has_floor[p] = sq.floor;
+    if (!sq.floor) { *levels = reinterpret_cast<const float*>(sq.dev.dev()); return M17HIP_OK; }
+    {
+        Timed tm(c, KT_SQUELCH_FLOOR, st);
+        hipLaunchKernelGGL(squelch_floor_kernel, dim3(w.S), dim3(SQUELCH_FLOOR_THREADS), 0, st, w.sp.plane[w.sp.latest].get(), w.sp.logn, J, sq.B, sq.f_open,
+                           sq.f_close, sq.f_rise, sq.f_fall, sq.f_min, sq.fcarry.get(), sq.fplane[p].get(), w.S);
+        HIPCHK(c, hipGetLastError());
+    }
+    *levels = sq.fplane[p].get() + 2 * (size_t)w.S;
+    return M17HIP_OK;
+}
+static int squelch_levels_done(m17hip_ctx* c, hipStream_t st)
+{
+    auto& sq = c->wide.sq;
+    if (!sq.floor) HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    return M17HIP_OK;
+}
 // The squelch of one block (m17hip_wide_squelch is on), on the block's stream between its spectrum and its tuner: it reads the plane launch_spectrum has
 // just queued, the channel table the tuner is about to read and the levels, steps the hold counts and writes the state and band planes whose turn it is.
 // The state plane is what the block's tuner reads: its next writer, two blocks on, is behind that tuner through ev_iq.
@@ -1912,25 +1969,16 @@ static int launch_squelch(m17hip_ctx* c, uint32_t C, hipStream_t st)
         for (auto& b : sq.band) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
         sq.fresh = true;
     }
-    if (sq.dirty || !sq.dev.live()) {   // the levels, into the copy no queued launch reads
-        uint32_t* staging = nullptr;
-        HIPCHK(c, sq.dev.begin_write(2 * 256, &staging));
-        std::memcpy(staging, sq.levels.data(), sq.levels.size() * 4);
-        HIPCHK(c, sq.dev.publish(sq.levels.size(), st));
-        sq.dirty = false;
-    }
-    HIPCHK(c, sq.dev.before_read(st));
     sq.valid[p] = false;
-    // A fresh feed of decisions: every count of the array is 0, not only those of this block's channels — a later block may carry more channels than this
-    // one.  On the block's stream, which iq_order has put behind whatever read or wrote the array last: nothing is waited for.
-    if (sq.fresh) HIPCHK(c, hipMemsetAsync(sq.hold.get(), 0, (size_t)c->maxC * sizeof(uint32_t), st));
+    const float* levels = nullptr;
+    if ((r = squelch_levels(c, p, w.sp.frames[ps], st, &levels))) return r;
     {
         Timed tm(c, KT_SQUELCH, st);
         hipLaunchKernelGGL(wide_squelch_kernel, dim3((C + SQUELCH_THREADS - 1) / SQUELCH_THREADS), dim3(SQUELCH_THREADS), 0, st, w.sp.plane[ps].get(), w.sp.logn,
-                           w.sp.frames[ps], w.dev.dev(), c->maxC, reinterpret_cast<const float*>(sq.dev.dev()), w.S, sq.B, sq.hang, sq.hold.get(), sq.state[p].get(), sq.band[p].get(), C);
+                           w.sp.frames[ps], w.dev.dev(), c->maxC, levels, w.S, sq.B, sq.hang, sq.hold.get(), sq.state[p].get(), sq.band[p].get(), C);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    if ((r = squelch_levels_done(c, st))) return r;
     HIPCHK(c, hipEventRecord(sq.ev[p], st));
     sq.fresh = false;
     sq.C[p] = C; sq.frames[p] = w.sp.frames[ps]; sq.valid[p] = true; sq.latest = p;
@@ -1964,15 +2012,8 @@ static int launch_squelch_slots(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t 
         if ((r = alloc_code(c, sq.sband[p].grow((size_t)C * G, &c->last_hip)))) return r;
         if ((r = alloc_code(c, sq.mask[p].grow((size_t)C * MW, &c->last_hip)))) return r;
     }
-    if (sq.dirty || !sq.dev.live()) {   // the levels, into the copy no queued launch reads
-        uint32_t* staging = nullptr;
-        HIPCHK(c, sq.dev.begin_write(2 * 256, &staging));
-        std::memcpy(staging, sq.levels.data(), sq.levels.size() * 4);
-        HIPCHK(c, sq.dev.publish(sq.levels.size(), st));
-        sq.dirty = false;
-    }
-    HIPCHK(c, sq.dev.before_read(st));
-    if (sq.fresh) HIPCHK(c, hipMemsetAsync(sq.hold.get(), 0, (size_t)c->maxC * sizeof(uint32_t), st));   // (as launch_squelch does)
+    const float* levels = nullptr;
+    if ((r = squelch_levels(c, p, J, st, &levels))) return r;   // (as launch_squelch does)
     {
         Timed tm(c, KT_SQUELCH_SLOTS, st);
         if (G) {
@@ -1981,13 +2022,13 @@ static int launch_squelch_slots(m17hip_ctx* c, uint32_t C, uint32_t T, uint32_t 
             HIPCHK(c, hipGetLastError());
         }
         hipLaunchKernelGGL(squelch_slots_step_kernel, dim3((C + SQUELCH_THREADS - 1) / SQUELCH_THREADS), dim3(SQUELCH_THREADS), 0, st, sq.sband[p].get(), G, J,
-                           w.dev.dev(), reinterpret_cast<const float*>(sq.dev.dev()), w.S, sq.hang, sq.hold.get(), sq.state[p].get(), sq.sbits.get(), C);
+                           w.dev.dev(), levels, w.S, sq.hang, sq.hold.get(), sq.state[p].get(), sq.sbits.get(), C);
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(squelch_slots_tile_kernel, dim3((uint32_t)(((uint64_t)C * MW + SQUELCH_THREADS - 1) / SQUELCH_THREADS)), dim3(SQUELCH_THREADS), 0, st,
                            sq.sbits.get(), G, first, w.sp.hop, sq.lead, TO, T, W, tiles, MW, sq.mask[p].get(), C);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    if ((r = squelch_levels_done(c, st))) return r;
     HIPCHK(c, hipEventRecord(sq.ev[p], st));
     sq.fresh = false;
     sq.C[p] = C; sq.frames[p] = J; sq.G[p] = G; sq.tiles[p] = tiles; sq.valid[p] = true; sq.latest = p;
@@ -2286,6 +2327,8 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     for (auto& b : w.sp.plane) b.release(&c->last_hip);
     w.sq.on = false; w.sq.forget();   // (the squelch goes with the spectrum)
     w.sq.hold.release(&c->last_hip);
+    w.sq.fcarry.release(&c->last_hip);
+    for (auto& b : w.sq.fplane) b.release(&c->last_hip);
     for (auto& b : w.sq.state) b.release(&c->last_hip);
     for (auto& b : w.sq.band) b.release(&c->last_hip);
     w.sq.sbits.release(&c->last_hip);
@@ -2615,6 +2658,7 @@ static int squelch_set(m17hip_ctx* c, uint32_t half_bins, const float* open_leve
     sq.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
     sq.fresh = true;
     sq.on = !off;
+    sq.floor = false;   // (the levels this call carries serve; m17hip_wide_squelch_floor comes after it)
     if (off) return M17HIP_OK;
     sq.B = half_bins; sq.hang = hang; sq.slots = slots; sq.lead = lead;
     sq.levels.assign(open_level, open_level + nlevels);
@@ -2668,6 +2712,41 @@ int m17hip_wide_squelch_fetch(m17hip_ctx* c, uint32_t back, uint32_t* state_host
     HIPCHK(c, hipMemcpyAsync(band_host, sq.band[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, sq.fetch));
     HIPCHK(c, hipStreamSynchronize(sq.fetch));
     if (channels) *channels = (uint32_t)n;
+    if (frames) *frames = sq.frames[p];
+    return M17HIP_OK;
+}
+// ---- the floor on the device (ABI 621): the levels of either mode from the block's own plane ------------------------------------------------------------
+int m17hip_wide_squelch_floor(m17hip_ctx* c, float open_ratio, float close_ratio, float rise, float fall, float floor_min)
+{
+    if (!c) return M17HIP_EINVAL;
+    auto& sq = c->wide.sq;
+    if (!std::isfinite(open_ratio) || !std::isfinite(close_ratio) || !std::isfinite(rise) || !std::isfinite(fall) || !std::isfinite(floor_min)) return M17HIP_EINVAL;
+    const bool off = open_ratio == 0.0f && close_ratio == 0.0f;
+    if (!off && (!(close_ratio > 0.0f) || !(close_ratio <= open_ratio))) return M17HIP_EINVAL;
+    if (!(rise > 0.0f) || !(rise <= 1.0f) || !(fall > 0.0f) || !(fall <= 1.0f) || floor_min < 0.0f) return M17HIP_EINVAL;
+    if (!c->wide.S || c->front_queued) return M17HIP_ESTATE;   // (the staged block belongs to the run being made)
+    if (!off && !sq.on) return M17HIP_ESTATE;
+    sq.forget();   // (as either squelch call: the next block uploaded is the first it holds for, hold counts zeroed and floor forgotten; nothing is queued here)
+    sq.fresh = true;
+    sq.floor = !off && sq.on;
+    if (off) return M17HIP_OK;
+    sq.f_open = open_ratio; sq.f_close = close_ratio; sq.f_rise = rise; sq.f_fall = fall; sq.f_min = floor_min;
+    return M17HIP_OK;
+}
+int m17hip_wide_squelch_floor_fetch(m17hip_ctx* c, uint32_t back, float* plane_host, uint64_t capacity, uint32_t* sources, uint32_t* frames)
+{
+    if (!c || back > 1 || !plane_host) return M17HIP_EINVAL;
+    auto& sq = c->wide.sq;
+    if (!c->wide.S || !sq.on || !sq.floor) return M17HIP_ESTATE;
+    const int p = sq.latest ^ (int)back;
+    if (!sq.valid[p] || !sq.has_floor[p]) return M17HIP_ESTATE;
+    const size_t n = (size_t)4 * c->wide.S;
+    if (capacity < n) return M17HIP_EINVAL;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sq.ev[p]));   // (that block's floor and squelch kernels and what its stream held in front of them: not its tuner, no run, no later block)
+    HIPCHK(c, hipMemcpyAsync(plane_host, sq.fplane[p].get(), n * sizeof(float), hipMemcpyDeviceToHost, sq.fetch));
+    HIPCHK(c, hipStreamSynchronize(sq.fetch));
+    if (sources) *sources = c->wide.S;
     if (frames) *frames = sq.frames[p];
     return M17HIP_OK;
 }

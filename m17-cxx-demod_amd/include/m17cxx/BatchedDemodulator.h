@@ -200,6 +200,25 @@ public:
         if (tiles) *tiles = t;
         if (frames) *frames = j;
     }
+    // The sources' noise floor on the device (m17hip_wide_squelch_floor), beside whichever squelch mode is on: from the blocks uploaded after the call each
+    // source's levels are its tracked floor — the upper median of the block's own plane times 2 half_bins + 1 over the frames, at least floor_min, moved
+    // by `rise` towards a higher floor and by `fall` towards a lower one (both in (0, 1]) — times open_ratio and close_ratio; the mode's given levels are
+    // set aside.  wide_squelch_floor_off gives them back; every wide_squelch and wide_squelch_slots call turns it off as well.  wide_squelch_floor_fetch:
+    // plane[4][sources] = median | floor | open level | close level of the latest such block (back = 0) or the one before; it waits for that block's floor
+    // and squelch kernels only.
+    void wide_squelch_floor(float open_ratio, float close_ratio, float rise = 1.0f, float fall = 1.0f, float floor_min = 0.0f)
+    {
+        check(m17hip_wide_squelch_floor(ctx_, open_ratio, close_ratio, rise, fall, floor_min), "m17hip_wide_squelch_floor");
+    }
+    void wide_squelch_floor_off() { check(m17hip_wide_squelch_floor(ctx_, 0.0f, 0.0f, 1.0f, 1.0f, 0.0f), "m17hip_wide_squelch_floor"); }
+    void wide_squelch_floor_fetch(uint32_t back, std::vector<float>& plane, uint32_t* sources = nullptr, uint32_t* frames = nullptr)
+    {
+        plane.resize(4 * 256);
+        uint32_t n = 0;
+        check(m17hip_wide_squelch_floor_fetch(ctx_, back, plane.data(), plane.size(), &n, frames), "m17hip_wide_squelch_floor_fetch");
+        plane.resize((size_t)4 * n);
+        if (sources) *sources = n;
+    }
     // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
     // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
     // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,

@@ -352,6 +352,7 @@ struct M17Demodulator
         squelch_half_ = half_bins; squelch_open_db_ = open_db; squelch_close_db_ = close_db; squelch_hang_ = hang;
         squelch_report_ = std::move(report);
         squelch_slots_ = false;
+        squelch_floor_ = false;
         squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
         return true;
     }
@@ -371,7 +372,29 @@ struct M17Demodulator
         squelch_half_ = half_bins; squelch_open_db_ = open_db; squelch_close_db_ = close_db; squelch_hang_ = hang; squelch_lead_ = lead;
         squelch_slots_report_ = std::move(report);
         squelch_slots_ = true;
+        squelch_floor_ = false;
         squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
+        return true;
+    }
+    // The floor on the device (m17hip_wide_squelch_floor), behind wide_squelch or wide_squelch_slots, whose half_bins, hang, lead and report stay and whose
+    // own open_db / close_db are set aside: no block runs unsquelched and the host takes no median — every block, the next one included, is squelched at
+    // open_db / close_db over the floor the device takes from that very block's plane (its upper median), tracked by `rise` towards a higher floor and by
+    // `fall` towards a lower one (each in (0, 1]; 1 follows at once).  After each block `report`, if any, gets the tracked floor, the two levels (per frame)
+    // and the block's frames.  Returns false, with nothing changed, on the host form.  Whatever turns the squelch off, and each of the two squelch calls,
+    // turns it off.
+    using squelch_floor_callback_t = std::function<void(float floor, float open_level, float close_level, uint32_t frames)>;
+    bool wide_squelch_floor(double open_db, double close_db, float rise = 1.0f, float fall = 1.0f, squelch_floor_callback_t report = {})
+    {
+        if (!gpu_) return false;
+        if (!squelch_mode_) throw std::logic_error("M17Demodulator::wide_squelch_floor needs wide_squelch or wide_squelch_slots");
+        if (!(close_db <= open_db) || !(rise > 0.0f) || !(rise <= 1.0f) || !(fall > 0.0f) || !(fall <= 1.0f)) throw std::invalid_argument("M17Demodulator::wide_squelch_floor");
+        flush();
+        if (squelch_slots_) gpu_->wide_squelch_slots(squelch_half_, {1.0f}, {1.0f}, squelch_hang_, squelch_lead_);   // (the mode on; its levels are never read)
+        else gpu_->wide_squelch(squelch_half_, {1.0f}, {1.0f}, squelch_hang_);
+        gpu_->wide_squelch_floor((float)std::pow(10.0, open_db / 10.0), (float)std::pow(10.0, close_db / 10.0), rise, fall);
+        squelch_floor_report_ = std::move(report);
+        squelch_floor_ = true;
+        squelch_mode_ = 2;
         return true;
     }
     // The channel meter beside any wideband configuration on the GPU path (m17hip_wide_meter): per window of `window` outputs of the feed (16..65536; 0
@@ -570,6 +593,11 @@ private:
             gpu_->wide_squelch_fetch(0, squelch_state_, squelch_band_, &frames);
             squelch_report_((squelch_state_[0] >> 31) != 0, squelch_state_[0] & 0x7FFFFFFFu, squelch_band_[0], frames);
         }
+        if (squelched && squelch_floor_ && squelch_floor_report_) {   // (likewise: the fetch waits for the block's floor and squelch kernels)
+            uint32_t frames = 0;
+            gpu_->wide_squelch_floor_fetch(0, squelch_floor_plane_, nullptr, &frames);
+            squelch_floor_report_(squelch_floor_plane_[1], squelch_floor_plane_[2], squelch_floor_plane_[3], frames);
+        }
         if (meter_window_ && meter_report_) {   // (likewise: the fetch waits for the block's meter kernel)
             uint32_t pieces = 0, outputs = 0;
             uint64_t first_window = 0, first_output = 0;
@@ -628,6 +656,9 @@ private:
     std::vector<float> meter_planes_;
     int squelch_mode_ = 0;                           // wide_squelch: 0 = off, 1 = armed (the next block's plane sets the levels), 2 = on
     bool squelch_slots_ = false;                     // wide_squelch_slots in wide_squelch's place
+    bool squelch_floor_ = false;                     // wide_squelch_floor: the levels are the device's
+    squelch_floor_callback_t squelch_floor_report_;
+    std::vector<float> squelch_floor_plane_;
     uint32_t squelch_half_ = 0, squelch_hang_ = 0, squelch_lead_ = 0;
     squelch_slots_callback_t squelch_slots_report_;
     std::vector<uint32_t> squelch_mask_;

@@ -376,6 +376,46 @@ M17_HD uint32_t squelch_step(uint32_t h, float b, float to, float tc, uint32_t h
     else hn = h > 0u ? h - 1u : 0u;
     return hn | (hn > 0u ? SQUELCH_OPEN : 0u);
 }
+// ---- a-1h: the sources' noise floor (m17hip_wide_squelch_floor): the levels of both squelch modes made from the block's own plane P[source][N] of J frames.
+// The floor of a row is its UPPER MEDIAN by key: squelch_floor_key orders the powers — sums of chan_power from +0, so no non-NaN value has its sign bit set —
+// as unsigned words, every NaN last.  The median is the element whose key has rank N / 2 (0-based) among the row's N keys in ascending order: a selection,
+// so every correct algorithm gives the same word.  It is NOT np.median, which takes the mean of the two middle values in float64.
+constexpr uint32_t SQUELCH_FLOOR_NAN = 0x7FC00000u;   // the carry in front of the first block, and the median of a row with more than N / 2 NaNs
+M17_HD uint32_t squelch_floor_key(float x) { return x != x ? 0xFFFFFFFFu : __builtin_bit_cast(uint32_t, x); }
+M17_HD float squelch_floor_value(uint32_t key) { return __builtin_bit_cast(float, key == 0xFFFFFFFFu ? SQUELCH_FLOOR_NAN : key); }
+// the row's upper median, stated as plainly as possible (the host form; the kernel selects the same key by radix): the key with exactly N / 2 keys in
+// front of it when ties are broken by index
+M17_HD float squelch_floor_median(const float* row, uint32_t N)
+{
+    for (uint32_t i = 0; i < N; ++i) {
+        const uint32_t k = squelch_floor_key(row[i]);
+        uint32_t below = 0;
+        for (uint32_t j = 0; j < N; ++j) {
+            const uint32_t q = squelch_floor_key(row[j]);
+            below += (q < k || (q == k && j < i)) ? 1u : 0u;
+        }
+        if (below == N / 2) return squelch_floor_value(k);
+    }
+    return squelch_floor_value(0xFFFFFFFFu);   // (N == 0: not reached)
+}
+// the block's floor per frame and band: the median times the band's bins over the block's frames, two rounded operations, not below floor_min.  A NaN
+// stays a NaN.  J >= 1.
+M17_HD float squelch_floor(float med, uint32_t B, uint32_t J, float floor_min)
+{
+    const float f = (med * (float)(2u * B + 1u)) / (float)J;
+    return f < floor_min ? floor_min : f;
+}
+// the source's carried floor F behind a block whose floor is f: the first block sets it whatever it is (the carry starts as a NaN); a non-finite f leaves
+// it; otherwise F moves towards f by `rise` or `fall`, and a factor of 1 or more returns f to the bit (fmaf(1, f - F, F) need not)
+M17_HD float squelch_track(float F, float f, float rise, float fall)
+{
+    if (!(F == F)) return f;
+    if (!(f - f == 0.0f)) return F;
+    const float a = f > F ? rise : fall;
+    return a >= 1.0f ? f : __builtin_fmaf(a, f - F, F);
+}
+// the block's levels per frame from the carried floor: one rounded multiply each (squelch_level takes them from there, as it takes given levels)
+M17_HD float squelch_floor_level(float F, float ratio) { return F * ratio; }
 // ---- a-1g: the time-resolved squelch (m17hip_wide_squelch_slots): the same four functions per SLOT of a block — a group of CHAN_SURVEY_GROUP frames of the
 // block's spectrum, whose row is the spectrum's first-level sum — and the tuners skip per TILE of outputs.  A block of J frames has squelch_slots(J) slots;
 // slot g holds squelch_slot_frames(J, g) frames and is stepped with squelch_step(h, band, level x frames, ..., hang, frames): hang counts slots.

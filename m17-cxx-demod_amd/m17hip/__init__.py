@@ -31,7 +31,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
            "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16, "squelch": 17,
-           "squelch_slots": 18}
+           "squelch_slots": 18, "squelch_floor": 19}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -81,6 +81,7 @@ EXPORTS = [
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
     "m17hip_wide_meter", "m17hip_wide_meter_shape", "m17hip_wide_meter_fetch",
     "m17hip_wide_squelch", "m17hip_wide_squelch_fetch", "m17hip_wide_squelch_slots", "m17hip_wide_squelch_slots_fetch",
+    "m17hip_wide_squelch_floor", "m17hip_wide_squelch_floor_fetch",
     "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
@@ -387,6 +388,11 @@ def wide_squelch_levels(power, frames, half_bins, open_db, close_db):
         raise ValueError("wide_squelch_levels: a plane of at least one frame")
     floor = np.median(p, axis=1) * (2 * int(half_bins) + 1) / float(int(frames))
     return ((floor * 10.0 ** (float(open_db) / 10.0)).astype(np.float32), (floor * 10.0 ** (float(close_db) / 10.0)).astype(np.float32))
+
+
+def wide_squelch_ratio(db):
+    """A ratio of Context.wide_squelch_floor from a margin over the floor in dB: np.float32(10 ** (db / 10))."""
+    return np.float32(10.0 ** (float(db) / 10.0))
 
 
 def wide_fcw(offset_hz, decim):
@@ -755,6 +761,26 @@ class Context:
             break
         c, mw = n.value, (t.value + 31) // 32
         return (state[:c].copy(), bands[: c * g.value].reshape(c, g.value).copy(), mask[: c * mw].reshape(c, mw).copy(), int(t.value), int(frames.value))
+
+    def wide_squelch_floor(self, open_ratio, close_ratio, rise=1.0, fall=1.0, floor_min=0.0):
+        """The sources' noise floor on the device, beside whichever squelch mode is on (wide_squelch or wide_squelch_slots first; its half_bins, hang and
+        lead stay, its given levels are set aside): from the blocks uploaded after this call a kernel in front of the squelch takes each source's floor from
+        the block's own plane — the row's upper median times 2 half_bins + 1 over the frames, at least floor_min —, tracks it from block to block (towards a
+        higher floor by `rise`, towards a lower one by `fall`, both in (0, 1]; 1 follows at once) and the block's levels are the tracked floor times
+        open_ratio and close_ratio (wide_squelch_ratio(dB)).  open_ratio == close_ratio == 0 turns it off: the given levels serve again.  Every
+        wide_squelch and wide_squelch_slots call turns it off — m17hip_wide_squelch_floor."""
+        self._chk(self.lib.m17hip_wide_squelch_floor(self.h, C.c_float(open_ratio), C.c_float(close_ratio), C.c_float(rise), C.c_float(fall), C.c_float(floor_min)))
+
+    def wide_squelch_floor_fetch(self, back=0):
+        """(plane float32 [4][S], frames) of the latest block uploaded with wide_squelch_floor on (back = 0) or the one before it (back = 1): per source the
+        plane's median, the tracked floor behind the block, and the open and close levels the squelch read.  Waits for that block's floor and squelch
+        kernels only — m17hip_wide_squelch_floor_fetch."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_squelch_floor_fetch: back is 0 or 1")
+        buf = np.zeros(4 * 256, dtype=np.float32)
+        n, frames = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.lib.m17hip_wide_squelch_floor_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(buf.size), C.byref(n), C.byref(frames)))
+        return buf[: 4 * n.value].reshape(4, n.value).copy(), int(frames.value)
 
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]] [--slots KEYED[,KEYED...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]] [--squelch-floor FRACTION[,FRACTION...]] [--slots KEYED[,KEYED...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -39,6 +39,11 @@ measured 4 x slower per open workgroup under the two-stage tuners), one unsquelc
 close 6 dB over the median floor), and the squelched launch — the spectrum, wide_squelch_kernel (library timer "squelch") and the squelched instantiation of
 the tuner — is timed per fraction beside the unsquelched tuner and spectrum on the same source in the same call.  Fraction 0 is a grid of all-closed
 workgroups: the floor of the design.
+With --squelch-floor FRACTION[,FRACTION...] the same sources are squelched (block mode, 10 / 6 dB) with the floor taken ON THE DEVICE
+(m17hip_wide_squelch_floor: squelch_floor_kernel, library timer "squelch_floor", beside the spectrum's of the same call), and then at given levels equal to
+the ones the device derived for the last block (where the block is no whole number of hops the frames shift from block to block, and a channel at the
+margin may decide differently: both counts are reported): the two launches — spectrum + floor + squelch + tuner against spectrum + squelch + tuner —
+side by side.
 With --slots KEYED[,KEYED...] beside --spectrum under one of the three tuners EVERY channel has a carrier, keyed for the first KEYED (0 to 1) of each block
 over weak noise; the levels come from the plane of a block of that noise alone (10 and 6 dB over the median floor, a 9 kHz band).  Per value the same
 source is timed in the same call unsquelched (tuner and spectrum), under the block squelch (m17hip_wide_squelch: spectrum, "squelch", tuner) and under the
@@ -100,6 +105,12 @@ if "--squelch" in ARGS:
     SQUELCH = [float(v) for v in ARGS[k + 1].split(",")]
     del ARGS[k:k + 2]
     assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in SQUELCH), "--squelch FRACTION (0 to 1) goes with --spectrum N --hop H and a tuner"
+FLOOR = []   # (empty: not timed)
+if "--squelch-floor" in ARGS:
+    k = ARGS.index("--squelch-floor")
+    FLOOR = [float(v) for v in ARGS[k + 1].split(",")]
+    del ARGS[k:k + 2]
+    assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in FLOOR), "--squelch-floor FRACTION (0 to 1) goes with --spectrum N --hop H and a tuner"
 SLOTS = []   # (empty: not timed)
 if "--slots" in ARGS:
     k = ARGS.index("--slots")
@@ -236,21 +247,28 @@ if METER:   # the same blocks once more with the meter on: a warm-up block (scra
              "own_kernel_ms_metered": round(ms_o / n_o, 3), "metered_over_unmetered": round(ms_o / n_o / (ms / n), 4), "meter_ms": round(ms_m / n_m, 3),
              "copy_ms_median": round(float(np.median(cp)), 3), "bytes_read": 2 * 4 * C * T,
              "meter_over_copy": round(ms_m / n_m / float(np.median(cp)), 2)}
+def carrier_source(frac):
+    """(int16 [S][ROW][2] on the device, carriers per source): weak noise with 300 exp(2 pi i f n / Fs) for that share of every source's channels, chosen at
+    random (at most 64 x 300 < 32767 - 200)."""
+    n64 = torch.arange(ROW, dtype=torch.float64, device='cuda')
+    on = int(round(frac * PER))
+    xs = torch.randint(-200, 201, (S, ROW, 2), dtype=torch.int16, device='cuda', generator=g)
+    for s_ in range(S):
+        pick = np.sort(rng.permutation(PER)[:on]) if PLACE == "random" else np.arange(on)
+        f = torch.tensor(OFFSETS[s_ * PER + pick] / (48000.0 * RATIO), dtype=torch.float64, device='cuda')
+        for k0 in range(0, on, 8):
+            ph = 2.0 * np.pi * torch.remainder(f[k0:k0 + 8, None] * n64[None, :], 1.0)
+            xs[s_, :, 0] += torch.round(300.0 * torch.cos(ph).sum(0)).to(torch.int16)
+            xs[s_, :, 1] += torch.round(300.0 * torch.sin(ph).sum(0)).to(torch.int16)
+    torch.cuda.synchronize()
+    return xs, on
+
+
 squelch = []
 if SQUELCH:   # per fraction: a source with carriers on that share of the channels; unsquelched (spectrum + tuner), then squelched (spectrum + squelch + tuner)
     half = m17hip.wide_squelch_half_bins(9000.0, 48000.0 * RATIO, SPECTRUM)   # (at most 64: a narrower band at fine bins)
-    n64 = torch.arange(ROW, dtype=torch.float64, device='cuda')
     for frac in SQUELCH:
-        on = int(round(frac * PER))
-        xs = torch.randint(-200, 201, (S, ROW, 2), dtype=torch.int16, device='cuda', generator=g)
-        for s_ in range(S):   # 300 exp(2 pi i f n / Fs) for `on` of the source's channels, chosen at random (at most 64 x 300 < 32767 - 200)
-            pick = np.sort(rng.permutation(PER)[:on]) if PLACE == "random" else np.arange(on)
-            f = torch.tensor(OFFSETS[s_ * PER + pick] / (48000.0 * RATIO), dtype=torch.float64, device='cuda')
-            for k0 in range(0, on, 8):
-                ph = 2.0 * np.pi * torch.remainder(f[k0:k0 + 8, None] * n64[None, :], 1.0)
-                xs[s_, :, 0] += torch.round(300.0 * torch.cos(ph).sum(0)).to(torch.int16)
-                xs[s_, :, 1] += torch.round(300.0 * torch.sin(ph).sum(0)).to(torch.int16)
-        torch.cuda.synchronize()
+        xs, on = carrier_source(frac)
 
         def call_s():
             ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
@@ -279,6 +297,43 @@ if SQUELCH:   # per fraction: a source with carriers on that share of the channe
                         "unsquelched_tuner_ms": round(uns, 3), "unsquelched_spectrum_ms": round(ms_pu / n_pu, 3), "squelched_tuner_ms": round(ms_q / n_q, 3),
                         "squelched_spectrum_ms": round(ms_pq / n_pq, 3), "squelch_kernel_ms": round(ms_k / n_k, 4), "squelched_launch_ms": round(sq_, 3),
                         "squelched_launch_over_unsquelched_tuner": round(sq_ / uns, 4)})
+        del xs
+    ctx.reset()
+floor = []
+if FLOOR:   # per fraction: the squelched launch with the floor taken on the device, beside the same launch at given levels equal to the ones the device derived
+    half = m17hip.wide_squelch_half_bins(9000.0, 48000.0 * RATIO, SPECTRUM)
+    ro, rc = m17hip.wide_squelch_ratio(10.0), m17hip.wide_squelch_ratio(6.0)
+    for frac in FLOOR:
+        xs, on = carrier_source(frac)
+
+        def call_f():
+            ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
+
+        def timed(extra):
+            call_f(); call_f()
+            ctx.timing_reset()
+            for _ in range(REP):
+                call_f()
+            opened = int(ctx.wide_squelch_fetch()[0].sum())
+            parts = {k: ctx.timing_get(k) for k in (OWN, "spectrum", "squelch") + extra}
+            return {k: v[0] / v[1] for k, v in parts.items()}, opened
+
+        ctx.reset()
+        ctx.wide_spectrum(SPECTRUM, HOP)
+        ctx.wide_squelch(half, np.ones(S, dtype=np.float32), np.ones(S, dtype=np.float32), 0)
+        ctx.wide_squelch_floor(ro, rc)
+        dev_ms, dev_open = timed(("squelch_floor",))
+        plane, frames = ctx.wide_squelch_floor_fetch()
+        ctx.wide_squelch(half, plane[2], plane[3], 0)   # (the same block again and again: the same levels up to the frames' shift from block to block)
+        giv_ms, giv_open = timed(())
+        ctx.wide_squelch(0, None)
+        ctx.wide_spectrum(0, 0)
+        dev, giv = sum(dev_ms.values()), sum(giv_ms.values())
+        floor.append({"fraction": frac, "carriers": on * S, "open_channels": dev_open, "open_channels_given_levels": giv_open, "half_bins": half, "frames_per_block": frames,
+                      "floor_kernel_ms": round(dev_ms["squelch_floor"], 4), "spectrum_ms": round(dev_ms["spectrum"], 3),
+                      "floor_over_spectrum": round(dev_ms["squelch_floor"] / dev_ms["spectrum"], 4), "tuner_ms_floor_on": round(dev_ms[OWN], 3),
+                      "tuner_ms_given_levels": round(giv_ms[OWN], 3), "launch_ms_floor_on": round(dev, 3), "launch_ms_given_levels": round(giv, 3),
+                      "floor_on_over_given": round(dev / giv, 4)})
         del xs
     ctx.reset()
 slots = []
@@ -393,6 +448,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}), **({"slots": slots} if SLOTS else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}), **({"squelch_floor": floor} if FLOOR else {}), **({"slots": slots} if SLOTS else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
