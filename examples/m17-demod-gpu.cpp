@@ -20,7 +20,10 @@
 // block's spectrum and the tuner skips per tile of its outputs (--hang then counts slots, --lead N opens the tiles up to N slots in front of an opening),
 // so a transmission that begins inside a block is kept from its start; the tiles tuned are printed per block; with --auto-floor [--rise A] [--fall A]
 // beside --squelch the floor is taken on the device from every block's own plane and tracked (towards a higher floor by A, towards a lower one by A, each
-// in (0, 1], default 1), so the first block is squelched too and a floor that moves is followed; the floor is printed in dB per block.  One line per frame callback on
+// in (0, 1], default 1), so the first block is squelched too and a floor that moves is followed; the floor is printed in dB per block; with --scan-pool N
+// beside --rate, --squelch and --auto-floor a pool of N channels is tuned by the carrier scan on the device, each transmission from the block in which it
+// first appears (rtl_sdr -s 2048000 ... | m17-demod-gpu --wide-u8 --rate 2048000 --spectrum 2048 --squelch 10 --auto-floor --scan-pool 8): the
+// assignments and misses are printed per block, the frames with their channel in front.  One line per frame callback on
 // stdout.  It is written the way apps/m17-demod.cpp drives the reference (construct M17Demodulator<float> with a
 // handle_frame callback, push sample / 41067.0 per sample) — audio (codec2) and the CLI options are out of scope.
 //   g++ -std=c++20 -O2 examples/m17-demod-gpu.cpp -I m17-cxx-demod_amd/include -L m17-cxx-demod_amd -lm17hip -Wl,-rpath,... -o m17-demod-gpu
@@ -96,6 +99,55 @@ static std::vector<std::pair<double, double>> carriers(const std::vector<float>&
     return out;
 }
 
+// --scan-pool N beside --rate HZ --spectrum P --squelch DB --auto-floor: a pool of N channels on the one source, all seeded at --offset-hz, tuned by the
+// carrier scan on the device (m17hip_wide_scan) in blocks of 4800 outputs (100 ms).  Per block the assignments and the misses are printed to stderr, the
+// assigned channels are reset before the block's run (the reset rule of include/m17hip.h), and every frame is printed with its channel in front.
+static int scan_pool_main(int wide, uint32_t rate, double offset_hz, uint32_t points, uint32_t hop, double squelch_db, uint32_t hang, float rise, float fall,
+                          uint32_t pool, float iq_gain)
+{
+    using namespace mobilinkd;
+    uint32_t d1, up, down;
+    BatchedDemodulator::wide_resample_ratio(rate, d1, up, down);
+    const uint32_t block = 4800 / (192 * up) * (192 * up);   // (whole groups of `up` outputs and whole ticks of 192: the listed reset's rule)
+    const size_t W = (size_t)block / up * down * d1, bytes = wide == M17HIP_IQ_F32 ? 8 : wide == M17HIP_IQ_I16 ? 4 : 2;
+    BatchedDemodulator gpu(pool, block);
+    gpu.wide_resample(1, d1, up, down, wide);
+    const int32_t seed = (int32_t)(uint32_t)std::llround(offset_hz / (double)rate * 4294967296.0);
+    std::vector<uint32_t> src(pool, 0u);
+    std::vector<int32_t> words(pool, seed);
+    gpu.wide_channels(src.data(), words.data(), pool);
+    gpu.reset();
+    gpu.wide_spectrum(points, hop);
+    const double df = (double)rate / points;
+    const uint32_t half = std::min<uint32_t>((uint32_t)std::lrint(9000.0 / 2.0 / df), std::min<uint32_t>(64u, points / 2 - 1));
+    const uint32_t guard = std::max<uint32_t>(3u, std::min<uint32_t>((uint32_t)std::ceil(9000.0 / df), points / 4));
+    gpu.wide_squelch(half, {1.0f}, {1.0f}, hang);
+    gpu.wide_squelch_floor((float)std::pow(10.0, squelch_db / 10.0), (float)std::pow(10.0, (squelch_db - 3.0) / 10.0), rise, fall);
+    gpu.wide_scan(std::vector<uint8_t>(pool, 1), guard);
+    std::vector<char> buf(W * bytes);
+    std::vector<uint32_t> flags, missed, assigned;
+    for (uint64_t b = 0;; ++b) {
+        std::cin.read(buf.data(), (std::streamsize)buf.size());
+        const size_t got = (size_t)std::cin.gcount() / bytes / ((size_t)down * d1) * ((size_t)down * d1);   // (whole groups; what is left over at the end is dropped)
+        if (!got) break;
+        gpu.upload_wide(buf.data(), pool, (uint32_t)(got / ((size_t)down * d1) * up), got, iq_gain);
+        gpu.wide_scan_fetch(0, words, flags, missed, &assigned);   // (waits for the block's scan kernel, not for its tuner)
+        for (const uint32_t c : assigned)
+            std::fprintf(stderr, "scan: block %llu, channel %u assigned %.1f Hz\n", (unsigned long long)b, c, (double)words[c] * (double)rate / 4294967296.0);
+        if (missed[0]) std::fprintf(stderr, "scan: block %llu, %u carriers found no free slot\n", (unsigned long long)b, missed[0]);
+        if (!assigned.empty()) gpu.reset_channels(assigned.data(), (uint32_t)assigned.size());
+        gpu.run();
+        for (const auto& r : gpu.frames()) {
+            static const size_t len[] = {30, 6, 18, 26, 26, 25};
+            std::printf("%u %d %d ", r.channel, (int)r.frame_type, (int)r.cost);
+            for (size_t i = 0; i < (r.frame_type < 6 ? len[r.frame_type] : 26); ++i) std::printf("%02x", r.payload[i]);
+            std::printf("\n");
+        }
+        if (!std::cin) break;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     using namespace mobilinkd;
@@ -122,6 +174,7 @@ int main(int argc, char** argv)
     bool auto_floor = false;          // (--auto-floor: the floor from each block's plane, on the device; --rise and --fall track it)
     float rise = 1.0f, fall = 1.0f;
     bool track_given = false;
+    uint32_t scan_pool = 0;           // (--scan-pool N: N channels tuned by the carrier scan on the device)
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-f") || !std::strcmp(argv[i], "--float32")) float_input = true;
         else if (!std::strcmp(argv[i], "--iq-i16")) iq = 1;
@@ -145,11 +198,12 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--slots")) slots = true;
         else if (!std::strcmp(argv[i], "--lead") && i + 1 < argc) { lead = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!lead) lead = ~0u; }
         else if (!std::strcmp(argv[i], "--auto-floor")) auto_floor = true;
+        else if (!std::strcmp(argv[i], "--scan-pool") && i + 1 < argc) { scan_pool = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!scan_pool) scan_pool = ~0u; }
         else if (!std::strcmp(argv[i], "--rise") && i + 1 < argc) { rise = std::strtof(argv[++i], nullptr); track_given = true; }
         else if (!std::strcmp(argv[i], "--fall") && i + 1 < argc) { fall = std::strtof(argv[++i], nullptr); track_given = true; }
         else if (!std::strcmp(argv[i], "--hop") && i + 1 < argc) { hop = (uint32_t)std::strtoul(argv[++i], nullptr, 10); if (!hop) hop = ~0u; }
         else {
-            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N] [--slots [--lead N]] [--auto-floor [--rise A] [--fall A]]]] [--meter W] [--iq-gain G] < samples\n");
+            std::fprintf(stderr, "usage: m17-demod-gpu [-f | --float32 | --iq-i16 | --iq-f32 | --wide-i16 | --wide-f32 | --wide-u8] [--decim R [--decim2 R2] | --rate HZ] [--offset-hz F | --raster M --bin B [--scan STRIDE [--scan-margin DB]]] [--spectrum N [--hop H] [--squelch DB [--hang N] [--slots [--lead N]] [--auto-floor [--rise A] [--fall A] [--scan-pool N]]]] [--meter W] [--iq-gain G] < samples\n");
             return 2;
         }
     }
@@ -193,6 +247,13 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "m17-demod-gpu: --spectrum N (a power of two, 64 to 4096) [--hop H (1 to 16777216)] goes with a wideband format\n");
             return 2;
         }
+    }
+    if (scan_pool) {
+        if (!rate || !auto_floor || slots || meter || scan_pool > 256) {
+            std::fprintf(stderr, "m17-demod-gpu: --scan-pool N (1 to 256 channels) goes with --rate, --spectrum, --squelch and --auto-floor, without --slots and --meter\n");
+            return 2;
+        }
+        return scan_pool_main(wide, (uint32_t)rate, offset_hz, spectrum, hop, squelch_db, hang, rise, fall, scan_pool, iq_gain);
     }
     M17Demodulator<float> demod(handle_frame);
     demod.diagnostics([](bool, float, float, float, bool, float, int, int, int, int) {});

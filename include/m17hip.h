@@ -580,7 +580,7 @@ int m17hip_wide_squelch_slots_fetch(m17hip_ctx* ctx, uint32_t back, uint32_t* st
  * outside (0, 1]; floor_min < 0.  M17HIP_ESTATE, nothing changed: no wideband configuration; between m17hip_demod_front and its run; turning it on with no
  * squelch mode on.
  * OUT OF SCOPE: a floor per slot, or one that ignores bins already known to hold carriers; percentiles other than the median; per-source ratios; the
- * carrier list (wide_spectrum_carriers) and channel assignment on the device; the raster; the demodulator's behaviour on long runs of exact zeros
+ * carrier list (wide_spectrum_carriers) and channel assignment on the device (m17hip_wide_scan below, ABI 622); the raster; the demodulator's behaviour on long runs of exact zeros
  * (NOTES.md; unchanged here); compacting the grid; AFC. */
 int m17hip_wide_squelch_floor(m17hip_ctx* ctx, float open_ratio, float close_ratio, float rise, float fall, float floor_min);
 /* The floor plane of the latest block uploaded with the mode on (back = 0) or of the one before it (back = 1): plane_host[4][sources] = med | F' | open_level |
@@ -589,6 +589,71 @@ int m17hip_wide_squelch_floor(m17hip_ctx* ctx, float open_ratio, float close_rat
  * squelch's fetch stream.  M17HIP_ESTATE if no such plane exists: the mode is off, not enough blocks since it was turned on, or none since
  * m17hip_demod_reset.  M17HIP_EINVAL for back > 1, a NULL context or plane_host, or capacity (in floats) below 4 x sources; nothing is written then. */
 int m17hip_wide_squelch_floor_fetch(m17hip_ctx* ctx, uint32_t back, float* plane_host, uint64_t capacity, uint32_t* sources, uint32_t* frames);
+
+/* ---- the carrier scan: the block's carriers found and a pool of channels tuned to them on the device (ABI 622) ------------------------------------------
+ * Who transmits where was the host's to decide: m17hip.wide_spectrum_carriers is numpy on a fetched plane (a wait for the device; nothing for C and C++),
+ * and a carrier it finds is tuned a block late at the earliest, because m17hip_wide_channels holds for the blocks uploaded after it — an M17 transmission
+ * has then lost its link setup frame and the receiver waits for the LICH to come round.  With this mode on, a kernel between the block's floor kernel and its
+ * squelch kernel finds the carriers of the block in its own plane and writes the frequency words of a pool of channels, so a transmission is tuned in the
+ * block in which it first appears.  It needs m17hip_wide_spectrum at no more than 4096 points, m17hip_wide_squelch (the block mode) and
+ * m17hip_wide_squelch_floor, under one of the three tuners.
+ * pool[c] != 0 makes local channel c < n a SLOT; channels at n and above are none.  A slot belongs to the source its m17hip_wide_channels entry names; the
+ * slots of source s among the block's channels, in ascending channel order, are that source's pool in that block (a slot at or above the block's channel
+ * count keeps its word).  At most 256 slots per source, checked per block against the table in force: the upload returns M17HIP_ESTATE, nothing queued.
+ * guard_bins = X, 3 .. points / 4: the least distance of two reported carriers, and the distance within which a held slot covers a peak
+ * (m17hip.wide_scan_guard_bins: ceil(9000 / (rate / points))).  Per block and source, N the points, J the block's frames, B the squelch's half_bins,
+ * row = the source's row of the plane, med | . | open | close the source's column of the block's floor plane, to = squelch_level(open, J), tc likewise:
+ *     BAND.  band[k] = squelch_band(row, N, k, B) of EVERY bin, unchanged.
+ *     PEAK.  scan_peak(band, N, k, X, to): bin k is a peak iff band[k] >= to — a true comparison: a NaN band is no peak — and no bin j within circular
+ *     distance X beats it; j beats k iff band[j] > band[k], or band[j] == band[k] && j < k (a NaN neighbour beats nothing).  A local maximum, deliberately
+ *     not wide_spectrum_carriers' greedy pick with shoulders: it does not depend on the order of evaluation, so it is parallel, and a monotone skirt is
+ *     never a peak (its inner neighbour beats it).  A row flat to the bit has exactly one candidate, bin 0.
+ *     WORD.  scan_fcw(row, N, logn, k, B, med): w_d = max(row[(k + d) & (N - 1)] - med, +0) for d = -B .. B ascending (a NaN difference counts +0); two
+ *     chains from +0 in that order, sum w_d and sum (float)d * w_d (the product rounded, then the add); delta their quotient, or 0 where the sum of weights
+ *     is not positive or the quotient is not finite; the word is (int32)(k << (32 - logn)) + (int32)rint(delta * 2^(32 - logn)), wrapping.  delta is NOT
+ *     clamped: a peak on the edge of a plateau of the band lies up to B bins from the carrier, and the centroid is what brings the word back.
+ *     THE OPEN GUARANTEE.  scan_assign: where band[squelch_bin(word)] < to, the bin-centre word of k serves instead, whose band is not below `to`.  The
+ *     unchanged wide_squelch_kernel therefore opens every slot in the block that assigns it.
+ *     HELD.  A slot is held iff squelch_step(hold[c], band[squelch_bin(fcw_c)], to, tc, hang, J) has the open bit: exactly what the squelch kernel will
+ *     compute from the unchanged word.  A held slot covers the peaks within circular distance X of its bin and is never retuned (no jitter; AFC is out of
+ *     scope).
+ *     ASSIGN.  The uncovered peaks are ranked by band descending, then bin ascending; the peak of rank r goes to the r-th slot of the source that is not
+ *     held, in ascending channel order; the peaks left over are counted in missed[s].  A slot neither held nor assigned keeps its word and the squelch
+ *     closes it by its own rule.
+ *     IDLE.  A block without a frame (J == 0), and a source whose open level or median is not finite, assign nothing, hold nothing and leave every word.
+ * m17cxx/detail/core.h has scan_peak, scan_beats, scan_distance, scan_fcw, scan_assign, scan_idle and scan_source (a source's block, the host form): one
+ * text for host and device.  On the device wide_scan_kernel (csrc/m17_scan_kernel.hpp; a workgroup of 256 per source; row and bands in LDS, the peaks and the
+ * slots compacted in ascending order by ballots and prefix counts, a rank by counting) writes the block's COMPLETE table [source | fcw] into a plane of the
+ * scan's own: the entries of the channels that are no slots, and every source, are the host's; only a slot's word is the device's.  That block's squelch
+ * kernel and tuner read this plane in place of the host's table; none of them is changed.
+ * With the scan on m17hip_wide_channels keeps working for every channel, except that a call which would change a slot's SOURCE returns M17HIP_ESTATE with
+ * nothing changed.  A slot's fcw entry is its SEED: it is read where the scan's feed starts over — the first block after this call, after either squelch
+ * call or the floor call that leaves the scan on, after m17hip_demod_reset — and ignored otherwise.  This call starts the hold counts and the floor over as
+ * either squelch call does, holds for the blocks uploaded after it and never waits for anything in flight.  pool == NULL with n == 0 turns the scan off (the
+ * host's table serves again, the slots' seeds included); so does everything that turns off one of the three things it needs: every m17hip_wide_squelch and
+ * _squelch_slots call, m17hip_wide_squelch_floor with both ratios 0, m17hip_wide_spectrum, a configuration.  With the scan off a block queues exactly what
+ * it queued before.  m17hip_demod_reset_channels and m17hip_set_channel_polarity behave as they do.
+ * THE RESET RULE.  A freshly assigned slot starts a new transmission on a demodulator that has been fed zeros — the false-lock case recorded under ABI 620.
+ * The caller reads bit 1 of the flags from m17hip_wide_scan_fetch and lists those channels in m17hip_demod_reset_channels before the block's
+ * m17hip_demod_run; by stream order the fetch waits for about a spectrum's worth of work, not for the tuner (when it returns in practice: NOTES.md).  (The listed reset also zeroes those channels' hold counts: the
+ * next block holds them on their band alone.)  The Python layer (Context.run), M17Demodulator<float> and the example do this by themselves.
+ * M17HIP_EINVAL, nothing changed: a NULL context; pool NULL with n != 0 or the reverse; n above the context's channels; guard_bins outside 3 .. points / 4.
+ * M17HIP_ESTATE, nothing changed: no wideband configuration; a raster; between m17hip_demod_front and its run; turning it on without the spectrum (or with
+ * more than 4096 points), without the block squelch (the slot mode is none) or without the floor.  m17hip_timing_get index 20 is the kernel, one entry per
+ * scanned block; m17hip_iq_bytes counts the pool marks, the carry and the planes.
+ * OUT OF SCOPE: the scan under the slot squelch or the raster; a reset list made on the device, so that the run needs no fetch; AFC of held slots from the
+ * meter; bins to ignore — a dongle's DC spike is a carrier to the scan, which spends a slot on it; slots that move between sources; compacting the tuner's
+ * grid to open channels. */
+int m17hip_wide_scan(m17hip_ctx* ctx, const uint8_t* pool, uint32_t n, uint32_t guard_bins);
+/* The scan of the latest block uploaded with it on (back = 0) or of the one before it (back = 1): fcw_host[C] the table the block was tuned with (every
+ * channel's word, slot or not), flags_host[C] bit 0 = is a slot, bit 1 = assigned in this block, bit 2 = held over, missed_host[S] the peaks that found no
+ * free slot (room for 256 serves every configuration); *channels = C, *sources = S, *frames = J (each may be NULL).  It waits for that block's scan kernel
+ * only — not for its squelch kernel, its tuner, a run or a later block — and copies on the squelch's fetch stream.  cap_channels < C: the first
+ * cap_channels entries and all of missed are written and M17HIP_ETRUNC returned, *channels = C.  M17HIP_ESTATE if no such block exists: the scan is off,
+ * not enough blocks since it was turned on, or none since m17hip_demod_reset.  M17HIP_EINVAL for back > 1, a NULL context or a NULL array; nothing is
+ * written then. */
+int m17hip_wide_scan_fetch(m17hip_ctx* ctx, uint32_t back, int32_t* fcw_host, uint32_t* flags_host, uint32_t* missed_host, uint64_t cap_channels,
+                           uint32_t* channels, uint32_t* sources, uint32_t* frames);
 
 /* ---- the wideband signal generator: FM-multiplex basebands on the device (ABI 617) -----------------------------
  * Everything above is the receive side.  The project owns the transmit side up to baseband (m17hip_synth_tx_i16); what the reference's users attach behind
@@ -1204,7 +1269,8 @@ int m17hip_timing_enable(m17hip_ctx* ctx, int on);
  * 16 = meter (wide_meter_kernel of m17hip_wide_meter, one entry per metered block; the metered tuner keeps its own index),
  * 17 = squelch (wide_squelch_kernel of m17hip_wide_squelch, one entry per squelched block; its spectrum and its tuner keep their own indices),
  * 18 = squelch_slots (the three kernels of m17hip_wide_squelch_slots, one entry per squelched block; likewise),
- * 19 = squelch_floor (squelch_floor_kernel of m17hip_wide_squelch_floor, one entry per block uploaded with that mode on; none with it off). */
+ * 19 = squelch_floor (squelch_floor_kernel of m17hip_wide_squelch_floor, one entry per block uploaded with that mode on; none with it off),
+ * 20 = scan (wide_scan_kernel of m17hip_wide_scan, one entry per scanned block; none with it off). */
 int m17hip_timing_get(m17hip_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int m17hip_timing_reset(m17hip_ctx* ctx);
 

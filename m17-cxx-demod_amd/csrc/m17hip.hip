@@ -15,6 +15,7 @@
 #include "m17_spectrum_kernels.hpp"
 #include "m17_meter_kernels.hpp"
 #include "m17_squelch_kernels.hpp"
+#include "m17_scan_kernel.hpp"
 #include "m17_wide_tx_kernels.hpp"
 #include "m17_state.hpp"
 #include "m17_wave_demod_kernel.hpp"
@@ -41,7 +42,7 @@ using namespace m17;
 
 namespace {
 
-enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_SQUELCH_SLOTS, KT_SQUELCH_FLOOR, KT_N };
+enum { KT_FIR = 0, KT_DCD, KT_SEQ, KT_DEC, KT_CORR, KT_COMPACT, KT_GATE, KT_VOICE, KT_IQ, KT_WIDE, KT_WIDE2, KT_CHAN, KT_SURVEY, KT_RESAMPLE, KT_SPECTRUM, KT_WIDE_TX, KT_METER, KT_SQUELCH, KT_SQUELCH_SLOTS, KT_SQUELCH_FLOOR, KT_SCAN, KT_N };
 
 // Device memory (hipMalloc) that gives itself back: the member that names a buffer owns it.  Reads as the pointer it holds (nullptr while
 // empty).  It never synchronises: a caller that regrows a buffer which queued work may still read waits for that work first.  A failed
@@ -459,6 +460,27 @@ struct m17hip_ctx {
             void forget() { valid[0] = valid[1] = false; }
             ~Squelch() { if (fetch) (void)hipStreamDestroy(fetch); }
         } sq;
+        // The carrier scan (m17hip_wide_scan; csrc/m17_scan_kernel.hpp): `on` needs the block squelch and its floor on (active()).  The pool marks [maxC]
+        // stay on the host until the next block brings them to the device in a turn-taking table (`dirty`).  wide_scan_kernel goes between the block's
+        // floor kernel and its squelch kernel and writes the block's COMPLETE channel table [source[maxC] | fcw[maxC]] into the plane whose turn it is: the
+        // squelch kernel and the tuner of that block read it in place of the host's table.  Two planes, two flag planes [maxC] and two miss planes [256]
+        // take turns with the squelch's state planes — the next writer of a plane, two blocks on, is behind this block's tuner through ev_iq —, each with
+        // the event recorded behind the block's scan kernel.  The slots' words [maxC] are the feed's carry, ordered by ev_iq like `hold`; the squelch's
+        // `fresh` says that the block's kernel takes the host's words, the seeds, in their place.
+        struct Scan {
+            bool on = false;
+            uint32_t X = 0;
+            std::vector<uint32_t> pool;   // [maxC] while on
+            bool dirty = true;
+            TurnTable dev;
+            DevBuf<uint32_t> carry, plane[2], flags[2], missed[2];
+            Event ev[2];
+            bool valid[2] = {false, false};
+            uint32_t C[2] = {0, 0}, frames[2] = {0, 0};
+            int latest = 0;
+            void forget() { valid[0] = valid[1] = false; }
+        } sc;
+        bool scanning() const { return sc.on && sq.on && !sq.slots && sq.floor; }
         size_t bytes() const
         {
             return (taps.size() + taps2.size() + sv.scratch.size() + sv.plane[0].size() + sv.plane[1].size() + sp.scratch.size() + sp.plane[0].size() +
@@ -466,7 +488,8 @@ struct m17hip_ctx {
                    (hist[0].size() + hist[1].size() + znew.size() + tw.size()) * sizeof(float2) + (dev.words() + rdev.words() + sp.dev.words()) * 4 +
                    (sq.dev.words() + sq.hold.size() + sq.state[0].size() + sq.state[1].size() + sq.band[0].size() + sq.band[1].size() +
                     sq.sbits.size() + sq.mask[0].size() + sq.mask[1].size() + sq.sband[0].size() + sq.sband[1].size() + sq.fcarry.size() + sq.fplane[0].size() +
-                    sq.fplane[1].size()) * 4;
+                    sq.fplane[1].size() + sc.dev.words() + sc.carry.size() + sc.plane[0].size() + sc.plane[1].size() + sc.flags[0].size() + sc.flags[1].size() +
+                    sc.missed[0].size() + sc.missed[1].size()) * 4;
         }
     } wide;
     // THE WIDEBAND SIGNAL GENERATOR (m17hip_synth_wide_config, m17hip_synth_wide; csrc/m17_wide_tx_kernels.hpp): the int16 input slab's rows FM-modulated into
@@ -1315,7 +1338,7 @@ int m17hip_advice(const m17hip_ctx* ctx)
     const int n = hw_queues_env();
     return (n < 8 ? M17HIP_ADVICE_HW_QUEUES : 0) | (n < 16 ? M17HIP_ADVICE_HW_QUEUES_16 : 0);
 }
-int m17hip_version(void) { return 621; }
+int m17hip_version(void) { return 622; }
 
 // The two device tables every matched-filter form reads (c->taps: K5, K2, the rolled K1; c->taps_skew: the skew K1 forms), from taps149 or, for
 // nullptr, the RRC taps.  Tap 150 (and the padding behind it) is zero.  Blocking copies: the caller has nothing in flight that reads them.
@@ -1683,6 +1706,7 @@ static int iq_fresh_feed(m17hip_ctx* c, const uint32_t* channels, uint32_t n)
             c->wide.mt.outputs = 0;
             c->wide.sq.forget();   // (the squelch stays on: every channel's hold count starts over)
             c->wide.sq.fresh = true;
+            c->wide.sc.forget();   // (the scan likewise: its slots take their seeds again)
         }
     } else {
         auto& sq = c->wide.sq;
@@ -1952,6 +1976,47 @@ static int squelch_levels_done(m17hip_ctx* c, hipStream_t st)
     if (!sq.floor) HIPCHK(c, sq.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
     return M17HIP_OK;
 }
+// The carrier scan of one block (m17hip_wide_scan is on), on the block's stream between its floor kernel and its squelch kernel: it reads the plane
+// launch_spectrum has just queued, the floor plane `p` squelch_levels has just queued, the host's channel table (launch_tune has put the stream behind its
+// upload and records the read behind the tuner), the pool marks and the hold counts, and writes the scan's planes whose turn it is.  *table is what the
+// block's squelch kernel and tuner read from here on.
+static int launch_scan(m17hip_ctx* c, int p, uint32_t C, hipStream_t st, const uint32_t** table)
+{
+    auto& w = c->wide;
+    auto& sq = w.sq;
+    auto& sc = w.sc;
+    const int ps = w.sp.latest;
+    int r;
+    for (auto& e : sc.ev) if (!e) HIPCHK(c, e.create());
+    if (!sc.carry) {   // ([maxC], [2 maxC], [maxC] and [256], once per configuration: never regrown)
+        if ((r = alloc_code(c, sc.carry.alloc(c->maxC)))) return r;
+        for (auto& b : sc.plane) if ((r = alloc_code(c, b.alloc(2 * (size_t)c->maxC)))) return r;
+        for (auto& b : sc.flags) if ((r = alloc_code(c, b.alloc(c->maxC)))) return r;
+        for (auto& b : sc.missed) if ((r = alloc_code(c, b.alloc(256)))) return r;
+        sq.fresh = true;
+    }
+    if (sc.dirty || !sc.dev.live()) {   // the pool marks, into the copy no queued launch reads
+        uint32_t* staging = nullptr;
+        HIPCHK(c, sc.dev.begin_write(c->maxC, &staging));
+        std::memcpy(staging, sc.pool.data(), (size_t)c->maxC * 4);
+        HIPCHK(c, sc.dev.publish(c->maxC, st));
+        sc.dirty = false;
+    }
+    HIPCHK(c, sc.dev.before_read(st));
+    sc.valid[p] = false;
+    {
+        Timed tm(c, KT_SCAN, st);
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(w.S), dim3(SCAN_THREADS), 0, st, w.sp.plane[ps].get(), w.sp.logn, w.sp.frames[ps], w.dev.dev(), c->maxC,
+                           sc.dev.dev(), sq.fplane[p].get(), w.S, sq.B, sc.X, sq.hang, sq.hold.get(), sc.carry.get(), sq.fresh ? 1u : 0u, C, sc.plane[p].get(),
+                           sc.flags[p].get(), sc.missed[p].get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, sc.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));
+    HIPCHK(c, hipEventRecord(sc.ev[p], st));
+    sc.C[p] = C; sc.frames[p] = w.sp.frames[ps]; sc.valid[p] = true; sc.latest = p;
+    *table = sc.plane[p].get();
+    return M17HIP_OK;
+}
 // The squelch of one block (m17hip_wide_squelch is on), on the block's stream between its spectrum and its tuner: it reads the plane launch_spectrum has
 // just queued, the channel table the tuner is about to read and the levels, steps the hold counts and writes the state and band planes whose turn it is.
 // The state plane is what the block's tuner reads: its next writer, two blocks on, is behind that tuner through ev_iq.
@@ -1972,10 +2037,12 @@ static int launch_squelch(m17hip_ctx* c, uint32_t C, hipStream_t st)
     sq.valid[p] = false;
     const float* levels = nullptr;
     if ((r = squelch_levels(c, p, w.sp.frames[ps], st, &levels))) return r;
+    const uint32_t* table = w.dev.dev();
+    if (w.scanning()) if ((r = launch_scan(c, p, C, st, &table))) return r;   // (m17hip_wide_scan: the block's table is the scan's from here on)
     {
         Timed tm(c, KT_SQUELCH, st);
         hipLaunchKernelGGL(wide_squelch_kernel, dim3((C + SQUELCH_THREADS - 1) / SQUELCH_THREADS), dim3(SQUELCH_THREADS), 0, st, w.sp.plane[ps].get(), w.sp.logn,
-                           w.sp.frames[ps], w.dev.dev(), c->maxC, levels, w.S, sq.B, sq.hang, sq.hold.get(), sq.state[p].get(), sq.band[p].get(), C);
+                           w.sp.frames[ps], table, c->maxC, levels, w.S, sq.B, sq.hang, sq.hold.get(), sq.state[p].get(), sq.band[p].get(), C);
         HIPCHK(c, hipGetLastError());
     }
     if ((r = squelch_levels_done(c, st))) return r;
@@ -2079,6 +2146,8 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         if (int r = launch_spectrum<IQT>(c, src, pitch, W, st)) return r;
         if (int r = slots ? launch_squelch_slots(c, C, T, W, w.U ? RG * w.U : (uint32_t)WIDE_TILE, tiles, st) : launch_squelch(c, C, st)) return r;
     }
+    // the table the tuner reads: the host's, or — m17hip_wide_scan — the one the block's scan kernel has just written (launch_squelch)
+    const uint32_t* table = squelch && w.scanning() ? w.sc.plane[w.sc.latest].get() : w.dev.dev();
     const SquelchIn qi{squelch ? w.sq.state[w.sq.latest].get() : nullptr};
     const SquelchTilesIn ti{slots ? w.sq.mask[w.sq.latest].get() : nullptr, squelch_tile_words(tiles)};
     if (w.U) {
@@ -2087,78 +2156,78 @@ static int launch_tune(m17hip_ctx* c, const void* dev, size_t pitch, float* x, u
         if (slots && meter)
             tm.launch(resample_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
                       resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
-                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
+                      w.D, G, Q, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
         else if (slots)
             tm.launch(resample_kernel<IQT, false, true, SquelchTilesIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
                       resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
-                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
+                      w.D, G, Q, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
         else if (squelch && meter)
             tm.launch(resample_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
                       resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
-                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
+                      w.D, G, Q, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
         else if (squelch)
             tm.launch(resample_kernel<IQT, false, true, SquelchIn>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS),
                       resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U,
-                      w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
+                      w.D, G, Q, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
         else if (meter)
             tm.launch(resample_kernel<IQT, true, false, MeterOut>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st,
-                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count,
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, table, c->maxC, (uint32_t)w.count,
                       x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
         else
         tm.launch(resample_kernel<IQT>, dim3((T / w.U + G - 1) / G, C), dim3(WIDE_THREADS), resample_lds_bytes(w.L, w.R, w.L2, w.U, w.D, G, Q), st, src, pitch,
-                  W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, w.dev.dev(), c->maxC, (uint32_t)w.count, x,
+                  W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.U, w.D, G, Q, table, c->maxC, (uint32_t)w.count, x,
                   c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else if (w.R2) {
         TimedK tm(c, KT_WIDE2);
         if (slots && meter)
             tm.launch(tune2_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
                       wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
-                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
+                      wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, ti);
         else if (slots)
             tm.launch(tune2_kernel<IQT, false, true, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
                       wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
-                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
+                      wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, ti);
         else if (squelch && meter)
             tm.launch(tune2_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
                       wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
-                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
+                      wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo, qi);
         else if (squelch)
             tm.launch(tune2_kernel<IQT, false, true, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS),
                       wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2,
-                      wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
+                      wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, qi);
         else if (meter)
             tm.launch(tune2_kernel<IQT, true, false, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src,
-                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC,
                       (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain, mo);
         else
         tm.launch(tune2_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide2_lds_bytes(w.L, w.R, w.L2, w.R2), st, src, pitch, W,
-                  w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), w.dev.dev(), c->maxC,
+                  w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.taps2.get(), w.L2, w.R2, wide2_q(w.L, w.R, w.L2, w.R2), table, c->maxC,
                   (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     } else {
         TimedK tm(c, KT_WIDE);
         if (slots && meter)
             tm.launch(tune_kernel<IQT, true, true, MeterOut, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st,
-                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
                       w.znew.get(), gain, mo, ti);
         else if (slots)
             tm.launch(tune_kernel<IQT, false, true, SquelchTilesIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src,
-                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
                       w.znew.get(), gain, ti);
         else if (squelch && meter)
             tm.launch(tune_kernel<IQT, true, true, MeterOut, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st,
-                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      src, pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
                       w.znew.get(), gain, mo, qi);
         else if (squelch)
             tm.launch(tune_kernel<IQT, false, true, SquelchIn>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src,
-                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
+                      pitch, W, w.hist[w.par].get(), w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(),
                       w.znew.get(), gain, qi);
         else if (meter)
             tm.launch(tune_kernel<IQT, true, false, MeterOut>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W,
-                      w.hist[w.par].get(), w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(),
+                      w.hist[w.par].get(), w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(),
                       gain, mo);
         else
         tm.launch(tune_kernel<IQT>, dim3((T + WIDE_TILE - 1) / WIDE_TILE, C), dim3(WIDE_THREADS), wide_lds_bytes(w.L, w.R), st, src, pitch, W, w.hist[w.par].get(),
-                  w.taps.get(), w.L, w.R, w.dev.dev(), c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
+                  w.taps.get(), w.L, w.R, table, c->maxC, (uint32_t)w.count, x, c->xpitch, T, c->iq_carry.get(), w.znew.get(), gain);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, w.dev.after_read(st == c->stream ? RD_MAIN : RD_FRONT, st));   // (two readers: the main stream and the copy stream)
@@ -2223,6 +2292,11 @@ static int upload_wide(m17hip_ctx* c, const void* p, float gain, uint32_t C, uin
         if (!c->wide.S) return M17HIP_ESTATE;   // (m17hip_wide_config first)
         if (c->wide.U && T % c->wide.U) return M17HIP_EINVAL;   // (a block holds whole groups of `up` outputs: the phase never depends on the feed's history)
         W = c->wide.row(T);
+        if (c->wide.scanning()) {   // (m17hip_wide_scan: at most 256 slots a source among the block's channels, by the table in force)
+            uint32_t slots[256] = {0};
+            for (uint32_t ch = 0; ch < C && ch < c->maxC; ++ch)
+                if (c->wide.sc.pool[ch] && ++slots[c->wide.table[ch]] > core::SCAN_MAX_SLOTS) return M17HIP_ESTATE;
+        }
         return pitch < W || W > 0xFFFFFFFFull ? M17HIP_EINVAL : M17HIP_OK;   // (the kernels count a row's samples in 32 bits)
     };
     return upload_frame<float>(c, p, C, T, (how & IQ_STAGED) != 0, own, [&](float* x, hipStream_t st) -> int {
@@ -2329,6 +2403,11 @@ static int wide_setup(m17hip_ctx* c, uint32_t sources, int iq_format, uint32_t d
     w.sq.hold.release(&c->last_hip);
     w.sq.fcarry.release(&c->last_hip);
     for (auto& b : w.sq.fplane) b.release(&c->last_hip);
+    w.sc.on = false; w.sc.forget();   // (the scan goes with the squelch)
+    w.sc.carry.release(&c->last_hip);
+    for (auto& b : w.sc.plane) b.release(&c->last_hip);
+    for (auto& b : w.sc.flags) b.release(&c->last_hip);
+    for (auto& b : w.sc.missed) b.release(&c->last_hip);
     for (auto& b : w.sq.state) b.release(&c->last_hip);
     for (auto& b : w.sq.band) b.release(&c->last_hip);
     w.sq.sbits.release(&c->last_hip);
@@ -2442,6 +2521,8 @@ int m17hip_wide_channels(m17hip_ctx* c, const uint32_t* source, const int32_t* f
     auto& w = c->wide;
     if (!w.S || w.M) return M17HIP_ESTATE;   // (which sources exist is m17hip_wide_config's to say; under a raster the table is m17hip_wide_raster_channels')
     for (uint32_t ch = 0; ch < n; ++ch) if (source[ch] >= w.S) return M17HIP_EINVAL;
+    if (w.scanning())   // (m17hip_wide_scan: a slot stays with its source; its word is its seed, read where the scan's feed starts over)
+        for (uint32_t ch = 0; ch < n; ++ch) if (w.sc.pool[ch] && source[ch] != w.table[ch]) return M17HIP_ESTATE;
     for (uint32_t ch = 0; ch < n; ++ch) { w.table[ch] = source[ch]; w.table[c->maxC + ch] = (uint32_t)fcw[ch]; }
     w.dirty = true;   // (the next block uploaded brings it to the device: nothing is queued and nothing waited for here)
     return M17HIP_OK;
@@ -2563,6 +2644,7 @@ int m17hip_wide_spectrum(m17hip_ctx* c, uint32_t points, uint32_t hop, const flo
     if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the planes have a row per source; the staged block belongs to the run being made)
     sp.forget();   // (the next block uploaded is the first it holds for: nothing is queued and nothing waited for here)
     w.sq.on = false; w.sq.forget();   // (the squelch's bins are this call's to redefine: off until m17hip_wide_squelch is called again)
+    w.sc.on = false; w.sc.forget();   // (and the scan with it)
     sp.points = points;
     if (!points) return M17HIP_OK;
     sp.logn = spectrum_logn(points); sp.hop = hop;
@@ -2659,6 +2741,7 @@ static int squelch_set(m17hip_ctx* c, uint32_t half_bins, const float* open_leve
     sq.fresh = true;
     sq.on = !off;
     sq.floor = false;   // (the levels this call carries serve; m17hip_wide_squelch_floor comes after it)
+    w.sc.on = false; w.sc.forget();   // (the scan needs the floor: m17hip_wide_scan comes after that)
     if (off) return M17HIP_OK;
     sq.B = half_bins; sq.hang = hang; sq.slots = slots; sq.lead = lead;
     sq.levels.assign(open_level, open_level + nlevels);
@@ -2729,7 +2812,8 @@ int m17hip_wide_squelch_floor(m17hip_ctx* c, float open_ratio, float close_ratio
     sq.forget();   // (as either squelch call: the next block uploaded is the first it holds for, hold counts zeroed and floor forgotten; nothing is queued here)
     sq.fresh = true;
     sq.floor = !off && sq.on;
-    if (off) return M17HIP_OK;
+    c->wide.sc.forget();   // (the scan's feed starts over with the squelch's)
+    if (off) { c->wide.sc.on = false; return M17HIP_OK; }   // (the scan reads the floor plane: off with it)
     sq.f_open = open_ratio; sq.f_close = close_ratio; sq.f_rise = rise; sq.f_fall = fall; sq.f_min = floor_min;
     return M17HIP_OK;
 }
@@ -2749,6 +2833,56 @@ int m17hip_wide_squelch_floor_fetch(m17hip_ctx* c, uint32_t back, float* plane_h
     if (sources) *sources = c->wide.S;
     if (frames) *frames = sq.frames[p];
     return M17HIP_OK;
+}
+// ---- the carrier scan (ABI 622): the block's carriers found and a pool of channels tuned to them on the device, in front of the block squelch -----------
+int m17hip_wide_scan(m17hip_ctx* c, const uint8_t* pool, uint32_t n, uint32_t guard_bins)
+{
+    if (!c) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sc = w.sc;
+    const bool off = !pool && n == 0;
+    if (!off && (!pool || n < 1 || n > c->maxC || guard_bins < 3)) return M17HIP_EINVAL;
+    if (!w.S || c->front_queued) return M17HIP_ESTATE;   // (the staged block belongs to the run being made)
+    if (!off) {
+        if (w.M || !w.sp.points || w.sp.points > SCAN_MAX_POINTS || !w.sq.on || w.sq.slots || !w.sq.floor) return M17HIP_ESTATE;
+        if (guard_bins > w.sp.points / 4) return M17HIP_EINVAL;
+    }
+    if (off && !sc.on) return M17HIP_OK;   // (off stays off: the squelch's feed is not touched)
+    // as either squelch call and the floor call: the next block uploaded is the first it holds for, the hold counts and the floor start over and the slots
+    // take their seeds; nothing is queued and nothing waited for here
+    w.sq.forget();
+    w.sq.fresh = true;
+    sc.forget();
+    sc.on = !off;
+    if (off) return M17HIP_OK;
+    sc.X = guard_bins;
+    sc.pool.assign(c->maxC, 0u);
+    for (uint32_t ch = 0; ch < n; ++ch) sc.pool[ch] = pool[ch] ? 1u : 0u;
+    sc.dirty = true;
+    return M17HIP_OK;
+}
+int m17hip_wide_scan_fetch(m17hip_ctx* c, uint32_t back, int32_t* fcw_host, uint32_t* flags_host, uint32_t* missed_host, uint64_t cap_channels,
+                           uint32_t* channels, uint32_t* sources, uint32_t* frames)
+{
+    if (!c || back > 1 || !fcw_host || !flags_host || !missed_host) return M17HIP_EINVAL;
+    auto& w = c->wide;
+    auto& sc = w.sc;
+    if (!w.S || !w.scanning()) return M17HIP_ESTATE;
+    const int p = sc.latest ^ (int)back;
+    if (!sc.valid[p]) return M17HIP_ESTATE;
+    const size_t C = sc.C[p], n = cap_channels < C ? (size_t)cap_channels : C;
+    GUARD(c);
+    HIPCHK(c, hipEventSynchronize(sc.ev[p]));   // (that block's scan kernel and what its stream held in front of it: not its squelch kernel, not its tuner, no run, no later block)
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(fcw_host, sc.plane[p].get() + c->maxC, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.sq.fetch));
+        HIPCHK(c, hipMemcpyAsync(flags_host, sc.flags[p].get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.sq.fetch));
+    }
+    HIPCHK(c, hipMemcpyAsync(missed_host, sc.missed[p].get(), (size_t)w.S * sizeof(uint32_t), hipMemcpyDeviceToHost, w.sq.fetch));
+    HIPCHK(c, hipStreamSynchronize(w.sq.fetch));
+    if (channels) *channels = (uint32_t)C;
+    if (sources) *sources = w.S;
+    if (frames) *frames = sc.frames[p];
+    return n < C ? M17HIP_ETRUNC : M17HIP_OK;
 }
 int m17hip_upload_wide(m17hip_ctx* c, const void* host, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, host, gain, C, T, pitch, IQ_FROM_HOST); }
 int m17hip_upload_wide_device(m17hip_ctx* c, const void* dev, float gain, uint32_t C, uint32_t T, size_t pitch) { return upload_wide(c, dev, gain, C, T, pitch, 0); }

@@ -219,6 +219,30 @@ public:
         plane.resize((size_t)4 * n);
         if (sources) *sources = n;
     }
+    // The carrier scan (m17hip_wide_scan), beside wide_spectrum (at most 4096 points), wide_squelch and wide_squelch_floor: pool[c] != 0 makes channel c a
+    // slot of the source its wide_channels entry names; from the blocks uploaded after the call a kernel in front of the squelch finds each source's
+    // carriers in the block's own plane and tunes the source's slots that no carrier holds to them (guard_bins, 3 .. points / 4: the least distance of two
+    // carriers).  wide_scan_off turns it off; so does everything that turns off what it needs.  wide_scan_fetch: the table the latest scanned block (back =
+    // 0) or the one before was tuned with, per channel the flags 1 = slot, 2 = assigned in this block, 4 = held over, per source the carriers that found no
+    // free slot; `assigned`, if given, gets the channels with flag 2 — THE CALLER LISTS THEM IN reset_channels BEFORE THE BLOCK'S run() (a freshly assigned
+    // slot starts a transmission on a demodulator fed zeros).  It waits for that block's scan kernel only.
+    void wide_scan(const std::vector<uint8_t>& pool, uint32_t guard_bins)
+    {
+        check(m17hip_wide_scan(ctx_, pool.data(), (uint32_t)pool.size(), guard_bins), "m17hip_wide_scan");
+    }
+    void wide_scan_off() { check(m17hip_wide_scan(ctx_, nullptr, 0, 0), "m17hip_wide_scan"); }
+    void wide_scan_fetch(uint32_t back, std::vector<int32_t>& fcw, std::vector<uint32_t>& flags, std::vector<uint32_t>& missed,
+                         std::vector<uint32_t>* assigned = nullptr, uint32_t* frames = nullptr)
+    {
+        fcw.resize(channels_); flags.resize(channels_); missed.resize(256);
+        uint32_t n = 0, s = 0;
+        check(m17hip_wide_scan_fetch(ctx_, back, fcw.data(), flags.data(), missed.data(), fcw.size(), &n, &s, frames), "m17hip_wide_scan_fetch");
+        fcw.resize(n); flags.resize(n); missed.resize(s);
+        if (assigned) {
+            assigned->clear();
+            for (uint32_t c = 0; c < n; ++c) if (flags[c] & 2u) assigned->push_back(c);
+        }
+    }
     // The wideband signal generator (m17hip_synth_wide_config): the int16 input slab's basebands FM-modulated into `sources` wide IQ streams at
     // 48000 * p / q samples per second.  k = 0: M17's deviation (wide_tx_k).  synth_wide_channels: channel c transmits as tx[c] says from the next block.
     // synth_wide: one block, W = samples / q * p complex samples per source into dst[sources][pitch] — host memory, or device memory with device = true —,

@@ -161,7 +161,7 @@ struct M17Demodulator
             taps.resize(n);
         }
         wide_decim_ = decim;
-        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        spectrum_points_ = 0; scan_ = false;   // (every configuration turns the spectrum off, and the scan with it)
         meter_window_ = 0;      // (and the meter)
         squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = 0;
@@ -200,7 +200,7 @@ struct M17Demodulator
             if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
         }
         wide_decim_ = decim1 * decim2;
-        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        spectrum_points_ = 0; scan_ = false;   // (every configuration turns the spectrum off, and the scan with it)
         meter_window_ = 0;      // (and the meter)
         squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = decim1;
@@ -243,7 +243,7 @@ struct M17Demodulator
             if (taps2.empty()) taps2.assign(d2.begin(), d2.begin() + n2);
         }
         wide_decim_ = decim1 * down;   // (the samples of a group)
-        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        spectrum_points_ = 0; scan_ = false;   // (every configuration turns the spectrum off, and the scan with it)
         meter_window_ = 0;      // (and the meter)
         squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = decim1;
@@ -281,7 +281,7 @@ struct M17Demodulator
             taps.resize(n);
         }
         wide_decim_ = decim;
-        spectrum_points_ = 0;   // (every configuration turns the spectrum off)
+        spectrum_points_ = 0; scan_ = false;   // (every configuration turns the spectrum off, and the scan with it)
         meter_window_ = 0;      // (and the meter)
         squelch_mode_ = 0;      // (and the squelch)
         wide_r1_ = 0;
@@ -332,7 +332,7 @@ struct M17Demodulator
         gpu_->wide_spectrum(points, hop, window.empty() ? nullptr : window.data(), (uint32_t)window.size());
         spectrum_points_ = points;
         spectrum_report_ = std::move(report);
-        squelch_mode_ = 0;   // (every wide_spectrum call turns the squelch off)
+        squelch_mode_ = 0; scan_ = false;   // (every wide_spectrum call turns the squelch off, and the scan with it)
         return true;
     }
     // The spectrum squelch beside wide_config / wide_rate on the GPU path (m17hip_wide_squelch; wide_spectrum first): the NEXT block runs unsquelched, and
@@ -353,6 +353,7 @@ struct M17Demodulator
         squelch_report_ = std::move(report);
         squelch_slots_ = false;
         squelch_floor_ = false;
+        scan_ = false;
         squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
         return true;
     }
@@ -373,6 +374,7 @@ struct M17Demodulator
         squelch_slots_report_ = std::move(report);
         squelch_slots_ = true;
         squelch_floor_ = false;
+        scan_ = false;
         squelch_mode_ = 1;   // (armed: the next block's plane sets the levels)
         return true;
     }
@@ -395,6 +397,26 @@ struct M17Demodulator
         squelch_floor_report_ = std::move(report);
         squelch_floor_ = true;
         squelch_mode_ = 2;
+        return true;
+    }
+    // The carrier scan (m17hip_wide_scan), behind wide_squelch_floor: a pool of the one channel, so the demodulator follows the strongest carrier of its
+    // source — where no carrier holds it, the block's scan tunes it to the strongest one, from the very block in which that carrier appears — and is reset
+    // before the run of a block that retunes it (a new transmission on a demodulator fed zeros).  The offset given at construction is the seed.  guard_bins 0:
+    // 9 kHz at the source's rate.  After each block `report`, if any, gets the frequency word the block was tuned with, whether it was assigned in this
+    // block, whether a carrier held it, and the carriers that found it taken.  Returns false, with nothing changed, on the host form.
+    using scan_callback_t = std::function<void(int32_t fcw, bool assigned, bool held, uint32_t missed)>;
+    bool wide_scan(uint32_t guard_bins = 0, scan_callback_t report = {})
+    {
+        if (!gpu_) return false;
+        if (!squelch_floor_ || squelch_slots_) throw std::logic_error("M17Demodulator::wide_scan needs wide_squelch and wide_squelch_floor");
+        flush();
+        if (!guard_bins) {
+            const double rate = 48000.0 * (double)wide_decim_ / (double)wide_up_;
+            guard_bins = std::max<uint32_t>(3u, std::min<uint32_t>((uint32_t)std::ceil(9000.0 / (rate / spectrum_points_)), spectrum_points_ / 4));
+        }
+        gpu_->wide_scan({1}, guard_bins);
+        scan_report_ = std::move(report);
+        scan_ = true;
         return true;
     }
     // The channel meter beside any wideband configuration on the GPU path (m17hip_wide_meter): per window of `window` outputs of the feed (16..65536; 0
@@ -598,6 +620,11 @@ private:
             gpu_->wide_squelch_floor_fetch(0, squelch_floor_plane_, nullptr, &frames);
             squelch_floor_report_(squelch_floor_plane_[1], squelch_floor_plane_[2], squelch_floor_plane_[3], frames);
         }
+        if (squelched && squelch_floor_ && scan_) {   // (the reset rule: the fetch waits for the block's scan kernel, not for its tuner)
+            gpu_->wide_scan_fetch(0, scan_fcw_, scan_flags_, scan_missed_, &scan_assigned_);
+            if (!scan_assigned_.empty()) gpu_->reset_channels(scan_assigned_.data(), (uint32_t)scan_assigned_.size());
+            if (scan_report_) scan_report_(scan_fcw_[0], (scan_flags_[0] & 2u) != 0, (scan_flags_[0] & 4u) != 0, scan_missed_[0]);
+        }
         if (meter_window_ && meter_report_) {   // (likewise: the fetch waits for the block's meter kernel)
             uint32_t pieces = 0, outputs = 0;
             uint64_t first_window = 0, first_output = 0;
@@ -657,6 +684,10 @@ private:
     int squelch_mode_ = 0;                           // wide_squelch: 0 = off, 1 = armed (the next block's plane sets the levels), 2 = on
     bool squelch_slots_ = false;                     // wide_squelch_slots in wide_squelch's place
     bool squelch_floor_ = false;                     // wide_squelch_floor: the levels are the device's
+    bool scan_ = false;                              // wide_scan: the one channel is a slot
+    scan_callback_t scan_report_;
+    std::vector<int32_t> scan_fcw_;
+    std::vector<uint32_t> scan_flags_, scan_missed_, scan_assigned_;
     squelch_floor_callback_t squelch_floor_report_;
     std::vector<float> squelch_floor_plane_;
     uint32_t squelch_half_ = 0, squelch_hang_ = 0, squelch_lead_ = 0;

@@ -416,6 +416,98 @@ M17_HD float squelch_track(float F, float f, float rise, float fall)
 }
 // the block's levels per frame from the carried floor: one rounded multiply each (squelch_level takes them from there, as it takes given levels)
 M17_HD float squelch_floor_level(float F, float ratio) { return F * ratio; }
+// ---- a-1i: the carrier scan (m17hip_wide_scan): which bins of a source's row hold a carrier, and the frequency word of one.  band[k] is squelch_band(row,
+// N, k, B) of every bin, `to` the block's open threshold squelch_level(open[s], J).  Bin k is a PEAK iff band[k] >= to — a true comparison: a NaN band is no
+// peak — and no bin within circular distance X beats it; bin j beats k iff band[j] > band[k], or band[j] == band[k] && j < k (a NaN neighbour beats nothing).
+// A local maximum, not a greedy pick: it does not depend on the order of evaluation, a monotone skirt is never a peak (its inner neighbour beats it), and two
+// peaks are more than X bins apart.  3 <= X <= N / 4.
+M17_HD bool scan_beats(float bj, uint32_t j, float bk, uint32_t k) { return bj > bk || (bj == bk && j < k); }
+M17_HD bool scan_peak(const float* band, uint32_t N, uint32_t k, uint32_t X, float to)
+{
+    const float b = band[k];
+    if (!(b >= to)) return false;
+    for (uint32_t d = 1; d <= X; ++d) {
+        const uint32_t lo = (k + N - d) & (N - 1), hi = (k + d) & (N - 1);
+        if (scan_beats(band[lo], lo, b, k) || scan_beats(band[hi], hi, b, k)) return false;
+    }
+    return true;
+}
+// the circular distance of two bins of N
+M17_HD uint32_t scan_distance(uint32_t a, uint32_t b, uint32_t N)
+{
+    const uint32_t d = (a - b) & (N - 1);
+    return d < N - d ? d : N - d;
+}
+// The frequency word of the carrier whose peak is bin k: the bin's word plus the centroid of what the band's bins hold over the row's median `med`.
+// w_d = max(row[(k + d) & (N - 1)] - med, +0) for d = -B .. B ascending (a NaN difference is +0); two chains from +0 in that order, sum w_d and sum d w_d;
+// delta their quotient, or 0 where the sum of weights is not positive or the quotient is not finite (an inf bin).  delta is NOT clamped: on the edge of a
+// plateau it exceeds half a bin, and that is the carrier's offset.  The word wraps.
+M17_HD int32_t scan_fcw(const float* row, uint32_t N, uint32_t logn, uint32_t k, uint32_t B, float med)
+{
+    float sw = 0.0f, sd = 0.0f;
+    for (uint32_t i = 0; i <= 2 * B; ++i) {
+        const float v = row[(k + N - B + i) & (N - 1)] - med;
+        const float wd = v > 0.0f ? v : 0.0f;
+        sw = sw + wd;
+        sd = sd + (float)((int32_t)i - (int32_t)B) * wd;
+    }
+    float delta = sw > 0.0f ? sd / sw : 0.0f;
+    if (!(delta - delta == 0.0f)) delta = 0.0f;
+    const int64_t off = (int64_t)__builtin_rintf(delta * (float)(1u << (32 - logn)));   // (|delta| <= B < N / 2: within int64 by far)
+    return (int32_t)((k << (32 - logn)) + (uint32_t)off);
+}
+// the word a slot is assigned for peak k.  THE OPEN GUARANTEE: where the centroid's word lands in a bin whose band is below `to`, the bin-centre word of k
+// serves, whose band is not: the squelch opens every slot in the block that assigns it.
+M17_HD int32_t scan_assign(const float* row, const float* band, uint32_t N, uint32_t logn, uint32_t k, uint32_t B, float med, float to)
+{
+    const int32_t f = scan_fcw(row, N, logn, k, B, med);
+    return band[squelch_bin(f, logn)] < to ? (int32_t)(k << (32 - logn)) : f;
+}
+// a block assigns nothing where it has no frame or the source's open level or median is not finite
+M17_HD bool scan_idle(uint32_t J, float open_level, float med) { return J == 0 || !(open_level - open_level == 0.0f) || !(med - med == 0.0f); }
+// the flags of a channel in the scan's fetch
+constexpr uint32_t SCAN_SLOT = 1u, SCAN_ASSIGNED = 2u, SCAN_HELD = 4u;
+constexpr uint32_t SCAN_MAX_SLOTS = 256;   // per source
+// One source's block, stated as plainly as possible (the host form; wide_scan_kernel gives the same words).  slot[0 .. n) are the source's pool channels
+// in ascending order, fcw[] and hold[] indexed by CHANNEL: fcw the words in front of the block, rewritten for the assigned slots; flags[] by channel gets
+// SCAN_SLOT | SCAN_ASSIGNED | SCAN_HELD.  A slot is HELD iff squelch_step of its unchanged word has the open bit — what the squelch kernel will compute —
+// and covers the peaks within X of its bin; the uncovered peaks, band descending then bin ascending, go to the slots that are not held in ascending
+// order.  Returns the peaks left over.  `scratch` holds N floats (the bands).
+M17_HD uint32_t scan_source(const float* row, uint32_t N, uint32_t logn, uint32_t J, uint32_t B, uint32_t X, float open_level, float close_level, float med,
+                            uint32_t hang, const uint32_t* slot, uint32_t n, const uint32_t* hold, int32_t* fcw, uint32_t* flags, float* scratch)
+{
+    for (uint32_t i = 0; i < n; ++i) flags[slot[i]] = SCAN_SLOT;
+    if (scan_idle(J, open_level, med)) return 0;
+    const float to = squelch_level(open_level, J), tc = squelch_level(close_level, J);
+    for (uint32_t k = 0; k < N; ++k) scratch[k] = squelch_band(row, N, k, B);
+    for (uint32_t i = 0; i < n; ++i)
+        if (squelch_step(hold[slot[i]], scratch[squelch_bin(fcw[slot[i]], logn)], to, tc, hang, J) & SQUELCH_OPEN) flags[slot[i]] |= SCAN_HELD;
+    uint32_t missed = 0;
+    for (uint32_t k = 0; k < N; ++k) {
+        if (!scan_peak(scratch, N, k, X, to)) continue;
+        bool covered = false;
+        for (uint32_t i = 0; i < n && !covered; ++i)
+            covered = (flags[slot[i]] & SCAN_HELD) && !(flags[slot[i]] & SCAN_ASSIGNED) && scan_distance(squelch_bin(fcw[slot[i]], logn), k, N) <= X;
+        if (covered) continue;
+        uint32_t rank = 0;   // the uncovered peaks that beat this one
+        for (uint32_t j = 0; j < N; ++j) {
+            if (j == k || !scan_beats(scratch[j], j, scratch[k], k) || !scan_peak(scratch, N, j, X, to)) continue;
+            bool cov = false;
+            for (uint32_t i = 0; i < n && !cov; ++i)
+                cov = (flags[slot[i]] & SCAN_HELD) && !(flags[slot[i]] & SCAN_ASSIGNED) && scan_distance(squelch_bin(fcw[slot[i]], logn), j, N) <= X;
+            rank += cov ? 0u : 1u;
+        }
+        uint32_t i = 0;
+        for (uint32_t r = 0; i < n; ++i) {   // the rank-th slot that is not held
+            if (flags[slot[i]] & SCAN_HELD) continue;
+            if (r++ == rank) break;
+        }
+        if (i == n) { ++missed; continue; }
+        fcw[slot[i]] = scan_assign(row, scratch, N, logn, k, B, med, to);
+        flags[slot[i]] |= SCAN_ASSIGNED;
+    }
+    return missed;
+}
 // ---- a-1g: the time-resolved squelch (m17hip_wide_squelch_slots): the same four functions per SLOT of a block — a group of CHAN_SURVEY_GROUP frames of the
 // block's spectrum, whose row is the spectrum's first-level sum — and the tuners skip per TILE of outputs.  A block of J frames has squelch_slots(J) slots;
 // slot g holds squelch_slot_frames(J, g) frames and is stepped with squelch_step(h, band, level x frames, ..., hang, frames): hang counts slots.

@@ -31,7 +31,7 @@ assert FRAME_REC.itemsize == 64 and DIAG.itemsize == 64
 FLAG_INVERT = 1
 KERNELS = {"fir_rrc150": 0, "dcd": 1, "demod_seq": 2, "decode": 3, "correlator": 4, "compact": 5, "limit_track": 6, "voice": 7, "discriminate": 8, "tune": 9,
            "tune2": 10, "channelise": 11, "survey": 12, "resample": 13, "spectrum": 14, "synth_wide": 15, "meter": 16, "squelch": 17,
-           "squelch_slots": 18, "squelch_floor": 19}
+           "squelch_slots": 18, "squelch_floor": 19, "scan": 20}
 LSF_INFO = np.dtype([("dst", "S10"), ("src", "S10"), ("type", "<u2"), ("crc_ok", "u1"), ("reserved", "u1", (9,))])
 BERT_STAT = np.dtype([("bits", "<u4"), ("errors", "<u4"), ("synced", "<u4"), ("frames", "<u4")])
 PACKET_REC = np.dtype([("channel", "<u4"), ("seq", "<u4"), ("sample_pos", "<u8"), ("size", "<u2"), ("checksum", "<u2"), ("crc_ok", "u1"),
@@ -81,7 +81,7 @@ EXPORTS = [
     "m17hip_wide_spectrum", "m17hip_wide_spectrum_default_window", "m17hip_wide_spectrum_twiddles", "m17hip_wide_spectrum_fetch",
     "m17hip_wide_meter", "m17hip_wide_meter_shape", "m17hip_wide_meter_fetch",
     "m17hip_wide_squelch", "m17hip_wide_squelch_fetch", "m17hip_wide_squelch_slots", "m17hip_wide_squelch_slots_fetch",
-    "m17hip_wide_squelch_floor", "m17hip_wide_squelch_floor_fetch",
+    "m17hip_wide_squelch_floor", "m17hip_wide_squelch_floor_fetch", "m17hip_wide_scan", "m17hip_wide_scan_fetch",
     "m17hip_synth_wide_k", "m17hip_synth_wide_config", "m17hip_synth_wide_channels", "m17hip_synth_wide", "m17hip_synth_wide_device",
     "m17hip_decode_sequences", "m17hip_set_fir_taps",
 ]
@@ -393,6 +393,21 @@ def wide_squelch_levels(power, frames, half_bins, open_db, close_db):
 def wide_squelch_ratio(db):
     """A ratio of Context.wide_squelch_floor from a margin over the floor in dB: np.float32(10 ** (db / 10))."""
     return np.float32(10.0 ** (float(db) / 10.0))
+
+
+SCAN_SLOT, SCAN_ASSIGNED, SCAN_HELD = 1, 2, 4   # the flags of Context.wide_scan_fetch
+
+
+def wide_scan_guard_bins(width_hz, rate_hz, points):
+    """The guard of Context.wide_scan for carriers `width_hz` wide on sources of `rate_hz` samples per second and a spectrum of `points` bins:
+    ceil(width_hz / (rate_hz / points)), at least 3 and at most points / 4 (what m17hip_wide_scan takes)."""
+    x = int(np.ceil(float(width_hz) / (float(rate_hz) / int(points))))
+    return max(3, min(x, int(points) // 4))
+
+
+def wide_scan_hz(fcw, rate_hz):
+    """The offsets in Hz (float64) of frequency words (Context.wide_scan_fetch) on sources of `rate_hz` samples per second: fcw * rate_hz / 2^32."""
+    return np.asarray(fcw, dtype=np.int64).astype(np.int32).astype(np.float64) * (float(rate_hz) / 4294967296.0)
 
 
 def wide_fcw(offset_hz, decim):
@@ -782,6 +797,41 @@ class Context:
         self._chk(self.lib.m17hip_wide_squelch_floor_fetch(self.h, C.c_uint32(back), _ptr(buf), C.c_uint64(buf.size), C.byref(n), C.byref(frames)))
         return buf[: 4 * n.value].reshape(4, n.value).copy(), int(frames.value)
 
+    def wide_scan(self, pool, guard_bins=None, rate_hz=None):
+        """The carrier scan, beside wide_spectrum (at most 4096 points), wide_squelch and wide_squelch_floor: `pool` is an array-like of 0 / 1 for local
+        channels 0 .. len - 1, a 1 makes the channel a SLOT of the source its wide_channels entry names.  From the blocks uploaded after this call a kernel
+        in front of the squelch finds the carriers of each source's block and writes the frequency words of the source's slots that are not held by a
+        carrier already: a transmission is tuned in the block in which it first appears.  guard_bins (3 .. points / 4) is the least distance of two
+        carriers; None takes wide_scan_guard_bins(9000, rate_hz, points) — `rate_hz` the sources' sample rate, by default the configuration's 48000 x
+        decimation.  pool None turns it off.  run() then resets the channels a block has just assigned before it queues the run — m17hip_wide_scan."""
+        if pool is None:
+            self._chk(self.lib.m17hip_wide_scan(self.h, None, C.c_uint32(0), C.c_uint32(0)))
+            self._scan = False
+            return
+        a = np.ascontiguousarray((np.asarray(pool).reshape(-1) != 0).astype(np.uint8))
+        if guard_bins is None:
+            points, (_, R, _) = getattr(self, "_spectrum_points", 0), getattr(self, "_wide", (0, 0, 0))
+            rate = rate_hz or 48000.0 * R / getattr(self, "_wide_up", 1)   # (the configuration's own rate)
+            guard_bins = wide_scan_guard_bins(9000.0, rate, points) if rate and points else 3
+        self._chk(self.lib.m17hip_wide_scan(self.h, _ptr(a) if a.size else None, C.c_uint32(a.size), C.c_uint32(guard_bins)))
+        self._scan = True
+        self._scan_pending = False
+
+    def wide_scan_fetch(self, back=0):
+        """(fcw int32 [C], flags uint32 [C], missed uint32 [S], assigned) of the latest block uploaded with wide_scan on (back = 0) or the one before it
+        (back = 1): the frequency words the block was tuned with, per channel SCAN_SLOT | SCAN_ASSIGNED (in this block) | SCAN_HELD (a carrier it had
+        holds it), per source the carriers that found no free slot, and the list of the channels assigned in this block.  Waits for that block's scan
+        kernel only — m17hip_wide_scan_fetch."""
+        if back not in (0, 1):
+            raise M17HipError("m17hip_wide_scan_fetch: back is 0 or 1")
+        cap = max(self.max_channels, 1)
+        fcw, flags, missed = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint32), np.zeros(256, dtype=np.uint32)
+        n, srcs, frames = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.lib.m17hip_wide_scan_fetch(self.h, C.c_uint32(back), fcw.ctypes.data_as(C.c_void_p), _ptr(flags), _ptr(missed), C.c_uint64(cap),
+                                                  C.byref(n), C.byref(srcs), C.byref(frames)))
+        fcw, flags = fcw[: n.value].copy(), flags[: n.value].copy()
+        return fcw, flags, missed[: srcs.value].copy(), [int(c) for c in np.flatnonzero(flags & np.uint32(SCAN_ASSIGNED))]
+
     def wide_channels(self, source, fcw):
         """Local channel c listens to source[c] at the frequency word fcw[c] (wide_fcw) from the blocks uploaded after this call — m17hip_wide_channels."""
         src = np.ascontiguousarray(np.asarray(source, dtype=np.uint32).reshape(-1))
@@ -823,6 +873,7 @@ class Context:
     def _upload_wide_raw(self, name, ptr, channels, samples, pitch, gain):
         self.C, self.T = int(channels), int(samples)
         self._chk(getattr(self.lib, name)(self.h, C.c_void_p(int(ptr)), C.c_float(gain), C.c_uint32(self.C), C.c_uint32(self.T), C.c_size_t(pitch)))
+        self._scan_pending = getattr(self, "_scan", False)   # (wide_scan: run() resets what this block assigns)
 
     def upload_wide_async(self, host_ptr, channels, samples, pitch, gain=1.0):
         """Stage the NEXT run's input from a wideband block in pinned host memory (pitch in complex samples; kept unmodified until upload_wait)."""
@@ -1135,6 +1186,16 @@ class Context:
 
     def run(self, flags=0, channels=None, samples=None):
         self._fed_channels = None
+        if getattr(self, "_scan_pending", False):   # (wide_scan: a slot assigned in the block starts a new transmission on a demodulator fed zeros)
+            self._scan_pending = False
+            try:
+                assigned = self.wide_scan_fetch()[3]
+            except M17HipError as e:
+                if "error -4" not in str(e):   # (M17HIP_ESTATE: a call since wide_scan has turned the scan off — every squelch, spectrum and configuration call does)
+                    raise
+                self._scan, assigned = False, []
+            if assigned:
+                self.reset_channels(assigned)
         self._chk(self.lib.m17hip_demod_run(self.h, C.c_uint32(channels or self.C), C.c_uint32(samples or self.T), C.c_uint32(flags)))
 
     def frames_select(self, back):

@@ -1,5 +1,5 @@
 """The tuner of m17hip_upload_wide_device (tune_kernel, csrc/m17_wide_kernels.hpp) at a receiver's shape, against its own VALU floor.
-    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]] [--squelch-floor FRACTION[,FRACTION...]] [--slots KEYED[,KEYED...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
+    python tools/wide_time.py [--decim2 R2 | --resample UP DOWN | --raster M [--survey STRIDE]] [--spectrum N --hop H [--squelch FRACTION[,FRACTION...]] [--squelch-floor FRACTION[,FRACTION...]] [--scan POOL] [--slots KEYED[,KEYED...]]] [--meter W] [sources [channels_per_source [outputs [decim [repeats]]]]]     (default 64 x 64 = 4096 channels, 48 000 outputs, R = 5, 10 timed blocks)
 int16 input, device form, default taps (L = 32 R + 1).  With --decim2 R2 it is the two-stage tuner of m17hip_wide_config2 (tune2_kernel,
 csrc/m17_wide2_kernels.hpp; library timer "tune2") at decim x R2 with the default taps of both stages: the filter term of the floor is then
 C T (R2 L1 + L2) — R2 first-stage sums of L1 taps and one second-stage sum of L2 per output — and the mixing term C T decim R2 samples.  The kernel's own device time comes from the library (m17hip_timing_get "tune": events bound to the
@@ -44,6 +44,10 @@ With --squelch-floor FRACTION[,FRACTION...] the same sources are squelched (bloc
 the ones the device derived for the last block (where the block is no whole number of hops the frames shift from block to block, and a channel at the
 margin may decide differently: both counts are reported): the two launches — spectrum + floor + squelch + tuner against spectrum + squelch + tuner —
 side by side.
+With --scan POOL beside --spectrum (at most 4096 points) the first POOL channels of every source are slots of the carrier scan (m17hip_wide_scan:
+wide_scan_kernel, library timer "scan"), a carrier stands on a tenth of every source's channels, block mode at 10 / 6 dB with the floor on the device: the
+scan kernel beside squelch_floor_kernel of the same call, and the scanned launch — spectrum + floor + scan + squelch + tuner — beside the same launch of
+the same build with the scan off and the scan's fetched table given through m17hip_wide_channels, twice (the second pass is the yardstick's own spread).
 With --slots KEYED[,KEYED...] beside --spectrum under one of the three tuners EVERY channel has a carrier, keyed for the first KEYED (0 to 1) of each block
 over weak noise; the levels come from the plane of a block of that noise alone (10 and 6 dB over the median floor, a 9 kHz band).  Per value the same
 source is timed in the same call unsquelched (tuner and spectrum), under the block squelch (m17hip_wide_squelch: spectrum, "squelch", tuner) and under the
@@ -111,6 +115,12 @@ if "--squelch-floor" in ARGS:
     FLOOR = [float(v) for v in ARGS[k + 1].split(",")]
     del ARGS[k:k + 2]
     assert SPECTRUM and not RASTER and all(0.0 <= v <= 1.0 for v in FLOOR), "--squelch-floor FRACTION (0 to 1) goes with --spectrum N --hop H and a tuner"
+SCAN = 0   # (0: not timed)
+if "--scan" in ARGS:
+    k = ARGS.index("--scan")
+    SCAN = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+    assert SPECTRUM and SPECTRUM <= 4096 and not RASTER and SCAN >= 1, "--scan POOL (slots per source) goes with --spectrum N (at most 4096) --hop H and a tuner"
 SLOTS = []   # (empty: not timed)
 if "--slots" in ARGS:
     k = ARGS.index("--slots")
@@ -336,6 +346,57 @@ if FLOOR:   # per fraction: the squelched launch with the floor taken on the dev
                       "floor_on_over_given": round(dev / giv, 4)})
         del xs
     ctx.reset()
+scan = []
+if SCAN:   # the scanned launch beside the same launch with the scan's own table given by the host
+    half = m17hip.wide_squelch_half_bins(9000.0, 48000.0 * RATIO, SPECTRUM)
+    guard = m17hip.wide_scan_guard_bins(9000.0, 48000.0 * RATIO, SPECTRUM)
+    ro, rc = m17hip.wide_squelch_ratio(10.0), m17hip.wide_squelch_ratio(6.0)
+    srcs, words0 = np.repeat(np.arange(S), PER), [m17hip.wide_fcw(f, RATIO) for f in OFFSETS]
+    pool = (np.arange(C) % PER < min(SCAN, PER)).astype(np.uint8)
+    xs, on = carrier_source(0.1)
+
+    def call_c():
+        ctx.upload_wide_device(xs.data_ptr(), C, T, ROW)
+
+    def timed_c(extra):
+        call_c(); call_c()
+        ctx.timing_reset()
+        for _ in range(REP):
+            call_c()
+        opened = int(ctx.wide_squelch_fetch()[0].sum())
+        parts = {k: ctx.timing_get(k) for k in (OWN, "spectrum", "squelch", "squelch_floor") + extra}
+        return {k: v[0] / v[1] for k, v in parts.items()}, opened
+
+    def setup():
+        ctx.reset()
+        ctx.wide_spectrum(SPECTRUM, HOP)
+        ctx.wide_squelch(half, np.ones(S, dtype=np.float32), np.ones(S, dtype=np.float32), 0)
+        ctx.wide_squelch_floor(ro, rc)
+
+    setup()
+    ctx.wide_scan(pool, guard)
+    call_c()
+    first = ctx.wide_scan_fetch()
+    on_ms, on_open = timed_c(("scan",))
+    words, flags, missed, _ = ctx.wide_scan_fetch()
+    given = []
+    for _ in range(2):
+        setup()
+        ctx.wide_channels(srcs, words)
+        given.append(timed_c(()))
+    ctx.wide_channels(srcs, words0)
+    ctx.wide_squelch(0, None)
+    ctx.wide_spectrum(0, 0)
+    tot, giv = sum(on_ms.values()), [sum(g_[0].values()) for g_ in given]
+    scan.append({"slots_per_source": int(min(SCAN, PER)), "guard_bins": guard, "half_bins": half, "carriers": on * S, "assigned_first_block": len(first[3]),
+                 "held_slots": int((flags & m17hip.SCAN_HELD != 0).sum()), "missed": int(missed.sum()), "open_channels": on_open,
+                 "open_channels_given_table": [g_[1] for g_ in given], "scan_kernel_ms": round(on_ms["scan"], 4),
+                 "floor_kernel_ms": round(on_ms["squelch_floor"], 4), "scan_over_floor": round(on_ms["scan"] / on_ms["squelch_floor"], 2),
+                 "spectrum_ms": round(on_ms["spectrum"], 3), "tuner_ms_scan_on": round(on_ms[OWN], 3), "tuner_ms_given_table": [round(g_[0][OWN], 3) for g_ in given],
+                 "launch_ms_scan_on": round(tot, 3), "launch_ms_given_table": [round(v, 3) for v in giv], "scan_on_over_given": round(tot / giv[0], 4),
+                 "given_spread": round(giv[1] / giv[0], 4)})
+    del xs
+    ctx.reset()
 slots = []
 if SLOTS:   # per keyed share: unsquelched, block squelch, slot squelch on one source whose every channel has a carrier for the first part of each block
     assert PER * 300 + 200 <= 32767, "--slots: at most 108 channels per source (300 per carrier)"
@@ -448,6 +509,6 @@ print(json.dumps({
     "wall_ms_median": round(float(np.median(wall)), 3),
     "floor_ms": round(floor_ms, 3), "floor_filter_share": round(FILTER / cycles, 3), "kernel_over_floor": round(kernel_ms / floor_ms, 2),
     "demod_step_ms_same_samples": [round(v, 3) for v in step], "tuner_over_demod_step": [round(kernel_ms / v, 2) for v in step],
-    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}), **({"squelch_floor": floor} if FLOOR else {}), **({"slots": slots} if SLOTS else {}),
+    **({"survey": survey} if SURVEY else {}), **({"spectrum": spectrum} if SPECTRUM else {}), **({"meter": meter} if METER else {}), **({"squelch": squelch} if SQUELCH else {}), **({"squelch_floor": floor} if FLOOR else {}), **({"scan": scan} if SCAN else {}), **({"slots": slots} if SLOTS else {}),
     "cus": cus, "sclk_mhz_max_seen": clocks.seen, "iq_bytes": ctx.iq_bytes(),
 }))
